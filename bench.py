@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: event-frames/s (B x T) of one SODa / TinyYolo training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config gen1|1mpx|deep12]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config gen1|1mpx|deep12] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy (``dump_outputs``); the inputs are
+seeded, so two builds run with the same arguments can be compared array for array.
 
 One step = the whole hot path on one batch of synthetic events: layer-major forward over all T, loss on the
 last timestep, BPTT backward producing every parameter gradient, (N>1: one RCCL all-reduce of the flat
@@ -161,6 +164,36 @@ def deep12_probe(B, H, W, device):
     """Read-out of the backbone at the last timestep: a fixed random projection (the gradient then flows back through
     all T steps of all 12 layers)."""
     return torch.randn(B, 64, H, W, generator=torch.Generator().manual_seed(3)).to(device)
+
+
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(directory, loss, trainer, model) -> dict:
+    """Write what the last timed step handed its caller as ``directory/<name>.npy`` (float32): ``loss``, ``param_grad``
+    (the gradient of every trainable parameter) and ``param`` (the parameters after the Adamax update), both in
+    ``model.parameters()`` order with each tensor flattened in its logical shape (not the trainer's storage order), and
+    ``bn_running_stats`` (the floating-point buffers, ``model.buffers()`` order).  Should the total exceed 64 MB, every
+    array above an equal share of it is cut to a fixed sample of its elements (the sorted first ``share`` of
+    ``torch.randperm`` seeded with 0, the same on every run).  Returns ``{name: element count written}``."""
+    import numpy as np
+
+    def flat(tensors):
+        tensors = [t.detach().reshape(-1).float() for t in tensors]
+        return torch.cat(tensors) if tensors else torch.zeros(0)
+    arrays = {"loss": loss.detach().reshape(1).float(), "param_grad": flat(trainer.grad_views),
+              "param": flat(trainer.params), "bn_running_stats": flat(b for b in model.buffers() if b.is_floating_point())}
+    share = DUMP_LIMIT_BYTES // (4 * len(arrays))   # float32 elements per array when the total must be sampled
+    sample = sum(a.numel() for a in arrays.values()) * 4 > DUMP_LIMIT_BYTES
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = a.cpu()
+        if sample and a.numel() > share:
+            a = a[torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values]
+        np.save(os.path.join(directory, f"{name}.npy"), a.numpy())
+        written[name] = a.numel()
+    return written
 
 
 def csrc_fingerprint() -> str:
@@ -381,7 +414,9 @@ def dry_run(args, world: int, rank: int) -> int:
             trainer.all_reduce()
             n_coll = 1 + 2 * len(bns) + (2 if overlapped else 1)
         equal = replicas_equal(trainer, dist, "flat_grad") and replicas_equal(trainer, dist, "flat_param")
-        dist.barrier()
+        # join the ranks with a CPU collective: dist.barrier() probes the accelerator, which opens the GPU device in every
+        # rank of this CPU-only rehearsal (8 ranks at world 8)
+        dist.all_reduce(torch.zeros(1))
     if rank == 0:
         emit_json({"metric": "event-frames/sec (BxT) SODa-3M GEN1 304x240 fwd+bwd", "value": None,
                    "unit": "event-frames/s", "n_gpus": world, "dry_run": True,
@@ -428,9 +463,14 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearse the launch / rendezvous / collective control flow only: no GPU work, no timing; "
                          "the JSON line carries n_gpus and dist but value null (CPU boxes, SNN_DIST_BACKEND=gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, parameter gradients, updated "
+                         "parameters, BatchNorm running statistics) as DIR/<name>.npy, float32, at most 64 MB (rank 0)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves - BEFORE anything touches the GPU
         # (no HIP call has happened in this process; the ranks are child processes, this one only relays their exit code)
@@ -541,6 +581,10 @@ def main():
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / steps
     frames_per_s = world * B * T * steps / elapsed
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before the profiled steps below, which update the parameters again
+        dumped = {"dir": args.dump_outputs, "elements": dump_outputs(args.dump_outputs, loss, trainer, model)}
     replicas_eq = None
     if distributed:
         # evidence that the gradient exchange kept the replicas together: after `warmup + steps` updates every rank
@@ -680,6 +724,7 @@ def main():
                                       "between GPUs"} if args.rehearse_dist and world == 1 else {})},
             "roofline": roofline,
             "cpu_baseline": cpu,
+            "dumped_outputs": dumped,
         }
         if args.config == "gen1" and (H, W, classes) == (cfg["H"], cfg["W"], cfg["classes"]):
             # whole-step view against BASELINE.md section 2 (ideal-fusion byte model of this network: 114.0 M tensor elements

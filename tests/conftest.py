@@ -1,7 +1,13 @@
 import os
 import sys
 
-import pytest
+# Before anything imports torch: MKL (torch's CPU log / exp / tanh and GEMMs) picks its code branch by CPU vendor and ISA,
+# and the branches round differently, so the bit-exact pins against tests/golden/ (recorded with this setting by
+# tests/golden/make_golden.py) would hold on one host and not another.  COMPATIBLE is the branch MKL keeps identical
+# on every x86 processor.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

@@ -17,8 +17,11 @@ import os
 import sys
 import types
 
-import numpy as np
-import torch
+# the MKL branch the tests run on (tests/conftest.py): identical bits on every x86 host
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 REF = os.environ.get("SNN_REFERENCE", "/root/reference")
 OUT = os.path.dirname(os.path.abspath(__file__))
@@ -533,6 +536,7 @@ def tiny_yolo_description():
 
 
 def main():
+    torch.set_num_threads(8)   # the thread count tests/test_oracle_pins.py replays the pins with
     box, anchors_mod, roi_mod = load_reference_utils()
     torch.manual_seed(0)
     gen = torch.Generator().manual_seed(1234)

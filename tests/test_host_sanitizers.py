@@ -68,7 +68,11 @@ def test_c_abi_host_side_under_asan_and_ubsan(tmp_path):
     assert os.path.exists(info["lib"]) and os.path.exists(info["asan_runtime"]), info
     script = tmp_path / "sweep.py"
     script.write_text(CHILD)
+    # the child is a process without a device, as on a CPU host, wherever the suite runs: the planning helpers ask the
+    # runtime for the compute-unit count, and with a visible GPU that first query would initialise the HIP runtime
+    # against the empty stand-in code objects of this host-only build
     env = dict(os.environ, SNN_HIP_LIB=info["lib"], LD_PRELOAD=info["asan_runtime"],
+               HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1",
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:halt_on_error=1",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     res = subprocess.run([sys.executable, str(script), ROOT], env=env, capture_output=True, text=True, timeout=850)

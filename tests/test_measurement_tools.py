@@ -164,3 +164,57 @@ def test_chain_row_prices_the_scans_at_the_ideal_fusion_bytes():
     assert row["moved_bytes_per_neuron_timestep"] == pytest.approx(40.0)
     assert row["frac_hbm"] == pytest.approx(20.0 * n / 6.08e-3 / 8e12, rel=1e-6) and 0.34 < row["frac_hbm"] < 0.36
     assert bench.chain_row(table, 2 * n, 2, sb=True)["ideal_bytes_per_neuron_timestep"] == 10.0
+
+
+def _cpu_trainer():
+    import torch
+    import snn_for_object_detection_amd as S
+    from snn_for_object_detection_amd.trainer import FlatTrainer
+    torch.manual_seed(0)
+    model = S.BlockGen(2, [S.Conv(8, 3), S.Norm(), S.LIF(), S.Conv(4, 1)])
+    trainer = FlatTrainer(model, lr=1e-3, find_unused_parameters=False)
+    trainer.flat_grad.copy_(torch.randn(trainer.flat_grad.shape))
+    return model, trainer
+
+
+def test_dump_outputs_writes_the_step_results_as_float32(tmp_path):
+    """``bench.py --dump-outputs``: loss, gradient, parameters and BatchNorm statistics, float32, in parameter order."""
+    import numpy as np
+    import torch
+    model, trainer = _cpu_trainer()
+    written = bench.dump_outputs(str(tmp_path), torch.tensor(0.25), trainer, model)
+    assert set(written) == {"loss", "param_grad", "param", "bn_running_stats"}
+    arrays = {name: np.load(tmp_path / f"{name}.npy") for name in written}
+    assert all(a.dtype == np.float32 and a.size == written[k] for k, a in arrays.items())
+    assert arrays["loss"].tolist() == [0.25]
+    # each tensor in its logical shape, in parameter order (not the trainer's channels-last storage order)
+    assert np.array_equal(arrays["param_grad"], torch.cat([g.reshape(-1) for g in trainer.grad_views]).numpy())
+    assert np.array_equal(arrays["param"], torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy())
+    assert not np.array_equal(arrays["param_grad"], trainer.flat_grad[:trainer.numel].numpy())
+    bn = [b for b in model.buffers() if b.is_floating_point()]
+    assert arrays["bn_running_stats"].size == sum(b.numel() for b in bn) > 0
+
+
+def test_dump_outputs_samples_a_larger_output_the_same_way_every_time(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    model, trainer = _cpu_trainer()
+    limit = 4 * trainer.numel // 2           # half the size of one gradient
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    runs = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        bench.dump_outputs(str(d), torch.tensor(1.0), trainer, model)
+        runs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+        assert sum(os.path.getsize(d / f) - 128 for f in os.listdir(d)) <= limit   # (128 B .npy header each)
+    assert all(np.array_equal(runs[0][f], runs[1][f]) for f in runs[0])
+    grad = trainer.flat_grad[:trainer.numel].numpy()
+    assert 0 < runs[0]["param_grad.npy"].size < grad.size and np.isin(runs[0]["param_grad.npy"], grad).all()
+
+
+def test_bench_refuses_a_step_count_below_one():
+    import subprocess
+    import sys
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         timeout=120)
+    assert res.returncode != 0 and "--steps must be >= 1" in res.stderr
