@@ -283,7 +283,11 @@ int snn_conv1x1_spikes_wgrad(const float* vdec, int64_t ld, float v_th, const fl
  *   snn_conv2d_spikes_wgrad : as snn_conv2d_wgrad (workspace / splitk from snn_conv2d_wgrad_splitk, SNN_PREC_BF16X3); 3x3
  *                             layers the halo-resident weight gradient covers take it (two products)
  *   snn_conv3x3_halo_spikes : the halo-resident 3x3 / stride 1 / pad 1 forward (snn_conv3x3_halo, fp16 x 3 image) on the
- *                             potentials; shapes: snn_conv3x3_halo_supported */
+ *                             potentials; shapes: snn_conv3x3_halo_supported
+ * The *_supported queries see shapes and strides only.  The implicit-GEMM kernels behind snn_conv2d_spikes_fwd /
+ * snn_conv1x1_spikes_fwd also need 16-byte aligned potentials and weight, the weight gradients 16-byte aligned potentials
+ * and dy with lddy % 4 == 0; a call outside that is refused on the host (error, nothing launched) - the caller writes
+ * the spikes and takes snn_conv2d_fwd / snn_conv2d_wgrad instead (functional._spikes_fwd_ok / _spikes_wgrad_ok). */
 int snn_conv2d_spikes_supported(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride,
                                 int pad, int64_t ld, int fwd_precision, int bwd_precision);
 int snn_conv2d_spikes_fwd(const float* vdec, int64_t ld, float v_th, const float* w, float* y, int64_t ldy, int64_t N, int H,

@@ -638,14 +638,16 @@ def _dgrad_accumulate(acc, gy, ldg, wt, x, geom, st, prec, wt_split=None, wt_ima
         _hip.call("snn_conv3x3_halo_bn", rec.gx.data_ptr(), rec.y.data_ptr(), rec.coef.data_ptr(), B, dy_out.data_ptr(),
                   wt_image.data_ptr(), dx.data_ptr(), cl_stride(dx), T * B, H, W, Cout, Cin, addend, ld_add, addend2, ld_add2,
                   st)
-    elif (prec in _HALO_BWD_PRECS and ldg % 4 == 0 and USE_HALO_CONV and (KH, KW, stride, pad) == (3, 3, 2, 1)
+    elif (prec in _HALO_BWD_PRECS and _halo_operand_ok(gy.data_ptr(), ldg, prec == _hip.PREC_BF16S) and USE_HALO_CONV
+            and (KH, KW, stride, pad) == (3, 3, 2, 1)
             and _hip.query("snn_conv3x3_s2_dgrad_supported", T * B, H, W, Cin, Ho, Wo, Cout)):
         # stride 2: all four phase classes of dx from ONE staged pass over dy (k_conv_s2dgrad3)
         if wt_image is None:
             wt_image = _frag_image(wt, Cin, Cout, 1, _hip.PREC_BF16X3)
         _hip.call("snn_conv3x3_s2_dgrad", gy.data_ptr(), ldg, wt_image.data_ptr(), dx.data_ptr(), cl_stride(dx), T * B, H, W, Cin, Ho,
                   Wo, Cout, addend, ld_add, addend2, ld_add2, prec, st)
-    elif (prec in _HALO_BWD_PRECS and ldg % 4 == 0 and _halo_ok(T * B, H, W, Cout, Cin, KH, KW, stride, pad)):
+    elif (prec in _HALO_BWD_PRECS and _halo_operand_ok(gy.data_ptr(), ldg, prec == _hip.PREC_BF16S)
+            and _halo_ok(T * B, H, W, Cout, Cin, KH, KW, stride, pad)):
         # dx = conv3x3(dy, mirrored taps of w^T): the halo-resident kernel with the data gradient's weight image
         if wt_image is None:
             wt_image = _frag_image(wt, Cin, Cout, 1, _hip.PREC_BF16X3)
@@ -678,6 +680,34 @@ _HALO_BWD_PRECS = (_hip.PREC_BF16X3, _hip.PREC_BF16S)
 def _halo_ok(N: int, H: int, W: int, Cin: int, Cout: int, KH: int, KW: int, stride: int, pad: int) -> bool:
     return (USE_HALO_CONV and KH == 3 and KW == 3 and stride == 1 and pad == 1
             and bool(_hip.query("snn_conv3x3_halo_supported", N, H, W, Cin, Cout)))
+
+
+def _halo_operand_ok(ptr: int, ld: int, bf16: bool) -> bool:
+    """The operand the halo-resident kernels stage (snn_conv3x3_halo x / dy, snn_conv3x3_s2_dgrad dy): pixel stride a
+    multiple of 4 and 16-byte aligned (8 for bf16 storage).  A channel slice of a concat buffer or of a concat gradient at
+    another offset is not; the implicit GEMM takes it instead."""
+    return ld % 4 == 0 and ptr % (8 if bf16 else 16) == 0
+
+
+def _spikes_fwd_ok(supported: bool, halo: bool, x_ptr: int, w_ptr: int) -> bool:
+    """A convolution over saved potentials can run its thresholding forward kernel.  ``supported``: the shape query
+    (snn_conv2d_spikes_supported / snn_conv1x1_spikes_supported), which sees shapes and strides only.  The implicit GEMM
+    (k_conv_gather XSP) also needs 16-byte aligned potentials and weight - a FlatTrainer parameter may start on any float
+    of the flat buffer; the halo-resident kernel reads its own weight image instead (``halo``)."""
+    return bool(supported) and x_ptr % 16 == 0 and (halo or w_ptr % 16 == 0)
+
+
+def _spikes_wgrad_ok(x_ptr: int, ldx: int, gy_ptr: int, ldg: int) -> bool:
+    """The thresholding weight gradient (snn_conv2d_spikes_wgrad) covers the pipelined kernel only - the halo-resident one
+    drops to it for buffers it cannot address: pixel strides multiples of 4 and 16-byte aligned potentials AND output
+    gradient.  A gradient that is a slice of a concat gradient at another channel offset fails that; its convolution
+    writes the spikes out for its weight gradient instead."""
+    return ldx % 4 == 0 and ldg % 4 == 0 and x_ptr % 16 == 0 and gy_ptr % 16 == 0
+
+
+def _spikes_dense(x: torch.Tensor, x_th: float) -> torch.Tensor:
+    """z = (x > x_th) of saved potentials ``x`` ([T,B,C,H,W] channels-last view) as a dense fp32 spike tensor."""
+    return _cl_view((x.permute(0, 1, 3, 4, 2) > x_th).to(_F32).contiguous())
 
 
 def _frag_image(src: torch.Tensor, O: int, I: int, flip: int, prec: int) -> torch.Tensor:
@@ -766,13 +796,15 @@ class _Conv2d(Function):
         Ho = (H + 2 * pad - KH) // stride + 1
         Wo = (W + 2 * pad - KW) // stride + 1
         x = _raw_to_cl(x)
-        if x_th is not None and (sb or not _hip.query("snn_conv2d_spikes_supported", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW,
-                                                       stride, pad, cl_stride(x), fwd_prec, bwd_prec)):
-            # arithmetic or shape the thresholding kernels do not cover: the spikes are written after all
-            x = _cl_view((x.permute(0, 1, 3, 4, 2) > x_th).to(_F32).contiguous())
-            x_th = None
         w = weight.detach()
         w_ohwi = w if is_channels_last(w) else _raw_dense_cl(w)
+        if x_th is not None and (sb or not _spikes_fwd_ok(
+                _hip.query("snn_conv2d_spikes_supported", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, cl_stride(x),
+                           fwd_prec, bwd_prec),
+                _halo_ok(T * B, H, W, Cin, Cout, KH, KW, stride, pad), x.data_ptr(), w_ohwi.data_ptr())):
+            # arithmetic, shape or weight alignment the thresholding kernels do not cover: the spikes are written after all
+            x = _spikes_dense(x, x_th)
+            x_th = None
         y = _out_tensor(dest, T, B, Cout, Ho, Wo, x, _BF16 if sb else None)
         partial = layout = None
         if bn_out is not None:  # a train-mode BatchNorm follows: its statistics come out of this kernel's epilogue
@@ -784,7 +816,8 @@ class _Conv2d(Function):
         if (fwd_prec == _hip.PREC_FP16X3 and USE_PRESPLIT_WEIGHTS and w_ohwi is w
                 and getattr(weight, "_snn_w16", None) is not None and weight._snn_wt_version == weight._version):
             w16 = weight._snn_w16.data_ptr()   # a tensor view on the parameter: alive as long as the parameter is
-        halo = _halo_ok(T * B, H, W, Cin, Cout, KH, KW, stride, pad) and cl_stride(x) % 4 == 0
+        halo = (_halo_ok(T * B, H, W, Cin, Cout, KH, KW, stride, pad)
+                and _halo_operand_ok(x.data_ptr(), cl_stride(x), x.dtype == _BF16))
         if halo and fwd_prec in (_hip.PREC_FP16X3, _hip.PREC_BF16S):
             # the image holds fp16 pieces (fp16 x 3) or bf16 pieces (bf16 storage: the hi pieces are the rounded weights)
             img_prec = _hip.PREC_BF16X3 if sb else _hip.PREC_FP16X3
@@ -876,13 +909,17 @@ class _Conv2d(Function):
                 dx = _dgrad_accumulate(ctx.acc, gy, ldg, wt, x, ctx.geom, st, ctx.prec, wt_split=wt16, wt_image=wt_img)
         if ctx.needs_input_grad[1]:
             splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ctx.prec)
+            xw, ldxw, x_th = x, ldx, ctx.x_th
+            if x_th is not None and not _spikes_wgrad_ok(x.data_ptr(), ldx, gy.data_ptr(), ldg):
+                xw, x_th = _spikes_dense(x, x_th), None   # (same bits: the plain kernel on the stored spikes)
+                ldxw = cl_stride(xw)
 
             def wgrad(dst_ptr, accumulate, ws_, stream_ptr):
-                if ctx.x_th is not None:   # x holds potentials: thresholded on load
-                    _hip.call("snn_conv2d_spikes_wgrad", x.data_ptr(), ldx, ctx.x_th, gy.data_ptr(), ldg, dst_ptr, T * B, H,
+                if x_th is not None:   # x holds potentials: thresholded on load
+                    _hip.call("snn_conv2d_spikes_wgrad", xw.data_ptr(), ldxw, x_th, gy.data_ptr(), ldg, dst_ptr, T * B, H,
                               W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, accumulate, ws_.data_ptr(), splitk, stream_ptr)
                 else:
-                    _hip.call("snn_conv2d_wgrad", x.data_ptr(), ldx, gy.data_ptr(), ldg, dst_ptr, T * B, H, W, Cin, Ho, Wo,
+                    _hip.call("snn_conv2d_wgrad", xw.data_ptr(), ldxw, gy.data_ptr(), ldg, dst_ptr, T * B, H, W, Cin, Ho, Wo,
                               Cout, KH, KW, stride, pad, accumulate, ws_.data_ptr(), splitk, ctx.prec, stream_ptr)
             if ctx.slot is not None and _wgrad_on_side():
                 # gradient goes straight into the flat buffer: nothing downstream in autograd needs it, so
@@ -893,7 +930,7 @@ class _Conv2d(Function):
                 with torch.cuda.stream(side):
                     ws = torch.empty((splitk, Cout * KH * KW * Cin), device=x.device, dtype=_F32)
                     wgrad(ctx.slot.buf.data_ptr(), ctx.slot.claim(), ws, side.cuda_stream)
-                _side_hold(side, x, gy)
+                _side_hold(side, x, xw, gy)
             elif ctx.slot is not None:
                 ws = torch.empty((splitk, Cout * KH * KW * Cin), device=x.device, dtype=_F32)
                 wgrad(ctx.slot.buf.data_ptr(), ctx.slot.claim(), ws, st)
@@ -1134,10 +1171,12 @@ class _SiblingConv1x1(Function):
             if w1m is None and need_t:
                 wct.copy_(wc.t())
         y = _out_tensor(dest, T, B, Ct, H, W, x)
-        if x_th is not None and not _hip.query("snn_conv1x1_spikes_supported", T * B, H, W, Cin, Ct, cl_stride(x), fwd_prec,
-                                               bwd_prec):
-            # (arithmetic or shape the thresholding kernels do not cover: the spikes are materialised after all)
-            x = _cl_view((x.permute(0, 1, 3, 4, 2) > x_th).to(_F32).contiguous())
+        if x_th is not None and not _spikes_fwd_ok(
+                _hip.query("snn_conv1x1_spikes_supported", T * B, H, W, Cin, Ct, cl_stride(x), fwd_prec, bwd_prec), False,
+                x.data_ptr(), wc.data_ptr()):
+            # (arithmetic, shape or weight alignment the thresholding kernels do not cover: the spikes are materialised
+            # after all)
+            x = _spikes_dense(x, x_th)
             x_th = None
         if x_th is not None:
             _hip.call("snn_conv1x1_spikes_fwd", x.data_ptr(), cl_stride(x), x_th, wc.data_ptr(), y.data_ptr(), cl_stride(y),
@@ -1172,6 +1211,10 @@ class _SiblingConv1x1(Function):
             slot1, slots2 = ctx.slot1, ctx.slots2
             slotted = all(s_ is not None for s_ in slots2) and (slot1 is not None or not composed)
             splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, H, W, Ct, 1, 1, 1, 0, ctx.prec)
+            xw, ldxw, x_th = x, ldx, ctx.x_th
+            if x_th is not None and not _spikes_wgrad_ok(x.data_ptr(), ldx, gy.data_ptr(), ldg):
+                xw, x_th = _spikes_dense(x, x_th), None   # (same bits: the plain kernel on the stored spikes)
+                ldxw = cl_stride(xw)
             side_ok = slotted and _wgrad_on_side()
             main = torch.cuda.current_stream()
             stream = _side_stream(x.device) if side_ok else main
@@ -1181,11 +1224,11 @@ class _SiblingConv1x1(Function):
             with torch.cuda.stream(stream):
                 ws = torch.empty((splitk, Ct * Cin), device=x.device, dtype=_F32)
                 G = torch.empty((Ct, Cin), device=x.device, dtype=_F32)
-                if ctx.x_th is not None:   # x holds the potentials of the LIF layer in front: thresholded on load
-                    _hip.call("snn_conv1x1_spikes_wgrad", x.data_ptr(), ldx, ctx.x_th, gy.data_ptr(), ldg, G.data_ptr(),
+                if x_th is not None:   # x holds the potentials of the LIF layer in front: thresholded on load
+                    _hip.call("snn_conv1x1_spikes_wgrad", xw.data_ptr(), ldxw, x_th, gy.data_ptr(), ldg, G.data_ptr(),
                               T * B, H, W, Cin, Ct, 0, ws.data_ptr(), splitk, stream.cuda_stream)
                 else:
-                    _hip.call("snn_conv2d_wgrad", x.data_ptr(), ldx, gy.data_ptr(), ldg, G.data_ptr(), T * B, H, W, Cin, H,
+                    _hip.call("snn_conv2d_wgrad", xw.data_ptr(), ldxw, gy.data_ptr(), ldg, G.data_ptr(), T * B, H, W, Cin, H,
                               W, Ct, 1, 1, 1, 0, 0, ws.data_ptr(), splitk, ctx.prec, stream.cuda_stream)
                 g1 = None
                 if composed:
@@ -1212,7 +1255,7 @@ class _SiblingConv1x1(Function):
                 if composed and not slotted:
                     dw1 = g1.view(C1, Cin, 1, 1)
             if side_ok:
-                _side_hold(stream, x, gy)
+                _side_hold(stream, x, xw, gy)
         return (dx, dw1, None, None, None, None, None, None, *dw2s)
 
 
