@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SNN_ABI_VERSION 11
+#define SNN_ABI_VERSION 12
 
 /* neuron kinds for the fused affine+neuron temporal scan */
 enum {
@@ -529,6 +529,29 @@ int snn_det_loss_fwd(const float* cls_logits, const float* bbox_preds, const flo
 int snn_det_loss_bwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset, const float* bbox_mask,
                      const int64_t* class_labels, int64_t rows, int K, float loss_ratio, const double* stats,
                      const float* g_loss, float* g_logits, float* g_bbox, void* stream);
+
+/* ---------------------------------------------------------------- detection mAP (ABI v12)
+ * COCO bounding-box mAP as the reference computes it in validation_step / test_step (models/soda.py:160-182, 283-321:
+ * torchmetrics MeanAveragePrecision, iou_type "bbox", area range "all", no crowd boxes).
+ * snn_map_match: one block per (image, class).  dets [B][A][6] rows (class, score, x1, y1, x2, y2), labels [B][G][5] rows
+ * (class, x1, y1, x2, y2), class < 0 = padding; order [B][A] int32 row ids sorted by (class ascending, score descending),
+ * stably; seg [B][num_classes + 1] int32: the rows of class c are order[b][seg[b][c] .. seg[b][c+1]).  The first `slots`
+ * of them (= the largest maxDet, <= 1024) are matched greedily at each of the num_iou (<= 31) thresholds (device fp64
+ * table) against the image's ground truth of the class (G <= 2048 rows per image).  Records [B][num_classes][slots]:
+ * score (-inf for an empty slot) and match_mask (bit 31: slot used, bit t: matched at threshold t); npig[c] += the
+ * image's ground-truth count of class c (one integer atomic per block, zeroed by the caller once per evaluation).
+ * snn_map_accumulate: order [num_classes][records] int32: positions (image * slots + slot) of each class's records
+ * sorted by score descending, stably; match_mask [num_classes][records] in position order; max_dets [num_max_dets] int32
+ * ascending (device), rec_thresholds [num_rec] fp64 ascending (device, <= 1024); t50 / t75: index of IoU 0.5 / 0.75 in
+ * the threshold table or -1.  out[3 + num_max_dets] fp32 = map, map_50, map_75, mar at each max_dets entry; -1 where no
+ * class has ground truth.  workspace: snn_map_workspace_size(num_classes, num_max_dets, num_iou) bytes. */
+int snn_map_match(const float* dets, const float* labels, const int* order, const int* seg, int B, int A, int G,
+                  int num_classes, int slots, const double* iou_thresholds, int num_iou, float* score,
+                  unsigned* match_mask, int* npig, void* stream);
+size_t snn_map_workspace_size(int num_classes, int num_max_dets, int num_iou);
+int snn_map_accumulate(const int* order, const unsigned* match_mask, const int* npig, int num_classes, int records,
+                       int slots, const int* max_dets, int num_max_dets, const double* rec_thresholds, int num_rec,
+                       int num_iou, int t50, int t75, void* workspace, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,7 @@ from .anchors import AnchorGenerator  # noqa: F401
 from .data import EventBatcher  # noqa: F401
 from .generator import BackboneGen, BlockGen, Head, HeadGen, ListGen, ListState, ModelGen, NeckGen  # noqa: F401
 from .layer_gen import *  # noqa: F401,F403
+from .metrics import MeanAveragePrecision  # noqa: F401
 from .roi import RoI  # noqa: F401
 from .soda import SODa  # noqa: F401
 from .tiny_yolo import TinyYolo  # noqa: F401

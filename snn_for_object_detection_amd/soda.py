@@ -8,7 +8,12 @@ Same constructor, hooks and step logic; what differs:
   both give the same result and the second exists for parity tests and streaming use.
 * Lightning / torchmetrics are not dependencies: the class is a plain ``nn.Module`` exposing the
   Lightning hook names (``training_step``, ``configure_optimizers`` ...) so a trainer loop or a
-  LightningModule shim can drive it.  mAP evaluation (``soda.py:283-321``) is out of scope.
+  LightningModule shim can drive it.
+* mAP evaluation (``soda.py:160-182, 283-321``) keeps the reference's hooks and keys but runs on the device:
+  ``validation_step`` / ``test_step`` hand ``multibox_detection`` of the step's predictions to
+  ``metrics.MeanAveragePrecision.update_padded`` (no host synchronisation), ``on_validation_epoch_end`` /
+  ``on_test_epoch_end`` log ``map, map_50, mar_1, mar_10, mar_100`` through ``log_dict``.  As in the reference
+  (``sync_on_compute=False``) each rank's mAP covers the images that rank saw.
 """
 
 from types import SimpleNamespace
@@ -19,6 +24,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import box
+from .metrics import MeanAveragePrecision
 from .generator import BackboneGen, Head, ListGen, ListState, NeckGen
 from .roi import RoI
 
@@ -57,6 +63,8 @@ class SODa(nn.Module):
         self.roi_blk = RoI(self.hparams.iou_threshold)
         self.cls_loss = nn.CrossEntropyLoss(reduction="none")
         self.box_loss = nn.L1Loss(reduction="none")
+        # soda.py:89-96; a plain attribute, not a submodule: state_dict() is unchanged
+        self.map_metric = MeanAveragePrecision(self.hparams.num_classes)
 
     # ------------------------------------------------------------------ description hooks
     def backbone_cfgs(self) -> ListGen:
@@ -79,6 +87,11 @@ class SODa(nn.Module):
         self.logged[name] = value.detach() if isinstance(value, torch.Tensor) else value
         if sync_dist:
             self._sync_logged.add(name)
+
+    def log_dict(self, dictionary, sync_dist: bool = False, **kwargs) -> None:
+        """Lightning's ``self.log_dict``: ``log`` for every entry."""
+        for name, value in dictionary.items():
+            self.log(name, value, sync_dist=sync_dist, **kwargs)
 
     def synced_logs(self, process_group=None) -> dict:
         """The logged values with the ``sync_dist`` entries averaged over the ranks (Lightning's reduction)."""
@@ -130,14 +143,36 @@ class SODa(nn.Module):
         return loss
 
     def validation_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
-        loss = self._step(batch)
+        preds = self.forward(batch[0][self._rand_start_time():])
+        loss = self._loss(preds, batch[1])
         self.log("val_loss", loss, batch_size=batch[0].shape[1], sync_dist=True)
+        self._map_estimate(preds, batch[1])
         return loss
 
+    def on_validation_epoch_end(self) -> None:
+        self._map_compute()
+
     def test_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
-        loss = self._step(batch)
+        preds = self.forward(batch[0][self._rand_start_time():])
+        loss = self._loss(preds, batch[1])
         self.log("test_loss", loss, batch_size=batch[0].shape[1], sync_dist=True)
+        self._map_estimate(preds, batch[1])
         return loss
+
+    def on_test_epoch_end(self) -> None:
+        self._map_compute()
+
+    def _map_estimate(self, preds: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], labels: torch.Tensor) -> None:
+        # soda.py:294-321 without the per-image boolean masks: padded rows (class -1) are skipped by the kernels
+        anchors, cls_preds, bbox_preds = (p.detach() for p in preds)
+        dets = box.multibox_detection(F.softmax(cls_preds, dim=2), bbox_preds, anchors)
+        self.map_metric.update_padded(dets, labels)
+
+    def _map_compute(self) -> None:
+        # soda.py:283-292
+        result = self.map_metric.compute()
+        self.log_dict({k: result[k] for k in ("map", "map_50", "mar_1", "mar_10", "mar_100")})
+        self.map_metric.reset()
 
     def predict(self, X: torch.Tensor, state: Optional[ListState]) -> Tuple[torch.Tensor, ListState]:
         """Streaming inference for one event frame ``X[2,H,W]`` (soda.py:202-233).
