@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SNN_ABI_VERSION 12
+#define SNN_ABI_VERSION 13
 
 /* neuron kinds for the fused affine+neuron temporal scan */
 enum {
@@ -368,6 +368,13 @@ size_t snn_affine_neuron_bwd_sums_size(int T, int64_t M, int C);
  * 32-bit buffer addressing, fp32 tensors, all T gradients, c_mem in [1/64, 1]) */
 int snn_affine_neuron_bwd_sums_from_state(int neuron, int T, int64_t M, int C, int64_t ldg, const snn_neuron_params* p,
                                           int flags);
+/* host-only: the instance snn_affine_neuron_bwd(neuron, ..., ldg, ..., ldy, ..., sums != NULL iff with_sums, ..., p, flags)
+ * launches, into out[10] = { vec (channels per thread), mode (0 no sums, 1 ordered per-wave slabs, 2 LDS atomics), BUF
+ * (1: buffer-resource addressing), NP (pixel rows per thread), cvb (channel groups per block), gy (channel blocks), gx
+ * (pixel blocks), rpb (pixel rows of P = 256 / cvb pixels per block), 1 if the last pixel row is partial, LDS bytes }.
+ * 0, or 1 for a shape or SNN_SCAN_SUMS_FROM_STATE request the scan would refuse. */
+int snn_affine_neuron_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, int with_sums,
+                               const snn_neuron_params* p, int flags, int64_t* out);
 int snn_affine_neuron_bwd(int neuron, const float* g_out, int64_t ldg, const float* state,
                           const float* y, int64_t ldy, const float* g_vT, const float* g_iT,
                           const float* alpha, const float* beta, int apply_scale,

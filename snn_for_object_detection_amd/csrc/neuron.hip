@@ -1719,6 +1719,38 @@ extern "C" int snn_affine_neuron_bwd_sums_from_state(int neuron, int T, int64_t 
     return sums_from_state_ok(neuron, T, M, C, ldg, p, flags) ? 1 : 0;
 }
 
+// The instance snn_affine_neuron_bwd launches for this call (host-only; the launch path below takes the same bwd_plan and
+// the same BUF / NP choice).  out[10]: vec, mode, BUF, NP, cvb, gy, gx, rpb, partial last pixel row,
+// LDS bytes.  Returns 0, or 1 (message in snn_last_error) for a call snn_affine_neuron_bwd would refuse by its shape or
+// flags alone.
+extern "C" int snn_affine_neuron_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, int with_sums,
+                                          const snn_neuron_params* p, int flags, int64_t* out) {
+    SNN_REQUIRE(out && p, "snn_affine_neuron_bwd_plan: null pointer");
+    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldg >= C, "snn_affine_neuron_bwd_plan: bad shape");
+    const bool yfree = (flags & SNN_SCAN_SUMS_FROM_STATE) != 0;
+    const int rest = flags & ~(SNN_SCAN_SUMS_FROM_STATE | SNN_SCAN_STATE_LOOKBACK);
+    SNN_REQUIRE(!yfree || (with_sums && sums_from_state_ok(neuron, T, M, C, ldg, p, rest)),
+                "snn_affine_neuron_bwd_plan: SNN_SCAN_SUMS_FROM_STATE not covered");
+    const BwdPlan pl = bwd_plan(T, M, C, with_sums != 0);
+    const int64_t ld_max = ldg > ldy ? (ldg > C ? ldg : C) : (ldy > C ? ldy : C);
+    const bool buf = yfree || (pl.vec == 4 && !(rest & SNN_SCAN_WIDE_ADDRESSING) && M * ld_max * 4 < 0x7fffffffLL);
+    int np;
+    if (yfree) np = pl.rpb == 1 ? 1 : (pl.rpb == 2 ? 2 : 3);
+    else np = (buf && pl.rpb == 1) ? 1 : kBwdNP;
+    const int P = kThreads / pl.cvb;
+    out[0] = pl.vec;
+    out[1] = pl.mode;
+    out[2] = buf ? 1 : 0;
+    out[3] = np;
+    out[4] = pl.cvb;
+    out[5] = pl.gy;
+    out[6] = pl.gx;
+    out[7] = pl.rpb;
+    out[8] = (M % P) != 0 ? 1 : 0;
+    out[9] = (int64_t)pl.lds_bytes;
+    return 0;
+}
+
 extern "C" int snn_affine_neuron_bwd(int neuron, const float* g_out, int64_t ldg, const float* state, const float* y,
                                      int64_t ldy, const float* g_vT, const float* g_iT, const float* alpha,
                                      const float* beta, int apply_scale, float* gx, float* g_v0, float* g_i0,

@@ -1366,6 +1366,12 @@ class _AffineNeuron(Function):
         y = _raw_to_cl(y)
         ldy = cl_stride(y)
         T, B, C, H, W = _dims5(y)
+        if (C % 4 == 0 and (y.data_ptr() % (8 if sb else 16) or ldy % 4)
+                and (has_bn or neuron in (_hip.NEURON_SLI, _hip.NEURON_SYNAPSE))):
+            # a channel slice at an offset or pixel stride that is not a multiple of 4 (a split_channels part): the
+            # statistics pass and the reverse scan read y in 4-channel vectors - they get a dense copy
+            y = _raw_dense_cl(y)
+            ldy = C
         M = B * H * W
         st = _stream()
         dev = y.device
@@ -1662,6 +1668,28 @@ class _AffineNeuron(Function):
         if need_y:
             dy = _cl_view(gx)
         return dy, dgamma, dbias, g_v0, g_i0, g_addend, None
+
+
+class BwdPlan(NamedTuple):
+    """The reverse-scan instance snn_affine_neuron_bwd launches (include/snn_hip.h, snn_affine_neuron_bwd_plan)."""
+    vec: int
+    mode: int
+    buf: int
+    np: int
+    cvb: int
+    gy: int
+    gx: int
+    rpb: int
+    partial_row: int
+    lds_bytes: int
+
+
+def affine_neuron_bwd_plan(neuron: int, T: int, M: int, C: int, ldg: int, ldy: int, with_sums: bool, flags: int = 0,
+                           params: Optional[NeuronParams] = None) -> BwdPlan:
+    out = (ctypes.c_int64 * 10)()
+    _hip.call("snn_affine_neuron_bwd_plan", neuron, T, M, C, ldg, ldy, int(bool(with_sums)), params or neuron_params(),
+              flags, ctypes.addressof(out))
+    return BwdPlan(*out)
 
 
 def _expand_state(s: torch.Tensor, shape, dev) -> torch.Tensor:

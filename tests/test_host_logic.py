@@ -210,3 +210,44 @@ def test_profiler_byte_model_of_both_storage_modes():
     lab, _, byts = work_of("snn_conv2d_fwd", first + [6, 0])
     assert lab.startswith("k_conv_first") and byts == 4.0 * N * 240 * 304 * 2 + 2.0 * N * 240 * 304 * 64 + 4.0 * 64 * 9 * 2
     assert work_of("snn_bn_bwd_apply_bf16", [0] * 8 + [T, M, C])[2] == 6.0 * T * M * C
+
+
+def test_reverse_scan_plan_invariants(hip_lib):
+    """snn_affine_neuron_bwd_plan over a grid of (T, M, C): every plan fits the block, covers every pixel and channel,
+    stays inside 64 KiB of LDS, and takes the ordered-slab sums only where the wave combine is defined."""
+    from snn_for_object_detection_amd import _hip
+    from snn_for_object_detection_amd import functional as HF
+    prm = HF.neuron_params()
+    seen = set()
+    for T in (1, 2, 4, 32, 33, 70, 128):
+        for C in (1, 3, 4, 6, 8, 16, 24, 32, 36, 64, 100, 128, 256, 384, 512, 1024):
+            for M in (1, 7, 126, 400, 1425, 5700, 22800, 91200, 364800):
+                for with_sums in (False, True):
+                    pl = HF.affine_neuron_bwd_plan(_hip.NEURON_LIF, T, M, C, C, C, with_sums, 0, prm)
+                    P = 256 // pl.cvb
+                    assert pl.vec == (4 if C % 4 == 0 else 1)
+                    assert 1 <= pl.cvb and pl.cvb * P <= 256 and P >= 1, pl
+                    assert pl.gy * pl.cvb >= C // pl.vec and (pl.gy - 1) * pl.cvb < C // pl.vec, pl
+                    assert pl.gx * pl.rpb * P >= M and (pl.gx - 1) * pl.rpb * P < M, pl      # no idle pixel block
+                    assert pl.partial_row == (1 if M % P else 0)
+                    assert pl.mode == (0 if not with_sums else (1 if pl.mode == 1 else 2))
+                    if pl.mode == 1:
+                        assert (pl.cvb & (pl.cvb - 1)) == 0 or pl.cvb >= 64, pl
+                    slabs = {0: 0, 1: 4, 2: 1}[pl.mode]
+                    assert pl.lds_bytes == slabs * T * pl.cvb * pl.vec * 2 * 4 and pl.lds_bytes <= 64 * 1024, pl
+                    assert pl.np == (1 if (pl.buf and pl.rpb == 1) else 4), pl
+                    assert pl.buf == (1 if pl.vec == 4 and M * C * 4 < 2 ** 31 - 1 else 0), pl
+                    if with_sums:
+                        assert hip_lib.snn_affine_neuron_bwd_sums_size(T, M, C) == pl.gx * T * C * 2
+                    seen.add((pl.vec, pl.mode, pl.np, pl.gy > 1, pl.partial_row))
+    assert {(4, 1, 4, True, 1), (4, 1, 1, True, 1), (1, 2, 4, False, 1), (4, 2, 1, False, 1), (4, 0, 4, False, 0)} <= seen
+    # the forced 64-bit addressing takes the branchy instance; the y-free sums take 1 / 2 / 3 pixel rows per thread
+    assert HF.affine_neuron_bwd_plan(_hip.NEURON_LIF, 32, 1425, 256, 256, 256, True, _hip.SCAN_WIDE_ADDRESSING).buf == 0
+    assert HF.affine_neuron_bwd_plan(_hip.NEURON_LIF, 32, 1425, 256, 256, 256, True, _hip.SCAN_WIDE_ADDRESSING).np == 4
+    for M in (1425, 5700, 22800, 91200):
+        pl = HF.affine_neuron_bwd_plan(_hip.NEURON_LIF, 32, M, 128, 128, 128, True, _hip.SCAN_SUMS_FROM_STATE)
+        assert pl.buf == 1 and pl.np == min(pl.rpb, 3), (M, pl)
+    with pytest.raises(RuntimeError, match="SNN_SCAN_SUMS_FROM_STATE not covered"):
+        HF.affine_neuron_bwd_plan(_hip.NEURON_LI, 32, 5700, 256, 256, 256, True, _hip.SCAN_SUMS_FROM_STATE)
+    with pytest.raises(RuntimeError, match="bad shape"):
+        HF.affine_neuron_bwd_plan(_hip.NEURON_LIF, 32, 5700, 256, 128, 256, True)
