@@ -63,7 +63,6 @@ struct HaloGeom {
     int out_vec;
     double* bn_partial;         // forward statistics partials [t][c][chunk][2] (null: none); chunk = tile of the group
     int OH, OW;                 // k_conv_s2dgrad3 only: size of the produced tensor dx (the strip grid H x W is dy's)
-    int bn_T, bn_tc, bn_fps;    // BNAP: timesteps, T * Cin (distance of the coefficient planes), frames per timestep
     int tiles_x, tiles_img;     // RECT: 4 x 32 pixel tiles per image row, tiles per image
     float x_th;                 // XSP: x holds saved LIF potentials, the operand is z = (x > x_th)
 };
@@ -124,13 +123,6 @@ __device__ __forceinline__ int cell_slot_off(int cell, int slot) { return cell *
 // 4 waves as 2 x 2: a wave owns 64 cells x CO/2 channels (TM = 2 row tiles, TN = CO/64 column tiles of 32 x 32).
 // ABL (tuning builds only, timing experiments with WRONG results): 1 no weight DMA, 2 no per-k-step wait + barrier,
 // 4 no halo prefetch loads, 8 no output stores, 16 no fragment reads of the halo image (one read per k-step instead)
-// BNAP (data gradient behind a train-mode BatchNorm): the operand x is gx, the gradient BEFORE the BatchNorm-backward
-// affine; dy = A[t][c] * gx + B[t][c] * y + C[t][c] (the statement of snn_bn_bwd_apply, t = image / frames per step) is
-// formed when a staging pass has landed - one pass per tap, behind that tap's MFMAs - stored to dy_out for the cells
-// the tile owns (the weight gradient reads it) and split into the LDS image.  The separate apply pass over the layer
-// (12 bytes per element) disappears; coefficients of the <= 3 timesteps a halo can touch are staged in LDS once per block.
-constexpr int BN_NT = 3;      // timesteps of coefficients a block stages
-constexpr int BN_CMAX = 128;  // input channels (K) the BNAP variant supports
 
 // RECT (rows longer than 78 pixels: the halo of a 128-cell strip tile would not fit): a block owns a 4 x 32 pixel
 // rectangle of ONE image instead; the LDS image is its 6 x 34 halo (204 cells, row pitch 34), a row tile of the MFMA is
@@ -146,36 +138,30 @@ constexpr int RTH = 4, RTW = 32, RPITCH = RTW + 2, RCELLS = (RTH + 2) * RPITCH;
 // its spikes - that layer wrote no spike tensor (SNN_SCAN_SPIKES_FROM_VDEC) - and the operand z = (v_dec > x_th) is formed while
 // the halo goes to LDS: ONE exact fp16 piece (1.0 x 2^4 or 0), no low image, the product low(x) * high(w) is not issued (two
 // MFMA products instead of three).  Same bits as the plain kernel on the stored spikes, whose low pieces are zeros.
-template <int CO, bool F16, int ABL = 0, bool BNAP = false, bool RECT = false, bool SBF = false, bool XSP = false>
+template <int CO, bool F16, int ABL = 0, bool RECT = false, bool SBF = false, bool XSP = false>
 __global__ __launch_bounds__(kThreads, 2) void k_conv_halo3(const float* __restrict__ x,
                                                            const unsigned char* __restrict__ wimg,
                                                            float* __restrict__ y, HaloGeom g,
                                                            const float* __restrict__ addend,
-                                                           const float* __restrict__ addend2,
-                                                           const float* __restrict__ bn_y = nullptr,
-                                                           const float* __restrict__ bn_coef = nullptr,
-                                                           float* __restrict__ dy_out = nullptr) {
+                                                           const float* __restrict__ addend2) {
     // CO = 32 (the 32-channel layers of the full-resolution stage): the four waves side by side along the cells, one
     // 32 x 32 tile each
     constexpr int WM = CO == 32 ? 4 : 2, WN = 4 / WM, TM = CO == 32 ? 1 : 2, TN = CO == 32 ? 1 : CO / 64;
     static_assert(CO == 32 || CO == 64 || CO == 128, "channel tile");
-    static_assert(!BNAP || CO >= 64, "the BatchNorm-apply variant covers the 64 / 128-channel tiles");
     constexpr int BTILE = (CO / 32) * 4096;     // bytes of one k-step's weight tile
     constexpr int NDMA = (CO / 32) * 4 / 4;     // 1-KiB LDS-DMA pieces per wave and k-step
     constexpr int ES = SBF ? 2 : 4;             // bytes per activation element in HBM
-    static_assert(!SBF || (!F16 && !BNAP && ABL == 0), "bf16 storage: bf16 MFMA, plain variant");
-    static_assert(!XSP || (F16 && !BNAP && !SBF && ABL == 0), "spikes from potentials: the forward arithmetic, plain variant");
-    constexpr int CF_BYTES = BNAP ? 3 * BN_NT * BN_CMAX * 4 : 0;
+    static_assert(!SBF || (!F16 && ABL == 0), "bf16 storage: bf16 MFMA, plain variant");
+    static_assert(!XSP || (F16 && !SBF && ABL == 0), "spikes from potentials: the forward arithmetic, plain variant");
     // cells the LDS halo image holds: a rectangle tile's halo is 6 x 34 = 204 cells (7 staging passes), not the 288 of the
     // widest strip tile - 37 instead of 45 KiB of LDS for the 32-channel instance, i.e. FOUR instead of three blocks per CU
     // on the 120x152 layers, whose blocks (54 MFMAs per wave) live on latency, not on the matrix pipe
     constexpr int HC = RECT ? (RCELLS + 31) / 32 * 32 : HCELLS;
     constexpr int HP = HC * 64;                        // bytes of one piece image
     constexpr int RED_BYTES = (F16 || SBF) ? 4 * (CO == 128 ? 64 : 32) * 16 : 0;   // statistics: [wave][channels of a wave][2] fp64
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * HP + 2 * BTILE + CF_BYTES + RED_BYTES];   // ONE array
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * HP + 2 * BTILE + RED_BYTES];   // ONE array
     unsigned char* Aimg = smem;                        // [2 pieces][HC][64 B]
     unsigned char* Bimg = smem + 2 * HP;               // [2 buffers][BTILE]
-    [[maybe_unused]] float* Cf = reinterpret_cast<float*>(smem + 2 * HP + 2 * BTILE);   // [3 planes][BN_NT][Cin]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -218,24 +204,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_halo3(const float* __restr
     __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
         reinterpret_cast<char*>(const_cast<float*>(x)) + (int64_t)nb * ipix * g.ldx * ES, 0,
         xbytes > 0x7fffffffLL ? 0x7fffffff : (int)xbytes, 0x00020000);
-    [[maybe_unused]] __amdgpu_buffer_rsrc_t rs_y = rs_x, rs_dy = rs_x;
-    [[maybe_unused]] const int t_lo = BNAP ? nb / g.bn_fps : 0;
-    [[maybe_unused]] int cofs[NPASS];      // BNAP: float offset of (timestep of the cell, channel quad) inside a coefficient plane
-    [[maybe_unused]] unsigned imask = 0;   // BNAP: bit p = the cell of pass p belongs to the tile (its dy is stored)
-    [[maybe_unused]] unsigned vmask = 0;   // BNAP: bit p = the cell of pass p is an image pixel (pad cells stay ZERO: the
-                                           // affine's constant term must not leak into the convolution's zero padding)
-    if constexpr (BNAP) {   // gx, y and dy_out are dense tensors of one layout (host-checked): one set of offsets
-        rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bn_y + (int64_t)nb * ipix * g.ldx), 0,
-                                                 xbytes > 0x7fffffffLL ? 0x7fffffff : (int)xbytes, 0x00020000);
-        rs_dy = __builtin_amdgcn_make_buffer_rsrc(dy_out + (int64_t)nb * ipix * g.ldx, 0,
-                                                  xbytes > 0x7fffffffLL ? 0x7fffffff : (int)xbytes, 0x00020000);
-        for (int idx = tid; idx < 3 * BN_NT * g.Cin; idx += kThreads) {
-            const int pl = idx / (BN_NT * g.Cin), rem = idx - pl * BN_NT * g.Cin;
-            const int k = rem / g.Cin, c = rem - k * g.Cin;
-            const int t = t_lo + k < g.bn_T ? t_lo + k : g.bn_T - 1;
-            Cf[idx] = bn_coef[(int64_t)pl * g.bn_tc + (int64_t)t * g.Cin + c];
-        }
-    }
     unsigned voff[NPASS];
     int awr[NPASS];      // LDS byte offset (inside a piece) this thread writes for pass p
 #pragma unroll
@@ -264,21 +232,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_halo3(const float* __restr
         const int64_t pix = (int64_t)(n - nb) * ipix + (int64_t)yy * g.W + xx;
         voff[p] = ok ? (unsigned)((pix * g.ldx + quad * 4) * ES) : 0x80000000u;   // >= 2 GiB: range check -> zeros
         awr[p] = cell_slot_off(cell, quad >> 1) + (quad & 1) * 8;
-        if constexpr (BNAP) {
-            int ts = ok ? n / g.bn_fps - t_lo : 0;
-            ts = ts < BN_NT ? ts : BN_NT - 1;   // (never taken for host-accepted shapes)
-            cofs[p] = ts * g.Cin + quad * 4;
-            bool mine;
-            if constexpr (RECT) {
-                const int rr = cell / RPITCH, cc = cell - rr * RPITCH;
-                mine = rr >= 1 && rr <= RTH && cc >= 1 && cc <= RTW;
-            } else {
-                const int m = cell - (g.PW + 1);
-                mine = m >= 0 && m < HBM_ && m < g.group_cells - c0;
-            }
-            imask |= (ok && mine) ? 1u << p : 0u;
-            vmask |= ok ? 1u << p : 0u;
-        }
     }
 
     // The wait that closes a k-step DRAINS the vector-memory queue (vmcnt(0)).  Rounds 3's first form counted instead
@@ -348,20 +301,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_halo3(const float* __restr
         else return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, off, 0, 0));
     };
 
-    // BNAP: gx -> dy for one landed pass (the statement of k_bn_bwd_apply, same roundings) and the store of the tile's own cells
-    [[maybe_unused]] f32x4 pfy[2];
-    [[maybe_unused]] auto bn_combine = [&](f32x4& gxv, const f32x4& yv, int p, int chan_floats, bool live) {
-        const int planes = BN_NT * g.Cin;
-        const float* cf = Cf + cofs[p] + chan_floats;
-        const f32x4 ca = *reinterpret_cast<const f32x4*>(cf), cb = *reinterpret_cast<const f32x4*>(cf + planes),
-                    cc = *reinterpret_cast<const f32x4*>(cf + 2 * planes);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) gxv[e] = ca[e] * gxv[e] + cb[e] * yv[e] + cc[e];
-        if (!((vmask >> p) & 1u)) gxv = f32x4{0.f, 0.f, 0.f, 0.f};
-        const unsigned so = (live && ((imask >> p) & 1u)) ? voff[p] + (unsigned)chan_floats * 4u : 0x80000000u;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, gxv), rs_dy, (int)so, 0, 0);
-    };
-
     f32x16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -422,15 +361,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_halo3(const float* __restr
     dma_b(0, 0);
 #pragma unroll
     for (int p = 0; p < NPASS; ++p) pf[p] = load_pass((int)voff[p]);
-    if constexpr (BNAP) {
-        f32x4 py[NPASS];
-#pragma unroll
-        for (int p = 0; p < NPASS; ++p)
-            py[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_y, (int)voff[p], 0, 0));
-        __syncthreads();   // the coefficient planes are staged
-#pragma unroll
-        for (int p = 0; p < NPASS; ++p) bn_combine(pf[p], py[p], p, 0, true);
-    }
     store_halo();
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
@@ -449,35 +379,19 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_halo3(const float* __restr
             __builtin_amdgcn_sched_barrier(0);
             // one staging pass of the next chunk's halo per tap (none when there is no next chunk)
             if constexpr (!(ABL & 4)) {
-                if (BNAP || more) pf[tap] = load_pass(more ? (int)(voff[tap] + (unsigned)cbytes) : (int)0x80000000u);
+                if (more) pf[tap] = load_pass((int)(voff[tap] + (unsigned)cbytes));
             }
-            if constexpr (BNAP)
-                pfy[tap & 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                              rs_y, more ? (int)(voff[tap] + (unsigned)cbytes) : (int)0x80000000u, 0, 0));
             __builtin_amdgcn_sched_barrier(0);
             const int kh = tap / 3, kw = tap - 3 * kh;
             kstep((kh - 1) * pitch + (kw - 1), Bimg + cur * BTILE);
             // this wave's share of the next weight tile has landed (the queue is drained, see above); the barrier makes every
             // wave's share visible and retires this step's reads of the current buffer
             // (lgkmcnt(0): this wave's fragment reads have really left the LDS before another wave may overwrite them)
-            if constexpr (BNAP) {
-                // the pass requested during the PREVIOUS tap has landed (it is older than this tap's weight DMA, which this
-                // k-step's MFMAs have covered): gx -> dy in place, dy stored for the tile's own cells.  Behind it the queue
-                // holds this tap's two loads and that store: the weight DMA is the fourth-youngest operation.
-                const int pp = tap >= 1 ? tap - 1 : 0;   // (static after unrolling)
-                __builtin_amdgcn_sched_barrier(0);       // not above the MFMAs: its wait would expose this tap's DMA
-                if (tap >= 1) bn_combine(pf[pp], pfy[pp & 1], pp, more ? (chunk + 1) * 32 : 0, more);
-                __builtin_amdgcn_sched_barrier(0);
-                // (this variant drains the queue: besides the two loads it also queues the dy STORE of the previous pass, which
-                // is out of range - answered at once, see above - for every pass outside the tile's own cells, so a
-                // counted wait cannot tell whether the weight DMA has landed.  The variant is off by default.)
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            } else if constexpr (ABL & 2) asm volatile("" ::: "memory");
+            if constexpr (ABL & 2) asm volatile("" ::: "memory");
             else if constexpr (ABL & 4) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
         if (more) {   // every wave is past its last read of this chunk's halo image: swap in the next one
-            if constexpr (BNAP) bn_combine(pf[8], pfy[0], 8, (chunk + 1) * 32, true);
             store_halo();
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
@@ -607,7 +521,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_halo3(const float* __restr
             qsum[q] += partner32(qsum[q]);
         }
         // (a region of its own, not the staging rows: no barrier until the partials are written)
-        double* red = reinterpret_cast<double*>(smem + 2 * HP + 2 * BTILE + CF_BYTES);   // [wave][LPR * 4 channels][2]
+        double* red = reinterpret_cast<double*>(smem + 2 * HP + 2 * BTILE);   // [wave][LPR * 4 channels][2]
         if (lane >= 48 && lane < 48 + LPR) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -1019,7 +933,6 @@ extern "C" int snn_conv3x3_s2_dgrad(const float* dy, int64_t lddy, const void* w
                 (!addend2 || (ld_addend2 % 4 == 0 && out_aligned(addend2, sbf)));
     g.bn_partial = nullptr;
     g.x_th = 0.0f;
-    g.bn_T = g.bn_tc = 0; g.bn_fps = 1;
     dim3 grid((unsigned)((int64_t)g.tiles_per_xcd * 8 * g.ntiles_n));
     const unsigned char* wi = static_cast<const unsigned char*>(wt_image);
     if (sbf && rect)
@@ -1062,63 +975,6 @@ extern "C" int snn_weight_frag_image_batched(const float* flat_src, void* flat_d
         hipLaunchKernelGGL(k_weight_frag_image<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, flat_src,
                            static_cast<unsigned char*>(flat_dst), table, flip);
     SNN_CHECK_LAUNCH("snn_weight_frag_image_batched");
-    return 0;
-}
-
-extern "C" int snn_conv3x3_halo_bn_supported(int64_t N, int H, int W, int Cin, int Cout, int frames_per_step) {
-    // Cin: channels of gx / y / dy (the K dimension), Cout: channels of dx
-    if (halo_mode(N, H, W, Cin, Cout) != 1 || Cin > BN_CMAX || frames_per_step <= 0 || N % frames_per_step != 0) return 0;
-    if (Cout != 64 && Cout != 128) return 0;   // ONE channel tile: the block that computes dx also stores dy
-    // images a 288-cell halo can touch, and the timesteps they belong to: at most BN_NT
-    const int64_t images = HCELLS / ((int64_t)(H + 1) * (W + 1)) + 2;
-    return ((images + frames_per_step - 1) / frames_per_step + 1 <= BN_NT) ? 1 : 0;
-}
-
-extern "C" int snn_conv3x3_halo_bn(const float* gx, const float* y, const float* coef, int frames_per_step, float* dy_out,
-                                   const void* wt_image, float* dx, int64_t lddx, int64_t N, int H, int W, int Cin,
-                                   int Cout, const float* addend, int64_t ld_addend, const float* addend2,
-                                   int64_t ld_addend2, void* stream) {
-    SNN_REQUIRE(gx && y && coef && dy_out && wt_image && dx, "snn_conv3x3_halo_bn: null pointer");
-    SNN_REQUIRE(snn_conv3x3_halo_bn_supported(N, H, W, Cin, Cout, frames_per_step),
-                "snn_conv3x3_halo_bn: shape not covered (N %lld, %dx%d, %d -> %d channels, %d frames per step; ask "
-                "snn_conv3x3_halo_bn_supported)", (long long)N, H, W, Cin, Cout, frames_per_step);
-    SNN_REQUIRE(lddx >= Cout, "snn_conv3x3_halo_bn: dx pixel stride smaller than channel count");
-    SNN_REQUIRE(aligned16(gx) && aligned16(y) && aligned16(dy_out) && aligned16(wt_image) && aligned16(coef),
-                "snn_conv3x3_halo_bn: operands must be 16-byte aligned");
-    SNN_REQUIRE(!addend || ld_addend >= Cout, "snn_conv3x3_halo_bn: addend pixel stride smaller than channel count");
-    SNN_REQUIRE(!addend2 || ld_addend2 >= Cout, "snn_conv3x3_halo_bn: addend2 pixel stride smaller than channel count");
-    SNN_REQUIRE((int64_t)4 * H * W * Cin * 4 < 0x7fffffffLL, "snn_conv3x3_halo_bn: four images must span less than 2 GiB");
-    HaloGeom g;
-    g.ldx = Cin; g.ldy = lddx; g.ld_add = ld_addend; g.ld_add2 = ld_addend2;     // gx, y, dy_out: dense [N][H][W][Cin]
-    g.N = (int)N; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout;
-    g.PW = W + 1; g.PH = H + 1;
-    g.G = (int)N;
-    const int64_t group_cells = (int64_t)g.G * g.PH * g.PW;
-    g.group_cells = (int)group_cells;
-    g.tiles_per_group = (int)snn_ceil_div(group_cells, HBM_);
-    g.tiles = g.tiles_per_group;
-    const int co_tile = Cout % 128 == 0 ? 128 : 64;
-    g.ntiles_n = Cout / co_tile;
-    // every channel tile would store the same dy: only ONE may, so the variant is for layers that fit one tile
-    SNN_REQUIRE(g.ntiles_n == 1, "snn_conv3x3_halo_bn: %d output channels need more than one channel tile", Cout);
-    g.tiles_per_xcd = (int)snn_ceil_div(g.tiles, 8);
-    g.magic_pw = magic_u32(g.PW); g.magic_ph = magic_u32(g.PH);
-    g.out_vec = (lddx % 4 == 0) && aligned16(dx) && (!addend || (ld_addend % 4 == 0 && aligned16(addend))) &&
-                (!addend2 || (ld_addend2 % 4 == 0 && aligned16(addend2)));
-    g.bn_partial = nullptr;
-    g.x_th = 0.0f;
-    g.OH = H; g.OW = W;
-    g.bn_fps = frames_per_step; g.bn_T = (int)(N / frames_per_step); g.bn_tc = g.bn_T * Cin;
-    g.tiles_x = g.tiles_img = 0;
-    dim3 grid((unsigned)((int64_t)g.tiles_per_xcd * 8));
-    const unsigned char* wi = static_cast<const unsigned char*>(wt_image);
-    if (co_tile == 128)
-        hipLaunchKernelGGL((k_conv_halo3<128, false, 0, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, gx, wi, dx, g,
-                           addend, addend2, y, coef, dy_out);
-    else
-        hipLaunchKernelGGL((k_conv_halo3<64, false, 0, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, gx, wi, dx, g,
-                           addend, addend2, y, coef, dy_out);
-    SNN_CHECK_LAUNCH("snn_conv3x3_halo_bn");
     return 0;
 }
 
@@ -1175,7 +1031,6 @@ static int conv3x3_halo_impl(const float* x, int64_t ldx, const void* w_image, f
                 (!addend2 || (ld_addend2 % 4 == 0 && out_aligned(addend2, sbf)));
     g.bn_partial = bn_partial;
     g.OH = H; g.OW = W;
-    g.bn_T = g.bn_tc = 0; g.bn_fps = 1;
     g.x_th = x_th;
     if (bn_partial) bn_layout[0] = g.tiles_per_group;   // every slot of every step is written: rows_per_chunk stays 0
     dim3 grid((unsigned)((int64_t)g.tiles_per_xcd * 8 * g.ntiles_n));
@@ -1184,11 +1039,11 @@ static int conv3x3_halo_impl(const float* x, int64_t ldx, const void* w_image, f
 #define SNN_HALO_LAUNCH(CO_, F16_)                                                                                   \
     do {                                                                                                              \
         if (rect)                                                                                                     \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, F16_, 0, false, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, wi, \
-                               y, g, addend, addend2, nullptr, nullptr, nullptr);                                     \
+            hipLaunchKernelGGL((k_conv_halo3<CO_, F16_, 0, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, wi, \
+                               y, g, addend, addend2);                                                                \
         else                                                                                                          \
             hipLaunchKernelGGL((k_conv_halo3<CO_, F16_>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, wi, y, g, addend, \
-                               addend2, nullptr, nullptr, nullptr);                                                   \
+                               addend2);                                                                              \
     } while (0)
 #ifdef SNN_TUNING
     if (const char* e = snn_tuning_env("SNN_HALO_ABL")) {   // timing experiments (tools/halo_abl.py): WRONG results
@@ -1207,11 +1062,11 @@ static int conv3x3_halo_impl(const float* x, int64_t ldx, const void* w_image, f
 #define SNN_HALO_LAUNCH_X(CO_)                                                                                       \
     do {                                                                                                              \
         if (rect)                                                                                                     \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, true, 0, false, true, false, true>), grid, dim3(kThreads), 0,          \
-                               (hipStream_t)stream, x, wi, y, g, addend, addend2, nullptr, nullptr, nullptr);          \
+            hipLaunchKernelGGL((k_conv_halo3<CO_, true, 0, true, false, true>), grid, dim3(kThreads), 0,              \
+                               (hipStream_t)stream, x, wi, y, g, addend, addend2);                                    \
         else                                                                                                          \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, true, 0, false, false, false, true>), grid, dim3(kThreads), 0,         \
-                               (hipStream_t)stream, x, wi, y, g, addend, addend2, nullptr, nullptr, nullptr);          \
+            hipLaunchKernelGGL((k_conv_halo3<CO_, true, 0, false, false, true>), grid, dim3(kThreads), 0,             \
+                               (hipStream_t)stream, x, wi, y, g, addend, addend2);                                    \
     } while (0)
         if (co_tile == 128) SNN_HALO_LAUNCH_X(128);
         else if (co_tile == 64) SNN_HALO_LAUNCH_X(64);
@@ -1224,11 +1079,11 @@ static int conv3x3_halo_impl(const float* x, int64_t ldx, const void* w_image, f
 #define SNN_HALO_LAUNCH_S(CO_)                                                                                       \
     do {                                                                                                              \
         if (rect)                                                                                                     \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, false, 0, false, true, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, \
-                               wi, y, g, addend, addend2, nullptr, nullptr, nullptr);                                 \
+            hipLaunchKernelGGL((k_conv_halo3<CO_, false, 0, true, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, \
+                               wi, y, g, addend, addend2);                                                            \
         else                                                                                                          \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, false, 0, false, false, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, \
-                               x, wi, y, g, addend, addend2, nullptr, nullptr, nullptr);                              \
+            hipLaunchKernelGGL((k_conv_halo3<CO_, false, 0, false, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, \
+                               x, wi, y, g, addend, addend2);                                                         \
     } while (0)
         if (co_tile == 128) SNN_HALO_LAUNCH_S(128);
         else if (co_tile == 64) SNN_HALO_LAUNCH_S(64);

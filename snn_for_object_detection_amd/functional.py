@@ -190,45 +190,7 @@ def _side_stream(device) -> "torch.cuda.Stream":
     return st
 
 
-# Independent sub-networks (the detection heads behind the ``Return`` taps, generator.Head) CAN run on auxiliary streams
-# beside the main stream: the 30x38 head then overlaps the latency-bound 15x19 / 8x10 neck stages, forward and - because
-# autograd runs a node's backward on the stream of its forward - backward.  Built, bit-identical (tests/test_gpu_model.py)
-# and measured in round 4: NOT faster - same-call A/B, three rounds: 23.37 / 23.15 / 23.24 ms with one head stream
-# against 23.11 / 23.01 / 22.95 without, 22.97 with two (tools/ab.sh): what runs beside a kernel that fills the CUs only
-# takes its share of them, and the cross-stream events cost more than the launch tails they fill.  So: OFF unless
-# SNN_HEAD_STREAMS=<n> asks for n streams.
-HEAD_STREAMS = int(os.environ.get("SNN_HEAD_STREAMS", "0") or 0)   # heads (largest maps first) with a stream of their own
-USE_HEAD_STREAMS = HEAD_STREAMS > 0
-_AUX_STREAMS = {}   # device -> [streams], probed like the weight-gradient stream
-_AUX_HOME = {}      # device -> the stream the auxiliary streams run beside (the "main" stream of the step)
-
-
-def aux_streams(device, n: int) -> List["torch.cuda.Stream"]:
-    """``n`` streams that really run beside the current stream (and beside the weight-gradient stream)."""
-    have = _AUX_STREAMS.setdefault(device, [])
-    if len(have) < n:
-        main = torch.cuda.current_stream(device)
-        _AUX_HOME[device] = main
-        while len(have) < n:
-            have.append(concurrent_stream(main, avoid=tuple(_SIDE_STREAMS.values()) + tuple(have)))
-    return have[:n]
-
-
-def on_aux_stream(device=None) -> bool:
-    """True while the current stream is one of the auxiliary streams (weight gradients then run inline on it: the
-    side-stream bookkeeping below assumes ONE main stream)."""
-    cur = torch.cuda.current_stream(device)
-    return any(cur.cuda_stream == s.cuda_stream for ss in _AUX_STREAMS.values() for s in ss)
-
-
-def aux_streams_sync() -> None:
-    """Make the current stream wait for everything queued on the auxiliary streams (weight gradients of the heads are
-    written there; autograd joins only the streams of gradient-accumulation leaves)."""
-    for dev, ss in _AUX_STREAMS.items():
-        cur = torch.cuda.current_stream(dev)
-        for s in ss:
-            if s.cuda_stream != cur.cuda_stream:
-                cur.wait_stream(s)
+USE_HEAD_STREAMS = False   # bench.py saves and restores it around its profiled steps; nothing else reads it
 
 
 # Operands of a side-stream kernel are kept alive HERE until the main stream has waited for that kernel, instead of
@@ -255,16 +217,10 @@ def _side_hold(side, *tensors) -> None:
 
 
 def wgrad_stream_sync() -> None:
-    """Make the current stream wait for every weight-gradient kernel queued on the side stream (and on the auxiliary
-    streams of the detection heads)."""
+    """Make the current stream wait for every weight-gradient kernel queued on the side stream."""
     _SIDE_PENDING.clear()
     for dev, st in _SIDE_STREAMS.items():
         torch.cuda.current_stream(dev).wait_stream(st)
-    aux_streams_sync()
-
-
-def _wgrad_on_side() -> bool:
-    return USE_WGRAD_STREAM and not (_AUX_STREAMS and on_aux_stream())
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -525,12 +481,9 @@ class GradAccumulator:
     convolution that runs for the fanned-out tensor add the gradients other branches have already produced
     in its epilogue (``snn_conv2d_dgrad(addend=...)``) instead of a separate add pass afterwards."""
 
-    __slots__ = ("deposits", "result", "fused", "outer", "exclusive", "grad_in_slot", "marks")
+    __slots__ = ("deposits", "result", "fused", "outer", "exclusive", "grad_in_slot")
 
     def __init__(self):
-        self.marks = {}       # key (or "result") -> (stream, event): where and when that tensor was produced - consulted
-        #                       only while auxiliary streams exist (the consumers of a Return tap run on different streams,
-        #                       and these tensors travel behind autograd's back)
         self.deposits = {}    # alias index -> gradient produced for that alias by a pass-through consumer
         self.result = None    # dx written by the fusing convolution
         self.fused = {}       # alias index -> deposit that went into ``result``
@@ -545,32 +498,9 @@ class GradAccumulator:
             self.deposits[key] = g
             if exclusive:
                 self.exclusive.add(key)
-            if _AUX_STREAMS:
-                self.marks[key] = _stream_mark()
 
     def set_result(self, dx: torch.Tensor) -> None:
         self.result = dx
-        if _AUX_STREAMS:
-            self.marks["result"] = _stream_mark()
-
-
-def _stream_mark():
-    cur = torch.cuda.current_stream()
-    ev = torch.cuda.Event()
-    ev.record(cur)
-    return cur, ev
-
-
-def _await_mark(acc: "GradAccumulator", key, t: Optional[torch.Tensor]) -> None:
-    """The current stream waits for the producer of a tensor handed over through a GradAccumulator on another stream."""
-    mark = acc.marks.get(key) if _AUX_STREAMS else None
-    if mark is None:
-        return
-    cur = torch.cuda.current_stream()
-    if mark[0].cuda_stream != cur.cuda_stream:
-        cur.wait_event(mark[1])
-        if t is not None:
-            t.record_stream(cur)   # allocated on the producer's stream, read by a kernel of this one
 
 
 def _acc_of(x):
@@ -586,7 +516,7 @@ def _slot_of(param) -> Optional[GradSlot]:
 
 
 # ------------------------------------------------------------------------------------------- conv
-def _dgrad_accumulate(acc, gy, ldg, wt, x, geom, st, prec, wt_split=None, wt_image=None, pend=None):
+def _dgrad_accumulate(acc, gy, ldg, wt, x, geom, st, prec, wt_split=None, wt_image=None):
     """Data gradient of a convolution with the gradient accumulation of its input folded into the epilogue
     (up to two addends; see ``GradAccumulator``).  ``wt`` is the transposed weight ``[Cin][KH][KW][Cout]``."""
     T, B, Cin, H, W, Cout, KH, KW, Ho, Wo, stride, pad = geom
@@ -596,7 +526,6 @@ def _dgrad_accumulate(acc, gy, ldg, wt, x, geom, st, prec, wt_split=None, wt_ima
     if acc is not None and acc[0].result is None and acc[0].deposits:
         # another branch of the block already produced its gradient for this tensor: add it here
         key, other = next(iter(acc[0].deposits.items()))
-        _await_mark(acc[0], key, other)
         other = _raw_to_cl(other)
         if tuple(other.shape) == dx_shape:
             addend, ld_add = other.data_ptr(), cl_stride(other)
@@ -608,7 +537,6 @@ def _dgrad_accumulate(acc, gy, ldg, wt, x, geom, st, prec, wt_split=None, wt_ima
         o_acc, o_key = acc[0].outer
         if o_acc.result is None and len(o_acc.deposits) == 1 and o_key not in o_acc.deposits:
             key2, other2 = next(iter(o_acc.deposits.items()))
-            _await_mark(o_acc, key2, other2)
             other2 = _raw_to_cl(other2)
             if tuple(other2.shape) == dx_shape:
                 addend2, ld_add2 = other2.data_ptr(), cl_stride(other2)
@@ -625,20 +553,11 @@ def _dgrad_accumulate(acc, gy, ldg, wt, x, geom, st, prec, wt_split=None, wt_ima
         # a sibling convolution already produced (its gradient + the fused deposits) for this tensor: add
         # that here and become the accumulated result (two convolutions on one input: the C2f split)
         prev = acc[0].result
-        _await_mark(acc[0], "result", prev)
         addend, ld_add = prev.data_ptr(), cl_stride(prev)
         chained = True
     if dx is None:
         dx = _new_cl((T, B), Cin, H, W, x)
-    if pend is not None:
-        # (gy is gx here) dy = A*gx + B*y + C inside the halo-resident kernel, stored to pend[1] for the weight gradient
-        rec, dy_out = pend
-        if wt_image is None:
-            wt_image = _frag_image(wt, Cin, Cout, 1, _hip.PREC_BF16X3)
-        _hip.call("snn_conv3x3_halo_bn", rec.gx.data_ptr(), rec.y.data_ptr(), rec.coef.data_ptr(), B, dy_out.data_ptr(),
-                  wt_image.data_ptr(), dx.data_ptr(), cl_stride(dx), T * B, H, W, Cout, Cin, addend, ld_add, addend2, ld_add2,
-                  st)
-    elif (prec in _HALO_BWD_PRECS and _halo_operand_ok(gy.data_ptr(), ldg, prec == _hip.PREC_BF16S) and USE_HALO_CONV
+    if (prec in _HALO_BWD_PRECS and _halo_operand_ok(gy.data_ptr(), ldg, prec == _hip.PREC_BF16S) and USE_HALO_CONV
             and (KH, KW, stride, pad) == (3, 3, 2, 1)
             and _hip.query("snn_conv3x3_s2_dgrad_supported", T * B, H, W, Cin, Ho, Wo, Cout)):
         # stride 2: all four phase classes of dx from ONE staged pass over dy (k_conv_s2dgrad3)
@@ -741,11 +660,6 @@ class PendingBnApply(NamedTuple):
 
 _PENDING_APPLY = {}   # gx.data_ptr() -> PendingBnApply
 USE_DEFERRED_BN_APPLY = not os.environ.get("SNN_NO_DEFERRED_BN_APPLY")   # tuning / bisecting aid
-# The same inside the halo-resident DATA gradient (snn_conv3x3_halo_bn) is built and parity-tested but OFF by default:
-# measured (rocprofv3, profiles/r03_*) the fused kernel takes 390 us where data gradient + apply take ~300 us on the
-# 64-channel layers (both are near the HBM rate there and the fused form reads y through the halo overlap as well) and
-# 144 vs ~117 us on the 128-channel ones (the per-tap combine sits in front of every k-step's barrier).  DESIGN section 5.
-USE_DEFERRED_BN_APPLY_DGRAD = bool(os.environ.get("SNN_DEFERRED_BN_APPLY_DGRAD"))
 
 
 def reset_backward_state() -> None:
@@ -761,18 +675,14 @@ def _apply_pending(pend: PendingBnApply) -> None:
 
 
 def _wgrad_bn_ok(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> bool:
-    """The convolution's backward can apply the BatchNorm-backward affine itself: its weight gradient when nothing else
-    needs dy (the event-frame layer), or its halo-resident data gradient (which also leaves dy for the weight gradient)."""
-    if not (USE_DEFERRED_BN_APPLY and weight.requires_grad and x.dim() == 5):
+    """The convolution's backward can apply the BatchNorm-backward affine itself: in its weight gradient, when nothing
+    else needs dy (the event-frame layer)."""
+    if not (USE_DEFERRED_BN_APPLY and weight.requires_grad and x.dim() == 5) or x.requires_grad:
         return False
     T, B, Cin, H, W = x.shape
     Cout, _, KH, KW = weight.shape
     Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-    if not x.requires_grad:
-        return bool(_hip.query("snn_conv2d_wgrad_bn_supported", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad))
-    return (USE_DEFERRED_BN_APPLY_DGRAD and USE_HALO_CONV and (KH, KW, stride, pad) == (3, 3, 1, 1)
-            and _backward_precision == "bf16x3"
-            and bool(_hip.query("snn_conv3x3_halo_bn_supported", T * B, H, W, Cout, Cin, B)))
+    return bool(_hip.query("snn_conv2d_wgrad_bn_supported", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad))
 
 
 class _Conv2d(Function):
@@ -867,7 +777,7 @@ class _Conv2d(Function):
                 # dy is formed while the weight-gradient kernel reads gx and y: no apply pass, no dy tensor
                 splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ctx.prec)
                 main = torch.cuda.current_stream()
-                on_side = _wgrad_on_side()
+                on_side = USE_WGRAD_STREAM
                 stream = _side_stream(x.device) if on_side else main
                 if on_side:
                     _side_retire(main, WGRAD_SIDE_DEPTH)
@@ -880,13 +790,7 @@ class _Conv2d(Function):
                 if on_side:
                     _side_hold(stream, x, pend.gx, pend.y, pend.coef)
                 return None, None, None, None, None, None, None, None, None, None
-            fused_dgrad = (ctx.needs_input_grad[0] and ctx.prec == _hip.PREC_BF16X3 and USE_HALO_CONV
-                           and (KH, KW, stride, pad) == (3, 3, 1, 1) and pend.dims == (T, B, Cout, Ho, Wo)
-                           and is_channels_last(pend.y)
-                           and _hip.query("snn_conv3x3_halo_bn_supported", T * B, H, W, Cout, Cin, B))
-            if not fused_dgrad:
-                _apply_pending(pend)   # this convolution takes a materialised dy after all
-                pend = None
+            _apply_pending(pend)   # this convolution takes a materialised dy after all
         if ctx.needs_input_grad[0]:
             wref = ctx.weight_ref
             wt16 = wt_img = None
@@ -898,15 +802,7 @@ class _Conv2d(Function):
             else:
                 wt = torch.empty((Cin, KH, KW, Cout), device=x.device, dtype=_F32)
                 _hip.call("snn_weight_transpose", w_ohwi.data_ptr(), wt.data_ptr(), Cout, KH, KW, Cin, st)
-            if pend is not None:
-                # dy is formed inside the data-gradient kernel from (gx, y, coef) and left in `gy_new` for the weight gradient
-                gy_new = torch.empty_like(pend.gx)
-                dx = _dgrad_accumulate(ctx.acc, gy, ldg, wt, x, ctx.geom, st, ctx.prec, wt_split=wt16, wt_image=wt_img,
-                                       pend=(pend, gy_new))
-                gy = _cl_view(gy_new)
-                ldg = cl_stride(gy)
-            else:
-                dx = _dgrad_accumulate(ctx.acc, gy, ldg, wt, x, ctx.geom, st, ctx.prec, wt_split=wt16, wt_image=wt_img)
+            dx = _dgrad_accumulate(ctx.acc, gy, ldg, wt, x, ctx.geom, st, ctx.prec, wt_split=wt16, wt_image=wt_img)
         if ctx.needs_input_grad[1]:
             splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ctx.prec)
             xw, ldxw, x_th = x, ldx, ctx.x_th
@@ -921,7 +817,7 @@ class _Conv2d(Function):
                 else:
                     _hip.call("snn_conv2d_wgrad", xw.data_ptr(), ldxw, gy.data_ptr(), ldg, dst_ptr, T * B, H, W, Cin, Ho, Wo,
                               Cout, KH, KW, stride, pad, accumulate, ws_.data_ptr(), splitk, ctx.prec, stream_ptr)
-            if ctx.slot is not None and _wgrad_on_side():
+            if ctx.slot is not None and USE_WGRAD_STREAM:
                 # gradient goes straight into the flat buffer: nothing downstream in autograd needs it, so
                 # the kernel runs on the side stream, concurrently with the data-gradient chain
                 main, side = torch.cuda.current_stream(), _side_stream(x.device)
@@ -1021,7 +917,7 @@ class _ComposedConv1x1(Function):
             slot1, slot2 = ctx.slots
             slotted = slot1 is not None and slot2 is not None
             splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, H, W, C2, 1, 1, 1, 0, ctx.prec)
-            side_ok = slotted and _wgrad_on_side()
+            side_ok = slotted and USE_WGRAD_STREAM
             main = torch.cuda.current_stream()
             stream = _side_stream(x.device) if side_ok else main
             if side_ok:
@@ -1215,7 +1111,7 @@ class _SiblingConv1x1(Function):
             if x_th is not None and not _spikes_wgrad_ok(x.data_ptr(), ldx, gy.data_ptr(), ldg):
                 xw, x_th = _spikes_dense(x, x_th), None   # (same bits: the plain kernel on the stored spikes)
                 ldxw = cl_stride(xw)
-            side_ok = slotted and _wgrad_on_side()
+            side_ok = slotted and USE_WGRAD_STREAM
             main = torch.cuda.current_stream()
             stream = _side_stream(x.device) if side_ok else main
             if side_ok:
@@ -1903,7 +1799,6 @@ class _Fanout(Function):
         if acc.result is not None:
             # a data-gradient convolution already holds (its own + the fused deposits'); add only what is missing
             total = acc.result
-            _await_mark(acc, "result", total)   # (it may have been written on another stream than this node's)
             for k, g in enumerate(gs):
                 if g is None:
                     continue
@@ -1935,7 +1830,6 @@ class _Fanout(Function):
         acc.deposits.clear()
         acc.fused.clear()
         acc.exclusive.clear()
-        acc.marks.clear()
         acc.result = None
         if ctx.outer is not None:
             ctx.outer[0].deposit(ctx.outer[1], total)

@@ -73,7 +73,7 @@ def _family(name: str, bf16s: bool) -> str:
     if base == "k_conv_gather":  # <BN, WM, WN, DGRAD, VEC, ...>: the first five arguments, as profiler.py labels them
         t = re.search(r"k_conv_gather<([^>]*)>", name)
         return f"k_conv_gather<{', '.join(a.strip() for a in t.group(1).split(',')[:5])}>" if t else base
-    if base == "k_conv_halo3":  # <CO, F16, ABL, BNAP>: forward (fp16 pieces) or data gradient, as profiler.py labels them
+    if base == "k_conv_halo3":  # <CO, F16, ABL, RECT, SBF, XSP>: forward (fp16 pieces) or data gradient, as profiler.py labels them
         t = re.search(r"k_conv_halo3<(\d+), (true|false)", name)
         if t and bf16s:
             return f"k_conv_halo3<{t.group(1)}, bf16s>"   # one instance serves forward and data gradient
