@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SNN_ABI_VERSION 14
+#define SNN_ABI_VERSION 15
 
 /* neuron kinds for the fused affine+neuron temporal scan */
 enum {
@@ -209,6 +209,21 @@ int snn_conv2d_wgrad_bn(const float* x, int64_t ldx, const float* gx, int64_t ld
  * (Cout channels), Ho = (H-1)/2 + 1; addend / addend2 as for snn_conv2d_dgrad.  bf16 x 3 arithmetic, or bf16 storage.
  * Covers Cout % 32 == 0, Cin % 64 == 0, any width (dy rows of up to 157 cells as padded strips, longer ones as rectangles). */
 int snn_conv3x3_s2_dgrad_supported(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout);
+/* Host-only plan queries of the halo-resident kernels: they read the plan function the launch reads.
+ *   snn_conv3x3_halo_plan : the grid snn_conv3x3_halo launches for the shape (frames_per_step > 0: with statistics
+ *       partials, tiles never straddle two timesteps; <= 0: without).  snn_conv3x3_s2_dgrad_plan : the same for
+ *       snn_conv3x3_s2_dgrad (arguments as snn_conv3x3_s2_dgrad_supported).  out[7] = { mode (1 padded-strip tiles of
+ *       128 cells, 2 rectangles of 4 x 32 pixels), output channels per block (32, 64, 128), tiles, tiles per group (=
+ *       per timestep with statistics), tiles per XCD share, channel tiles, blocks (whole groups of 8: the blocks past the
+ *       last tile return at once) }.  Return 0, or 1 (out[0] = 0) for a shape the launch would refuse.
+ *   snn_conv2d_wgrad_halo_plan : the halo-resident weight-gradient plan snn_conv2d_wgrad runs for a 3x3 / pad 1 layer on a
+ *       device with num_cu compute units (0: the current device's; 256 without one).  out[16] = { ok (0: the implicit
+ *       GEMM takes the shape), R, CW (patch rows / columns), wco, wk (waves over output channels / over K-steps), nks
+ *       (16-pixel K-steps per patch), npr, npc (patches per image column / row), patches, splits, pps (patches per
+ *       split), HR, HC (halo rows / columns), HWD (LDS row pitch in pixels), tiles_co, tiles_ci }.  Returns 0. */
+int snn_conv3x3_s2_dgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int* out);
+int snn_conv3x3_halo_plan(int64_t N, int H, int W, int Cin, int Cout, int frames_per_step, int* out);
+int snn_conv2d_wgrad_halo_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int stride, int num_cu, int* out);
 int snn_conv3x3_s2_dgrad(const float* dy, int64_t lddy, const void* wt_image, float* dx, int64_t lddx, int64_t N, int H, int W,
                          int Cin, int Ho, int Wo, int Cout, const float* addend, int64_t ld_addend, const float* addend2,
                          int64_t ld_addend2, int precision /* SNN_PREC_BF16X3 | SNN_PREC_BF16S */, void* stream);

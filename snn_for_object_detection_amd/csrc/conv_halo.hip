@@ -869,7 +869,8 @@ static int halo_mode(int64_t N, int H, int W, int Cin, int Cout) {
 }
 static bool halo_shape_ok(int64_t N, int H, int W, int Cin, int Cout) { return halo_mode(N, H, W, Cin, Cout) != 0; }
 
-// strip tiles need the tile and the PW + 1 cells behind it inside the staged halo; wider rows take 4 x 32 rectangles
+// strip tiles need the tile and the PW + 1 cells behind it inside the staged halo (cells 0 .. 128 + PW of it, one spare):
+// 128 + (Wo + 1) + 2 <= HCELLS, so Wo = 157 is the widest strip row; wider rows take 4 x 32 rectangles
 static bool s2dgrad_rect(int Wo) { return 128 + (Wo + 1) + 2 > HCELLS; }
 static bool s2dgrad_shape_ok(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout) {
     // Cin: the layer's input channels (dx), Cout: its output channels (dy, the K dimension)
@@ -879,6 +880,81 @@ static bool s2dgrad_shape_ok(int64_t N, int H, int W, int Cin, int Ho, int Wo, i
     if (s2dgrad_rect(Wo)) return N * snn_ceil_div(Ho, RTH) * snn_ceil_div(Wo, RTW) < 0x7fffffffLL;   // rectangles: any width
     if (N * (int64_t)(Ho + 1) * (Wo + 1) >= 0x7fffffffLL) return false;
     return true;
+}
+
+// The grid a halo launch runs: the launches and the host-only plan queries (snn_conv3x3_halo_plan,
+// snn_conv3x3_s2_dgrad_plan) read the same function.  Blocks are padded to whole groups of 8 (one per XCD); the padding
+// blocks of the last XCD share return at once.
+struct HaloPlan {
+    int mode;                    // 0 not covered (or grid too large), 1 padded-strip tiles, 2 4 x 32 rectangles
+    int co_tile, ntiles_n;       // output channels per block, channel tiles
+    int G;                       // images per group (tiles never straddle two groups)
+    int tiles_x, tiles_img;      // RECT: rectangles per image row / per image
+    int group_cells;             // strip: cells of a group (0 with RECT)
+    int tiles_per_group, tiles, tiles_per_xcd, grid;
+};
+static void plan_grid(HaloPlan& p) {
+    if (p.tiles * (int64_t)p.ntiles_n + 8 >= 0x7fffffffLL) {
+        p.mode = 0;
+        return;
+    }
+    p.tiles_per_xcd = (int)snn_ceil_div(p.tiles, 8);
+    const int64_t grid = (int64_t)p.tiles_per_xcd * 8 * p.ntiles_n;
+    if (grid > 0x7fffffffLL) p.mode = 0;
+    p.grid = (int)grid;
+}
+// G: images per group (frames per timestep with statistics partials, N without)
+static HaloPlan halo_plan(int64_t N, int H, int W, int Cin, int Cout, int G) {
+    HaloPlan p = {};
+    p.mode = halo_mode(N, H, W, Cin, Cout);
+    if (p.mode == 0 || G <= 0 || N % G != 0) return HaloPlan{};
+    p.G = G;
+    p.co_tile = Cout % 128 == 0 ? 128 : (Cout % 64 == 0 ? 64 : 32);
+    p.ntiles_n = Cout / p.co_tile;
+    p.tiles_x = (int)snn_ceil_div(W, RTW);
+    p.tiles_img = p.tiles_x * (int)snn_ceil_div(H, RTH);
+    int64_t tiles;
+    if (p.mode == 2) {
+        p.tiles_per_group = G * p.tiles_img;
+        tiles = N * (int64_t)p.tiles_img;
+    } else {
+        const int64_t group_cells = (int64_t)G * (H + 1) * (W + 1);
+        p.group_cells = (int)group_cells;
+        p.tiles_per_group = (int)snn_ceil_div(group_cells, HBM_);
+        tiles = (N / G) * p.tiles_per_group;
+    }
+    if (tiles >= 0x7fffffffLL) return HaloPlan{};
+    p.tiles = (int)tiles;
+    plan_grid(p);
+    return p;
+}
+// the stride-2 data gradient: H, W the produced dx, Ho, Wo dy (its strip grid); Cin = dx channels, Cout = dy channels
+static HaloPlan s2dgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout) {
+    HaloPlan p = {};
+    if (!s2dgrad_shape_ok(N, H, W, Cin, Ho, Wo, Cout)) return p;
+    p.mode = s2dgrad_rect(Wo) ? 2 : 1;
+    p.G = (int)N;
+    p.co_tile = 64;
+    p.ntiles_n = Cin / 64;
+    p.tiles_x = (int)snn_ceil_div(Wo, RTW);
+    p.tiles_img = p.tiles_x * (int)snn_ceil_div(Ho, RTH);
+    if (p.mode == 2) {
+        p.tiles_per_group = p.tiles_img;
+        p.tiles = (int)(N * p.tiles_img);
+    } else {
+        const int64_t cells = N * (int64_t)(Ho + 1) * (Wo + 1);
+        p.group_cells = (int)cells;
+        p.tiles_per_group = (int)snn_ceil_div(cells, HBM_);
+        p.tiles = p.tiles_per_group;
+    }
+    plan_grid(p);
+    return p;
+}
+// out[7] = {mode, channel tile, tiles, tiles per group, tiles per XCD share, channel tiles, blocks}
+static int plan_out(const HaloPlan& p, int* out) {
+    const int v[7] = {p.mode, p.co_tile, p.tiles, p.tiles_per_group, p.tiles_per_xcd, p.ntiles_n, p.grid};
+    for (int i = 0; i < 7; ++i) out[i] = v[i];
+    return p.mode == 0 ? 1 : 0;
 }
 }  // namespace
 
@@ -902,6 +978,13 @@ extern "C" int snn_conv3x3_s2_dgrad(const float* dy, int64_t lddy, const void* w
                 "snn_conv3x3_s2_dgrad: dy (16 bytes; 8 for bf16) and the weight image (16) must be aligned");
     SNN_REQUIRE(!addend || ld_addend >= Cin, "snn_conv3x3_s2_dgrad: addend pixel stride smaller than channel count");
     SNN_REQUIRE(!addend2 || ld_addend2 >= Cin, "snn_conv3x3_s2_dgrad: addend2 pixel stride smaller than channel count");
+    const HaloPlan hp = s2dgrad_plan(N, H, W, Cin, Ho, Wo, Cout);
+    SNN_REQUIRE(hp.mode != 0, "snn_conv3x3_s2_dgrad: grid too large");
+    const bool rect = hp.mode == 2;
+    if (rect)
+        SNN_REQUIRE((int64_t)Ho * Wo * lddy * 4 < 0x7fffffffLL, "snn_conv3x3_s2_dgrad: a dy image must span less than 2 GiB");
+    else
+        SNN_REQUIRE((int64_t)4 * Ho * Wo * lddy * 4 < 0x7fffffffLL, "snn_conv3x3_s2_dgrad: four dy images must span less than 2 GiB");
     HaloGeom g;
     g.ldx = lddy; g.ldy = lddx; g.ld_add = ld_addend; g.ld_add2 = ld_addend2;
     g.N = (int)N; g.H = Ho; g.W = Wo;          // the strip grid is dy's
@@ -909,31 +992,20 @@ extern "C" int snn_conv3x3_s2_dgrad(const float* dy, int64_t lddy, const void* w
     g.Cout = Cin;                              // produced channels: dx
     g.OH = H; g.OW = W;
     g.PW = Wo + 1; g.PH = Ho + 1;
-    g.G = (int)N;
-    const bool rect = s2dgrad_rect(Wo);
-    g.tiles_x = (int)snn_ceil_div(Wo, RTW);
-    g.tiles_img = g.tiles_x * (int)snn_ceil_div(Ho, RTH);
-    if (rect) {
-        g.group_cells = 0;
-        g.tiles_per_group = g.tiles_img;
-        g.tiles = (int)(N * g.tiles_img);
-        SNN_REQUIRE((int64_t)Ho * Wo * lddy * 4 < 0x7fffffffLL, "snn_conv3x3_s2_dgrad: a dy image must span less than 2 GiB");
-    } else {
-        SNN_REQUIRE((int64_t)4 * Ho * Wo * lddy * 4 < 0x7fffffffLL, "snn_conv3x3_s2_dgrad: four dy images must span less than 2 GiB");
-        const int64_t cells = N * (int64_t)g.PH * g.PW;
-        g.group_cells = (int)cells;
-        g.tiles_per_group = (int)snn_ceil_div(cells, HBM_);
-        g.tiles = g.tiles_per_group;
-    }
-    g.ntiles_n = Cin / 64;
-    SNN_REQUIRE((int64_t)g.tiles * g.ntiles_n + 8 < 0x7fffffffLL, "snn_conv3x3_s2_dgrad: grid too large");
-    g.tiles_per_xcd = (int)snn_ceil_div(g.tiles, 8);
+    g.G = hp.G;
+    g.tiles_x = hp.tiles_x;
+    g.tiles_img = hp.tiles_img;
+    g.group_cells = hp.group_cells;
+    g.tiles_per_group = hp.tiles_per_group;
+    g.tiles = hp.tiles;
+    g.ntiles_n = hp.ntiles_n;
+    g.tiles_per_xcd = hp.tiles_per_xcd;
     g.magic_pw = magic_u32(g.PW); g.magic_ph = magic_u32(g.PH);
     g.out_vec = (lddx % 4 == 0) && out_aligned(dx, sbf) && (!addend || (ld_addend % 4 == 0 && out_aligned(addend, sbf))) &&
                 (!addend2 || (ld_addend2 % 4 == 0 && out_aligned(addend2, sbf)));
     g.bn_partial = nullptr;
     g.x_th = 0.0f;
-    dim3 grid((unsigned)((int64_t)g.tiles_per_xcd * 8 * g.ntiles_n));
+    dim3 grid((unsigned)hp.grid);
     const unsigned char* wi = static_cast<const unsigned char*>(wt_image);
     if (sbf && rect)
         hipLaunchKernelGGL((k_conv_s2dgrad3<true, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, dy, wi, dx, g, addend, addend2);
@@ -947,8 +1019,18 @@ extern "C" int snn_conv3x3_s2_dgrad(const float* dy, int64_t lddy, const void* w
     return 0;
 }
 
+extern "C" int snn_conv3x3_s2_dgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int* out) {
+    if (!out) return 1;
+    return plan_out(s2dgrad_plan(N, H, W, Cin, Ho, Wo, Cout), out);
+}
+
 extern "C" int snn_conv3x3_halo_supported(int64_t N, int H, int W, int Cin, int Cout) {
     return halo_shape_ok(N, H, W, Cin, Cout) ? 1 : 0;
+}
+
+extern "C" int snn_conv3x3_halo_plan(int64_t N, int H, int W, int Cin, int Cout, int frames_per_step, int* out) {
+    if (!out) return 1;
+    return plan_out(halo_plan(N, H, W, Cin, Cout, frames_per_step > 0 ? frames_per_step : (int)N), out);
 }
 
 // chunk slots per timestep of the statistics partials snn_conv3x3_halo writes (= its tiles per group)
@@ -1001,31 +1083,23 @@ static int conv3x3_halo_impl(const float* x, int64_t ldx, const void* w_image, f
                 "that divides N (%lld frames, %d per step)", (long long)N, frames_per_step);
     SNN_REQUIRE((int64_t)4 * H * W * ldx * 4 < 0x7fffffffLL, "snn_conv3x3_halo: four images must span less than 2 GiB");
     if (bn_layout) bn_layout[0] = bn_layout[1] = 0;
+    const HaloPlan hp = halo_plan(N, H, W, Cin, Cout, bn_partial ? frames_per_step : (int)N);
+    SNN_REQUIRE(hp.mode != 0, "snn_conv3x3_halo: grid too large");
+    const bool rect = hp.mode == 2;
+    if (rect) SNN_REQUIRE((int64_t)H * W * ldx * 4 < 0x7fffffffLL, "snn_conv3x3_halo: an image must span less than 2 GiB");
     HaloGeom g;
     g.ldx = ldx; g.ldy = ldy; g.ld_add = ld_addend; g.ld_add2 = ld_addend2;
     g.N = (int)N; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout;
-    const bool rect = halo_mode(N, H, W, Cin, Cout) == 2;
     g.PW = W + 1; g.PH = H + 1;
-    g.G = bn_partial ? frames_per_step : (int)N;
-    g.tiles_x = (int)snn_ceil_div(W, RTW);
-    g.tiles_img = g.tiles_x * (int)snn_ceil_div(H, RTH);
-    int64_t tiles;
-    if (rect) {
-        g.group_cells = 0;
-        g.tiles_per_group = g.G * g.tiles_img;
-        tiles = N * (int64_t)g.tiles_img;
-        SNN_REQUIRE((int64_t)H * W * ldx * 4 < 0x7fffffffLL, "snn_conv3x3_halo: an image must span less than 2 GiB");
-    } else {
-        const int64_t group_cells = (int64_t)g.G * g.PH * g.PW;
-        g.group_cells = (int)group_cells;
-        g.tiles_per_group = (int)snn_ceil_div(group_cells, HBM_);
-        tiles = (int64_t)(N / g.G) * g.tiles_per_group;
-    }
-    const int co_tile = Cout % 128 == 0 ? 128 : (Cout % 64 == 0 ? 64 : 32);
-    g.ntiles_n = Cout / co_tile;
-    SNN_REQUIRE(tiles * g.ntiles_n + 8 < 0x7fffffffLL, "snn_conv3x3_halo: grid too large");
-    g.tiles = (int)tiles;
-    g.tiles_per_xcd = (int)snn_ceil_div(tiles, 8);
+    g.G = hp.G;
+    g.tiles_x = hp.tiles_x;
+    g.tiles_img = hp.tiles_img;
+    g.group_cells = hp.group_cells;
+    g.tiles_per_group = hp.tiles_per_group;
+    const int co_tile = hp.co_tile;
+    g.ntiles_n = hp.ntiles_n;
+    g.tiles = hp.tiles;
+    g.tiles_per_xcd = hp.tiles_per_xcd;
     g.magic_pw = magic_u32(g.PW); g.magic_ph = magic_u32(g.PH);
     g.out_vec = (ldy % 4 == 0) && out_aligned(y, sbf) && (!addend || (ld_addend % 4 == 0 && out_aligned(addend, sbf))) &&
                 (!addend2 || (ld_addend2 % 4 == 0 && out_aligned(addend2, sbf)));
@@ -1033,7 +1107,7 @@ static int conv3x3_halo_impl(const float* x, int64_t ldx, const void* w_image, f
     g.OH = H; g.OW = W;
     g.x_th = x_th;
     if (bn_partial) bn_layout[0] = g.tiles_per_group;   // every slot of every step is written: rows_per_chunk stays 0
-    dim3 grid((unsigned)((int64_t)g.tiles_per_xcd * 8 * g.ntiles_n));
+    dim3 grid((unsigned)hp.grid);
     const unsigned char* wi = static_cast<const unsigned char*>(w_image);
     const bool f16 = precision == SNN_PREC_FP16X3;
 #define SNN_HALO_LAUNCH(CO_, F16_)                                                                                   \

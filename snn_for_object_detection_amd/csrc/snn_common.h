@@ -62,8 +62,9 @@ struct SnnWgradHaloPlan {
     int tiles_co, tiles_ci, splits, pps, patches;
     int slabs;                   // workspace slabs the launch writes (= splits: the K-sharing waves add up in LDS)
 };
+// num_cu: compute units the split count is planned for (0: the current device's, snn_num_cu)
 SnnWgradHaloPlan snn_wgrad_halo_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW,
-                                     int stride, int pad);
+                                     int stride, int pad, int num_cu = 0);
 // 0 ok, 2 launch error, -1 buffers not addressable by this kernel (caller falls back; the plan must not have been
 // used to size the workspace in that case - the caller checks the same conditions before planning)
 int snn_wgrad_halo_launch(const SnnWgradHaloPlan& p, const float* x, int64_t ldx, const float* dy, int64_t lddy,

@@ -376,8 +376,9 @@ static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7
 }  // namespace
 
 SnnWgradHaloPlan snn_wgrad_halo_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW,
-                                     int stride, int pad) {
+                                     int stride, int pad, int num_cu) {
     SnnWgradHaloPlan p = {};
+    if (num_cu <= 0) num_cu = snn_num_cu();
     if (snn_tuning_env("SNN_WGRAD_NO_HALO")) return p;
     if (KH != 3 || KW != 3 || pad != 1 || (stride != 1 && stride != 2)) return p;
     if (Cin % 32 != 0 || Cout % 32 != 0 || Wo < 8 || Ho < 1) return p;
@@ -436,7 +437,7 @@ SnnWgradHaloPlan snn_wgrad_halo_plan(int64_t N, int H, int W, int Cin, int Ho, i
     const double a_us = (double)patches * ((p.nks + p.wk - 1) / p.wk) * 0.41;
     const double b_us = (double)Cout * 9 * Cin * 4 / 1e6 * 0.5;
     int64_t s = (int64_t)(sqrt(a_us / b_us) + 0.5);
-    const int64_t by_residency = (2 * (int64_t)snn_num_cu()) / tiles;
+    const int64_t by_residency = (2 * (int64_t)num_cu) / tiles;
     if (s > by_residency) s = by_residency;
     const int64_t by_mem = (int64_t)(64 << 20) / ((int64_t)Cout * 9 * Cin);
     if (s > by_mem) s = by_mem;
@@ -449,6 +450,17 @@ SnnWgradHaloPlan snn_wgrad_halo_plan(int64_t N, int H, int W, int Cin, int Ho, i
     p.patches = (int)patches;
     p.ok = 1;
     return p;
+}
+
+// host-only: the plan snn_conv2d_wgrad runs for a 3x3 / pad 1 shape with a num_cu-CU device (0: the current device's count)
+extern "C" int snn_conv2d_wgrad_halo_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int stride, int num_cu,
+                                          int* out) {
+    if (!out) return 1;
+    const SnnWgradHaloPlan p = snn_wgrad_halo_plan(N, H, W, Cin, Ho, Wo, Cout, 3, 3, stride, 1, num_cu);
+    const int v[16] = {p.ok, p.R, p.CW, p.wco, p.wk, p.nks, p.npr, p.npc, p.patches, p.splits, p.pps,
+                       p.HR, p.HC, p.HWD, p.tiles_co, p.tiles_ci};
+    for (int i = 0; i < 16; ++i) out[i] = v[i];
+    return 0;
 }
 
 int snn_wgrad_halo_launch(const SnnWgradHaloPlan& p, const float* x, int64_t ldx, const float* dy, int64_t lddy,

@@ -251,3 +251,74 @@ def test_reverse_scan_plan_invariants(hip_lib):
         HF.affine_neuron_bwd_plan(_hip.NEURON_LI, 32, 5700, 256, 256, 256, True, _hip.SCAN_SUMS_FROM_STATE)
     with pytest.raises(RuntimeError, match="bad shape"):
         HF.affine_neuron_bwd_plan(_hip.NEURON_LIF, 32, 5700, 256, 128, 256, True)
+
+
+def test_halo_plan_invariants(hip_lib):
+    """The host-only plan queries of the halo-resident kernels over a grid of shapes: the launch geometry covers every tile
+    in whole XCD groups, the mode boundaries sit where the LDS halo stops fitting, and the weight-gradient patches fit the
+    staged halo, cover the output and are owned by the splits."""
+    from ctypes import addressof, c_int
+
+    def plan(name, n, *args):
+        out = (c_int * n)()
+        rc = getattr(hip_lib, name)(*args, addressof(out))
+        return rc, list(out)
+
+    for N, H, W in ((1, 1, 1), (3, 7, 5), (2, 9, 78), (2, 9, 79), (6, 30, 38), (4, 120, 152), (2, 1, 300)):
+        for Cin, Cout in ((32, 32), (64, 64), (32, 128), (128, 256), (64, 192)):
+            for fps in (0, 1, N):
+                rc, (mode, co, tiles, tpg, tpx, cot, blocks) = plan("snn_conv3x3_halo_plan", 7, N, H, W, Cin, Cout, fps)
+                assert rc == 0 and mode == (1 if W <= 78 else 2), (N, H, W, fps)        # W = 78 strip, W = 79 RECT
+                assert co == (128 if Cout % 128 == 0 else 64 if Cout % 64 == 0 else 32) and cot * co == Cout
+                G = fps or N
+                if mode == 1:
+                    assert tpg == -(-G * (H + 1) * (W + 1) // 128)                      # 128-cell tiles of a group
+                else:
+                    assert tpg == G * -(-H // 4) * -(-W // 32)                          # 4 x 32 rectangles
+                assert tiles == N // G * tpg and tpx == -(-tiles // 8) and blocks == 8 * tpx * cot
+                if fps:
+                    assert tpg == hip_lib.snn_conv3x3_halo_bn_chunks(G, H, W)
+    assert plan("snn_conv3x3_halo_plan", 7, 4, 8, 8, 64, 96, 0)[0] == 1                  # channel tile not covered
+    assert plan("snn_conv3x3_halo_plan", 7, 6, 8, 8, 64, 64, 4)[0] == 1                  # frames per step must divide N
+    # stride-2 data gradient: strip tiles while the tile and the PW + 1 cells behind it fit the 288 staged cells
+    for Wo, mode in ((1, 1), (155, 1), (157, 1), (158, 2), (321, 2)):
+        for W in (2 * Wo - 1, 2 * Wo):
+            for H in (1, 13, 14):
+                Ho = (H - 1) // 2 + 1
+                rc, (m, co, tiles, tpg, tpx, cot, blocks) = plan("snn_conv3x3_s2_dgrad_plan", 7, 2, H, W, 128, Ho, Wo, 32)
+                assert rc == 0 and m == mode and co == 64 and cot == 2 and blocks == 8 * tpx * cot, (H, W)
+                assert (m == 1) == (128 + Wo + 3 <= 288)
+                assert tiles == (-(-2 * (Ho + 1) * (Wo + 1) // 128) if m == 1 else 2 * -(-Ho // 4) * -(-Wo // 32))
+    # weight gradient: R x CW patches whose ((R-1)s+3) x ((CW-1)s+3) halo fits the 256 staged pixels
+    keys = "ok R CW wco wk nks npr npc patches splits pps HR HC HWD tiles_co tiles_ci".split()
+    seen = set()
+    for s in (1, 2):
+        for N, Ho, Wo in ((1, 300, 500), (2, 250, 301), (1, 61, 2459), (1, 60, 2500), (3, 390, 161), (1, 296, 517),
+                          (4, 120, 152), (1, 8, 18750), (160, 30, 38)):
+            H, W = (Ho, Wo) if s == 1 else (2 * Ho, 2 * Wo - 1)
+            for Cin, Cout in ((32, 32), (32, 64), (64, 128), (512, 512)):
+                for num_cu in (256, 80, 8):
+                    rc, v = plan("snn_conv2d_wgrad_halo_plan", 16, N, H, W, Cin, Ho, Wo, Cout, s, num_cu)
+                    p = dict(zip(keys, v))
+                    assert rc == 0 and p["ok"] == (1 if N * Ho * Wo >= 150_000 else 0), (N, Ho, Wo, p)
+                    if not p["ok"]:
+                        continue
+                    assert p["CW"] % 8 == 0 and p["HR"] == (p["R"] - 1) * s + 3 and p["HC"] == (p["CW"] - 1) * s + 3
+                    assert p["HR"] * p["HWD"] <= 256 and p["HWD"] >= p["HC"], p                     # HALO_CAP
+                    assert p["npr"] == -(-Ho // p["R"]) and p["npc"] == -(-Wo // p["CW"]), p      # patches cover Ho x Wo
+                    assert p["patches"] == N * p["npr"] * p["npc"] and p["nks"] == -(-p["R"] * p["CW"] // 16)
+                    assert p["wco"] == (4 if Cout >= 128 else 2 if Cout >= 64 else 1) and p["wco"] * p["wk"] == 4
+                    assert p["tiles_co"] == Cout // (32 * p["wco"]) and p["tiles_ci"] == Cin // 32
+                    assert 1 <= p["splits"] <= p["patches"] and p["pps"] == -(-p["patches"] // p["splits"])
+                    assert p["splits"] * p["pps"] >= p["patches"] and (p["splits"] < 16 or p["splits"] % 8 == 0), p
+                    assert p["splits"] <= max(1, 2 * num_cu // (p["tiles_co"] * p["tiles_ci"])), p
+                    seen.add(("splits1", num_cu) if p["splits"] == 1 else ("idle", num_cu)
+                             if (p["splits"] - 1) * p["pps"] >= p["patches"] else ("full", num_cu))
+                    seen.add("masked_k" if p["R"] * p["CW"] % 16 else "whole_k")
+                    if p["nks"] % p["wk"]:
+                        seen.add("nks_wk")
+                    if num_cu == 256 and not torch.cuda.is_available():   # no device: 0 plans for 256 CUs
+                        assert plan("snn_conv2d_wgrad_halo_plan", 16, N, H, W, Cin, Ho, Wo, Cout, s, 0)[1] == v
+    # splits owning no patch occur at 256 CUs; a single split only with few CUs per channel tile
+    assert {("idle", 256), ("splits1", 8), "masked_k", "whole_k", "nks_wk"} <= seen, seen
+    assert ("splits1", 256) not in seen
