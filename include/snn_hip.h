@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SNN_ABI_VERSION 15
+#define SNN_ABI_VERSION 16
 
 /* neuron kinds for the fused affine+neuron temporal scan */
 enum {
@@ -224,6 +224,17 @@ int snn_conv3x3_s2_dgrad_supported(int64_t N, int H, int W, int Cin, int Ho, int
 int snn_conv3x3_s2_dgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int* out);
 int snn_conv3x3_halo_plan(int64_t N, int H, int W, int Cin, int Cout, int frames_per_step, int* out);
 int snn_conv2d_wgrad_halo_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int stride, int num_cu, int* out);
+/* Host-only plan query of the event-frame row kernel (k_conv_first: Cin = 2, 3x3, Cout = 4 * 2^k <= 256, W + 2 pad <= 1408):
+ * the plan snn_conv2d_fwd (frames_per_step > 0: with statistics partials; <= 0: without), snn_conv2d_wgrad and
+ * snn_conv2d_wgrad_bn (wgrad = 1) launch for the shape on a device with num_cu compute units (0: the current device's;
+ * 256 without one).  It reads the plan function the launches read.  out[10] = { ok (0: another kernel takes the shape),
+ * rs (output rows staged per barrier pair, 1..4), LW (padded input row width W + 2 pad), cgs (channel groups Cout / 4),
+ * PP (pixel lanes 256 / cgs), blocks (the grid; weight gradient: = snn_conv2d_wgrad_splitk, one workspace slab each),
+ * group_rows, group_blocks (rows of a group - a timestep with statistics, else all N * Ho - and the blocks that walk
+ * them; = bn_layout[0] with statistics), the most rows a block walks, the rows of that block's last stage }.
+ * Returns 0, or 1 (out[0] = 0) for a shape the kernel does not take.  Pointer alignment and strides are the call's. */
+int snn_conv_first_plan(int64_t N, int H, int W, int Ho, int Wo, int Cout, int stride, int pad, int frames_per_step,
+                        int wgrad, int num_cu, int* out);
 int snn_conv3x3_s2_dgrad(const float* dy, int64_t lddy, const void* wt_image, float* dx, int64_t lddx, int64_t N, int H, int W,
                          int Cin, int Ho, int Wo, int Cout, const float* addend, int64_t ld_addend, const float* addend2,
                          int64_t ld_addend2, int precision /* SNN_PREC_BF16X3 | SNN_PREC_BF16S */, void* stream);

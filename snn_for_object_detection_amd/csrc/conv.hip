@@ -2236,13 +2236,78 @@ static int first_layer_rs(int W, int pad) {
     int rs = (20 << 10) / per_row;
     return rs < 1 ? 1 : (rs > 4 ? 4 : rs);
 }
-static size_t first_layer_lds(int W, int pad) { return (size_t)first_layer_rs(W, pad) * 3 * (W + 2 * pad) * sizeof(float2); }
-
-static int first_layer_blocks(int64_t rows) {  // grid of the row-walking kernels = slabs of the weight gradient
-    int64_t b = rows < 4 * snn_num_cu() ? rows : 4 * snn_num_cu();
+static int first_layer_blocks(int64_t rows, int num_cu = 0) {  // grid of the weight gradient = its slabs
+    if (num_cu <= 0) num_cu = snn_num_cu();
+    int64_t b = rows < 4 * num_cu ? rows : 4 * num_cu;
     return b < 1 ? 1 : (int)b;
 }
+
+// Forward with statistics partials: a group is one timestep, dealt to `blocks` blocks of at most `per_block` rows each
+// (about 8 blocks per CU over all timesteps; at least one per timestep)
+struct FirstGroups { int rows, blocks; };
+static FirstGroups first_layer_groups(int rows_per_step, int steps, int num_cu) {
+    int target = 8 * num_cu / (steps > 0 ? steps : 1);
+    if (target < 1) target = 1;
+    if (target > rows_per_step) target = rows_per_step;
+    const int per_block = (rows_per_step + target - 1) / target;
+    return {rows_per_step, (rows_per_step + per_block - 1) / per_block};
+}
+
+// The launch plan of k_conv_first, read by the three launches and by snn_conv_first_plan.  ok = 0: the shape is not
+// covered (the caller checks its pointers and strides on top).  frames_per_step > 0: the forward with statistics
+// partials.  num_cu: 0 the current device's.
+struct FirstPlan {
+    int ok;
+    int rs, LW, cgs, PP;            // rows per stage, padded input row width, channel groups, pixel lanes
+    int blocks;                     // grid (weight gradient: = snn_conv2d_wgrad_splitk, the slabs)
+    int group_rows, group_blocks;   // see FirstGeom
+    int max_rows, last_stage_rows;  // the most rows a block walks, and the rows of that block's last stage
+    size_t lds;                     // dynamic LDS bytes: rs staged output rows of 3 padded input rows
+};
+static FirstPlan first_layer_plan(int64_t N, int H, int W, int Ho, int Wo, int Cout, int stride, int pad,
+                                  int frames_per_step, bool wgrad, int num_cu) {
+    FirstPlan p = {};
+    if (num_cu <= 0) num_cu = snn_num_cu();
+    if (!first_layer_shape(2, Cout, 3, 3) || N <= 0 || stride <= 0 || pad < 0 || Ho <= 0 || Wo <= 0 ||
+        Ho != (H + 2 * pad - 3) / stride + 1 || Wo != (W + 2 * pad - 3) / stride + 1 || N * (int64_t)Ho >= 0x7fffffffLL ||
+        W + 2 * pad > 1408 || (Wo - 1) * stride + 3 > W + 2 * pad)
+        return p;
+    if (!wgrad && frames_per_step > 0 && N % frames_per_step != 0) return p;
+    const int rows = (int)(N * Ho);
+    p.rs = first_layer_rs(W, pad);
+    p.LW = W + 2 * pad;
+    p.cgs = Cout / 4;
+    p.PP = kThreads / p.cgs;
+    p.lds = (size_t)p.rs * 3 * p.LW * sizeof(float2);
+    p.group_rows = rows;
+    if (wgrad) {
+        p.blocks = p.group_blocks = first_layer_blocks(rows, num_cu);
+    } else if (frames_per_step > 0) {
+        const int steps = (int)(N / frames_per_step);
+        const FirstGroups g = first_layer_groups(frames_per_step * Ho, steps, num_cu);
+        p.group_rows = g.rows;
+        p.group_blocks = g.blocks;
+        p.blocks = steps * g.blocks;
+    } else {
+        p.blocks = p.group_blocks = rows < 8 * num_cu ? rows : 8 * num_cu;
+    }
+    // block 0 of a group walks its rows 0, group_blocks, ...: the most of any block; stages of rs rows, the last one partial
+    p.max_rows = (p.group_rows + p.group_blocks - 1) / p.group_blocks;
+    p.last_stage_rows = (p.max_rows - 1) % p.rs + 1;
+    p.ok = 1;
+    return p;
+}
 }  // namespace
+
+extern "C" int snn_conv_first_plan(int64_t N, int H, int W, int Ho, int Wo, int Cout, int stride, int pad,
+                                   int frames_per_step, int wgrad, int num_cu, int* out) {
+    if (!out) return 1;
+    const FirstPlan p = first_layer_plan(N, H, W, Ho, Wo, Cout, stride, pad, frames_per_step, wgrad != 0, num_cu);
+    const int v[10] = {p.ok, p.rs, p.LW, p.cgs, p.PP, p.blocks, p.group_rows, p.group_blocks, p.max_rows,
+                       p.last_stage_rows};
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return p.ok ? 0 : 1;
+}
 
 // ---- pre-split weight images (see PRESPLIT of k_conv_gather).  Elementwise over groups of 4 consecutive floats: the
 // group's 16 bytes become (4 hi pieces, 4 lo pieces) with exactly the arithmetic of the in-kernel conversion - fp16
@@ -2299,15 +2364,6 @@ extern "C" int snn_weight_presplit(const float* w, void* out, int64_t n, int pre
 
 // Chunk slots per timestep of the three forward kernels' statistics partials (see stat_flush); 0: not produced.
 namespace {
-struct FirstGroups { int rows, blocks; };
-// first-layer kernel, one group of rows per timestep: an equal number of rows for every block of the group
-static FirstGroups first_layer_groups(int rows_per_step, int steps) {
-    int target = 8 * snn_num_cu() / (steps > 0 ? steps : 1);
-    if (target < 1) target = 1;
-    if (target > rows_per_step) target = rows_per_step;
-    const int per_block = (rows_per_step + target - 1) / target;
-    return {rows_per_step, (rows_per_step + per_block - 1) / per_block};
-}
 static int64_t gather_bn_chunks(int64_t rows_per_step) { return (rows_per_step + BM - 1) / BM + 1; }
 static int64_t direct_bn_chunks(int frames_per_step, int Ho, int Wo) {
     return (int64_t)frames_per_step * ((Ho + DPH - 1) / DPH) * ((Wo + DPW - 1) / DPW);
@@ -2360,29 +2416,20 @@ extern "C" int snn_conv2d_fwd(const float* x, int64_t ldx, const float* w, const
     SNN_REQUIRE(N * (int64_t)H * W < 0x7fffffffLL && (int64_t)g.Ktot * Cin < 0xffffffffLL,
                 "snn_conv2d_fwd: tensor too large for 32-bit pixel indexing");
     SNN_REQUIRE(!addend || ld_addend >= Cout, "snn_conv2d_fwd: addend pixel stride smaller than channel count");
-    if (first_layer_shape(Cin, Cout, KH, KW) && !addend && ldx % 2 == 0 && aligned8(x) && ldy % 4 == 0 &&
-        (sbf ? aligned8(y) : aligned16(y)) &&
-        (int64_t)W * ldx < 0x7fffffffLL && (int64_t)Wo * ldy < 0x7fffffffLL && W + 2 * pad <= 1408 &&
-        (Wo - 1) * stride + 3 <= W + 2 * pad) {
-        FirstGeom fg = {ldx, ldy, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, (int)(N * Ho), 0, nullptr,
-                        nullptr, 0, nullptr, 0, 1, first_layer_rs(W, pad)};
-        int blocks = fg.rows < 8 * snn_num_cu() ? fg.rows : 8 * snn_num_cu();
-        fg.group_blocks = blocks;
-        if (bn_partial) {
-            const int steps = (int)(N / frames_per_step);
-            const FirstGroups fgr = first_layer_groups(frames_per_step * Ho, steps);
-            fg.group_rows = fgr.rows;
-            fg.group_blocks = fgr.blocks;
-            fg.bn_partial = bn_partial;
-            blocks = steps * fgr.blocks;
-            bn_layout[0] = fgr.blocks;
-        }
+    const FirstPlan fp = Cin == 2 && KH == 3 && KW == 3
+                             ? first_layer_plan(N, H, W, Ho, Wo, Cout, stride, pad, bn_partial ? frames_per_step : 0, false, 0)
+                             : FirstPlan{};
+    if (fp.ok && !addend && ldx % 2 == 0 && aligned8(x) && ldy % 4 == 0 && (sbf ? aligned8(y) : aligned16(y)) &&
+        (int64_t)W * ldx < 0x7fffffffLL && (int64_t)Wo * ldy < 0x7fffffffLL) {
+        FirstGeom fg = {ldx, ldy, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, fp.group_rows, fp.group_blocks,
+                        bn_partial, nullptr, 0, nullptr, 0, 1, fp.rs};
+        if (bn_partial) bn_layout[0] = fp.group_blocks;
         if (sbf)
-            hipLaunchKernelGGL((k_conv_first<2, 3, false, false, true>), dim3((unsigned)blocks), dim3(kThreads),
-                               first_layer_lds(W, pad), (hipStream_t)stream, x, w, nullptr, y, fg);
+            hipLaunchKernelGGL((k_conv_first<2, 3, false, false, true>), dim3((unsigned)fp.blocks), dim3(kThreads),
+                               fp.lds, (hipStream_t)stream, x, w, nullptr, y, fg);
         else
-            hipLaunchKernelGGL((k_conv_first<2, 3, false>), dim3((unsigned)blocks), dim3(kThreads),
-                               first_layer_lds(W, pad), (hipStream_t)stream, x, w, nullptr, y, fg);
+            hipLaunchKernelGGL((k_conv_first<2, 3, false>), dim3((unsigned)fp.blocks), dim3(kThreads),
+                               fp.lds, (hipStream_t)stream, x, w, nullptr, y, fg);
         SNN_CHECK_LAUNCH("snn_conv2d_fwd");
         return 0;
     }
@@ -2609,20 +2656,24 @@ static int wgrad_reduce_slabs(float* workspace, float* dw, int64_t n, int splitk
 }
 
 namespace {
-static bool first_layer_wgrad_ok(const float* x, int64_t ldx, const float* dy, int64_t lddy, int64_t N, int H, int W, int Cin,
-                                 int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, bool dy_bf16 = false) {
-    return first_layer_shape(Cin, Cout, KH, KW) && ldx % 2 == 0 && aligned8(x) && lddy % 4 == 0 &&
-           (dy_bf16 ? aligned8(dy) : aligned16(dy)) &&
-           (int64_t)W * ldx < 0x7fffffffLL && N * Ho < 0x7fffffffLL && W + 2 * pad <= 1408 &&
-           (Wo - 1) * stride + 3 <= W + 2 * pad;
+// the weight-gradient plan of k_conv_first, ok = 0 when the shape or the buffers are not covered
+static FirstPlan first_layer_wgrad_plan(const float* x, int64_t ldx, const float* dy, int64_t lddy, int64_t N, int H, int W,
+                                        int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
+                                        bool dy_bf16 = false) {
+    if (Cin != 2 || KH != 3 || KW != 3) return FirstPlan{};
+    FirstPlan p = first_layer_plan(N, H, W, Ho, Wo, Cout, stride, pad, 0, true, 0);
+    if (!(ldx % 2 == 0 && aligned8(x) && lddy % 4 == 0 && (dy_bf16 ? aligned8(dy) : aligned16(dy)) &&
+          (int64_t)W * ldx < 0x7fffffffLL))
+        p.ok = 0;
+    return p;
 }
 }  // namespace
 
 extern "C" int snn_conv2d_wgrad_bn_supported(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW,
                                              int stride, int pad) {
     // the event-frame layer's row kernel (pointer alignment is checked by the call itself)
-    return (N > 0 && first_layer_shape(Cin, Cout, KH, KW) && N * (int64_t)Ho < 0x7fffffffLL && W + 2 * pad <= 1408 &&
-            (Wo - 1) * stride + 3 <= W + 2 * pad) ? 1 : 0;
+    if (Cin != 2 || KH != 3 || KW != 3) return 0;
+    return first_layer_plan(N, H, W, Ho, Wo, Cout, stride, pad, 0, true, 0).ok;
 }
 
 extern "C" int snn_conv2d_wgrad_bn(const float* x, int64_t ldx, const float* gx, int64_t ldgx, const float* y, int64_t ldy,
@@ -2635,13 +2686,14 @@ extern "C" int snn_conv2d_wgrad_bn(const float* x, int64_t ldx, const float* gx,
                 "snn_conv2d_wgrad_bn: %lld frames are not %d timesteps of %d", (long long)N, T, frames_per_step);
     SNN_REQUIRE(ldx >= Cin && ldgx >= Cout && ldy >= Cout, "snn_conv2d_wgrad_bn: pixel stride smaller than channel count");
     SNN_REQUIRE(splitk >= 1 && splitk <= 32768, "snn_conv2d_wgrad_bn: bad splitk %d", splitk);
-    SNN_REQUIRE(first_layer_wgrad_ok(x, ldx, gx, ldgx, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad) && ldy % 4 == 0 &&
-                    aligned16(y) && aligned16(coef) && (int64_t)Wo * ldy < 0x7fffffffLL && (int64_t)Wo * ldgx < 0x7fffffffLL,
+    const FirstPlan fp = first_layer_wgrad_plan(x, ldx, gx, ldgx, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
+    SNN_REQUIRE(fp.ok && ldy % 4 == 0 && aligned16(y) && aligned16(coef) && (int64_t)Wo * ldy < 0x7fffffffLL &&
+                    (int64_t)Wo * ldgx < 0x7fffffffLL,
                 "snn_conv2d_wgrad_bn: shape / alignment not covered (ask snn_conv2d_wgrad_bn_supported)");
-    FirstGeom fg = {ldx, ldgx, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, (int)(N * Ho), splitk, nullptr,
-                    y, ldy, coef, T * Cout, frames_per_step, first_layer_rs(W, pad)};
+    FirstGeom fg = {ldx, ldgx, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, fp.group_rows, splitk, nullptr,
+                    y, ldy, coef, T * Cout, frames_per_step, fp.rs};
     hipLaunchKernelGGL((k_conv_first<2, 3, true, true>), dim3((unsigned)splitk), dim3(kThreads),
-                       first_layer_lds(W, pad), (hipStream_t)stream, x, nullptr, gx, workspace, fg);
+                       fp.lds, (hipStream_t)stream, x, nullptr, gx, workspace, fg);
     SNN_CHECK_LAUNCH("snn_conv2d_wgrad_bn");
     return wgrad_reduce_slabs(workspace, dw, (int64_t)Cout * KH * KW * Cin, splitk, accumulate, (hipStream_t)stream);
 }
@@ -2667,15 +2719,17 @@ static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t ld
     g.ldx = ldx; g.lddy = lddy;
     g.Ktot = KH * KW * Cin;
     g.x_th = x_th;
-    if (!xsp && first_layer_wgrad_ok(x, ldx, dy, lddy, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, sbf)) {
-        FirstGeom fg = {ldx, lddy, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, (int)(N * Ho), splitk, nullptr,
-                        nullptr, 0, nullptr, 0, 1, first_layer_rs(W, pad)};
+    const FirstPlan fp = xsp ? FirstPlan{}
+                             : first_layer_wgrad_plan(x, ldx, dy, lddy, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, sbf);
+    if (fp.ok) {
+        FirstGeom fg = {ldx, lddy, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, fp.group_rows, splitk, nullptr,
+                        nullptr, 0, nullptr, 0, 1, fp.rs};
         if (sbf)
             hipLaunchKernelGGL((k_conv_first<2, 3, true, false, true>), dim3((unsigned)splitk), dim3(kThreads),
-                               first_layer_lds(W, pad), (hipStream_t)stream, x, nullptr, dy, workspace, fg);
+                               fp.lds, (hipStream_t)stream, x, nullptr, dy, workspace, fg);
         else
             hipLaunchKernelGGL((k_conv_first<2, 3, true>), dim3((unsigned)splitk), dim3(kThreads),
-                               first_layer_lds(W, pad), (hipStream_t)stream, x, nullptr, dy, workspace, fg);
+                               fp.lds, (hipStream_t)stream, x, nullptr, dy, workspace, fg);
         SNN_CHECK_LAUNCH("snn_conv2d_wgrad");
         return wgrad_reduce_slabs(workspace, dw, (int64_t)Cout * g.Ktot, splitk, accumulate, (hipStream_t)stream);
     }

@@ -322,3 +322,74 @@ def test_halo_plan_invariants(hip_lib):
     # splits owning no patch occur at 256 CUs; a single split only with few CUs per channel tile
     assert {("idle", 256), ("splits1", 8), "masked_k", "whole_k", "nks_wk"} <= seen, seen
     assert ("splits1", 256) not in seen
+
+
+def test_first_layer_plan_invariants(hip_lib):
+    """The host-only plan query of the event-frame row kernel (k_conv_first): staged rows per barrier pair at the LDS
+    boundaries, the shapes it takes, the grid of each launch and the statistics groups (one timestep each)."""
+    from ctypes import addressof, c_int
+
+    def plan(N, H, W, Cout, s, pad, fps=0, wgrad=0, num_cu=256):
+        Ho, Wo = (H + 2 * pad - 3) // s + 1, (W + 2 * pad - 3) // s + 1
+        out = (c_int * 10)()
+        rc = hip_lib.snn_conv_first_plan(N, H, W, Ho, Wo, Cout, s, pad, fps, wgrad, num_cu, addressof(out))
+        keys = "ok rs LW cgs PP blocks group_rows group_blocks max_rows last_stage".split()
+        p = dict(zip(keys, out))
+        assert rc == (0 if p["ok"] else 1), p
+        return p
+
+    # rs = floor(20 KiB / (24 LW)) clamped to 1..4: 4 up to LW 213, 3 to 284, 2 to 426, 1 to 853, then clamped 1 to 1408
+    for LW, rs in ((213, 4), (214, 3), (284, 3), (285, 2), (426, 2), (427, 1), (853, 1), (854, 1), (1408, 1)):
+        assert (20 << 10) // (24 * LW) == (rs if LW < 854 else 0), LW
+        for pad in (0, 1):
+            p = plan(2, 5, LW - 2 * pad, 16, 1, pad)
+            assert p["ok"] == 1 and p["rs"] == rs and p["LW"] == LW, (LW, pad, p)
+    assert plan(2, 5, 1406, 16, 1, 1)["ok"] == 1 and plan(2, 5, 1407, 16, 1, 1)["ok"] == 0     # LW 1408 / 1409
+    assert plan(2, 5, 1408, 16, 2, 0)["ok"] == 1 and plan(2, 5, 1409, 16, 2, 0)["ok"] == 0
+    for Cout in (4, 8, 16, 32, 64, 128, 256):
+        p = plan(2, 5, 9, Cout, 1, 1)
+        assert p["ok"] == 1 and p["cgs"] == Cout // 4 and p["PP"] == 256 // (Cout // 4), (Cout, p)
+    for Cout in (2, 12, 20, 48, 96, 192, 260, 512):                                            # not 4 * 2^k <= 256
+        assert plan(2, 5, 9, Cout, 1, 1)["ok"] == 0, Cout
+    out = (c_int * 10)()                                                                         # Ho / Wo must match
+    assert hip_lib.snn_conv_first_plan(2, 5, 9, 5, 8, 16, 1, 1, 0, 0, 256, addressof(out)) == 1 and out[0] == 0
+    assert plan(6, 5, 9, 16, 1, 1, fps=4)["ok"] == 0                                             # fps must divide N
+    seen = set()
+    for num_cu in (256, 80, 8):
+        for N, H, W, s, pad in ((1, 3, 3, 1, 0), (3, 17, 23, 2, 1), (160, 240, 304, 2, 1), (8, 720, 1280, 2, 1),
+                                (4, 9, 1406, 1, 1), (600, 4, 6, 1, 1), (2, 1500, 40, 1, 0), (64, 30, 38, 2, 1)):
+            Ho = (H + 2 * pad - 3) // s + 1
+            rows = N * Ho
+            for Cout in (4, 64, 256):
+                p = plan(N, H, W, Cout, s, pad, num_cu=num_cu)                                   # forward
+                assert p["blocks"] == p["group_blocks"] == min(rows, 8 * num_cu) and p["group_rows"] == rows, p
+                m = -(-rows // p["blocks"])
+                assert p["max_rows"] == m and p["last_stage"] == (m - 1) % p["rs"] + 1, p
+                seen.add("multi_row" if m > 1 else "one_row")
+                if m > 1 and p["last_stage"] < p["rs"]:
+                    seen.add("partial_stage")
+                w = plan(N, H, W, Cout, s, pad, wgrad=1, num_cu=num_cu)                          # weight gradient
+                assert w["blocks"] == w["group_blocks"] == min(rows, 4 * num_cu) and w["max_rows"] == -(-rows // w["blocks"])
+                assert w["rs"] == p["rs"] and w["LW"] == p["LW"]
+                if num_cu == 256 and not torch.cuda.is_available():   # no device: snn_conv2d_wgrad_splitk plans 256 CUs
+                    Wo = (W + 2 * pad - 3) // s + 1
+                    assert w["blocks"] == hip_lib.snn_conv2d_wgrad_splitk(N, H, W, 2, Ho, Wo, Cout, 3, 3, s, pad, 0)
+                    assert plan(N, H, W, Cout, s, pad, wgrad=1, num_cu=0) == w
+                for fps in {1, N} | ({N // 2} if N % 2 == 0 else set()):                        # statistics groups
+                    b = plan(N, H, W, Cout, s, pad, fps=fps, num_cu=num_cu)
+                    steps, rps = N // fps, fps * Ho
+                    target = min(max(8 * num_cu // steps, 1), rps)
+                    per = -(-rps // target)
+                    assert b["group_rows"] == rps and b["group_blocks"] == -(-rps // per), b
+                    assert b["blocks"] == steps * b["group_blocks"] and b["max_rows"] == per, b
+                    assert (b["group_blocks"] - 1) * per < rps <= b["group_blocks"] * per     # the last block is short
+                    seen.add("target1" if 8 * num_cu // steps < 1 else "per_block" if per > 1 else "row_per_block")
+    assert {"multi_row", "one_row", "partial_stage", "target1", "per_block", "row_per_block"} <= seen, seen
+    # the three workloads' event-frame layers (Cout 64, pad 1) at 256 CUs
+    g = plan(160, 240, 304, 64, 2, 1)                                                            # GEN1
+    assert (g["rs"], g["LW"], g["PP"], g["blocks"], g["max_rows"]) == (2, 306, 16, 2048, 10), g
+    assert plan(160, 240, 304, 64, 2, 1, wgrad=1)["blocks"] == 1024
+    m = plan(256, 720, 1280, 64, 2, 1)                                                           # 1 Mpx
+    assert (m["rs"], m["LW"], m["blocks"], m["max_rows"], m["last_stage"]) == (1, 1282, 2048, 45, 1), m
+    d = plan(256, 240, 304, 64, 1, 1, fps=2)                                                     # deep-12, T = 128
+    assert (d["rs"], d["group_rows"], d["group_blocks"], d["blocks"], d["max_rows"]) == (2, 480, 16, 2048, 30), d
