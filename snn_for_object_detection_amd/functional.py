@@ -124,6 +124,15 @@ def _prec_codes(forward: Optional[str], backward: Optional[str]) -> Tuple[int, i
             BACKWARD_MODES[_checked(backward or _backward_precision, BACKWARD_MODES, "backward")])
 
 
+def _conv_precs(prec: Optional[Tuple[int, int]], bf16_storage: bool) -> Tuple[int, int]:
+    """``(forward, backward)`` codes of one convolution call: ``prec`` (else the session defaults), or the one-product
+    bf16-storage mode for both when the call reads or writes bf16 activations."""
+    fwd_prec, bwd_prec = prec if prec is not None else _prec_codes(None, None)
+    if bf16_storage:
+        fwd_prec = bwd_prec = _hip.PREC_BF16S
+    return fwd_prec, bwd_prec
+
+
 # ------------------------------------------------------------------------------------------- helpers
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
@@ -221,6 +230,41 @@ def wgrad_stream_sync() -> None:
     _SIDE_PENDING.clear()
     for dev, st in _SIDE_STREAMS.items():
         torch.cuda.current_stream(dev).wait_stream(st)
+
+
+class _WgradLaunch:
+    """``with _WgradLaunch(...) as (stream handle, split-K workspace [splitk, rows*cols], G [rows, cols] or None):`` the
+    stream and scratch of one weight-gradient launch, both allocated on that stream.  A gradient that goes straight into
+    the flat buffer (``slotted``) feeds nothing downstream in autograd, so it runs on the side stream, concurrently with
+    the data-gradient chain: the launch before the previous one is joined first (its operands go), the side stream waits
+    for the main stream (gy and every earlier use of the slot are complete), and ``hold`` - the tensors the launched
+    kernels read - stays alive until the main stream has waited for them.  (A class, not a generator: it runs for every
+    weight gradient of a step, on the host's critical path.)"""
+
+    __slots__ = ("device", "on_side", "shape", "hold", "with_g", "stream", "scope")
+
+    def __init__(self, device, slotted: bool, splitk: int, rows: int, cols: int, hold: Sequence[torch.Tensor] = (),
+                 with_g: bool = False):
+        self.device, self.on_side, self.shape = device, slotted and USE_WGRAD_STREAM, (splitk, rows, cols)
+        self.hold, self.with_g = hold, with_g
+
+    def __enter__(self):
+        main = torch.cuda.current_stream()
+        self.stream = _side_stream(self.device) if self.on_side else main
+        if self.on_side:
+            _side_retire(main, WGRAD_SIDE_DEPTH)
+            self.stream.wait_stream(main)
+        self.scope = torch.cuda.stream(self.stream)
+        self.scope.__enter__()
+        splitk, rows, cols = self.shape
+        ws = torch.empty((splitk, rows * cols), device=self.device, dtype=_F32)
+        G = torch.empty((rows, cols), device=self.device, dtype=_F32) if self.with_g else None
+        return self.stream.cuda_stream, ws, G
+
+    def __exit__(self, *exc):
+        self.scope.__exit__(*exc)
+        if self.on_side:
+            _side_hold(self.stream, *self.hold)
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -629,6 +673,25 @@ def _spikes_dense(x: torch.Tensor, x_th: float) -> torch.Tensor:
     return _cl_view((x.permute(0, 1, 3, 4, 2) > x_th).to(_F32).contiguous())
 
 
+def _spikes_fwd_operand(x: torch.Tensor, x_th: Optional[float], covered) -> Tuple[torch.Tensor, Optional[float]]:
+    """Forward operand of a convolution: ``(x, x_th)`` when ``x`` holds no potentials or a thresholding kernel takes the
+    call (``covered()``, asked only then: the call's own test on top of ``_spikes_fwd_ok``), else the spikes written out
+    after all and no threshold."""
+    if x_th is None or covered():
+        return x, x_th
+    return _spikes_dense(x, x_th), None
+
+
+def _spikes_wgrad_operand(x: torch.Tensor, ldx: int, x_th: Optional[float], gy: torch.Tensor, ldg: int):
+    """Weight-gradient operand -> ``(operand, its pixel stride, threshold)``: the potentials and their threshold where
+    ``_spikes_wgrad_ok``, else the spikes written out (same bits: the plain kernel on the stored spikes) and no
+    threshold."""
+    if x_th is None or _spikes_wgrad_ok(x.data_ptr(), ldx, gy.data_ptr(), ldg):
+        return x, ldx, x_th
+    z = _spikes_dense(x, x_th)
+    return z, cl_stride(z), None
+
+
 def _frag_image(src: torch.Tensor, O: int, I: int, flip: int, prec: int) -> torch.Tensor:
     """Weight image in MFMA-fragment order of ONE ``[O][3][3][I]`` matrix (snn_weight_frag_image_batched with a
     one-row table): what a layer without a FlatTrainer-kept image builds per call (one small launch)."""
@@ -639,12 +702,17 @@ def _frag_image(src: torch.Tensor, O: int, I: int, flip: int, prec: int) -> torc
     return img
 
 
-def _cached_image(weight, name: str):
-    """FlatTrainer's per-step weight image (a tensor view kept on the parameter), while the version counter matches."""
-    img = getattr(weight, name, None)
-    if img is not None and weight._snn_wt_version == weight._version:
-        return img
-    return None
+def _kept_view(weight, name: str, frag_prec: int = _hip.PREC_FP16X3) -> Optional[torch.Tensor]:
+    """A weight view FlatTrainer keeps on the parameter and refreshes once per optimiser step (``_snn_wt``,
+    ``_snn_w16``, ``_snn_wt16``, ``_snn_wfrag``, ``_snn_wtfrag``; tensor views, alive as long as the parameter is), or
+    None: the parameter does not live in a FlatTrainer, it changed since the last refresh (version counter), or - the
+    forward fragment image - the image holds the pieces of another precision than ``frag_prec``."""
+    view = getattr(weight, name, None)
+    if view is None or weight._snn_wt_version != weight._version:
+        return None
+    if name == "_snn_wfrag" and getattr(weight, "_snn_wfrag_prec", _hip.PREC_FP16X3) != frag_prec:
+        return None
+    return view
 
 
 class PendingBnApply(NamedTuple):
@@ -693,14 +761,12 @@ class _Conv2d(Function):
         # x_th (a float): x holds the saved POTENTIALS of a LIF layer that wrote no spike tensor; the operand is
         # z = (x > x_th), formed by the kernels while they read (snn_conv2d_spikes_* / snn_conv3x3_halo_spikes)
         _require_device(x, "conv2d input", bf16_ok=True)
-        fwd_prec, bwd_prec = prec if prec is not None else _prec_codes(None, None)
         _require_device(weight, "conv2d weight")
         T, B, Cin, H, W = _dims5(x)
         Cout, Cin_w, KH, KW = weight.shape
         # bf16 storage: follows the input; enters at the event-frame layer (fp32 {0,1} frames in, bf16 out)
         sb = x.dtype == _BF16 or (_activation_storage == "bf16" and Cin == 2 and (KH, KW) == (3, 3))
-        if sb:
-            fwd_prec = bwd_prec = _hip.PREC_BF16S
+        fwd_prec, bwd_prec = _conv_precs(prec, sb)
         if Cin_w != Cin:
             raise RuntimeError(f"conv2d: input has {Cin} channels, weight expects {Cin_w}")
         Ho = (H + 2 * pad - KH) // stride + 1
@@ -708,32 +774,26 @@ class _Conv2d(Function):
         x = _raw_to_cl(x)
         w = weight.detach()
         w_ohwi = w if is_channels_last(w) else _raw_dense_cl(w)
-        if x_th is not None and (sb or not _spikes_fwd_ok(
-                _hip.query("snn_conv2d_spikes_supported", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, cl_stride(x),
-                           fwd_prec, bwd_prec),
-                _halo_ok(T * B, H, W, Cin, Cout, KH, KW, stride, pad), x.data_ptr(), w_ohwi.data_ptr())):
-            # arithmetic, shape or weight alignment the thresholding kernels do not cover: the spikes are written after all
-            x = _spikes_dense(x, x_th)
-            x_th = None
+        x, x_th = _spikes_fwd_operand(x, x_th, lambda: not sb and _spikes_fwd_ok(
+            _hip.query("snn_conv2d_spikes_supported", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, cl_stride(x),
+                       fwd_prec, bwd_prec),
+            _halo_ok(T * B, H, W, Cin, Cout, KH, KW, stride, pad), x.data_ptr(), w_ohwi.data_ptr()))
         y = _out_tensor(dest, T, B, Cout, Ho, Wo, x, _BF16 if sb else None)
         partial = layout = None
         if bn_out is not None:  # a train-mode BatchNorm follows: its statistics come out of this kernel's epilogue
             n_part = _hip.query("snn_conv2d_fwd_bn_partial_size", T * B, B, Ho, Wo, Cout)
             partial = torch.empty((n_part,), device=x.device, dtype=torch.float64)
             layout = (ctypes.c_int * 2)()
-        # FlatTrainer keeps a pre-split image of the weights (valid while the version counter matches): ready-made pieces
+        # FlatTrainer keeps a pre-split image of the weights: ready-made pieces
         w16 = None
-        if (fwd_prec == _hip.PREC_FP16X3 and USE_PRESPLIT_WEIGHTS and w_ohwi is w
-                and getattr(weight, "_snn_w16", None) is not None and weight._snn_wt_version == weight._version):
-            w16 = weight._snn_w16.data_ptr()   # a tensor view on the parameter: alive as long as the parameter is
+        if fwd_prec == _hip.PREC_FP16X3 and USE_PRESPLIT_WEIGHTS and w_ohwi is w:
+            w16 = _ptr(_kept_view(weight, "_snn_w16"))
         halo = (_halo_ok(T * B, H, W, Cin, Cout, KH, KW, stride, pad)
                 and _halo_operand_ok(x.data_ptr(), cl_stride(x), x.dtype == _BF16))
         if halo and fwd_prec in (_hip.PREC_FP16X3, _hip.PREC_BF16S):
             # the image holds fp16 pieces (fp16 x 3) or bf16 pieces (bf16 storage: the hi pieces are the rounded weights)
             img_prec = _hip.PREC_BF16X3 if sb else _hip.PREC_FP16X3
-            img = _cached_image(weight, "_snn_wfrag") if w_ohwi is w else None
-            if img is not None and getattr(weight, "_snn_wfrag_prec", _hip.PREC_FP16X3) != img_prec:
-                img = None
+            img = _kept_view(weight, "_snn_wfrag", img_prec) if w_ohwi is w else None
             if img is None:
                 img = _frag_image(w_ohwi, Cout, Cin, 0, img_prec)
             if x_th is not None:
@@ -754,7 +814,7 @@ class _Conv2d(Function):
         ctx.prec = bwd_prec
         ctx.x_th = x_th
         ctx.save_for_backward(x, w_ohwi)
-        ctx.weight_ref = weight if getattr(weight, "_snn_wt", None) is not None else None  # FlatTrainer's cached w^T
+        ctx.weight = weight   # (FlatTrainer's w^T views, _kept_view)
         ctx.geom = (T, B, Cin, H, W, Cout, KH, KW, Ho, Wo, stride, pad)
         ctx.slot = slot
         ctx.acc = acc
@@ -776,65 +836,44 @@ class _Conv2d(Function):
             if fused:
                 # dy is formed while the weight-gradient kernel reads gx and y: no apply pass, no dy tensor
                 splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ctx.prec)
-                main = torch.cuda.current_stream()
-                on_side = USE_WGRAD_STREAM
-                stream = _side_stream(x.device) if on_side else main
-                if on_side:
-                    _side_retire(main, WGRAD_SIDE_DEPTH)
-                    stream.wait_stream(main)
-                with torch.cuda.stream(stream):
-                    ws = torch.empty((splitk, Cout * KH * KW * Cin), device=x.device, dtype=_F32)
+                with _WgradLaunch(x.device, True, splitk, Cout, KH * KW * Cin,
+                                   hold=(x, pend.gx, pend.y, pend.coef)) as (stream, ws, _):
                     _hip.call("snn_conv2d_wgrad_bn", x.data_ptr(), ldx, pend.gx.data_ptr(), Cout, pend.y.data_ptr(),
                               cl_stride(pend.y), pend.coef.data_ptr(), T, B, ctx.slot.buf.data_ptr(), T * B, H, W, Cin, Ho,
-                              Wo, Cout, KH, KW, stride, pad, ctx.slot.claim(), ws.data_ptr(), splitk, stream.cuda_stream)
-                if on_side:
-                    _side_hold(stream, x, pend.gx, pend.y, pend.coef)
+                              Wo, Cout, KH, KW, stride, pad, ctx.slot.claim(), ws.data_ptr(), splitk, stream)
                 return None, None, None, None, None, None, None, None, None, None
             _apply_pending(pend)   # this convolution takes a materialised dy after all
         if ctx.needs_input_grad[0]:
-            wref = ctx.weight_ref
+            wt = _kept_view(ctx.weight, "_snn_wt")   # transposed once per optimiser step for all layers (FlatTrainer)
             wt16 = wt_img = None
-            if wref is not None and wref._snn_wt_version == wref._version:
-                wt = wref._snn_wt  # transposed once per optimiser step for all layers (trainer.FlatTrainer)
-                wt_img = getattr(wref, "_snn_wtfrag", None)   # ... and arranged for the halo-resident data gradient
+            if wt is not None:
+                wt_img = _kept_view(ctx.weight, "_snn_wtfrag")   # ... and arranged for the halo-resident data gradient
                 if ctx.prec == _hip.PREC_BF16X3 and USE_PRESPLIT_WEIGHTS and USE_PRESPLIT_DGRAD:
-                    wt16 = _ptr(getattr(wref, "_snn_wt16", None))   # ... and pre-split into its bf16 pieces
+                    wt16 = _ptr(_kept_view(ctx.weight, "_snn_wt16"))   # ... and pre-split into its bf16 pieces
             else:
                 wt = torch.empty((Cin, KH, KW, Cout), device=x.device, dtype=_F32)
                 _hip.call("snn_weight_transpose", w_ohwi.data_ptr(), wt.data_ptr(), Cout, KH, KW, Cin, st)
             dx = _dgrad_accumulate(ctx.acc, gy, ldg, wt, x, ctx.geom, st, ctx.prec, wt_split=wt16, wt_image=wt_img)
         if ctx.needs_input_grad[1]:
             splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ctx.prec)
-            xw, ldxw, x_th = x, ldx, ctx.x_th
-            if x_th is not None and not _spikes_wgrad_ok(x.data_ptr(), ldx, gy.data_ptr(), ldg):
-                xw, x_th = _spikes_dense(x, x_th), None   # (same bits: the plain kernel on the stored spikes)
-                ldxw = cl_stride(xw)
-
-            def wgrad(dst_ptr, accumulate, ws_, stream_ptr):
-                if x_th is not None:   # x holds potentials: thresholded on load
-                    _hip.call("snn_conv2d_spikes_wgrad", xw.data_ptr(), ldxw, x_th, gy.data_ptr(), ldg, dst_ptr, T * B, H,
-                              W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, accumulate, ws_.data_ptr(), splitk, stream_ptr)
+            xw, ldxw, x_th = _spikes_wgrad_operand(x, ldx, ctx.x_th, gy, ldg)
+            slot = ctx.slot
+            with _WgradLaunch(x.device, slot is not None, splitk, Cout, KH * KW * Cin,
+                              hold=(x, xw, gy)) as (stream, ws, _):
+                if slot is not None:
+                    dst, accumulate = slot.buf, slot.claim()
                 else:
-                    _hip.call("snn_conv2d_wgrad", xw.data_ptr(), ldxw, gy.data_ptr(), ldg, dst_ptr, T * B, H, W, Cin, Ho, Wo,
-                              Cout, KH, KW, stride, pad, accumulate, ws_.data_ptr(), splitk, ctx.prec, stream_ptr)
-            if ctx.slot is not None and USE_WGRAD_STREAM:
-                # gradient goes straight into the flat buffer: nothing downstream in autograd needs it, so
-                # the kernel runs on the side stream, concurrently with the data-gradient chain
-                main, side = torch.cuda.current_stream(), _side_stream(x.device)
-                _side_retire(main, WGRAD_SIDE_DEPTH)   # the weight gradient before the previous one is joined; its operands go
-                side.wait_stream(main)  # gy (and every earlier use of the slot) is complete
-                with torch.cuda.stream(side):
-                    ws = torch.empty((splitk, Cout * KH * KW * Cin), device=x.device, dtype=_F32)
-                    wgrad(ctx.slot.buf.data_ptr(), ctx.slot.claim(), ws, side.cuda_stream)
-                _side_hold(side, x, xw, gy)
-            elif ctx.slot is not None:
-                ws = torch.empty((splitk, Cout * KH * KW * Cin), device=x.device, dtype=_F32)
-                wgrad(ctx.slot.buf.data_ptr(), ctx.slot.claim(), ws, st)
-            else:
-                ws = torch.empty((splitk, Cout * KH * KW * Cin), device=x.device, dtype=_F32)
-                dw_ohwi = torch.empty((Cout, KH, KW, Cin), device=x.device, dtype=_F32)
-                wgrad(dw_ohwi.data_ptr(), 0, ws, st)
-                dw = dw_ohwi.permute(0, 3, 1, 2)
+                    dst, accumulate = torch.empty((Cout, KH, KW, Cin), device=x.device, dtype=_F32), 0
+                if x_th is not None:   # x holds potentials: thresholded on load
+                    _hip.call("snn_conv2d_spikes_wgrad", xw.data_ptr(), ldxw, x_th, gy.data_ptr(), ldg, dst.data_ptr(),
+                              T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, accumulate, ws.data_ptr(), splitk,
+                              stream)
+                else:
+                    _hip.call("snn_conv2d_wgrad", xw.data_ptr(), ldxw, gy.data_ptr(), ldg, dst.data_ptr(), T * B, H, W,
+                              Cin, Ho, Wo, Cout, KH, KW, stride, pad, accumulate, ws.data_ptr(), splitk, ctx.prec,
+                              stream)
+            if slot is None:
+                dw = dst.permute(0, 3, 1, 2)
         return dx, dw, None, None, None, None, None, None, None, None
 
 
@@ -847,113 +886,6 @@ def _small_gemm(a: torch.Tensor, trans_a: bool, b: torch.Tensor, trans_b: bool, 
     ct_ptr, ldct = (None, 0) if ct is None else (ct.data_ptr() + 4 * ct_col, ct.shape[1])
     _hip.call("snn_small_gemm", a.data_ptr(), a.shape[1], int(trans_a), b.data_ptr(), b.shape[1], int(trans_b),
               c.data_ptr(), n, m, n, k, int(accumulate), ct_ptr, ldct, _stream())
-
-
-class _ComposedConv1x1(Function):
-    """``conv1x1(conv1x1(x, w1), w2)`` without the intermediate tensor (no Norm / neuron between the two: the C2f
-    entry ``Conv(c, 1)`` followed by the branch-opening ``Conv(c/2, 1)`` of ``models/tiny_yolo.py:76-82``).
-
-    Both maps are linear, so ``y = (w2 w1) x``.  Forward runs ONE 1x1 convolution with the composed weight; backward
-    needs neither ``conv(x, w1)`` nor its gradient: with ``G = sum_pixels gy x^T`` (one weight-gradient kernel),
-    ``dw2 = G w1^T``, ``dw1 = w2^T G`` and ``dx = conv^T(gy, w2 w1)``.  The composed weight is rounded once in fp32
-    (a re-association of the reference's two fp32 sums, same error level as any other summation order).
-    """
-
-    @staticmethod
-    def forward(ctx, x, w1, w2, slot1, slot2, dest, acc, prec=None):
-        _require_device(x, "conv2d input", bf16_ok=True)
-        fwd_prec, bwd_prec = prec if prec is not None else _prec_codes(None, None)
-        if x.dtype == _BF16:
-            fwd_prec = bwd_prec = _hip.PREC_BF16S
-        T, B, Cin, H, W = _dims5(x)
-        C1, C2 = w1.shape[0], w2.shape[0]
-        if w1.shape[1] != Cin or w2.shape[1] != C1 or tuple(w1.shape[2:]) != (1, 1) or tuple(w2.shape[2:]) != (1, 1):
-            raise RuntimeError("composed 1x1 convolution: weight shapes do not chain")
-        x = _raw_to_cl(x)
-        w1m = w1.detach().reshape(C1, Cin)
-        w2m = w2.detach().reshape(C2, C1)
-        if not (w1m.is_contiguous() and w2m.is_contiguous()):
-            w1m, w2m = w1m.contiguous(), w2m.contiguous()
-        # FlatTrainer composes every registered pair once per optimiser step in ONE launch (snn_small_gemm_batched); the
-        # pair registers itself here on first use (w2._snn_compose_with) and is served from the next refresh on, while the
-        # version counters of both weights still match.  Same fmaf chains, same bits as the per-call product.
-        cached = getattr(w2, "_snn_composed", None)
-        if (cached is not None and cached[0] is w1 and cached[1] == (w1._version, w2._version)
-                and tuple(cached[2].shape) == (C2, Cin)):
-            wc, wct = cached[2], cached[3]
-        else:
-            if getattr(w1, "_snn_wt", None) is not None and getattr(w2, "_snn_wt", None) is not None:
-                w2._snn_compose_with = w1   # both live in a FlatTrainer's flat buffer
-            wc = torch.empty((C2, Cin), device=x.device, dtype=_F32)   # w2 w1: [C2, Cin] = OHWI of a 1x1 kernel
-            # ... and (w2 w1)^T, the operand of the data gradient, out of the same launch (same fmaf chains: the bits a
-            # separate w1^T w2^T product would give)
-            wct = torch.empty((Cin, C2), device=x.device, dtype=_F32) if ctx.needs_input_grad[0] else None
-            _small_gemm(w2m, False, w1m, False, wc, 0, ct=wct)
-        y = _out_tensor(dest, T, B, C2, H, W, x)
-        _hip.call("snn_conv2d_fwd", x.data_ptr(), cl_stride(x), wc.data_ptr(), None, y.data_ptr(), cl_stride(y), T * B,
-                  H, W, Cin, H, W, C2, 1, 1, 1, 0, None, 0, None, 0, None, fwd_prec, _stream())
-        ctx.prec = bwd_prec
-        ctx.save_for_backward(x, w1m, w2m, wc)
-        ctx.wct = wct
-        ctx.geom = (T, B, Cin, H, W, C2, 1, 1, H, W, 1, 0)
-        ctx.c1 = C1
-        ctx.slots = (slot1, slot2)
-        ctx.acc = acc
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w1m, w2m, wc = ctx.saved_tensors
-        T, B, Cin, H, W, C2 = ctx.geom[:6]
-        C1 = ctx.c1
-        gy = _raw_to_cl(gy)
-        ldg, ldx = cl_stride(gy), cl_stride(x)
-        st = _stream()
-        dx = dw1 = dw2 = None
-        if ctx.needs_input_grad[0]:
-            wct = ctx.wct   # (w2 w1)^T = w1^T w2^T: transposed 1x1 weight, left by the forward pass
-            dx = _dgrad_accumulate(ctx.acc, gy, ldg, wct, x, ctx.geom, st, ctx.prec)
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            slot1, slot2 = ctx.slots
-            slotted = slot1 is not None and slot2 is not None
-            splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, H, W, C2, 1, 1, 1, 0, ctx.prec)
-            side_ok = slotted and USE_WGRAD_STREAM
-            main = torch.cuda.current_stream()
-            stream = _side_stream(x.device) if side_ok else main
-            if side_ok:
-                _side_retire(main, WGRAD_SIDE_DEPTH)
-                stream.wait_stream(main)
-            with torch.cuda.stream(stream):
-                ws = torch.empty((splitk, C2 * Cin), device=x.device, dtype=_F32)
-                G = torch.empty((C2, Cin), device=x.device, dtype=_F32)
-                _hip.call("snn_conv2d_wgrad", x.data_ptr(), ldx, gy.data_ptr(), ldg, G.data_ptr(), T * B, H, W, Cin, H,
-                          W, C2, 1, 1, 1, 0, 0, ws.data_ptr(), splitk, ctx.prec, stream.cuda_stream)
-                # dw2 = G w1^T [C2, C1], dw1 = w2^T G [C1, Cin]: straight into the flat gradient slots when there are any
-                if slotted:
-                    g2, g1 = slot2.buf.view(C2, C1), slot1.buf.view(C1, Cin)
-                    acc2, acc1 = slot2.claim(), slot1.claim()
-                else:
-                    g2 = torch.empty((C2, C1), device=x.device, dtype=_F32)
-                    g1 = torch.empty((C1, Cin), device=x.device, dtype=_F32)
-                    acc2 = acc1 = 0
-                _small_gemm(G, False, w1m, True, g2, acc2)
-                _small_gemm(w2m, True, G, False, g1, acc1)
-            if side_ok:
-                _side_hold(stream, x, gy)
-            if not slotted:
-                dw1, dw2 = g1.view(C1, Cin, 1, 1), g2.view(C2, C1, 1, 1)
-        return dx, dw1, dw2, None, None, None, None, None
-
-
-def composed_conv1x1(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, dest: Optional[Dest] = None,
-                     forward_precision: Optional[str] = None, backward_precision: Optional[str] = None) -> torch.Tensor:
-    if x.dtype == _BF16 and (w1.shape[1] % 32 or w2.shape[0] % 32):   # (see conv2d)
-        y = to_bfloat16(composed_conv1x1(to_float32(x), w1, w2, None, forward_precision, backward_precision))
-        return place(y, dest) if dest is not None else y
-    seq, single = as_sequence(x)
-    y = _ComposedConv1x1.apply(seq, w1, w2, _slot_of(w1), _slot_of(w2), dest, _acc_of(seq),
-                               _prec_codes(forward_precision, backward_precision))
-    return y[0] if single else y
 
 
 class _SplitChannels(Function):
@@ -1013,24 +945,56 @@ def split_channels(x: torch.Tensor, widths: Sequence[int]) -> List[torch.Tensor]
     return list(_SplitChannels.apply(x, tuple(int(c) for c in widths)))
 
 
+# FlatTrainer builds the stacked (composed) weight of every registered group and its transpose once per optimiser step,
+# all groups in ONE launch (snn_small_gemm_batched, trainer.FlatTrainer._refresh_composed).  Both the registration and
+# the product live on the group's first w2 and are keyed by the WHOLE group (``_group_key``): a group registers itself on
+# first use (``w2s[0]._snn_sibling_group[key] = (w1, w2s)``) and the trainer fills ``w2s[0]._snn_sibling_weight[key] =
+# (w1, w2s, version counters, [w2_0; w2_1; ...] w1, its transpose)``.  The same w2a opens a two-branch group in a training
+# step and a one-branch group (``composed_conv1x1``) in a streaming prediction: two entries side by side.
+def _group_key(w1: torch.Tensor, w2s: Sequence[torch.Tensor]) -> Tuple[int, ...]:
+    return (id(w1),) + tuple(id(w) for w in w2s)
+
+
+def _group_versions(w1: torch.Tensor, w2s: Sequence[torch.Tensor]) -> Tuple[int, ...]:
+    return tuple(w._version for w in w2s) + (w1._version,)
+
+
+def _kept_product(w1: torch.Tensor, w2s: Sequence[torch.Tensor], shape: Tuple[int, int]):
+    """``(wc, wct)``: FlatTrainer's product of this group while every version counter matches, else None (same fmaf
+    chains, same bits as the per-call product)."""
+    kept = getattr(w2s[0], "_snn_sibling_weight", None)
+    entry = kept.get(_group_key(w1, w2s)) if kept is not None else None
+    if entry is None:
+        return None
+    k1, k2s, versions, wc, wct = entry
+    if (k1 is w1 and all(a is b for a, b in zip(k2s, w2s)) and versions == _group_versions(w1, w2s)
+            and tuple(wc.shape) == shape):
+        return wc, wct
+    return None
+
+
 class _SiblingConv1x1(Function):
     """Several plain 1x1 convolutions of ONE input as one convolution with the row-stacked weight - the two
     ``Conv(c/2, 1)`` that open the branches of a C2f block (``models/tiny_yolo.py:84-85``), whose outputs sit side by side
     in the block's Dense merge - optionally each composed with a shared 1x1 convolution in front (``w1``: the C2f entry
-    ``Conv(c, 1)``, see ``_ComposedConv1x1``).  The input is read once instead of once per branch; backward is ONE data
-    gradient (instead of two chained through an addend: one read and one write of dx less) and ONE pixel reduction
-    ``G = sum gy x^T`` whose row blocks give the branches' weight gradients (``dw2_b = G_b w1^T``, ``dw1 = sum_b w2_b^T G_b``).
+    ``Conv(c, 1)``, ``models/tiny_yolo.py:76-82``, with no Norm / neuron in between).  The input is read once instead of
+    once per branch; backward is ONE data gradient (instead of two chained through an addend: one read and one write of
+    dx less) and ONE pixel reduction ``G = sum gy x^T`` whose row blocks give the branches' weight gradients.
     Arithmetic per output element is that of the separate convolutions (the same k-ordered products); only ``dw1`` sums its
-    branch contributions in another order."""
+    branch contributions in another order.
+
+    Composition: both maps are linear, so ``y_b = (w2_b w1) x``.  Forward runs the convolution with the composed weight;
+    backward needs neither ``conv(x, w1)`` nor its gradient: ``dw2_b = G_b w1^T``, ``dw1 = sum_b w2_b^T G_b`` and
+    ``dx = conv^T(gy, [w2_0; w2_1; ...] w1)``.  The composed weight is rounded once in fp32 (a re-association of the
+    reference's two fp32 sums, same error level as any other summation order).  With one ``w2`` this is
+    ``composed_conv1x1``."""
 
     @staticmethod
     def forward(ctx, x, w1, dest, acc, prec, slot1, slots2, x_th, *w2s):
         """``x_th`` (not None): ``x`` holds the saved potentials of the LIF layer in front (``affine_neuron(spikes_ok=True)``),
         the operand is ``z = (x > x_th)``."""
         _require_device(x, "conv2d input", bf16_ok=True)
-        fwd_prec, bwd_prec = prec if prec is not None else _prec_codes(None, None)
-        if x.dtype == _BF16:
-            fwd_prec = bwd_prec = _hip.PREC_BF16S
+        fwd_prec, bwd_prec = _conv_precs(prec, x.dtype == _BF16)
         T, B, Cin, H, W = _dims5(x)
         C1 = w1.shape[0] if w1 is not None else Cin
         widths = [int(w.shape[0]) for w in w2s]
@@ -1043,19 +1007,18 @@ class _SiblingConv1x1(Function):
         x = _raw_to_cl(x)
         w1m = None if w1 is None else w1.detach().reshape(C1, Cin).contiguous()
         w2ms = [w.detach().reshape(c, C1).contiguous() for w, c in zip(w2s, widths)]
-        # FlatTrainer builds the stacked (composed) weight and its transpose once per optimiser step, in its batched GEMM
-        # launch; the group registers itself here on first use (w2s[0]._snn_sibling_group)
         need_t = ctx.needs_input_grad[0]
-        cached = getattr(w2s[0], "_snn_sibling_weight", None)
-        versions = tuple(w._version for w in w2s) + ((w1._version,) if w1 is not None else ())
-        if (cached is not None and cached[0] is w1 and len(cached[1]) == len(w2s)
-                and all(a is b for a, b in zip(cached[1], w2s)) and cached[2] == versions
-                and tuple(cached[3].shape) == (Ct, Cin)):
-            wc, wct = cached[3], cached[4]
+        kept = _kept_product(w1, w2s, (Ct, Cin)) if w1 is not None else None
+        if kept is not None:
+            wc, wct = kept
         else:
             if w1 is not None and all(getattr(w, "_snn_wt", None) is not None for w in (w1, *w2s)):
-                w2s[0]._snn_sibling_group = (w1, tuple(w2s))
+                # all live in a FlatTrainer's flat buffer: the group is served from its next refresh on
+                if getattr(w2s[0], "_snn_sibling_group", None) is None:
+                    w2s[0]._snn_sibling_group = {}
+                w2s[0]._snn_sibling_group[_group_key(w1, w2s)] = (w1, tuple(w2s))
             wc = torch.empty((Ct, Cin), device=x.device, dtype=_F32)
+            # ... and the transpose, the operand of the data gradient, out of the same launches (same fmaf chains)
             wct = torch.empty((Cin, Ct), device=x.device, dtype=_F32) if need_t else None
             row = 0
             for w2m, c in zip(w2ms, widths):
@@ -1067,13 +1030,9 @@ class _SiblingConv1x1(Function):
             if w1m is None and need_t:
                 wct.copy_(wc.t())
         y = _out_tensor(dest, T, B, Ct, H, W, x)
-        if x_th is not None and not _spikes_fwd_ok(
-                _hip.query("snn_conv1x1_spikes_supported", T * B, H, W, Cin, Ct, cl_stride(x), fwd_prec, bwd_prec), False,
-                x.data_ptr(), wc.data_ptr()):
-            # (arithmetic, shape or weight alignment the thresholding kernels do not cover: the spikes are materialised
-            # after all)
-            x = _spikes_dense(x, x_th)
-            x_th = None
+        x, x_th = _spikes_fwd_operand(x, x_th, lambda: _spikes_fwd_ok(
+            _hip.query("snn_conv1x1_spikes_supported", T * B, H, W, Cin, Ct, cl_stride(x), fwd_prec, bwd_prec), False,
+            x.data_ptr(), wc.data_ptr()))
         if x_th is not None:
             _hip.call("snn_conv1x1_spikes_fwd", x.data_ptr(), cl_stride(x), x_th, wc.data_ptr(), y.data_ptr(), cl_stride(y),
                       T * B, H, W, Cin, Ct, _stream())
@@ -1098,34 +1057,23 @@ class _SiblingConv1x1(Function):
         composed = w1m is not None
         gy = _raw_to_cl(gy)
         ldg, ldx = cl_stride(gy), cl_stride(x)
-        st = _stream()
         dx = dw1 = None
         dw2s = [None] * len(widths)
         if ctx.needs_input_grad[0]:
-            dx = _dgrad_accumulate(ctx.acc, gy, ldg, ctx.wct, x, ctx.geom, st, ctx.prec)
+            dx = _dgrad_accumulate(ctx.acc, gy, ldg, ctx.wct, x, ctx.geom, _stream(), ctx.prec)
         if any(ctx.needs_input_grad[8:]) or (composed and ctx.needs_input_grad[1]):
             slot1, slots2 = ctx.slot1, ctx.slots2
             slotted = all(s_ is not None for s_ in slots2) and (slot1 is not None or not composed)
             splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, H, W, Ct, 1, 1, 1, 0, ctx.prec)
-            xw, ldxw, x_th = x, ldx, ctx.x_th
-            if x_th is not None and not _spikes_wgrad_ok(x.data_ptr(), ldx, gy.data_ptr(), ldg):
-                xw, x_th = _spikes_dense(x, x_th), None   # (same bits: the plain kernel on the stored spikes)
-                ldxw = cl_stride(xw)
-            side_ok = slotted and USE_WGRAD_STREAM
-            main = torch.cuda.current_stream()
-            stream = _side_stream(x.device) if side_ok else main
-            if side_ok:
-                _side_retire(main, WGRAD_SIDE_DEPTH)
-                stream.wait_stream(main)
-            with torch.cuda.stream(stream):
-                ws = torch.empty((splitk, Ct * Cin), device=x.device, dtype=_F32)
-                G = torch.empty((Ct, Cin), device=x.device, dtype=_F32)
+            xw, ldxw, x_th = _spikes_wgrad_operand(x, ldx, ctx.x_th, gy, ldg)
+            with _WgradLaunch(x.device, slotted, splitk, Ct, Cin, hold=(x, xw, gy), with_g=True) as (stream, ws, G):
                 if x_th is not None:   # x holds the potentials of the LIF layer in front: thresholded on load
                     _hip.call("snn_conv1x1_spikes_wgrad", xw.data_ptr(), ldxw, x_th, gy.data_ptr(), ldg, G.data_ptr(),
-                              T * B, H, W, Cin, Ct, 0, ws.data_ptr(), splitk, stream.cuda_stream)
+                              T * B, H, W, Cin, Ct, 0, ws.data_ptr(), splitk, stream)
                 else:
-                    _hip.call("snn_conv2d_wgrad", xw.data_ptr(), ldxw, gy.data_ptr(), ldg, G.data_ptr(), T * B, H, W, Cin, H,
-                              W, Ct, 1, 1, 1, 0, 0, ws.data_ptr(), splitk, ctx.prec, stream.cuda_stream)
+                    _hip.call("snn_conv2d_wgrad", xw.data_ptr(), ldxw, gy.data_ptr(), ldg, G.data_ptr(), T * B, H, W,
+                              Cin, H, W, Ct, 1, 1, 1, 0, 0, ws.data_ptr(), splitk, ctx.prec, stream)
+                # straight into the flat gradient slots when there are any
                 g1 = None
                 if composed:
                     g1 = slot1.buf.view(C1, Cin) if slotted else torch.empty((C1, Cin), device=x.device, dtype=_F32)
@@ -1150,8 +1098,6 @@ class _SiblingConv1x1(Function):
                         dw2s[b] = g2.view(c, C1, 1, 1)
                 if composed and not slotted:
                     dw1 = g1.view(C1, Cin, 1, 1)
-            if side_ok:
-                _side_hold(stream, x, xw, gy)
         return (dx, dw1, None, None, None, None, None, None, *dw2s)
 
 
@@ -1162,6 +1108,20 @@ def sibling_conv1x1(x: torch.Tensor, w1: Optional[torch.Tensor], w2s: Sequence[t
     return _SiblingConv1x1.apply(x, w1, dest, _acc_of(x), _prec_codes(forward_precision, backward_precision),
                                  _slot_of(w1), tuple(_slot_of(w) for w in w2s), getattr(x, "_snn_spike_threshold", None),
                                  *w2s)
+
+
+def composed_conv1x1(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, dest: Optional[Dest] = None,
+                     forward_precision: Optional[str] = None, backward_precision: Optional[str] = None) -> torch.Tensor:
+    """``conv1x1(conv1x1(x, w1), w2)`` without the intermediate tensor: the sibling convolution with one branch (the
+    C2f entry in front of ONE branch-opening convolution: a block without sibling fusion, or a single timestep
+    ``[B,C,H,W]``).  ``x`` never holds saved potentials here (``generator.BlockGen`` plans none in front)."""
+    if x.dtype == _BF16 and (w1.shape[1] % 32 or w2.shape[0] % 32):   # (see conv2d)
+        y = to_bfloat16(composed_conv1x1(to_float32(x), w1, w2, None, forward_precision, backward_precision))
+        return place(y, dest) if dest is not None else y
+    seq, single = as_sequence(x)
+    y = _SiblingConv1x1.apply(seq, w1, dest, _acc_of(seq), _prec_codes(forward_precision, backward_precision),
+                              _slot_of(w1), (_slot_of(w2),), None, w2)
+    return y[0] if single else y
 
 
 class BnPartial(NamedTuple):

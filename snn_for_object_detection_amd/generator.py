@@ -166,7 +166,7 @@ class BlockGen(nn.Module):
             if (_is_plain_1x1(layer) and isinstance(nxt, BlockGen) and nxt._opens_with_1x1(layer.out_channels)
                     and not os.environ.get("SNN_NO_COMPOSED_CONV")):
                 # Conv(c,1) feeding only the branch-opening Conv(.,1)s of the next block (the C2f entry): the two
-                # linear maps are composed and the intermediate tensor never exists (functional._ComposedConv1x1)
+                # linear maps are composed and the intermediate tensor never exists (functional._SiblingConv1x1)
                 plan.append(("conv_block", idx, 2))
                 idx += 2
             elif isinstance(layer, HipBatchNorm2d) and nxt is not None and _neuron_cell(nxt) is not None:

@@ -442,6 +442,86 @@ def test_composed_1x1_weights_come_from_one_batched_launch_per_step(S):
     assert cnt3.names.count("snn_small_gemm") == n_gemm_cached + 2
 
 
+def test_training_and_streaming_composed_groups_are_kept_side_by_side(S):
+    """The C2f entry weight w1 opens a two-branch group in a training step ([w2a; w2b] w1: sibling fusion over a
+    sequence) and two one-branch groups in a streaming prediction (w2a w1 and w2b w1: composed_conv1x1 over one frame).
+    The trainer keeps all three, keyed by the whole group: after alternating training and prediction, neither kind
+    evicts the other, no composition GEMM runs per call, and the results are the bits of the per-call products."""
+    from snn_for_object_detection_amd import _hip
+    from snn_for_object_detection_amd.trainer import FlatTrainer
+    T, B, H, W = 3, 2, 32, 48
+    X, labels = synthetic_events(T, B, H, W, p=0.1).cuda(), synthetic_labels(B).cuda()
+    frames = synthetic_events(3, 1, H, W, p=0.1, seed=7)[:, 0].cuda()
+    torch.manual_seed(4)
+    model = S.TinyYolo(num_classes=2, time_window=0).cuda()
+    tr = FlatTrainer(model, lr=1e-3)
+
+    def train():
+        model.train()
+        tr.zero_grad()
+        loss = model.training_step((X, labels))
+        loss.backward()
+        S.functional.wgrad_stream_sync()
+        return loss.detach().clone(), tr.flat_grad.clone()
+
+    def leaves(s):
+        if isinstance(s, torch.Tensor):
+            return [s.clone()]
+        return [t for x in s for t in leaves(x)] if isinstance(s, (list, tuple)) else []
+
+    def predict():                          # -> the detections of every frame and the detector state after the last
+        model.eval()
+        st, out = None, []
+        with torch.no_grad():
+            for f in frames:
+                det, st = model.predict(f, st)
+                out.append(det.clone())
+        return out + leaves(st)
+
+    def gemms(fn):
+        names = []
+
+        class Count:
+            def before(self, name, args):
+                names.append(name)
+
+            def after(self, token):
+                pass
+
+        _hip.PROFILER = Count()
+        try:
+            out = fn()
+        finally:
+            _hip.PROFILER = None
+        return out, names.count("snn_small_gemm")
+
+    train()
+    tr.step()                               # composes the two-branch groups
+    predict()                               # registers the one-branch groups
+    train()
+    tr.step()                               # composes all of them in one launch
+    heads = [p for p in model.parameters() if getattr(p, "_snn_sibling_weight", None) is not None]
+    assert len(heads) == 10                 # w2a and w2b of every C2f block
+    # per block: (w1, w2a, w2b) and (w1, w2a) kept on w2a, (w1, w2b) on w2b
+    assert sorted(len(key) for p in heads for key in p._snn_sibling_weight) == [2] * 10 + [3] * 5
+    buffers = [b.clone() for b in model.buffers()]
+    dets_kept, n_predict = gemms(predict)
+    (loss_kept, grad_kept), n_train = gemms(train)
+    assert n_predict == 0                   # every one-branch group served from the trainer
+    for p in heads:
+        del p._snn_sibling_weight           # the per-call composition again
+    with torch.no_grad():
+        for b, saved in zip(model.buffers(), buffers):
+            b.copy_(saved)                  # (the training step moved the running statistics prediction reads)
+    dets_call, n_predict_call = gemms(predict)
+    (loss_call, grad_call), n_train_call = gemms(train)
+    assert n_predict_call == len(heads) * len(frames)          # one GEMM per branch and frame came back
+    assert n_train_call == n_train + len(heads)                # ... and one per branch of the training step
+    assert len(dets_kept) == len(dets_call) > len(frames)
+    assert all(torch.equal(a, b) for a, b in zip(dets_kept, dets_call))
+    assert torch.equal(loss_kept, loss_call) and torch.equal(grad_kept, grad_call)
+
+
 @pytest.mark.gpu
 def test_side_stream_is_probed_for_a_hardware_queue_of_its_own(hip_lib):
     """HIP maps streams onto a few hardware queues; two streams on one queue serialise (the weight-gradient stream lost
