@@ -859,7 +859,6 @@ static bool out_aligned(const void* p, bool bf16) { return bf16 ? aligned8(p) : 
 static int halo_mode(int64_t N, int H, int W, int Cin, int Cout) {
     if (N <= 0 || H <= 0 || W <= 0) return 0;
     if (Cin % 32 != 0 || Cin < 32 || (Cout % 64 != 0 && Cout != 32)) return 0;
-    if (Cout == 32 && snn_tuning_env("SNN_HALO_NO_CO32")) return 0;   // tuning / bisecting aid
     if (W + 1 <= 79) {                                              // halo of a 128-cell tile: 128 + 2*PW + 2 <= 288 cells
         if (N * (int64_t)(H + 1) * (W + 1) >= 0x7fffffffLL) return 0;   // strip cells of a group in 32 bits
         return 1;

@@ -40,8 +40,6 @@ def _conv_label(name: str, a) -> str:
     if not dgrad and cin == 2 and a[12] == 3 and a[13] == 3 and cout % 4 == 0 and (cout // 4) & (cout // 4 - 1) == 0 \
             and cout <= 256 and a[16] is None:
         return "k_conv_first<2, 3, false>"  # direct row kernel of the event-frame layer
-    if a[12] == 3 and a[13] == 3 and a[14] == 1 and a[15] == 1 and oc <= 32 and oc % 4 == 0 and ic % 32 == 0:
-        return f"k_conv_direct3<32, 4, 1, {'true' if dgrad else 'false'}>"  # halo-resident 3x3 kernel
     if oc <= 32:
         tile = "32, 4, 1"
     elif oc <= 64:
@@ -65,12 +63,7 @@ def work_of(name: str, a):
         es_in = 4.0 if (cin == 2 and name == "snn_conv2d_fwd") else es   # the event frames stay fp32
         flops = 2.0 * n * ho * wo * cout * kh * kw * cin
         byts = es_in * n * h * w * cin + es * n * ho * wo * cout + 4.0 * cout * kh * kw * cin
-        label = _conv_label(name, a)
-        if sb and not label.startswith("k_conv_first"):   # bf16 storage: always the implicit GEMM (no direct-3x3 form)
-            oc = cin if name == "snn_conv2d_dgrad" else cout
-            label = (f"k_conv_gather<{'32, 4, 1' if oc <= 32 else ('64, 2, 2' if oc <= 64 else '128, 2, 2')}, "
-                     f"{'true' if name == 'snn_conv2d_dgrad' else 'false'}, true>")
-        return label + (", bf16s" if sb else ""), flops, byts
+        return _conv_label(name, a) + (", bf16s" if sb else ""), flops, byts
     if name == "snn_conv2d_wgrad":
         n, h, w, cin, ho, wo, cout, kh, kw = a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], a[13]
         sb = a[19] == PREC_BF16S

@@ -65,7 +65,7 @@ CONV_CASES = [
     (6, 30, 38, 128, 128, 3, 1),     # halo-resident, 128-wide tile, strip tiles
     (3, 60, 76, 64, 64, 3, 1),       # halo-resident, 64-wide tile
     (2, 24, 100, 64, 128, 3, 1),     # halo-resident, rectangles (W > 78)
-    (5, 33, 41, 32, 32, 3, 1),       # 32 channels: the implicit GEMM (no bf16 form of the direct 3x3 kernel)
+    (5, 33, 41, 32, 32, 3, 1),       # 32 channels: halo-resident, 32-wide tile
     (4, 24, 20, 128, 64, 1, 1),      # 1x1: implicit GEMM, pipelined weight gradient
     (7, 37, 52, 64, 128, 3, 2),      # stride 2: implicit GEMM forward, one-pass data gradient, halo weight gradient
     (3, 15, 19, 256, 128, 3, 1),     # small deep map: pipelined (not halo-resident) 3x3 weight gradient

@@ -133,9 +133,9 @@ CASES = [
     (1, 8, 7, 7, 5, 3, 2),        # odd Cin and Cout: scalar gather and scalar stores, k_conv_wgrad<scalar>
     (1, 5, 6, 96, 27, 1, 1),      # the head's class convolution: Cout = 27
     (1, 13, 11, 32, 64, 5, 2),    # 5x5 stride 2 pipelined, 42 output pixels (not a multiple of the 128-pixel tile)
-    (2, 9, 13, 64, 64, 3, 1),     # 3x3 stride 1: k_conv_direct3 (fwd, dgrad) while aligned, the implicit GEMM otherwise
+    (2, 9, 13, 64, 64, 3, 1),     # 3x3 stride 1, 64 channels: the implicit GEMM (fwd, dgrad), pipelined while aligned
 ]
-CASE_IDS = ["first", "pipe-s2", "1x1-c36", "vec-5x5", "scalar-odd", "head-c27", "pipe-5x5-s2", "direct3"]
+CASE_IDS = ["first", "pipe-s2", "1x1-c36", "vec-5x5", "scalar-odd", "head-c27", "pipe-5x5-s2", "pipe-3x3"]
 
 
 def _case_data(N, H, W, Cin, Cout, k, s, seed):
@@ -450,8 +450,9 @@ SPIKE_CASES = [
     (1, 11, 9, 64, 32, 3, 2),     # snn_conv2d_spikes_fwd: k_conv_gather XSP, stride 2
     (2, 7, 10, 32, 36, 1, 1),     # 1x1: snn_conv1x1_spikes_fwd / _wgrad
     (1, 13, 11, 32, 64, 5, 2),    # 5x5 stride 2
+    (2, 9, 13, 64, 16, 3, 1),     # 3x3 stride 1 without a halo plan (16 channels): k_conv_gather XSP, two k-steps per tap
 ]
-SPIKE_IDS = ["halo3x3", "gather-s2", "1x1", "5x5-s2"]
+SPIKE_IDS = ["halo3x3", "gather-s2", "1x1", "5x5-s2", "gather-3x3-c16"]
 V_TH = 1.0
 
 

@@ -38,11 +38,11 @@ CONV_CASES = [
     (1, 1, 8, 9, 7, 16, 1, 2),        # k=1 stride 2: three of the four dgrad stride-phase classes have no tap
     (1, 2, 4, 11, 10, 8, 3, 3),       # stride 3
     (2, 1, 128, 15, 19, 256, 3, 2),   # neck downsampling conv shape (odd sizes)
-    # halo-resident direct 3x3 kernel (<= 32 output channels, Cin % 32 == 0), 8x16 patches:
-    (2, 2, 64, 13, 21, 16, 3, 1),     # two 32-channel chunks, partial patches on both edges
-    (1, 3, 32, 8, 16, 8, 3, 1),       # exactly one patch per image, 8 output channels
-    (1, 1, 96, 5, 7, 32, 3, 1),       # image smaller than a patch, three chunks
-    (4, 3, 32, 24, 40, 32, 3, 1),     # 108 patches: the persistent blocks loop over several patches each
+    # 3x3 / stride 1 with <= 32 output channels, Cin % 32 == 0:
+    (2, 2, 64, 13, 21, 16, 3, 1),     # 16 channels: implicit GEMM
+    (1, 3, 32, 8, 16, 8, 3, 1),       # 8 channels: implicit GEMM
+    (1, 1, 96, 5, 7, 32, 3, 1),       # 96 -> 32: halo-resident forward, implicit-GEMM data gradient
+    (4, 3, 32, 24, 40, 32, 3, 1),     # 32 -> 32: halo-resident forward and data gradient
 ]
 
 
@@ -70,8 +70,8 @@ BN_EPILOGUE_CASES = [
     # T, B, Cin, H, W, Cout, k, s, kernel that takes the shape
     (3, 2, 2, 34, 46, 64, 3, 2, "first"),       # row kernel: one group of blocks per timestep
     (8, 1, 2, 10, 12, 16, 3, 1, "first"),       # fewer rows per timestep than blocks
-    (3, 2, 32, 21, 27, 32, 3, 1, "direct3"),    # patches never straddle a frame
-    (2, 3, 64, 13, 21, 16, 3, 1, "direct3"),
+    (3, 2, 32, 21, 27, 32, 3, 1, "gather"),     # 1134 rows per step, 32-wide channel tile
+    (2, 3, 64, 13, 21, 16, 3, 1, "gather"),     # 819 rows per step, 16 channels in a 32-wide tile
     (3, 2, 64, 30, 38, 64, 3, 1, "gather"),     # 2280 rows per step: 128-row tiles straddle the timesteps
     (5, 1, 64, 19, 23, 128, 3, 2, "gather"),    # 120 output pixels per step < one tile: no partials, plain pass
     (4, 3, 64, 18, 22, 128, 3, 2, "gather"),    # two channel tiles... 297 rows per step
@@ -151,7 +151,7 @@ PRESPLIT_CASES = [
     (3, 64, 31, 45, 128, 3, 2),    # stride 2: four phase classes in the data gradient
     (5, 128, 20, 24, 64, 1, 1),    # 1x1
     (2, 96, 9, 11, 36, 1, 1),      # 36 channels in a 64-wide tile (rows past Cout read offset -1)
-    (2, 32, 12, 19, 32, 3, 1),     # halo-resident direct kernel: ignores the image
+    (2, 32, 12, 19, 32, 3, 1),     # 32-wide tile
     (2, 8, 13, 9, 16, 5, 1),       # generic loader: ignores the image
 ]
 

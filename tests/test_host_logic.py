@@ -73,7 +73,7 @@ def test_c_abi_exports_every_declared_symbol(hip_lib):
     # partials a forward convolution leaves for the BatchNorm behind it: bound over the three producing kernels
     n = hip_lib.snn_conv2d_fwd_bn_partial_size(160, 5, 120, 152, 64)
     assert n >= 32 * (5 * 120 * 152 // 128 + 1) * 64 * 2           # >= the implicit-GEMM layout (128-row tiles)
-    assert n >= 32 * 5 * 15 * 10 * 64 * 2                           # >= the 8x16-patch layout of the direct kernel
+    assert n >= 32 * hip_lib.snn_conv3x3_halo_bn_chunks(5, 120, 152) * 64 * 2   # >= the halo-resident layout (4 x 32 rectangles)
     assert hip_lib.snn_conv2d_fwd_bn_partial_size(160, 7, 120, 152, 64) == 0   # frames per step must divide N
     # ... and the halo-resident 3x3 kernel's layout (strip tiles of 128 cells per timestep), where that kernel applies
     assert hip_lib.snn_conv3x3_halo_supported(160, 30, 38, 128, 128) == 1
