@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SNN_ABI_VERSION 16
+#define SNN_ABI_VERSION 17
 
 /* neuron kinds for the fused affine+neuron temporal scan */
 enum {
@@ -270,6 +270,38 @@ int snn_conv2d_wgrad_splitk(int64_t N, int H, int W, int Cin, int Ho, int Wo, in
  * (k_conv_wgrad_halo), 2 event-frame row kernel (k_conv_first); host-only - labels of the measurement tools */
 int snn_conv2d_wgrad_kernel(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
                             int precision);
+/* Host-only plan queries of the implicit-GEMM kernels (k_conv_gather; k_conv_wgrad_pipe / k_conv_wgrad and the slab
+ * reducers): they read the plan functions the launches read and are callable without a device.  `align_bits` carries what a
+ * launch derives from its pointers: 1 / 2 the gathered tensor (x; dy of a data gradient) is 16- / 8-byte aligned, 4 the
+ * weight matrix is 16-byte aligned, 8 / 16 the produced tensor (y, dx; for snn_conv2d_wgrad_plan: dy) is 16- / 8-byte
+ * aligned, 32 / 64 the first addend is 16- / 8-byte aligned AND its pixel stride a multiple of 4 (snn_conv2d_wgrad_plan: 32 =
+ * dw and the workspace are 16-byte aligned), 128 / 256 the same for the second addend, 512 the pre-split weight image is
+ * 16-byte aligned; 1023 = everything aligned.  The 8-byte bits matter for SNN_PREC_BF16S only.
+ *   snn_conv2d_gather_plan : mode 0 snn_conv2d_fwd, 1 one stride phase of snn_conv2d_dgrad (phase = ph * min(stride, W) + pw,
+ *       the launch order), 2 snn_conv2d_spikes_fwd; geometry arguments as for those calls, ld_in / ld_out the pixel strides
+ *       of the gathered / produced tensor; frames_per_step > 0: a forward with statistics partials.  out[17] = { ok, loader
+ *       (0 scalar, 1 16-byte vectors, 2 pipelined buffer loads, 3 the same with the pre-split weight image, 4 bf16 storage,
+ *       5 spike operand), output channels per block (32, 64, 128), out_vec (16-byte stores), pixel tiles of 128, pixel
+ *       tiles per XCD share, channel tiles, blocks (= 8 * tiles per share * channel tiles), idle blocks past the last
+ *       tile, nkh, nkw (taps of this phase; KH, KW forward), k extent of this phase, OHc, OWc (pixel rows / columns of this
+ *       phase), phases of the call, statistics chunks per timestep, rows per chunk (0, 0: no partials from this kernel) }.
+ *       Returns 0, or 1 (out[0] = 0) for a call the entry point refuses or hands to another kernel (the event-frame
+ *       layer: snn_conv_first_plan).
+ *   snn_conv2d_wgrad_plan : snn_conv2d_wgrad (spikes = 1: snn_conv2d_spikes_wgrad) on a device with num_cu compute units
+ *       (0: the current device's; 256 without one) with splitk = snn_conv2d_wgrad_splitk.  out[18] = { ok, kernel (0
+ *       pipelined k_conv_wgrad_pipe, 1 vectorised k_conv_wgrad, 2 scalar k_conv_wgrad, 3 halo-resident, 4 event-frame row
+ *       kernel), tile id, bm, bn (block tile over Cout x (tap, ci)), tiles over Cout, tiles over (tap, ci), pixels per LDS
+ *       stage (32 / 64), splitk, pixels per split, pixels of the last split that owns any, splits that own none (zero
+ *       slabs), reducer (0 k_wgrad_reduce, 1 k_wgrad_reduce_once, 2 k_wgrad_reduce4 in two passes, 3 in one pass), KG
+ *       (thread groups sharing an element's slabs), non-empty row groups, slab rows per group, reducer blocks, grid of the
+ *       convolution kernel }.  For kernels 3 / 4 only splitk and the reducer fields are filled (snn_conv2d_wgrad_halo_plan /
+ *       snn_conv_first_plan describe the rest; whether the halo-resident kernel can address the buffers is the launch's
+ *       check - if not, the implicit GEMM runs with the same splitk).  Returns 0, or 1 (out[0] = 0) for a refused call. */
+int snn_conv2d_gather_plan(int mode, int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride,
+                           int pad, int64_t ld_in, int64_t ld_out, int align_bits, int has_split_image, int has_addend,
+                           int has_addend2, int frames_per_step, int precision, int phase, int* out);
+int snn_conv2d_wgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
+                          int64_t ldx, int64_t lddy, int align_bits, int precision, int spikes, int num_cu, int* out);
 /* ---- 1x1 convolutions over spikes that were never stored.  The stage-entry layers of the generated nets are
  * Conv -> Norm -> LIF feeding only 1x1 convolutions (reference models/tiny_yolo.py:76-85 behind :16-21); their LIF
  * (models/modules/layer_gen.py:232-235) saves v_dec for its backward pass anyway, so the spike tensor z = (v_dec > v_th)

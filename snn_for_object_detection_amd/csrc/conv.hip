@@ -1501,60 +1501,128 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
+// Alignment facts a launch derives from its pointers and strides (the `align_bits` of the host-only plan queries): a
+// tensor counts as vectorisable when its pointer is 16-byte (fp32) / 8-byte (bf16 storage) aligned; for an addend the bit
+// also requires a pixel stride that is a multiple of 4 elements.
+enum : unsigned {
+    kAlignIn16 = 1u, kAlignIn8 = 2u, kAlignW16 = 4u, kAlignOut16 = 8u, kAlignOut8 = 16u, kAlignAdd16 = 32u, kAlignAdd8 = 64u,
+    kAlignAdd2_16 = 128u, kAlignAdd2_8 = 256u, kAlignSplit16 = 512u, kAlignAll = 1023u
+};
+
+// The launch plan of k_conv_gather for one ConvGeom (the forward, or one stride phase of a data gradient), read by
+// launch_gather and by snn_conv2d_gather_plan.  ok = 0: the launch refuses the call (why: the reason).
+enum GatherLoader { kLoadScalar = 0, kLoadVec = 1, kLoadFast = 2, kLoadFastPresplit = 3, kLoadSB = 4, kLoadXSP = 5 };
+enum GatherRefusal { kGatherOk = 0, kGatherTooManyPixels, kGatherNotFastSB, kGatherNotFastXSP, kGatherGridTooLarge };
+struct GatherPlan {
+    int ok, why;
+    int loader;      // GatherLoader
+    int bn;          // output channels per block: 32, 64, 128
+    int out_vec;     // output (and addend) rows stored 16 bytes per lane
+    int mtiles, mtiles_per_xcd, ntiles;
+    int64_t blocks;  // mtiles_per_xcd * 8 * ntiles: the blocks past the last pixel tile of an XCD share return at once
+};
+static GatherPlan gather_plan(const ConvGeom& g, bool dgrad, int split, bool sb, bool xsp, unsigned align, bool has_split,
+                              bool has_add, bool has_add2) {
+    GatherPlan p = {};
+    const bool vec = (g.IC % 4 == 0) && (g.ldi % 4 == 0) && (align & (sb ? kAlignIn8 : kAlignIn16)) && (align & kAlignW16);
+    const int64_t gm = snn_ceil_div(g.Mtot, BM);
+    if (!(g.Mtot < 0x7fffffffLL && (int64_t)g.IH * g.IW < 0x7fffffffLL)) {
+        p.why = kGatherTooManyPixels;
+        return p;
+    }
+    const int nth = dgrad ? g.nkh : g.KH, ntw = dgrad ? g.nkw : g.KW;
+    const int ntaps = nth * ntw;
+    static const bool no_fast = snn_tuning_env("SNN_CONV_NO_FAST") != nullptr;  // tuning / bisecting aid
+    const bool fast = vec && !no_fast && g.IC % BK == 0 && ntaps >= 1 && ntaps <= 31 && nth <= 6 && ntw <= 6 &&
+                      (int64_t)g.IH * g.IW * g.ldi * 16 < 0x7fffffffLL && (int64_t)g.OC * g.KtotFull * 4 < 0x7fffffffLL;
+    p.out_vec = (g.ldo % 4 == 0) && (align & (sb ? kAlignOut8 : kAlignOut16)) &&
+                (!has_add || (align & (sb ? kAlignAdd8 : kAlignAdd16))) &&
+                (!has_add2 || (align & (sb ? kAlignAdd2_8 : kAlignAdd2_16)));
+    if (sb && !fast) {
+        p.why = kGatherNotFastSB;
+        return p;
+    }
+    if (xsp && !fast) {
+        p.why = kGatherNotFastXSP;
+        return p;
+    }
+    // the pre-split weight image serves the pipelined kernel in its two-piece modes; every other path converts wk itself
+    const bool presplit = has_split && (split == 2 || split == 4) && (align & kAlignSplit16);
+    p.loader = sb ? kLoadSB : xsp ? kLoadXSP : (fast && presplit) ? kLoadFastPresplit : fast ? kLoadFast : vec ? kLoadVec : kLoadScalar;
+    p.bn = g.OC <= 32 ? 32 : (g.OC <= 64 ? 64 : 128);
+    p.mtiles = (int)gm;
+    p.mtiles_per_xcd = (int)snn_ceil_div(gm, 8);
+    p.ntiles = (int)snn_ceil_div(g.OC, p.bn);
+    p.blocks = (int64_t)p.mtiles_per_xcd * 8 * p.ntiles;
+    if (p.blocks > 0x7fffffffLL) {
+        p.why = kGatherGridTooLarge;
+        return p;
+    }
+    p.ok = 1;
+    return p;
+}
+
+template <bool SB>
+static unsigned gather_align_bits(const void* in, const void* wk, const void* wk_split, const void* out, const void* addend,
+                                  int64_t ld_add, const void* addend2, int64_t ld_add2) {
+    unsigned a = 0;
+    if (aligned16(in)) a |= kAlignIn16;
+    if (aligned8(in)) a |= kAlignIn8;
+    if (aligned16(wk)) a |= kAlignW16;
+    if (aligned16(out)) a |= kAlignOut16;
+    if (aligned8(out)) a |= kAlignOut8;
+    if (addend && ld_add % 4 == 0 && aligned16(addend)) a |= kAlignAdd16;
+    if (addend && ld_add % 4 == 0 && aligned8(addend)) a |= kAlignAdd8;
+    if (addend2 && ld_add2 % 4 == 0 && aligned16(addend2)) a |= kAlignAdd2_16;
+    if (addend2 && ld_add2 % 4 == 0 && aligned8(addend2)) a |= kAlignAdd2_8;
+    if (wk_split && aligned16(wk_split)) a |= kAlignSplit16;
+    return a;
+}
+
 template <bool DGRAD, int SPLIT, bool SB = false, bool XSP = false>
 static int launch_gather(const float* in, const float* wk, const void* wk_split, float* out, const ConvGeom& g,
                          const float* addend, int64_t ld_add, const float* addend2, int64_t ld_add2, hipStream_t st,
                          const char* name) {
-    const bool vec = (g.IC % 4 == 0) && (g.ldi % 4 == 0) && (SB ? aligned8(in) : aligned16(in)) && aligned16(wk);
-    const int64_t gm = snn_ceil_div(g.Mtot, BM);
-    SNN_REQUIRE(g.Mtot < 0x7fffffffLL && (int64_t)g.IH * g.IW < 0x7fffffffLL, "%s: too many pixels", name);
-    const int ntaps = DGRAD ? g.nkh * g.nkw : g.KH * g.KW;
-    static const bool no_fast = snn_tuning_env("SNN_CONV_NO_FAST") != nullptr;  // tuning / bisecting aid
-    const bool fast = vec && !no_fast && g.IC % BK == 0 && ntaps >= 1 && ntaps <= 31 &&
-                      (DGRAD ? g.nkh : g.KH) <= 6 && (DGRAD ? g.nkw : g.KW) <= 6 &&
-                      (int64_t)g.IH * g.IW * g.ldi * 16 < 0x7fffffffLL && (int64_t)g.OC * g.KtotFull * 4 < 0x7fffffffLL;
+    const GatherPlan p = gather_plan(g, DGRAD, SPLIT, SB, XSP,
+                                     gather_align_bits<SB>(in, wk, wk_split, out, addend, ld_add, addend2, ld_add2),
+                                     wk_split != nullptr, addend != nullptr, addend2 != nullptr);
+    SNN_REQUIRE(p.why != kGatherTooManyPixels, "%s: too many pixels", name);
+    SNN_REQUIRE(p.why != kGatherNotFastSB, "%s: bf16 storage covers the pipelined implicit GEMM only (channels a multiple of 32, pixel "
+                "stride a multiple of 4, 8-byte aligned tensors): %d channels, stride %lld", name, g.IC, (long long)g.ldi);
+    SNN_REQUIRE(p.why != kGatherNotFastXSP, "%s: covers the pipelined implicit GEMM only (input channels a multiple of 32, pixel stride a "
+                "multiple of 4, 16-byte aligned tensors): %d channels, stride %lld", name, g.IC, (long long)g.ldi);
+    SNN_REQUIRE(p.why != kGatherGridTooLarge, "%s: grid too large", name);
     ConvGeom gg = g;
-    const auto avec = [](const void* p) { return SB ? aligned8(p) : aligned16(p); };   // 4 elements per access
-    gg.out_vec = (g.ldo % 4 == 0) && avec(out) && (!addend || (ld_add % 4 == 0 && avec(addend))) &&
-                 (!addend2 || (ld_add2 % 4 == 0 && avec(addend2)));
-    if constexpr (SB)
-        SNN_REQUIRE(fast, "%s: bf16 storage covers the pipelined implicit GEMM only (channels a multiple of 32, pixel "
-                    "stride a multiple of 4, 8-byte aligned tensors): %d channels, stride %lld", name, g.IC, (long long)g.ldi);
-    if constexpr (XSP)
-        SNN_REQUIRE(fast, "%s: covers the pipelined implicit GEMM only (input channels a multiple of 32, pixel stride a "
-                    "multiple of 4, 16-byte aligned tensors): %d channels, stride %lld", name, g.IC, (long long)g.ldi);
-    // the pre-split weight image serves the pipelined kernel in its two-piece modes; every other path converts wk itself
-    const bool presplit = wk_split != nullptr && (SPLIT == 2 || SPLIT == 4) && aligned16(wk_split);
+    gg.out_vec = p.out_vec;
+    gg.mtiles = p.mtiles;
+    gg.mtiles_per_xcd = p.mtiles_per_xcd;
+    gg.ntiles = p.ntiles;
+    const dim3 grid((unsigned)p.blocks);
 #define SNN_CONV_LAUNCH(BN_, WM_, WN_)                                                                      \
     do {                                                                                                    \
-        gg.mtiles = (int)gm;                                                                                \
-        gg.mtiles_per_xcd = (int)snn_ceil_div(gm, 8);                                                       \
-        gg.ntiles = (int)snn_ceil_div(g.OC, BN_);                                                           \
-        SNN_REQUIRE((int64_t)gg.mtiles_per_xcd * 8 * gg.ntiles <= 0x7fffffffLL, "%s: grid too large", name); \
-        dim3 grid((unsigned)(gg.mtiles_per_xcd * 8 * gg.ntiles));                                           \
         if constexpr (SB) {                                                                                 \
             hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, DGRAD, true, 5, true, false, true>), grid,     \
                                dim3(kThreads), 0, st, in, wk, out, gg, addend, ld_add, addend2, ld_add2);   \
         } else if constexpr (XSP) {                                                                         \
             hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, false, true, 4, true, false, false, true>), grid, \
                                dim3(kThreads), 0, st, in, wk, out, gg, addend, ld_add, addend2, ld_add2);   \
-        } else if (fast && presplit) {                                                                      \
+        } else if (p.loader == kLoadFastPresplit) {                                                         \
             if constexpr (SPLIT == 2 || SPLIT == 4)                                                         \
                 hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, DGRAD, true, SPLIT, true, true>), grid,    \
                                    dim3(kThreads), 0, st, in, static_cast<const float*>(wk_split), out, gg, addend, \
                                    ld_add, addend2, ld_add2);                                               \
-        } else if (fast)                                                                                    \
+        } else if (p.loader == kLoadFast)                                                                   \
             hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, DGRAD, true, SPLIT, true>), grid, dim3(kThreads), 0, \
                                st, in, wk, out, gg, addend, ld_add, addend2, ld_add2);                                        \
-        else if (vec)                                                                                       \
+        else if (p.loader == kLoadVec)                                                                      \
             hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, DGRAD, true, (SPLIT == 4 ? 3 : (SPLIT == 5 ? 2 : SPLIT)), false>), grid, dim3(kThreads), 0, \
                                st, in, wk, out, gg, addend, ld_add, addend2, ld_add2);                                        \
         else                                                                                                \
             hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, DGRAD, false, 0, false>), grid, dim3(kThreads), 0, st, \
                                in, wk, out, gg, addend, ld_add, addend2, ld_add2);                        \
     } while (0)
-    if (g.OC <= 32) SNN_CONV_LAUNCH(32, 4, 1);
-    else if (g.OC <= 64) SNN_CONV_LAUNCH(64, 2, 2);
+    if (p.bn == 32) SNN_CONV_LAUNCH(32, 4, 1);
+    else if (p.bn == 64) SNN_CONV_LAUNCH(64, 2, 2);
     else SNN_CONV_LAUNCH(128, 2, 2);
 #undef SNN_CONV_LAUNCH
     hipError_t e = hipGetLastError();
@@ -1933,6 +2001,67 @@ extern "C" int snn_weight_presplit(const float* w, void* out, int64_t n, int pre
 // forward kernels that leave them: the implicit GEMM, the first-layer row kernel and the halo-resident 3x3 kernel.
 namespace {
 static int64_t gather_bn_chunks(int64_t rows_per_step) { return (rows_per_step + BM - 1) / BM + 1; }
+
+// chunk slots per timestep the epilogue of k_conv_gather fills (rows per chunk: BM); 0: this kernel leaves no partials
+// (a timestep shorter than a row tile would meet more than two timesteps per tile) and the caller runs snn_bn_stats
+static int gather_bn_plan(bool want, int64_t step_rows) {
+    return want && step_rows >= BM && gather_bn_chunks(step_rows) <= 0x7fffffff ? (int)gather_bn_chunks(step_rows) : 0;
+}
+
+// geometry of a forward launch of k_conv_gather (no statistics, no threshold: the caller adds them)
+static ConvGeom gather_fwd_geom(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride,
+                                int pad, int64_t ldx, int64_t ldy) {
+    ConvGeom g;
+    g.Mtot = N * Ho * (int64_t)Wo;
+    g.IH = H; g.IW = W; g.IC = Cin;
+    g.OH = Ho; g.OW = Wo; g.OC = Cout;
+    g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
+    g.ldi = ldx; g.ldo = ldy;
+    g.Ktot = g.KtotFull = KH * KW * Cin;
+    g.nimg = (int)N;
+    g.ph = g.pw = g.kh0 = g.kw0 = 0; g.nkh = KH; g.nkw = KW; g.OHc = Ho; g.OWc = Wo;
+    g.magic_ic = magic_u32(Cin); g.magic_kw = magic_u32(KW);
+    g.out_vec = 0; g.mtiles = g.mtiles_per_xcd = g.ntiles = 0;
+    g.bn_partial = nullptr; g.bn_rows = 0; g.bn_chunks = 0; g.x_th = 0.0f;
+    return g;
+}
+
+// geometry of a data gradient: what every stride phase shares ...
+static ConvGeom gather_dgrad_geom(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride,
+                                  int pad, int64_t lddy, int64_t lddx) {
+    ConvGeom g;
+    g.IH = Ho; g.IW = Wo; g.IC = Cout;  // gathered tensor is dy
+    g.OH = H; g.OW = W; g.OC = Cin;     // one GEMM row per INPUT pixel
+    g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
+    g.ldi = lddy; g.ldo = lddx;
+    g.KtotFull = KH * KW * Cout;
+    g.nimg = (int)N;
+    g.out_vec = 0; g.mtiles = g.mtiles_per_xcd = g.ntiles = 0;
+    g.bn_partial = nullptr; g.bn_rows = 0; g.bn_chunks = 0; g.x_th = 0.0f;
+    g.Mtot = 0; g.Ktot = 0; g.ph = g.pw = g.kh0 = g.kw0 = g.nkh = g.nkw = g.OHc = g.OWc = 0; g.magic_ic = g.magic_kw = 0;
+    return g;
+}
+// ... and one launch per stride phase (ph, pw), ph < min(stride, H), pw < min(stride, W): each class multiplies only the
+// taps that can reach it (a class may have none: its pixels are the addends, or zeros)
+static void gather_dgrad_phase(ConvGeom& g, int ph, int pw) {
+    const int stride = g.stride, pad = g.pad, H = g.OH, W = g.OW;
+    g.ph = ph; g.pw = pw;
+    g.kh0 = (ph + pad) % stride; g.kw0 = (pw + pad) % stride;
+    g.nkh = g.kh0 < g.KH ? (g.KH - g.kh0 + stride - 1) / stride : 0;
+    g.nkw = g.kw0 < g.KW ? (g.KW - g.kw0 + stride - 1) / stride : 0;
+    g.OHc = (H - ph + stride - 1) / stride;
+    g.OWc = (W - pw + stride - 1) / stride;
+    g.Mtot = (int64_t)g.nimg * g.OHc * (int64_t)g.OWc;
+    g.Ktot = g.nkh * g.nkw * g.IC;
+    g.magic_ic = magic_u32(g.IC); g.magic_kw = magic_u32(g.nkw);
+}
+
+// does the event-frame row kernel take this forward call (see snn_conv2d_fwd)?  align: the kAlign* facts of x and y
+static bool fwd_takes_first(const FirstPlan& fp, bool has_addend, int64_t ldx, int64_t ldy, int W, int Wo, bool sbf,
+                            unsigned align) {
+    return fp.ok && !has_addend && ldx % 2 == 0 && (align & kAlignIn8) && ldy % 4 == 0 &&
+           (align & (sbf ? kAlignOut8 : kAlignOut16)) && (int64_t)W * ldx < 0x7fffffffLL && (int64_t)Wo * ldy < 0x7fffffffLL;
+}
 }  // namespace
 
 extern "C" size_t snn_conv2d_fwd_bn_partial_size(int64_t N, int frames_per_step, int Ho, int Wo, int Cout) {
@@ -1965,25 +2094,15 @@ extern "C" int snn_conv2d_fwd(const float* x, int64_t ldx, const float* w, const
     SNN_REQUIRE(!(bn_partial && addend), "snn_conv2d_fwd: statistics are of the convolution itself - no addend with bn_partial");
     if (bn_layout) bn_layout[0] = bn_layout[1] = 0;
     const int64_t step_rows = bn_partial ? (int64_t)frames_per_step * Ho * Wo : 0;
-    ConvGeom g;
-    g.Mtot = N * Ho * (int64_t)Wo;
-    g.IH = H; g.IW = W; g.IC = Cin;
-    g.OH = Ho; g.OW = Wo; g.OC = Cout;
-    g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-    g.ldi = ldx; g.ldo = ldy;
-    g.Ktot = g.KtotFull = KH * KW * Cin;
-    g.nimg = (int)N;
-    g.ph = g.pw = g.kh0 = g.kw0 = 0; g.nkh = KH; g.nkw = KW; g.OHc = Ho; g.OWc = Wo;
-    g.magic_ic = magic_u32(Cin); g.magic_kw = magic_u32(KW);
-    g.bn_partial = nullptr; g.bn_rows = 0; g.bn_chunks = 0; g.x_th = 0.0f;
+    ConvGeom g = gather_fwd_geom(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ldx, ldy);
     SNN_REQUIRE(N * (int64_t)H * W < 0x7fffffffLL && (int64_t)g.Ktot * Cin < 0xffffffffLL,
                 "snn_conv2d_fwd: tensor too large for 32-bit pixel indexing");
     SNN_REQUIRE(!addend || ld_addend >= Cout, "snn_conv2d_fwd: addend pixel stride smaller than channel count");
     const FirstPlan fp = Cin == 2 && KH == 3 && KW == 3
                              ? first_layer_plan(N, H, W, Ho, Wo, Cout, stride, pad, bn_partial ? frames_per_step : 0, false, 0)
                              : FirstPlan{};
-    if (fp.ok && !addend && ldx % 2 == 0 && aligned8(x) && ldy % 4 == 0 && (sbf ? aligned8(y) : aligned16(y)) &&
-        (int64_t)W * ldx < 0x7fffffffLL && (int64_t)Wo * ldy < 0x7fffffffLL) {
+    if (fwd_takes_first(fp, addend != nullptr, ldx, ldy, W, Wo, sbf,
+                        gather_align_bits<false>(x, w, nullptr, y, nullptr, 0, nullptr, 0))) {
         FirstGeom fg = {ldx, ldy, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, fp.group_rows, fp.group_blocks,
                         bn_partial, nullptr, 0, nullptr, 0, 1, fp.rs};
         if (bn_partial) bn_layout[0] = fp.group_blocks;
@@ -1998,10 +2117,10 @@ extern "C" int snn_conv2d_fwd(const float* x, int64_t ldx, const float* w, const
     }
     SNN_REQUIRE(!sbf || Cin % 32 == 0, "snn_conv2d_fwd: bf16 storage covers the event-frame layer (fp32 frames, Cin = 2, "
                 "3x3) and layers with a multiple of 32 input channels (got %d)", Cin);
-    if (bn_partial && step_rows >= BM && gather_bn_chunks(step_rows) <= 0x7fffffff) {
+    if (const int chunks = gather_bn_plan(bn_partial != nullptr, step_rows)) {
         g.bn_partial = bn_partial;
         g.bn_rows = step_rows;
-        g.bn_chunks = (int)gather_bn_chunks(step_rows);
+        g.bn_chunks = chunks;
         bn_layout[0] = g.bn_chunks;
         bn_layout[1] = BM;
     }
@@ -2032,29 +2151,14 @@ extern "C" int snn_conv2d_dgrad(const float* dy, int64_t lddy, const float* wt, 
     if (check_conv_shape("snn_conv2d_dgrad", N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad)) return 1;
     SNN_REQUIRE(lddy >= Cout && lddx >= Cin, "snn_conv2d_dgrad: pixel stride smaller than channel count");
     SNN_REQUIRE(!addend || ld_addend >= Cin, "snn_conv2d_dgrad: addend pixel stride smaller than channel count");
-    ConvGeom g;
-    g.IH = Ho; g.IW = Wo; g.IC = Cout;  // gathered tensor is dy
-    g.OH = H; g.OW = W; g.OC = Cin;     // one GEMM row per INPUT pixel
-    g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-    g.ldi = lddy; g.ldo = lddx;
-    g.KtotFull = KH * KW * Cout;
-    g.nimg = (int)N;
-    g.bn_partial = nullptr; g.bn_rows = 0; g.bn_chunks = 0;
+    ConvGeom g = gather_dgrad_geom(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, lddy, lddx);
     SNN_REQUIRE(N * (int64_t)Ho * Wo < 0x7fffffffLL && (int64_t)g.KtotFull * Cout < 0xffffffffLL,
                 "snn_conv2d_dgrad: tensor too large for 32-bit pixel indexing");
     const bool split = bwd_split != 0;
     // one launch per stride phase: each class multiplies only the taps that can reach it
     for (int ph = 0; ph < stride && ph < H; ++ph)
         for (int pw = 0; pw < stride && pw < W; ++pw) {
-            g.ph = ph; g.pw = pw;
-            g.kh0 = (ph + pad) % stride; g.kw0 = (pw + pad) % stride;
-            g.nkh = g.kh0 < KH ? (KH - g.kh0 + stride - 1) / stride : 0;
-            g.nkw = g.kw0 < KW ? (KW - g.kw0 + stride - 1) / stride : 0;
-            g.OHc = (H - ph + stride - 1) / stride;
-            g.OWc = (W - pw + stride - 1) / stride;
-            g.Mtot = N * g.OHc * (int64_t)g.OWc;
-            g.Ktot = g.nkh * g.nkw * Cout;
-            g.magic_ic = magic_u32(Cout); g.magic_kw = magic_u32(g.nkw);
+            gather_dgrad_phase(g, ph, pw);
             int rc = sbf ? launch_gather<true, 5, true>(dy, wt, nullptr, dx, g, addend, ld_addend, addend2, ld_addend2,
                                                         (hipStream_t)stream, "snn_conv2d_dgrad")
                      : bwd_split == SNN_PREC_BF16X1
@@ -2066,6 +2170,66 @@ extern "C" int snn_conv2d_dgrad(const float* dy, int64_t lddy, const float* wt, 
                                                            (hipStream_t)stream, "snn_conv2d_dgrad"));
             if (rc) return rc;
         }
+    return 0;
+}
+
+static bool spikes_shape_ok(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
+                            int64_t ld);
+
+// Host-only: the plan of the k_conv_gather launch behind snn_conv2d_fwd (mode 0), one stride phase of snn_conv2d_dgrad
+// (mode 1) or snn_conv2d_spikes_fwd (mode 2); see include/snn_hip.h.  It builds the geometry and reads the plan with the
+// functions the launches use.
+extern "C" int snn_conv2d_gather_plan(int mode, int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW,
+                                      int stride, int pad, int64_t ld_in, int64_t ld_out, int align_bits, int has_split_image,
+                                      int has_addend, int has_addend2, int frames_per_step, int precision, int phase,
+                                      int* out) {
+    if (!out) return 1;
+    for (int i = 0; i < 17; ++i) out[i] = 0;
+    if (mode < 0 || mode > 2 || check_conv_shape("snn_conv2d_gather_plan", N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad))
+        return 1;
+    const bool dgrad = mode == 1, xsp = mode == 2;
+    const bool sbf = precision == SNN_PREC_BF16S;
+    const unsigned align = (unsigned)align_bits;
+    ConvGeom g;
+    int split, nphases = 1, bn_chunks = 0;
+    if (!dgrad) {
+        if (xsp ? precision != SNN_PREC_FP16X3
+                : !(precision == SNN_PREC_FP32 || precision == SNN_PREC_BF16X6 || precision == SNN_PREC_FP16X3 ||
+                    precision == SNN_PREC_BF16X1 || sbf))
+            return 1;
+        if ((has_split_image && precision != SNN_PREC_FP16X3) || ld_in < Cin || ld_out < Cout || has_addend2) return 1;
+        if (frames_per_step > 0 && (N % frames_per_step != 0 || has_addend)) return 1;
+        if (xsp && (has_addend || has_split_image ||
+                    !spikes_shape_ok(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ld_in)))
+            return 1;
+        g = gather_fwd_geom(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ld_in, ld_out);
+        if (!(N * (int64_t)H * W < 0x7fffffffLL && (int64_t)g.Ktot * Cin < 0xffffffffLL)) return 1;
+        if (!xsp) {
+            const FirstPlan fp = Cin == 2 && KH == 3 && KW == 3
+                                     ? first_layer_plan(N, H, W, Ho, Wo, Cout, stride, pad, frames_per_step > 0 ? frames_per_step : 0, false, 0)
+                                     : FirstPlan{};
+            if (fwd_takes_first(fp, has_addend != 0, ld_in, ld_out, W, Wo, sbf, align)) return 1;   // k_conv_first: snn_conv_first_plan
+            if (sbf && Cin % 32 != 0) return 1;
+        }
+        bn_chunks = gather_bn_plan(frames_per_step > 0, frames_per_step > 0 ? (int64_t)frames_per_step * Ho * Wo : 0);
+        split = sbf ? 5 : precision;
+    } else {
+        if (!(precision == SNN_PREC_FP32 || precision == SNN_PREC_BF16X3 || precision == SNN_PREC_BF16X1 || sbf)) return 1;
+        if ((has_split_image && precision != SNN_PREC_BF16X3) || ld_in < Cout || ld_out < Cin || frames_per_step > 0) return 1;
+        g = gather_dgrad_geom(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ld_in, ld_out);
+        if (!(N * (int64_t)Ho * Wo < 0x7fffffffLL && (int64_t)g.KtotFull * Cout < 0xffffffffLL)) return 1;
+        const int nph = stride < H ? stride : H, npw = stride < W ? stride : W;
+        nphases = nph * npw;
+        if (phase < 0 || phase >= nphases) return 1;
+        gather_dgrad_phase(g, phase / npw, phase % npw);
+        split = sbf ? 5 : (precision == SNN_PREC_BF16X1 ? 5 : (precision != 0 ? 2 : 0));
+    }
+    const GatherPlan p = gather_plan(g, dgrad, split, sbf, xsp, align, has_split_image != 0, has_addend != 0, has_addend2 != 0);
+    if (!p.ok) return 1;
+    const int64_t idle = p.blocks - (int64_t)p.mtiles * p.ntiles;
+    const int v[17] = {1, p.loader, p.bn, p.out_vec, p.mtiles, p.mtiles_per_xcd, p.ntiles, (int)p.blocks, (int)idle, g.nkh, g.nkw,
+                       g.Ktot, g.OHc, g.OWc, nphases, bn_chunks, bn_chunks ? BM : 0};
+    for (int i = 0; i < 17; ++i) out[i] = v[i];
     return 0;
 }
 
@@ -2100,17 +2264,22 @@ static WgradTile wgrad_tile(int Cout, int Ktot, bool split, int64_t M) {
 }
 }  // namespace
 
-extern "C" int snn_conv2d_wgrad_splitk(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW,
-                                       int stride, int pad, int precision) {
-    if (N <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return 1;
+// ---- the plan of a weight gradient: kernel, block tile, pixel splits and the slab reducer, read by wgrad_common,
+// wgrad_reduce_slabs and the host-only queries (snn_conv2d_wgrad_plan, snn_conv2d_wgrad_splitk, snn_conv2d_wgrad_kernel)
+namespace {
+constexpr unsigned kAlignDy16 = kAlignOut16, kAlignDy8 = kAlignOut8, kAlignDw16 = kAlignAdd16;   // roles of a weight gradient
+
+// workspace slabs snn_conv2d_wgrad wants on a device with num_cu compute units
+static int wgrad_splitk(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
+                        int precision, int num_cu) {
     const int bwd_split = precision == SNN_PREC_FP32 ? 0 : 1;   // SNN_PREC_BF16S plans like the other 16-bit modes
     if (bwd_split) {  // 3x3 layers with whole 32-channel tiles: the halo-resident kernel (wgrad_halo.hip)
-        const SnnWgradHaloPlan hp = snn_wgrad_halo_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
+        const SnnWgradHaloPlan hp = snn_wgrad_halo_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, num_cu);
         if (hp.ok) return hp.slabs;
     }
     const int64_t M = N * Ho * (int64_t)Wo;
     const int64_t Ktot = (int64_t)KH * KW * Cin;
-    if (first_layer_shape(Cin, Cout, KH, KW)) return first_layer_blocks(N * Ho);  // one slab per block
+    if (first_layer_shape(Cin, Cout, KH, KW)) return first_layer_blocks(N * Ho, num_cu);  // one slab per block
     const bool split_mode = bwd_split && Cin % 4 == 0 && Cout % 4 == 0;
     const WgradTile t = wgrad_tile(Cout, (int)Ktot, split_mode, M);
     const int64_t tiles = snn_ceil_div(Cout, t.bm) * snn_ceil_div(Ktot, t.bn);
@@ -2122,12 +2291,12 @@ extern "C" int snn_conv2d_wgrad_splitk(int64_t N, int H, int W, int Cin, int Ho,
     if (split_mode && t.id == 4) resident = KH * KW > 1 ? 4 : 2;
     if (split_mode && t.id == 0) {
         // three blocks per CU only while a split keeps >= 24 stages of 32 pixels; shorter splits are all prologue
-        const int64_t s3 = (3 * (int64_t)snn_num_cu()) / tiles;
+        const int64_t s3 = (3 * (int64_t)num_cu) / tiles;
         const int64_t s3r = s3 >= 32 ? s3 / 8 * 8 : (s3 < 1 ? 1 : s3);
         if (M / s3r < 24 * WB_K) resident = 2;
     }
     if (const char* force = snn_tuning_env("SNN_WGRAD_RESIDENT")) resident = atoi(force) > 0 ? atoi(force) : resident;  // tuning aid
-    int64_t s = ((int64_t)resident * snn_num_cu()) / tiles;
+    int64_t s = ((int64_t)resident * num_cu) / tiles;
     const int64_t max_by_work = snn_ceil_div(M, 8 * WB_K);            // >= 8 LDS stages per block
     const int64_t max_by_mem = (int64_t)(64 << 20) / (Cout * Ktot);   // workspace <= 256 MiB
     if (s > max_by_work) s = max_by_work;
@@ -2138,65 +2307,97 @@ extern "C" int snn_conv2d_wgrad_splitk(int64_t N, int H, int W, int Cin, int Ho,
     return (int)s;
 }
 
-// which kernel snn_conv2d_wgrad launches for a shape: 0 the implicit GEMM (k_conv_wgrad_pipe / k_conv_wgrad), 1 the
-// halo-resident kernel (k_conv_wgrad_halo), 2 the event-frame row kernel (k_conv_first) - for measurement labels; host-only
-extern "C" int snn_conv2d_wgrad_kernel(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride,
-                                       int pad, int precision) {
-    if (N <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return 0;
-    if (first_layer_shape(Cin, Cout, KH, KW)) return 2;
-    if (precision != SNN_PREC_FP32 && snn_wgrad_halo_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad).ok) return 1;
-    return 0;
-}
-
-// dw (+)= sum over the splitk workspace slabs, fixed order
-static int wgrad_reduce_slabs(float* workspace, float* dw, int64_t n, int splitk, int accumulate, hipStream_t st) {
-    if (n % 4 == 0 && aligned16(workspace) && aligned16(dw) && splitk > 1) {
+// dw (+)= sum over the splitk workspace slabs, fixed order: which kernel walks which rows.  Rows [j * per, (j + 1) * per)
+// clipped to splitk belong to group j < groups (none of them empty); kg >= groups thread groups are launched (the ones
+// past `groups` add zeros).
+enum ReduceKind { kReduceScalar = 0, kReduceOnce = 1, kReduce4TwoPass = 2, kReduce4OnePass = 3 };
+struct ReducePlan {
+    int kind;
+    int kg;          // thread groups sharing the rows of an element (k_wgrad_reduce<KG>, k_wgrad_reduce_once<KG>); reduce4: 1
+    int groups, per; // non-empty row groups and rows per group (the last one may be shorter)
+    int64_t blocks;  // blocks of the (first) launch along x
+};
+static ReducePlan wgrad_reduce_plan(int64_t n, int splitk, bool aligned, int num_cu) {
+    ReducePlan r = {};
+    const bool vec = n % 4 == 0 && aligned;   // 16 bytes per lane: workspace and dw 16-byte aligned
+    if (vec && splitk > 1) {
         // one launch when the rows a wave has to walk stay short: blocks of 256 elements, KG waves sharing the slab rows
         const int64_t nb1 = snn_ceil_div(n, 256);
         int kg = 1;
-        while (kg < 16 && nb1 * kg < 8 * (int64_t)snn_num_cu() && splitk / (2 * kg) >= 4) kg *= 2;
+        while (kg < 16 && nb1 * kg < 8 * (int64_t)num_cu && splitk / (2 * kg) >= 4) kg *= 2;
         if (snn_ceil_div(splitk, kg) <= 48) {
-#define SNN_REDUCE_ONCE(KG_)                                                                                   \
-    hipLaunchKernelGGL((k_wgrad_reduce_once<KG_>), dim3((unsigned)nb1), dim3(64 * KG_), 0, st, workspace, n, splitk, dw, \
-                       accumulate)
-            switch (kg) {
-                case 1: SNN_REDUCE_ONCE(1); break;
-                case 2: SNN_REDUCE_ONCE(2); break;
-                case 4: SNN_REDUCE_ONCE(4); break;
-                case 8: SNN_REDUCE_ONCE(8); break;
-                default: SNN_REDUCE_ONCE(16); break;
-            }
-#undef SNN_REDUCE_ONCE
-            SNN_CHECK_LAUNCH("snn_conv2d_wgrad_reduce");
-            return 0;
+            r.kind = kReduceOnce;
+            r.kg = kg;
+            r.per = (int)snn_ceil_div(splitk, kg);
+            r.groups = (int)snn_ceil_div(splitk, r.per);
+            r.blocks = nb1;
+            return r;
         }
     }
-    if (n % 4 == 0 && aligned16(workspace) && aligned16(dw) && splitk > 8) {
+    if (vec && splitk > 8) {
         const int64_t nb = snn_ceil_div(n / 4, kThreads);
-        int64_t groups = snn_ceil_div(4 * snn_num_cu(), nb);   // ~4 blocks per CU in the first pass
+        int64_t groups = snn_ceil_div(4 * num_cu, nb);   // ~4 blocks per CU in the first pass
         if (groups > splitk / 4) groups = splitk / 4;          // at least 4 rows per group
         if (groups < 1) groups = 1;
         const int per = (int)snn_ceil_div(splitk, groups);
         groups = snn_ceil_div(splitk, per);
-        if (groups > 1) {
-            hipLaunchKernelGGL(k_wgrad_reduce4, dim3((unsigned)nb, (unsigned)groups), dim3(kThreads), 0, st, workspace,
-                               n, splitk, per, n, workspace, (int64_t)per * n, 0);
-            hipLaunchKernelGGL(k_wgrad_reduce4, dim3((unsigned)nb, 1), dim3(kThreads), 0, st, workspace, n,
-                               (int)groups, (int)groups, (int64_t)per * n, dw, 0, accumulate);
-        } else {
-            hipLaunchKernelGGL(k_wgrad_reduce4, dim3((unsigned)nb, 1), dim3(kThreads), 0, st, workspace, n, splitk,
-                               splitk, n, dw, 0, accumulate);
+        r.kind = groups > 1 ? kReduce4TwoPass : kReduce4OnePass;
+        r.kg = 1;
+        r.groups = (int)groups;
+        r.per = groups > 1 ? per : splitk;
+        r.blocks = nb;
+        return r;
+    }
+    r.kind = kReduceScalar;
+    r.kg = splitk <= 8 ? 1 : (splitk <= 64 ? 4 : (splitk <= 256 ? 16 : 64));
+    r.per = (int)snn_ceil_div(splitk, r.kg);
+    r.groups = (int)snn_ceil_div(splitk, r.per);
+    r.blocks = snn_ceil_div(n, kThreads / r.kg);
+    return r;
+}
+
+}  // namespace
+
+static int wgrad_reduce_slabs(float* workspace, float* dw, int64_t n, int splitk, int accumulate, hipStream_t st) {
+    const ReducePlan r = wgrad_reduce_plan(n, splitk, aligned16(workspace) && aligned16(dw), snn_num_cu());
+    if (r.kind == kReduceOnce) {
+#define SNN_REDUCE_ONCE(KG_)                                                                                   \
+    hipLaunchKernelGGL((k_wgrad_reduce_once<KG_>), dim3((unsigned)r.blocks), dim3(64 * KG_), 0, st, workspace, n, splitk, dw, \
+                       accumulate)
+        switch (r.kg) {
+            case 1: SNN_REDUCE_ONCE(1); break;
+            case 2: SNN_REDUCE_ONCE(2); break;
+            case 4: SNN_REDUCE_ONCE(4); break;
+            case 8: SNN_REDUCE_ONCE(8); break;
+            default: SNN_REDUCE_ONCE(16); break;
         }
+#undef SNN_REDUCE_ONCE
+        SNN_CHECK_LAUNCH("snn_conv2d_wgrad_reduce");
+        return 0;
+    }
+    if (r.kind == kReduce4TwoPass) {
+        hipLaunchKernelGGL(k_wgrad_reduce4, dim3((unsigned)r.blocks, (unsigned)r.groups), dim3(kThreads), 0, st, workspace,
+                           n, splitk, r.per, n, workspace, (int64_t)r.per * n, 0);
+        hipLaunchKernelGGL(k_wgrad_reduce4, dim3((unsigned)r.blocks, 1), dim3(kThreads), 0, st, workspace, n,
+                           r.groups, r.groups, (int64_t)r.per * n, dw, 0, accumulate);
+        SNN_CHECK_LAUNCH("snn_conv2d_wgrad_reduce");
+        return 0;
+    }
+    if (r.kind == kReduce4OnePass) {
+        hipLaunchKernelGGL(k_wgrad_reduce4, dim3((unsigned)r.blocks, 1), dim3(kThreads), 0, st, workspace, n, splitk,
+                           splitk, n, dw, 0, accumulate);
         SNN_CHECK_LAUNCH("snn_conv2d_wgrad_reduce");
         return 0;
     }
 #define SNN_REDUCE_LAUNCH(KG_)                                                                                  \
-    hipLaunchKernelGGL((k_wgrad_reduce<KG_>), dim3((unsigned)snn_ceil_div(n, kThreads / KG_)), dim3(kThreads), 0, \
-                       st, workspace, dw, n, splitk, accumulate)
-    if (splitk <= 8) SNN_REDUCE_LAUNCH(1);
-    else if (splitk <= 64) SNN_REDUCE_LAUNCH(4);
-    else if (splitk <= 256) SNN_REDUCE_LAUNCH(16);
-    else SNN_REDUCE_LAUNCH(64);
+    hipLaunchKernelGGL((k_wgrad_reduce<KG_>), dim3((unsigned)r.blocks), dim3(kThreads), 0, st, workspace, dw, n, splitk, \
+                       accumulate)
+    switch (r.kg) {
+        case 1: SNN_REDUCE_LAUNCH(1); break;
+        case 4: SNN_REDUCE_LAUNCH(4); break;
+        case 16: SNN_REDUCE_LAUNCH(16); break;
+        default: SNN_REDUCE_LAUNCH(64); break;
+    }
 #undef SNN_REDUCE_LAUNCH
     SNN_CHECK_LAUNCH("snn_conv2d_wgrad_reduce");
     return 0;
@@ -2204,17 +2405,122 @@ static int wgrad_reduce_slabs(float* workspace, float* dw, int64_t n, int splitk
 
 namespace {
 // the weight-gradient plan of k_conv_first, ok = 0 when the shape or the buffers are not covered
-static FirstPlan first_layer_wgrad_plan(const float* x, int64_t ldx, const float* dy, int64_t lddy, int64_t N, int H, int W,
-                                        int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
-                                        bool dy_bf16 = false) {
+static FirstPlan first_layer_wgrad_plan(unsigned align, int64_t ldx, int64_t lddy, int64_t N, int H, int W, int Cin, int Ho,
+                                        int Wo, int Cout, int KH, int KW, int stride, int pad, bool dy_bf16, int num_cu) {
     if (Cin != 2 || KH != 3 || KW != 3) return FirstPlan{};
-    FirstPlan p = first_layer_plan(N, H, W, Ho, Wo, Cout, stride, pad, 0, true, 0);
-    if (!(ldx % 2 == 0 && aligned8(x) && lddy % 4 == 0 && (dy_bf16 ? aligned8(dy) : aligned16(dy)) &&
+    FirstPlan p = first_layer_plan(N, H, W, Ho, Wo, Cout, stride, pad, 0, true, num_cu);
+    if (!(ldx % 2 == 0 && (align & kAlignIn8) && lddy % 4 == 0 && (align & (dy_bf16 ? kAlignDy8 : kAlignDy16)) &&
           (int64_t)W * ldx < 0x7fffffffLL))
         p.ok = 0;
     return p;
 }
+static unsigned wgrad_align_bits(const void* x, const void* dy) {
+    return (aligned16(x) ? kAlignIn16 : 0u) | (aligned8(x) ? kAlignIn8 : 0u) | (aligned16(dy) ? kAlignDy16 : 0u) |
+           (aligned8(dy) ? kAlignDy8 : 0u);
+}
+static FirstPlan first_layer_wgrad_plan(const float* x, int64_t ldx, const float* dy, int64_t lddy, int64_t N, int H, int W,
+                                        int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad) {
+    return first_layer_wgrad_plan(wgrad_align_bits(x, dy), ldx, lddy, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, false, 0);
+}
+
+// The plan of snn_conv2d_wgrad / snn_conv2d_spikes_wgrad (xsp) for valid arguments.  splitk > 0: the caller's slab count
+// (the halo-resident kernel insists on its own); 0: the count snn_conv2d_wgrad_splitk gives for num_cu compute units.
+// halo = false: the halo-resident kernel could not address the buffers, plan the implicit GEMM with the same slabs.
+enum WgradKernel { kWgradPipe = 0, kWgradVec = 1, kWgradScalar = 2, kWgradHalo = 3, kWgradFirst = 4 };
+enum WgradRefusal { kWgradOk = 0, kWgradHaloSplitk, kWgradNotPipeSB, kWgradNotPipeXSP, kWgradGridTooLarge };
+struct WgradPlan {
+    int ok, why;
+    int kernel;                   // WgradKernel
+    WgradTile t;                  // implicit GEMM: block tile (out-channels x (tap, ci) columns)
+    int tiles_m, tiles_n, wbk;    // ... tiles over Cout and over Ktot, pixels per LDS stage (32 / 64)
+    int splitk;
+    int64_t pix_per_split;        // ... a whole number of stages; split z owns pixels [z, z + 1) * pix_per_split below M
+    int64_t last_pix;             // ... pixels of the last split that owns any
+    int empty_splits;             // ... splits past it: they write a zero slab
+    bool one;                     // one bf16 product (bf16 x 1, bf16 storage)
+    FirstPlan fp;
+    SnnWgradHaloPlan hp;
+    ReducePlan r;
+};
+static WgradPlan wgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
+                            int64_t ldx, int64_t lddy, unsigned align, int precision, bool xsp, int num_cu, int splitk,
+                            bool halo = true) {
+    WgradPlan p = {};
+    if (num_cu <= 0) num_cu = snn_num_cu();
+    const int bwd_split = precision;
+    const bool sbf = precision == SNN_PREC_BF16S;   // x (but for the fp32 event frames) and dy are bf16
+    const int64_t M = N * Ho * (int64_t)Wo;
+    const int Ktot = KH * KW * Cin;
+    const int64_t n = (int64_t)Cout * Ktot;
+    p.splitk = splitk > 0 ? splitk : wgrad_splitk(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, precision, num_cu);
+    p.r = wgrad_reduce_plan(n, p.splitk, (align & kAlignDw16) != 0, num_cu);
+    p.fp = xsp ? FirstPlan{}
+               : first_layer_wgrad_plan(align, ldx, lddy, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, sbf, num_cu);
+    if (p.fp.ok) {
+        p.kernel = kWgradFirst;
+        p.ok = 1;
+        return p;
+    }
+    if (bwd_split && halo) {
+        p.hp = snn_wgrad_halo_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, num_cu);
+        if (p.hp.ok) {
+            p.kernel = kWgradHalo;
+            p.ok = p.splitk == p.hp.slabs;
+            p.why = p.ok ? kWgradOk : kWgradHaloSplitk;
+            return p;
+        }
+    }
+    const bool vec = (Cin % 4 == 0) && (Cout % 4 == 0) && (ldx % 4 == 0) && (lddy % 4 == 0) &&
+                     (sbf ? (align & kAlignIn8) && (align & kAlignDy8) : (align & kAlignIn16) && (align & kAlignDy16));
+    p.t = wgrad_tile(Cout, Ktot, bwd_split && Cin % 4 == 0 && Cout % 4 == 0, M);
+    // small tiles (64 x 64, 32 x 128) run 64-pixel stages in the pipelined kernel (latency cover), the others 32
+    static const int wbk_small = snn_tuning_env("SNN_WGRAD_WBK") ? atoi(snn_tuning_env("SNN_WGRAD_WBK")) : 64;  // tuning aid
+    p.wbk = (p.t.id >= 4 && wbk_small == 64) ? 64 : 32;
+    p.pix_per_split = snn_ceil_div(snn_ceil_div(M, p.splitk), p.wbk) * p.wbk;
+    // pipelined kernel: 32-bit byte offsets relative to the first image of a pixel split
+    const int64_t span_pix = p.pix_per_split * (int64_t)stride * stride + 3 * (int64_t)H * W;
+    static const bool no_pipe = snn_tuning_env("SNN_WGRAD_NO_PIPE") != nullptr;  // tuning / bisecting aid
+    const bool pipe = vec && bwd_split && !no_pipe && M < 0x7fffffffLL && span_pix * ldx * 4 < 0x7fffffffLL &&
+                      p.pix_per_split * lddy * 4 < 0x7fffffffLL && (int64_t)H * W * ldx * 4 < 0x7fffffffLL;
+    p.one = precision == SNN_PREC_BF16X1 || sbf;
+    p.kernel = pipe ? kWgradPipe : (vec ? kWgradVec : kWgradScalar);
+    if (sbf && !pipe) {
+        p.why = kWgradNotPipeSB;
+        return p;
+    }
+    if (xsp && !(pipe && !p.one)) {
+        p.why = kWgradNotPipeXSP;
+        return p;
+    }
+    p.tiles_m = (int)snn_ceil_div(Cout, p.t.bm);
+    p.tiles_n = (int)snn_ceil_div(Ktot, p.t.bn);
+    if ((int64_t)p.tiles_m * p.tiles_n * p.splitk > 0x7fffffff) {
+        p.why = kWgradGridTooLarge;
+        return p;
+    }
+    const int64_t owners = snn_ceil_div(M, p.pix_per_split);   // splits that own a pixel
+    p.last_pix = M - (owners - 1) * p.pix_per_split;
+    p.empty_splits = (int)(p.splitk - owners);
+    p.ok = 1;
+    return p;
+}
 }  // namespace
+
+extern "C" int snn_conv2d_wgrad_splitk(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW,
+                                       int stride, int pad, int precision) {
+    if (N <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return 1;
+    return wgrad_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Cin, Cout, kAlignAll, precision, false, 0, 0).splitk;
+}
+
+// which kernel snn_conv2d_wgrad launches for a shape: 0 the implicit GEMM (k_conv_wgrad_pipe / k_conv_wgrad), 1 the
+// halo-resident kernel (k_conv_wgrad_halo), 2 the event-frame row kernel (k_conv_first) - for measurement labels; host-only
+extern "C" int snn_conv2d_wgrad_kernel(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride,
+                                       int pad, int precision) {
+    if (N <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return 0;
+    if (first_layer_shape(Cin, Cout, KH, KW)) return 2;
+    const int k = wgrad_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, Cin, Cout, kAlignAll, precision, false, 0, 0).kernel;
+    return k == kWgradHalo ? 1 : (k == kWgradFirst ? 2 : 0);
+}
 
 extern "C" int snn_conv2d_wgrad_bn_supported(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW,
                                              int stride, int pad) {
@@ -2253,7 +2559,6 @@ static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t ld
     SNN_REQUIRE(precision == SNN_PREC_FP32 || precision == SNN_PREC_BF16X3 || precision == SNN_PREC_BF16X1 ||
                     precision == SNN_PREC_BF16S,
                 "snn_conv2d_wgrad: precision must be SNN_PREC_FP32, _BF16X3, _BF16X1 or _BF16S (got %d)", precision);
-    const int bwd_split = precision;
     const bool sbf = precision == SNN_PREC_BF16S;   // x (but for the fp32 event frames) and dy are bf16
     if (check_conv_shape("snn_conv2d_wgrad", N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad)) return 1;
     SNN_REQUIRE(ldx >= Cin && lddy >= Cout, "snn_conv2d_wgrad: pixel stride smaller than channel count");
@@ -2266,9 +2571,11 @@ static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t ld
     g.ldx = ldx; g.lddy = lddy;
     g.Ktot = KH * KW * Cin;
     g.x_th = x_th;
-    const FirstPlan fp = xsp ? FirstPlan{}
-                             : first_layer_wgrad_plan(x, ldx, dy, lddy, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, sbf);
-    if (fp.ok) {
+    // (the reducer plan in p.r is the one wgrad_reduce_slabs derives again from the same two pointers)
+    const unsigned align = wgrad_align_bits(x, dy) | (aligned16(dw) && aligned16(workspace) ? kAlignDw16 : 0u);
+    WgradPlan p = wgrad_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ldx, lddy, align, precision, xsp, 0, splitk);
+    if (p.kernel == kWgradFirst) {
+        const FirstPlan& fp = p.fp;
         FirstGeom fg = {ldx, lddy, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, fp.group_rows, splitk, nullptr,
                         nullptr, 0, nullptr, 0, 1, fp.rs};
         if (sbf)
@@ -2280,45 +2587,33 @@ static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t ld
         SNN_CHECK_LAUNCH("snn_conv2d_wgrad");
         return wgrad_reduce_slabs(workspace, dw, (int64_t)Cout * g.Ktot, splitk, accumulate, (hipStream_t)stream);
     }
-    if (bwd_split) {
-        const SnnWgradHaloPlan hp = snn_wgrad_halo_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
-        if (hp.ok) {
-            SNN_REQUIRE(splitk == hp.slabs, "snn_conv2d_wgrad: splitk %d, expected %d (snn_conv2d_wgrad_splitk)", splitk,
-                        hp.slabs);
-            const int rc = snn_wgrad_halo_launch(hp, x, ldx, dy, lddy, workspace, N, H, W, Cin, Ho, Wo, Cout, stride,
-                                                 xsp ? 2 : ((precision == SNN_PREC_BF16X1 || sbf) ? 1 : 3), sbf,
-                                                 (hipStream_t)stream, x_th);
-            if (rc == 0)
-                return wgrad_reduce_slabs(workspace, dw, (int64_t)Cout * g.Ktot, hp.slabs, accumulate,
-                                          (hipStream_t)stream);
-            if (rc > 0) return rc;
-            // rc < 0: buffers this kernel cannot address (unaligned / > 2 GiB per image): the implicit-GEMM kernel
-        }
+    if (p.kernel == kWgradHalo) {
+        const SnnWgradHaloPlan& hp = p.hp;
+        SNN_REQUIRE(p.why != kWgradHaloSplitk, "snn_conv2d_wgrad: splitk %d, expected %d (snn_conv2d_wgrad_splitk)", splitk,
+                    hp.slabs);
+        const int rc = snn_wgrad_halo_launch(hp, x, ldx, dy, lddy, workspace, N, H, W, Cin, Ho, Wo, Cout, stride,
+                                             xsp ? 2 : ((precision == SNN_PREC_BF16X1 || sbf) ? 1 : 3), sbf,
+                                             (hipStream_t)stream, x_th);
+        if (rc == 0)
+            return wgrad_reduce_slabs(workspace, dw, (int64_t)Cout * g.Ktot, hp.slabs, accumulate, (hipStream_t)stream);
+        if (rc > 0) return rc;
+        // rc < 0: buffers this kernel cannot address (unaligned / > 2 GiB per image): the implicit-GEMM kernel
+        p = wgrad_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ldx, lddy, align, precision, xsp, 0, splitk, false);
     }
-    const bool vec = (Cin % 4 == 0) && (Cout % 4 == 0) && (ldx % 4 == 0) && (lddy % 4 == 0) &&
-                     (sbf ? aligned8(x) && aligned8(dy) : aligned16(x) && aligned16(dy));
-    const WgradTile t = wgrad_tile(Cout, g.Ktot, bwd_split && Cin % 4 == 0 && Cout % 4 == 0, g.Mtot);
-    // small tiles (64 x 64, 32 x 128) run 64-pixel stages in the pipelined kernel (latency cover), the others 32
-    static const int wbk_small = snn_tuning_env("SNN_WGRAD_WBK") ? atoi(snn_tuning_env("SNN_WGRAD_WBK")) : 64;  // tuning aid
-    const int wbk = (t.id >= 4 && wbk_small == 64) ? 64 : 32;
-    g.pix_per_split = snn_ceil_div(snn_ceil_div(g.Mtot, splitk), wbk) * wbk;
-    g.nimg = (int)N;
-    // pipelined kernel: 32-bit byte offsets relative to the first image of a pixel split
-    const int64_t span_pix = g.pix_per_split * (int64_t)stride * stride + 3 * (int64_t)H * W;
-    static const bool no_pipe = snn_tuning_env("SNN_WGRAD_NO_PIPE") != nullptr;  // tuning / bisecting aid
-    const bool pipe = vec && bwd_split && !no_pipe && g.Mtot < 0x7fffffffLL && span_pix * ldx * 4 < 0x7fffffffLL &&
-                      g.pix_per_split * lddy * 4 < 0x7fffffffLL && (int64_t)H * W * ldx * 4 < 0x7fffffffLL;
-    const bool one = precision == SNN_PREC_BF16X1 || sbf;
-    SNN_REQUIRE(!sbf || pipe, "snn_conv2d_wgrad: bf16 storage covers the event-frame layer and the pipelined kernels only "
+    SNN_REQUIRE(p.why != kWgradNotPipeSB, "snn_conv2d_wgrad: bf16 storage covers the event-frame layer and the pipelined kernels only "
                 "(channels and strides multiples of 4, 8-byte aligned tensors, < 2 GiB per pixel split)");
-    SNN_REQUIRE(!xsp || (pipe && !one), "snn_conv1x1_spikes_wgrad: covers the pipelined bf16 x 3 kernel only (channels and "
+    SNN_REQUIRE(p.why != kWgradNotPipeXSP, "snn_conv1x1_spikes_wgrad: covers the pipelined bf16 x 3 kernel only (channels and "
                 "strides multiples of 4, 16-byte aligned tensors, < 2 GiB per pixel split)");
-    g.tiles_m = (int)snn_ceil_div(Cout, t.bm);
-    g.tiles_n = (int)snn_ceil_div(g.Ktot, t.bn);
+    SNN_REQUIRE(p.why != kWgradGridTooLarge, "snn_conv2d_wgrad: grid too large");
+    const WgradTile t = p.t;
+    const int wbk = p.wbk;
+    const bool pipe = p.kernel == kWgradPipe, vec = p.kernel != kWgradScalar, one = p.one;
+    g.pix_per_split = p.pix_per_split;
+    g.nimg = (int)N;
+    g.tiles_m = p.tiles_m;
+    g.tiles_n = p.tiles_n;
     g.splitk = splitk;
-    const int64_t nblocks = (int64_t)g.tiles_m * g.tiles_n * splitk;
-    SNN_REQUIRE(nblocks <= 0x7fffffff, "snn_conv2d_wgrad: grid too large");
-    dim3 grid((unsigned)nblocks);
+    dim3 grid((unsigned)((int64_t)g.tiles_m * g.tiles_n * splitk));
     hipStream_t st = (hipStream_t)stream;
 #define SNN_WGRAD_LAUNCH(TM_, TN_, WM_, WN_)                                                                   \
     do {                                                                                                       \
@@ -2371,6 +2666,30 @@ extern "C" int snn_conv2d_wgrad(const float* x, int64_t ldx, const float* dy, in
                         precision, stream, false, 0.0f);
 }
 
+// Host-only: the plan of snn_conv2d_wgrad (spikes = 1: snn_conv2d_spikes_wgrad) on a device with num_cu compute units; see
+// include/snn_hip.h.  It reads the plan function the launch and the slab reducer read.
+extern "C" int snn_conv2d_wgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride,
+                                     int pad, int64_t ldx, int64_t lddy, int align_bits, int precision, int spikes, int num_cu,
+                                     int* out) {
+    if (!out) return 1;
+    for (int i = 0; i < 18; ++i) out[i] = 0;
+    if (check_conv_shape("snn_conv2d_wgrad_plan", N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad)) return 1;
+    if (!(precision == SNN_PREC_FP32 || precision == SNN_PREC_BF16X3 || precision == SNN_PREC_BF16X1 ||
+          precision == SNN_PREC_BF16S) || ldx < Cin || lddy < Cout || !(N * (int64_t)H * W < 0x7fffffffLL))
+        return 1;
+    if (spikes && (precision != SNN_PREC_BF16X3 || !spikes_shape_ok(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ldx)))
+        return 1;
+    const WgradPlan p = wgrad_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ldx, lddy, (unsigned)align_bits, precision,
+                                   spikes != 0, num_cu, 0);
+    if (!p.ok) return 1;
+    const bool gemm = p.kernel <= kWgradScalar;
+    const int v[18] = {1, p.kernel, gemm ? p.t.id : 0, gemm ? p.t.bm : 0, gemm ? p.t.bn : 0, p.tiles_m, p.tiles_n, gemm ? p.wbk : 0,
+                       p.splitk, (int)p.pix_per_split, (int)p.last_pix, p.empty_splits, p.r.kind, p.r.kg, p.r.groups, p.r.per,
+                       (int)p.r.blocks, gemm ? (int)((int64_t)p.tiles_m * p.tiles_n * p.splitk) : 0};
+    for (int i = 0; i < 18; ++i) out[i] = v[i];
+    return 0;
+}
+
 // ---- convolutions over spikes that were never stored (see k_conv_gather XSP, include/snn_hip.h)
 static bool spikes_shape_ok(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
                             int64_t ld) {
@@ -2404,23 +2723,13 @@ extern "C" int snn_conv2d_spikes_fwd(const float* vdec, int64_t ld, float v_th, 
     SNN_REQUIRE(!bn_partial || (bn_layout && frames_per_step > 0 && N % frames_per_step == 0),
                 "snn_conv2d_spikes_fwd: statistics need bn_layout and a frames_per_step that divides N");
     if (bn_layout) bn_layout[0] = bn_layout[1] = 0;
-    ConvGeom g;
-    g.Mtot = N * Ho * (int64_t)Wo;
-    g.IH = H; g.IW = W; g.IC = Cin;
-    g.OH = Ho; g.OW = Wo; g.OC = Cout;
-    g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-    g.ldi = ld; g.ldo = ldy;
-    g.Ktot = g.KtotFull = KH * KW * Cin;
-    g.nimg = (int)N;
-    g.ph = g.pw = g.kh0 = g.kw0 = 0; g.nkh = KH; g.nkw = KW; g.OHc = Ho; g.OWc = Wo;
-    g.magic_ic = magic_u32(Cin); g.magic_kw = magic_u32(KW);
-    g.bn_partial = nullptr; g.bn_rows = 0; g.bn_chunks = 0;
+    ConvGeom g = gather_fwd_geom(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ld, ldy);
     g.x_th = v_th;
     const int64_t step_rows = bn_partial ? (int64_t)frames_per_step * Ho * Wo : 0;
-    if (bn_partial && step_rows >= BM && gather_bn_chunks(step_rows) <= 0x7fffffff) {
+    if (const int chunks = gather_bn_plan(bn_partial != nullptr, step_rows)) {
         g.bn_partial = bn_partial;
         g.bn_rows = step_rows;
-        g.bn_chunks = (int)gather_bn_chunks(step_rows);
+        g.bn_chunks = chunks;
         bn_layout[0] = g.bn_chunks;
         bn_layout[1] = BM;
     }

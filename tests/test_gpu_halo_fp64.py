@@ -21,15 +21,10 @@ import torch
 import torch.nn.functional as F
 
 from tests.conv_ref import ACC_TOL, PREC_TOL, TINY, _check, _dgrad_ref, _fwd_ref, _teeth
+from tests.fp64_buffers import BF16_ROUND, GUARD, SENT, V_TH, Buf, _exact_operands, _exact_weights, _random, _st
 from tests.util import rel_err
 
 pytestmark = pytest.mark.gpu
-
-SENT = 77.0          # guard channels / pixels around every slice
-GUARD = 4            # guard pixels at each end of a buffer
-V_TH = 1.0
-BF16_ROUND = 2.0 ** -8   # one bf16 rounding of the stored result (SBF)
-
 
 @pytest.fixture(scope="module")
 def H_(hip_lib):
@@ -37,10 +32,6 @@ def H_(hip_lib):
         pytest.skip("no HIP device")
     from snn_for_object_detection_amd import _hip
     return _hip
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ---------------------------------------------------------------------------------------------------- plan queries
@@ -70,35 +61,6 @@ def wgrad_plan(_hip, N, H, W, Cin, Ho, Wo, Cout, s, num_cu=0):
     return dict(zip(WGRAD_KEYS, out))
 
 
-# ---------------------------------------------------------------------------------------------------- buffers
-class Buf:
-    """[N,H,W,C] channels-last = channels off .. off+C of a [GUARD + N*H*W + GUARD, ld] buffer of SENT."""
-
-    def __init__(self, shape, off=0, ld=None, values=None, fill=None, dtype=torch.float32):
-        N, H, W, C = shape
-        ld = C if ld is None else ld
-        P = N * H * W
-        self.shape, self.ld = tuple(shape), ld
-        self.buf = torch.full((P + 2 * GUARD, ld), SENT, dtype=dtype, device="cuda")
-        self.view = self.buf[GUARD:GUARD + P, off:off + C]
-        if values is not None:
-            self.view.copy_(values.reshape(P, C))
-        elif fill is not None:
-            self.view.fill_(fill)
-        self.ptr = self.view.data_ptr()
-        self.mask = torch.zeros(self.buf.shape, dtype=torch.bool, device="cuda")
-        self.mask[GUARD:GUARD + P, off:off + C] = True
-        self.before = self.buf.clone()
-
-    def value(self):
-        return self.view.double().cpu().reshape(self.shape)
-
-    def guards_intact(self, whole=False):
-        it = torch.int32 if self.buf.dtype == torch.float32 else torch.int16
-        keep = torch.ones_like(self.mask) if whole else ~self.mask
-        return torch.equal(self.buf.view(it)[keep], self.before.view(it)[keep])
-
-
 def _image(_hip, src, O, I, flip, prec):
     src = src.contiguous().cuda()
     img = torch.empty(9 * O * I, device="cuda")
@@ -112,22 +74,6 @@ def _ratio(tag, out, ref, mag, tol):
     r = float(((out - ref).abs() / (tol * mag + TINY)).max())
     print(f"RATIO {tag} {r:.4g}")
     return r
-
-
-def _exact_operands(shape, seed, spikes=False, lim=4):
-    g = torch.Generator().manual_seed(seed)
-    if spikes:
-        return torch.randint(0, 2, shape, generator=g).float()
-    return torch.randint(-lim, lim + 1, shape, generator=g).float()
-
-
-def _exact_weights(shape, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-31, 32, shape, generator=g).float() * 2.0 ** -6
-
-
-def _random(shape, seed, scale=1.0):
-    return torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
 # ---------------------------------------------------------------------------------------------------- k_conv_halo3

@@ -8,6 +8,7 @@ import torch
 
 import snn_for_object_detection_amd as S
 from oracle.net import SODaRef
+from tests.fp64_buffers import GATHER_KEYS, WGRAD_PLAN_KEYS
 
 
 def test_tiny_yolo_structure_and_param_count():
@@ -393,3 +394,284 @@ def test_first_layer_plan_invariants(hip_lib):
     assert (m["rs"], m["LW"], m["blocks"], m["max_rows"], m["last_stage"]) == (1, 1282, 2048, 45, 1), m
     d = plan(256, 240, 304, 64, 1, 1, fps=2)                                                     # deep-12, T = 128
     assert (d["rs"], d["group_rows"], d["group_blocks"], d["blocks"], d["max_rows"]) == (2, 480, 16, 2048, 30), d
+
+
+# ---------------------------------------------------------------------------------------------------- implicit GEMM plans
+ALL_ALIGNED = 1023
+
+
+def gather_plan(lib, mode, N, H, W, Cin, Cout, KH, KW, s, pad, prec, *, phase=0, fps=0, align=ALL_ALIGNED, ld_in=None,
+                ld_out=None, split=0, add=0, add2=0):
+    """snn_conv2d_gather_plan as a dict (mode 0 forward, 1 data-gradient phase, 2 forward over spikes); None: refused."""
+    from ctypes import addressof, c_int
+    Ho, Wo = (H + 2 * pad - KH) // s + 1, (W + 2 * pad - KW) // s + 1
+    ci, co = (Cout, Cin) if mode == 1 else (Cin, Cout)                    # channels of the gathered / produced tensor
+    out = (c_int * 17)()
+    rc = lib.snn_conv2d_gather_plan(mode, N, H, W, Cin, Ho, Wo, Cout, KH, KW, s, pad, ld_in or ci, ld_out or co, align, split,
+                                    add, add2, fps, prec, phase, addressof(out))
+    assert rc == (0 if out[0] else 1)
+    return dict(zip(GATHER_KEYS, out)) if rc == 0 else None
+
+
+def wgrad_plan(lib, N, H, W, Cin, Cout, KH, KW, s, pad, prec, num_cu, *, align=ALL_ALIGNED, ldx=None, lddy=None, spikes=0):
+    """snn_conv2d_wgrad_plan as a dict; None: refused."""
+    from ctypes import addressof, c_int
+    Ho, Wo = (H + 2 * pad - KH) // s + 1, (W + 2 * pad - KW) // s + 1
+    out = (c_int * 18)()
+    rc = lib.snn_conv2d_wgrad_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, s, pad, ldx or Cin, lddy or Cout, align, prec, spikes,
+                                   num_cu, addressof(out))
+    assert rc == (0 if out[0] else 1)
+    return dict(zip(WGRAD_PLAN_KEYS, out)) if rc == 0 else None
+
+
+def _model_conv_layers(H, W, deep12=False):
+    """(Cin, Cout, k, stride, pad, H, W) of every convolution of TinyYolo (deep12: of the twelve-layer backbone config) on
+    an H x W frame, read off the model: the CPU reference runs one frame of the product's own description with a hook on
+    each convolution."""
+    if deep12:
+        from oracle.net import BlockRef
+        ref = BlockRef(2, [layer for _ in range(12) for layer in (S.Conv(64, 3), S.Norm(), S.LIF())]).eval()
+    else:
+        ref = SODaRef(S.TinyYolo(num_classes=2, time_window=0), 2).eval()
+    rows = []
+
+    def hook(mod, inp, out):
+        rows.append((mod.in_channels, mod.out_channels, mod.kernel_size[0], mod.stride[0], mod.padding[0],
+                     inp[0].shape[-2], inp[0].shape[-1]))
+
+    for c in ref.modules():
+        if isinstance(c, torch.nn.Conv2d):
+            c.register_forward_hook(hook)
+    with torch.no_grad():
+        ref(torch.zeros(1, 2, H, W) if deep12 else torch.zeros(1, 1, 2, H, W))
+    assert len(rows) == (12 if deep12 else 48)
+    return sorted(set(rows))
+
+
+# (Cin, Cout, k, stride, H, W): (tile id, stage pixels, splitk, reducer, KG) of the implicit-GEMM weight gradients at 256
+# CUs, bf16 x 3.  Every other convolution of the model takes the halo-resident or the event-frame kernel.
+GEN1_WGRAD = {   # TinyYolo GEN1 240 x 304, B = 5, T = 32: N = 160
+    (64, 32, 1, 1, 120, 152): (4, 64, 512, 1, 16),
+    (64, 64, 1, 1, 120, 152): (4, 64, 512, 1, 16),
+    (128, 64, 1, 1, 60, 76): (4, 64, 256, 1, 16),
+    (128, 64, 1, 1, 120, 152): (4, 64, 256, 1, 16),
+    (128, 128, 1, 1, 60, 76): (0, 32, 768, 1, 16),
+    (128, 128, 3, 1, 8, 10): (0, 32, 48, 1, 4),
+    (128, 128, 3, 1, 15, 19): (0, 32, 56, 1, 4),
+    (256, 27, 1, 1, 8, 10): (2, 32, 48, 1, 8),
+    (256, 27, 1, 1, 15, 19): (2, 32, 176, 1, 16),
+    (256, 27, 1, 1, 30, 38): (2, 32, 712, 1, 16),
+    (256, 36, 1, 1, 8, 10): (1, 32, 48, 1, 8),
+    (256, 36, 1, 1, 15, 19): (1, 32, 176, 1, 16),
+    (256, 36, 1, 1, 30, 38): (1, 32, 512, 1, 16),
+    (256, 128, 1, 1, 8, 10): (0, 32, 48, 1, 8),
+    (256, 128, 1, 1, 15, 19): (0, 32, 176, 1, 16),
+    (256, 128, 1, 1, 30, 38): (0, 32, 256, 1, 16),
+    (256, 256, 1, 1, 8, 10): (0, 32, 48, 1, 8),
+    (256, 256, 1, 1, 15, 19): (0, 32, 128, 1, 8),
+    (256, 256, 1, 1, 30, 38): (0, 32, 192, 1, 8),
+    (256, 256, 3, 2, 15, 19): (0, 32, 14, 1, 1),
+    (256, 256, 3, 2, 30, 38): (0, 32, 21, 1, 1),
+    (320, 128, 1, 1, 60, 76): (0, 32, 256, 1, 16),
+    (512, 256, 1, 1, 8, 10): (0, 32, 48, 1, 4),
+    (640, 256, 1, 1, 15, 19): (0, 32, 48, 1, 4),
+    (768, 256, 1, 1, 30, 38): (0, 32, 64, 1, 4),
+}
+MPX_WGRAD = {    # TinyYolo 1 Mpx 720 x 1280, B = 8, T = 32: N = 256
+    (64, 32, 1, 1, 360, 640): (4, 64, 512, 1, 16),
+    (64, 64, 1, 1, 360, 640): (4, 64, 512, 1, 16),
+    (128, 64, 1, 1, 180, 320): (4, 64, 256, 1, 16),
+    (128, 64, 1, 1, 360, 640): (4, 64, 256, 1, 16),
+    (128, 128, 1, 1, 180, 320): (0, 32, 768, 1, 16),
+    (256, 27, 1, 1, 23, 40): (2, 32, 920, 2, 1),
+    (256, 27, 1, 1, 45, 80): (2, 32, 1024, 2, 1),
+    (256, 27, 1, 1, 90, 160): (2, 32, 1024, 2, 1),
+    (256, 36, 1, 1, 23, 40): (1, 32, 512, 1, 16),
+    (256, 36, 1, 1, 45, 80): (1, 32, 512, 1, 16),
+    (256, 36, 1, 1, 90, 160): (1, 32, 512, 1, 16),
+    (256, 128, 1, 1, 23, 40): (0, 32, 256, 1, 16),
+    (256, 128, 1, 1, 45, 80): (0, 32, 384, 1, 16),
+    (256, 128, 1, 1, 90, 160): (0, 32, 384, 1, 16),
+    (256, 256, 1, 1, 23, 40): (0, 32, 192, 1, 8),
+    (256, 256, 1, 1, 45, 80): (0, 32, 192, 1, 8),
+    (256, 256, 1, 1, 90, 160): (0, 32, 192, 1, 8),
+    (320, 128, 1, 1, 180, 320): (0, 32, 256, 1, 16),
+    (512, 256, 1, 1, 23, 40): (0, 32, 96, 1, 4),
+    (640, 256, 1, 1, 45, 80): (0, 32, 72, 1, 4),
+    (768, 256, 1, 1, 90, 160): (0, 32, 64, 1, 4),
+}
+
+
+@pytest.mark.parametrize("name,N,H,W,table", [("gen1", 160, 240, 304, GEN1_WGRAD), ("1mpx", 256, 720, 1280, MPX_WGRAD)])
+def test_gemm_plans_of_the_model_layers(hip_lib, name, N, H, W, table):
+    """The plan of every implicit-GEMM layer of the model at 256 CUs is pinned: a retuning of wgrad_tile, split_resident or
+    the reducer choice shows here as the rows it moves.  The forward of every such layer takes the pipelined loader."""
+    from snn_for_object_detection_amd import _hip
+    got = {}
+    for Cin, Cout, k, s, pad, h, w in _model_conv_layers(H, W):
+        p = wgrad_plan(hip_lib, N, h, w, Cin, Cout, k, k, s, pad, _hip.PREC_BF16X3, 256)
+        assert p is not None
+        if p["kernel"] <= 2:
+            assert p["kernel"] == (0 if Cout % 4 == 0 else 2), (Cin, Cout, k, s, h, w, p)   # pipelined; the heads' 27: scalar
+            got[(Cin, Cout, k, s, h, w)] = (p["tile"], p["stage"], p["splitk"], p["reducer"], p["kg"])
+            f = gather_plan(hip_lib, 0, N, h, w, Cin, Cout, k, k, s, pad, _hip.PREC_FP16X3, fps=N // 32, split=1)
+            assert f["loader"] == 3 and f["bn"] == (32 if Cout <= 32 else 64 if Cout <= 64 else 128), (Cin, Cout, f)
+            rows = N // 32 * ((h + 2 * pad - k) // s + 1) * ((w + 2 * pad - k) // s + 1)   # output pixels of a timestep
+            assert rows >= 128 and (f["bn_chunks"], f["bn_rows"]) == (-(-rows // 128) + 1, 128), (Cin, Cout, f)
+        else:
+            assert (k == 3) and p["kernel"] == (4 if Cin == 2 else 3), (Cin, Cout, k, s, h, w, p)
+    assert got == table, {k: v for k, v in got.items() if table.get(k) != v}
+
+
+def test_deep12_has_no_implicit_gemm_layer(hip_lib):
+    """The deep-12 config (twelve 64-channel 3x3 layers behind the event-frame layer, 240 x 304, B = 2, T = 128) runs no
+    implicit GEMM: its forward / data gradients are halo-resident and so are its weight gradients."""
+    from snn_for_object_detection_amd import _hip
+    layers = _model_conv_layers(240, 304, deep12=True)
+    assert layers == [(2, 64, 3, 1, 1, 240, 304), (64, 64, 3, 1, 1, 240, 304)]
+    for Cin, Cout, k, s, pad, h, w in layers:
+        p = wgrad_plan(hip_lib, 256, h, w, Cin, Cout, k, k, s, pad, _hip.PREC_BF16X3, 256)
+        assert p["kernel"] == (4 if Cin == 2 else 3), (Cin, Cout, p)
+        if Cin == 2:
+            assert gather_plan(hip_lib, 0, 256, h, w, Cin, Cout, k, k, s, pad, _hip.PREC_FP16X3) is None   # k_conv_first takes it
+        else:
+            assert hip_lib.snn_conv3x3_halo_supported(256, h, w, Cin, Cout) == 1
+
+
+def _reduce_groups(p):
+    """The slab rows each group of the planned reducer walks, exactly as the kernels clip them."""
+    launched = p["kg"] if p["reducer"] in (0, 1) else p["groups"]
+    rows = [(j * p["per"], min((j + 1) * p["per"], p["splitk"])) for j in range(launched)]
+    return [r for r in rows if r[0] < r[1]], launched
+
+
+# Plan classes the sweep below must reach (it fails when one disappears) ...
+GEMM_REACHABLE = (
+    {("tile", i) for i in range(6)} | {("stage", 32), ("stage", 64)} | {("kernel", i) for i in range(5)}
+    | {("reducer", 0, kg) for kg in (1, 4, 16, 64)} | {("reducer", 1, kg) for kg in (1, 2, 4, 8, 16)}
+    | {("reducer", 2, 1), "empty_split", "idle_reduce_group", "splitk%8", "splitk%8!=0", "splitk>=32", "splitk=1"}
+    | {("loader", i) for i in range(6)} | {("bn", 32), ("bn", 64), ("bn", 128), "idle_blocks", "mtiles_per_xcd>1",
+                                           "phase_without_tap"})
+# ... and the ones it must NOT reach: dead code as the planners stand.  k_wgrad_reduce4 in ONE pass needs more than 48
+# slabs of at least 4 * num_cu * 1024 elements each and a 16-byte aligned dw; the 256 MiB workspace cap and the
+# one-resident-wave rule (splitk <= 3 * num_cu / tiles with tiles >= n / 128^2) keep splitk below 49 there for every
+# kernel family that feeds the reducer.
+GEMM_UNREACHABLE = {("reducer", 3, 1)}
+
+
+def test_gemm_plan_invariants(hip_lib):
+    """snn_conv2d_wgrad_plan / snn_conv2d_gather_plan over a host-side sweep of shapes, layouts and CU counts: the splits
+    cover every pixel in whole stages, the tiles cover Cout x Ktot, the workspace stays within 256 MiB, the reducer's
+    groups cover the slab rows exactly once, the XCD-padded grid covers the tiles and the phases of a data gradient
+    partition the taps and the pixels."""
+    from snn_for_object_detection_amd import _hip
+    seen = set()
+    chans = (1, 3, 4, 27, 32, 36, 64, 100, 130, 132, 256, 768, 1024)
+    frames = ((1, 1, 1), (1, 5, 7), (2, 9, 13), (3, 30, 38), (5, 60, 76), (160, 30, 38), (160, 120, 152), (256, 360, 640))
+    for num_cu in (64, 256, 304):
+        for N, H, W in frames:
+            for k in (1, 3, 5, 7):
+                for s in (1, 2, 3):
+                    pad = k // 2
+                    if H + 2 * pad < k or W + 2 * pad < k:
+                        continue
+                    Ho, Wo = (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
+                    M = N * Ho * Wo
+                    for Cin in chans:
+                        for Cout in chans:
+                            if (Cin * Cout > 1024 * 256 and k > 1) or k * k * Cin * Cout >= 2 ** 26:
+                                continue
+                            for prec in (_hip.PREC_BF16X3, _hip.PREC_FP32):
+                                for align in (ALL_ALIGNED, 0):
+                                    p = wgrad_plan(hip_lib, N, H, W, Cin, Cout, k, k, s, pad, prec, num_cu, align=align)
+                                    assert p is not None, (N, H, W, Cin, Cout, k, s)
+                                    what = (num_cu, N, H, W, Cin, Cout, k, s, prec, align, p)
+                                    n = Cout * k * k * Cin
+                                    assert 1 <= p["splitk"] <= 32768 and p["splitk"] * n * 4 <= 256 << 20 or p["splitk"] == 1, what
+                                    if num_cu == 256 and align and not torch.cuda.is_available():
+                                        assert p["splitk"] == hip_lib.snn_conv2d_wgrad_splitk(N, H, W, Cin, Ho, Wo, Cout, k, k, s, pad, prec)
+                                    seen.add(("kernel", p["kernel"]))
+                                    groups, launched = _reduce_groups(p)
+                                    assert len(groups) == p["groups"] and groups[0][0] == 0 and groups[-1][1] == p["splitk"], what
+                                    assert all(a[1] == b[0] for a, b in zip(groups, groups[1:])), what
+                                    assert (p["reducer"] in (1, 2, 3)) <= (n % 4 == 0 and align != 0), what
+                                    seen.add(("reducer", p["reducer"], p["kg"]))
+                                    if launched > p["groups"]:
+                                        seen.add("idle_reduce_group")
+                                    if p["kernel"] > 2:
+                                        continue
+                                    # pipelined: 32-bit byte offsets inside a pixel split (its images and one more on each side)
+                                    near = ((p["pps"] * s * s + 3 * H * W) * Cin * 4 < 2 ** 31 - 1 and p["pps"] * Cout * 4 < 2 ** 31 - 1)
+                                    assert p["kernel"] == (2 if (not align or Cin % 4 or Cout % 4) else 0 if prec and near else 1), what
+                                    assert p["splitk"] * p["pps"] >= M and p["pps"] % p["stage"] == 0, what
+                                    assert p["tiles_m"] * p["bm"] >= Cout > (p["tiles_m"] - 1) * p["bm"], what
+                                    assert p["tiles_n"] * p["bn"] >= k * k * Cin > (p["tiles_n"] - 1) * p["bn"], what
+                                    assert p["splitk"] < 32 or p["splitk"] % 8 == 0, what
+                                    owners = p["splitk"] - p["empty"]
+                                    assert (owners - 1) * p["pps"] + p["last_pix"] == M and 1 <= p["last_pix"] <= p["pps"], what
+                                    assert p["grid"] == p["tiles_m"] * p["tiles_n"] * p["splitk"], what
+                                    seen |= {("tile", p["tile"]), ("stage", p["stage"])}
+                                    seen.add("splitk=1" if p["splitk"] == 1 else "splitk>=32" if p["splitk"] >= 32
+                                             else "splitk%8" if p["splitk"] % 8 == 0 else "splitk%8!=0")
+                                    if p["empty"]:
+                                        seen.add("empty_split")
+                            # forward and every phase of the data gradient
+                            for mode, prec in ((0, _hip.PREC_FP16X3), (1, _hip.PREC_BF16X3)):
+                                if num_cu != 256:
+                                    continue
+                                taps, pix = set(), 0
+                                first = gather_plan(hip_lib, mode, N, H, W, Cin, Cout, k, k, s, pad, prec)
+                                if first is None:
+                                    assert mode == 0 and Cin == 2, (N, H, W, Cin, Cout, k, s)
+                                    continue
+                                for ph in range(first["nphases"]):
+                                    g = gather_plan(hip_lib, mode, N, H, W, Cin, Cout, k, k, s, pad, prec, phase=ph,
+                                                    split=(Cin + Cout) % 2, add=mode, add2=mode)
+                                    what = (mode, N, H, W, Cin, Cout, k, s, ph, g)
+                                    oc, ic = (Cout, Cin) if mode == 0 else (Cin, Cout)
+                                    assert g["bn"] == (32 if oc <= 32 else 64 if oc <= 64 else 128), what
+                                    assert g["ntiles"] * g["bn"] >= oc > (g["ntiles"] - 1) * g["bn"], what
+                                    assert g["mtiles"] == -(-N * g["ohc"] * g["owc"] // 128), what
+                                    assert g["mtiles_per_xcd"] * 8 >= g["mtiles"] > (g["mtiles_per_xcd"] - 1) * 8, what
+                                    assert g["blocks"] == g["mtiles_per_xcd"] * 8 * g["ntiles"], what
+                                    assert g["idle"] == g["blocks"] - g["mtiles"] * g["ntiles"], what
+                                    assert g["ktot"] == g["nkh"] * g["nkw"] * ic, what
+                                    ih, iw = (H, W) if mode == 0 else (Ho, Wo)            # the gathered image: < 2 GiB for four
+                                    fast_ok = (ic % 32 == 0 and 1 <= g["nkh"] * g["nkw"] <= 31 and max(g["nkh"], g["nkw"]) <= 6
+                                               and ih * iw * ic * 16 < 2 ** 31 - 1 and oc * k * k * ic * 4 < 2 ** 31 - 1)
+                                    assert g["loader"] == ((3 if (Cin + Cout) % 2 else 2) if fast_ok else 1 if ic % 4 == 0 else 0), what
+                                    seen |= {("loader", g["loader"]), ("bn", g["bn"])}
+                                    if g["idle"]:
+                                        seen.add("idle_blocks")
+                                    if g["mtiles_per_xcd"] > 1:
+                                        seen.add("mtiles_per_xcd>1")
+                                    if g["ktot"] == 0:
+                                        seen.add("phase_without_tap")
+                                    if mode == 1:
+                                        sh, sw = min(s, H), min(s, W)
+                                        ph_, pw_ = ph // sw, ph % sw
+                                        kh0, kw0 = (ph_ + pad) % s, (pw_ + pad) % s
+                                        mine = {(kh, kw) for kh in range(kh0, k, s) for kw in range(kw0, k, s)}
+                                        assert len(mine) == g["nkh"] * g["nkw"] and not (mine & taps), what
+                                        taps |= mine
+                                        assert (g["ohc"], g["owc"]) == (len(range(ph_, H, s)), len(range(pw_, W, s))), what
+                                        pix += g["ohc"] * g["owc"]
+                                if mode == 1:
+                                    assert first["nphases"] == min(s, H) * min(s, W) and pix == H * W, (H, W, s)
+                                    if s <= min(H, W):
+                                        assert taps == {(a, b) for a in range(k) for b in range(k)}, (k, s, taps)
+    # the two loaders the sweep's plain operands cannot select, on the shapes test_gpu_bf16_storage.py / test_gpu_siblings.py use
+    assert gather_plan(hip_lib, 0, 6, 9, 11, 64, 128, 3, 3, 2, 1, _hip.PREC_BF16S)["loader"] == 4
+    assert gather_plan(hip_lib, 2, 6, 9, 11, 64, 128, 1, 1, 1, 0, _hip.PREC_FP16X3)["loader"] == 5
+    seen |= {("loader", 4), ("loader", 5)}
+    for num_cu in (64, 256, 304):                      # the slab counts of the halo-resident and event-frame kernels
+        for N, H, W, Cin, Cout in ((1, 310, 517, 32, 32), (160, 120, 152, 32, 32), (160, 240, 304, 2, 64), (1, 9, 9, 2, 4),
+                                   (3, 17, 23, 2, 16), (256, 360, 640, 32, 32)):
+            p = wgrad_plan(hip_lib, N, H, W, Cin, Cout, 3, 3, 1, 1, _hip.PREC_BF16X3, num_cu)
+            assert p["kernel"] in (3, 4) and p["tile"] == p["stage"] == p["grid"] == 0
+            groups, launched = _reduce_groups(p)
+            assert len(groups) == p["groups"] and groups[0][0] == 0 and groups[-1][1] == p["splitk"]
+            seen |= {("kernel", p["kernel"]), ("reducer", p["reducer"], p["kg"])}
+    assert GEMM_REACHABLE <= seen, GEMM_REACHABLE - seen
+    assert not (GEMM_UNREACHABLE & seen), GEMM_UNREACHABLE & seen
+    assert {x for x in seen if isinstance(x, tuple) and x[0] == "reducer"} <= GEMM_REACHABLE, seen
