@@ -419,7 +419,9 @@ int snn_affine_neuron_bwd_sums_from_state(int neuron, int T, int64_t M, int C, i
  * launches, into out[10] = { vec (channels per thread), mode (0 no sums, 1 ordered per-wave slabs, 2 LDS atomics), BUF
  * (1: buffer-resource addressing), NP (pixel rows per thread), cvb (channel groups per block), gy (channel blocks), gx
  * (pixel blocks), rpb (pixel rows of P = 256 / cvb pixels per block), 1 if the last pixel row is partial, LDS bytes }.
- * 0, or 1 for a shape or SNN_SCAN_SUMS_FROM_STATE request the scan would refuse. */
+ * The launch and this query read one plan function.  0, or 1 (with the launch's message) for a call the scan refuses by
+ * its shape or flags alone: a bad shape or neuron code, unknown flag bits, a flag the neuron or the channel count does not
+ * cover, an SNN_SCAN_SUMS_FROM_STATE request that is not covered.  Pointer alignment is the launch's own check. */
 int snn_affine_neuron_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, int with_sums,
                                const snn_neuron_params* p, int flags, int64_t* out);
 int snn_affine_neuron_bwd(int neuron, const float* g_out, int64_t ldg, const float* state,

@@ -8,6 +8,8 @@
 // Reference semantics: layer_gen.py:211-214 (BatchNorm2d, per-timestep batch statistics),
 // layer_gen.py:232-235 / 252-254 (norse LIFCell / LICell), tiny_yolo.py:39-44 (LI -> Tanh).
 #include <stdlib.h>
+#include <algorithm>
+#include <initializer_list>
 #include <type_traits>
 #include "snn_common.h"
 
@@ -1452,8 +1454,126 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(const float* __restri
     }
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+// ---------------------------------------------------------------------------------- host side: plans and dispatch
+// every pointer of the list (NULL counts as aligned) on a `bytes` boundary / every value a multiple of n
+static bool aligned(size_t bytes, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* q : ptrs) bits |= reinterpret_cast<uintptr_t>(q);
+    return (bits & (bytes - 1)) == 0;
+}
+static bool multiples(int64_t n, std::initializer_list<int64_t> values) {
+    for (int64_t v : values)
+        if (v % n != 0) return false;
+    return true;
+}
+
+// Runtime values -> template arguments.  dispatch(f, OneOf<a, b, ...>{v}, ...) calls f with one std::integral_constant per
+// OneOf, holding the listed value its v equals, and returns what f returns; false when a v is not in its list.  f is a
+// generic lambda that launches under `if constexpr (<the instance exists>)`: what that condition rejects is never
+// instantiated.  (A chain of integer compares, all inlined: nothing is built or allocated per call.)
+template <auto... Vs> struct OneOf { std::common_type_t<decltype(Vs)...> v; };
+using AnyNeuron = OneOf<(int)SNN_NEURON_NONE, (int)SNN_NEURON_LIF, (int)SNN_NEURON_LI, (int)SNN_NEURON_LI_TANH,
+                        (int)SNN_NEURON_SLI, (int)SNN_NEURON_SYNAPSE>;
+using Flag = OneOf<false, true>;
+template <class F> static bool dispatch(F&& f) { return f(); }
+template <class F, auto... Vs, class... Rest> static bool dispatch(F&& f, OneOf<Vs...> first, Rest... rest) {
+    return ((first.v == Vs &&
+             dispatch([&](auto... cs) { return f(std::integral_constant<decltype(Vs), Vs>{}, cs...); }, rest...)) || ...);
+}
+
+constexpr bool bf16_neuron(int n) {   // the neurons with a bf16-storage scan
+    return n == SNN_NEURON_NONE || n == SNN_NEURON_LIF || n == SNN_NEURON_LI || n == SNN_NEURON_LI_TANH;
+}
+constexpr bool last_step_neuron(int n) { return n == SNN_NEURON_LIF || n == SNN_NEURON_LI || n == SNN_NEURON_LI_TANH; }
+constexpr bool rebuilds_x(int n) { return n == SNN_NEURON_SLI || n == SNN_NEURON_SYNAPSE; }
+const char* const kBf16Covers =
+    "bf16 storage covers NONE / LIF / LI / LI+Tanh on channel counts and strides that are multiples of 4 (8-byte aligned "
+    "tensors)";
+const char* const kSumsFromStateCovers =
+    "SNN_SCAN_SUMS_FROM_STATE not covered (ask snn_affine_neuron_bwd_sums_from_state; LIF from the initial state, sums "
+    "wanted, train-mode BatchNorm)";
+
+// ---- forward scan: which k_affine_neuron_fwd instance on which grid
+struct FwdPlan {
+    int vec, save;   // channels per access (1 / 4, bf16 tensors 4 / 8); SAVE of the kernel
+    unsigned blocks;
+};
+// lanes: the widest channel group (1 / 4 / 8) the strides and pointers of the call allow in one access
+static FwdPlan fwd_plan(int neuron, int64_t M, int C, int lanes, bool saves, bool ckpt) {
+    FwdPlan fp;
+    // 8 channels (16 bytes of bf16) per access when the layout allows: the scan is bound by the number of memory
+    // instructions, not by their bytes (8-byte accesses: 3.3 TB/s of bf16 against 5.1 TB/s with fp32 tensors)
+    static const bool no_v8 = snn_tuning_env("SNN_SCAN_NO_VEC8") != nullptr;   // tuning / bisecting aid
+    fp.vec = (lanes == 8 && no_v8) ? 4 : lanes;   // (8 is offered for bf16 tensors only)
+    const bool step_state = neuron == SNN_NEURON_LIF || rebuilds_x(neuron);   // the others save nothing per step
+    fp.save = (saves && step_state) ? (ckpt ? 2 : 1) : 0;
+    // every thread scans the same number of (pixel, channel group) items over all T (grid-stride, tail masked) and
+    // all blocks are resident at once: a capped grid with 1.4 items per thread would run 2 rounds for 1.4 of work
+    const int64_t total = M * (C / fp.vec);
+    const int64_t per_thread = snn_ceil_div(total, (int64_t)snn_max_blocks() * kThreads);
+    fp.blocks = (unsigned)snn_ceil_div(total, kThreads * per_thread);
+    return fp;
+}
+constexpr bool fwd_instance(int neuron, int vec, int save, bool sb) {
+    return (sb ? (vec != 1 && bf16_neuron(neuron) && save != 2) : vec != 8) &&
+           (save == 0 || neuron == SNN_NEURON_LIF || (save == 1 && rebuilds_x(neuron)));
+}
+
+// ---- reverse scan: everything snn_affine_neuron_bwd decides from shape and flags, pointer values apart.  The launch
+// consumes it and the host-only query snn_affine_neuron_bwd_plan exports it, so a test that asks the query asserts the
+// instance that really runs.
+struct ScanBwdPlan {
+    BwdPlan pl;
+    bool buf, sb, yf;         // BUF / SB / YF of the kernel
+    int np;                   // NP: pixel rows per thread
+    int lookback, last_only;
+    const char* refusal;      // what shape and flags alone rule out (nullptr: nothing)
+};
+static ScanBwdPlan scan_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, bool with_sums,
+                                 const snn_neuron_params* p, int flags) {
+    ScanBwdPlan sp = {};
+    auto refuse = [&sp](const char* why) {
+        sp.refusal = why;
+        return sp;
+    };
+    if (!p) return refuse("null neuron parameters");
+    if (flags & ~(SNN_SCAN_WIDE_ADDRESSING | SNN_SCAN_LAST_STEP_ONLY | SNN_SCAN_BF16_STORAGE | SNN_SCAN_SUMS_FROM_STATE |
+                  SNN_SCAN_STATE_LOOKBACK))
+        return refuse("unknown flags");
+    const bool wide = (flags & SNN_SCAN_WIDE_ADDRESSING) != 0;
+    sp.last_only = (flags & SNN_SCAN_LAST_STEP_ONLY) != 0;
+    sp.sb = (flags & SNN_SCAN_BF16_STORAGE) != 0;   // g_out, state, y, gx are bf16 tensors
+    sp.yf = (flags & SNN_SCAN_SUMS_FROM_STATE) != 0;
+    sp.lookback = (flags & SNN_SCAN_STATE_LOOKBACK) != 0;
+    if (sp.lookback && !sp.yf) return refuse("SNN_SCAN_STATE_LOOKBACK belongs to SNN_SCAN_SUMS_FROM_STATE");
+    if (!(T > 0 && M > 0 && C > 0 && ldg >= C)) return refuse("bad shape");
+    if (neuron < SNN_NEURON_NONE || neuron > SNN_NEURON_SYNAPSE) return refuse("bad neuron");
+    if (sp.last_only && !last_step_neuron(neuron)) return refuse("SNN_SCAN_LAST_STEP_ONLY is for LIF / LI / LI+Tanh");
+    sp.pl = bwd_plan(T, M, C, with_sums);
+    if (sp.sb && !(sp.pl.vec == 4 && bf16_neuron(neuron))) return refuse(kBf16Covers);
+    // buffer addressing (see k_affine_neuron_bwd): one timestep of every tensor must fit a 31-bit byte offset
+    const int64_t ld_max = std::max({ldg, sp.yf ? 0 : ldy, (int64_t)C});   // (the y-free scan does not address y)
+    sp.buf = sp.pl.vec == 4 && !wide && M * ld_max * 4 < 0x7fffffffLL;
+    if (sp.yf) {
+        // LIF with the ordered sums, buffer addressing, fp32 tensors, all T gradients; the rebuilt input divides by
+        // c_mem: keep the amplification of the potentials' rounding error bounded
+        const bool ok = neuron == SNN_NEURON_LIF && with_sums && sp.buf && sp.pl.mode == 1 && ldg % 4 == 0 && !sp.last_only &&
+                        !sp.sb && p->c_mem >= 1.0f / 64.0f && p->c_mem <= 1.0f;
+        if (!ok) return refuse(kSumsFromStateCovers);
+        // three pixels per thread: the four values a pixel keeps for the statistic of two steps later do not fit the
+        // 256 registers of two waves per SIMD beside four pixels' operand sets (287, or 21 spilled)
+        sp.np = sp.pl.rpb < 3 ? (int)sp.pl.rpb : 3;
+    } else {
+        // (blocks with a single pixel row take the one-pixel-per-thread instance: the three empty pixel slots of the
+        // four-pixel one are computed and issued in straight-line code - measured 58 us against 45 for the branchy kernel)
+        sp.np = (sp.buf && sp.pl.rpb == 1) ? 1 : kBwdNP;
+    }
+    return sp;
+}
+constexpr bool bwd_instance(int neuron, int vec, int mode, bool buf, int np, bool sb, bool yf) {
+    if (yf) return neuron == SNN_NEURON_LIF && vec == 4 && mode == 1 && buf && np <= 3 && !sb;
+    return (np == 1 ? buf : np == kBwdNP) && (vec == 4 || !(buf || sb)) && (!sb || bf16_neuron(neuron));
+}
 
 }  // namespace
 
@@ -1465,31 +1585,35 @@ extern "C" size_t snn_bn_stats_partial_size(int T, int64_t M, int C) {
     return (size_t)T * pl.chunks * C * 2 + (size_t)T * C;
 }
 
-extern "C" int snn_bn_stats(const float* y, int64_t ldy, int T, int64_t M, int C, double* partial, void* stream) {
-    SNN_REQUIRE(y && partial, "snn_bn_stats: null pointer");
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C, "snn_bn_stats: bad shape T=%d M=%lld C=%d ldy=%lld", T,
-                (long long)M, C, (long long)ldy);
-    StatsPlan pl = stats_plan(T, M, C);
-    if (pl.vec == 4) SNN_REQUIRE(aligned16(y) && ldy % 4 == 0, "snn_bn_stats: y must be 16-byte aligned with ldy%%4==0");
-    dim3 grid(pl.chunks, T, pl.zblocks);
-    if (pl.vec == 4)
-        hipLaunchKernelGGL(k_bn_stats<4>, grid, dim3(kThreads), 0, (hipStream_t)stream, y, ldy, M, C, pl.cvb, partial);
-    else
-        hipLaunchKernelGGL(k_bn_stats<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, y, ldy, M, C, pl.cvb, partial);
-    SNN_CHECK_LAUNCH("snn_bn_stats");
+static int bn_stats(const char* name, bool sb, const float* y, int64_t ldy, int T, int64_t M, int C, double* partial,
+                    void* stream) {
+    SNN_REQUIRE(y && partial, "%s: null pointer", name);
+    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C, "%s: bad shape T=%d M=%lld C=%d ldy=%lld", name, T, (long long)M, C,
+                (long long)ldy);
+    const StatsPlan pl = stats_plan(T, M, C);
+    SNN_REQUIRE(!sb || (pl.vec == 4 && ldy % 4 == 0 && aligned(8, {y})),
+                "%s: bad shape (C and ldy multiples of 4, y 8-byte aligned)", name);
+    SNN_REQUIRE(sb || pl.vec == 1 || (ldy % 4 == 0 && aligned(16, {y})), "%s: y must be 16-byte aligned with ldy%%4==0", name);
+    const dim3 grid(pl.chunks, T, pl.zblocks);
+    dispatch(
+        [&](auto VEC, auto SB) {
+            if constexpr (VEC() == 4 || !SB()) {
+                hipLaunchKernelGGL((k_bn_stats<VEC(), SB()>), grid, dim3(kThreads), 0, (hipStream_t)stream, y, ldy, M, C,
+                                   pl.cvb, partial);
+            }
+            return true;
+        },
+        OneOf<1, 4>{pl.vec}, Flag{sb});
+    SNN_CHECK_LAUNCH(name);
     return 0;
 }
 
+extern "C" int snn_bn_stats(const float* y, int64_t ldy, int T, int64_t M, int C, double* partial, void* stream) {
+    return bn_stats("snn_bn_stats", false, y, ldy, T, M, C, partial, stream);
+}
+
 extern "C" int snn_bn_stats_bf16(const float* y, int64_t ldy, int T, int64_t M, int C, double* partial, void* stream) {
-    SNN_REQUIRE(y && partial, "snn_bn_stats_bf16: null pointer");
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C && C % 4 == 0 && ldy % 4 == 0 && aligned8(y),
-                "snn_bn_stats_bf16: bad shape (T=%d M=%lld C=%d ldy=%lld; C and ldy multiples of 4, y 8-byte aligned)", T,
-                (long long)M, C, (long long)ldy);
-    StatsPlan pl = stats_plan(T, M, C);
-    dim3 grid(pl.chunks, T, pl.zblocks);
-    hipLaunchKernelGGL((k_bn_stats<4, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, y, ldy, M, C, pl.cvb, partial);
-    SNN_CHECK_LAUNCH("snn_bn_stats_bf16");
-    return 0;
+    return bn_stats("snn_bn_stats_bf16", true, y, ldy, T, M, C, partial, stream);
 }
 
 extern "C" int snn_bn_stats_finalize(const double* partial, int chunks, int rows_per_chunk, int T, int64_t M, int C,
@@ -1504,14 +1628,14 @@ extern "C" int snn_bn_stats_finalize(const double* partial, int chunks, int rows
     SNN_REQUIRE(chunks >= 0 && rows_per_chunk >= 0 && (chunks > 0 || rows_per_chunk == 0),
                 "snn_bn_stats_finalize: bad partial layout (chunks %d, rows per chunk %d)", chunks, rows_per_chunk);
     if (chunks == 0) chunks = stats_plan(T, M, C).chunks;   // the layout snn_bn_stats writes
-    if (chunks > 64 && !use_running)
-        hipLaunchKernelGGL(k_bn_stats_finalize_fused<32>, dim3(C), dim3(1024), 0, (hipStream_t)stream, partial, chunks,
-                           rows_per_chunk, T, M, C, gamma, bias, eps, momentum, running_mean, running_var, use_running,
-                           mean, invstd, alpha, beta);
-    else
-        hipLaunchKernelGGL(k_bn_stats_finalize_fused<8>, dim3(C), dim3(256), 0, (hipStream_t)stream, partial, chunks,
-                           rows_per_chunk, T, M, C, gamma, bias, eps, momentum, running_mean, running_var, use_running,
-                           mean, invstd, alpha, beta);
+    dispatch(
+        [&](auto SUB) {
+            hipLaunchKernelGGL(k_bn_stats_finalize_fused<SUB()>, dim3(C), dim3(32 * SUB()), 0, (hipStream_t)stream, partial,
+                               chunks, rows_per_chunk, T, M, C, gamma, bias, eps, momentum, running_mean, running_var,
+                               use_running, mean, invstd, alpha, beta);
+            return true;
+        },
+        OneOf<8, 32>{(chunks > 64 && !use_running) ? 32 : 8});
     SNN_CHECK_LAUNCH("snn_bn_stats_finalize");
     return 0;
 }
@@ -1548,19 +1672,9 @@ extern "C" int snn_bn_stats_from_sums(const double* sums, int T, int64_t M_total
     return 0;
 }
 
-#define SNN_DISPATCH_FWD(NEURON, SAVE)                                                                            \
-    do {                                                                                                          \
-        if (vec == 4)                                                                                             \
-            hipLaunchKernelGGL((k_affine_neuron_fwd<NEURON, 4, SAVE>), grid, dim3(kThreads), 0, (hipStream_t)stream, \
-                               y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, T, M, C, *p, last_only); \
-        else                                                                                                      \
-            hipLaunchKernelGGL((k_affine_neuron_fwd<NEURON, 1, SAVE>), grid, dim3(kThreads), 0, (hipStream_t)stream, \
-                               y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, T, M, C, *p, last_only); \
-    } while (0)
-
 static int neuron_fwd(int neuron, const float* y, int64_t ldy, const float* alpha, const float* beta, const float* v0,
                       const float* i0, float* out, int64_t ldo, const float* addend, int64_t ld_addend, float* vT,
-                      float* iT, float* vdec, int ckpt_mode, int T, int64_t M, int C, const snn_neuron_params* p,
+                      float* iT, float* vdec, bool ckpt, int T, int64_t M, int C, const snn_neuron_params* p,
                       int flags, void* stream) {
     SNN_REQUIRE((flags & ~(SNN_SCAN_LAST_STEP_ONLY | SNN_SCAN_BF16_STORAGE | SNN_SCAN_SPIKES_FROM_VDEC)) == 0,
                 "snn_affine_neuron_fwd: unknown flags 0x%x", flags);
@@ -1569,14 +1683,13 @@ static int neuron_fwd(int neuron, const float* y, int64_t ldy, const float* alph
     const bool no_out = (flags & SNN_SCAN_SPIKES_FROM_VDEC) != 0;   // no output tensor: the consumer thresholds vdec
     SNN_REQUIRE(y && p && (out || no_out), "snn_affine_neuron_fwd: null pointer");
     if (no_out) {
-        SNN_REQUIRE(neuron == SNN_NEURON_LIF && vdec && !ckpt_mode && !addend && !last_only && !sb && alpha && !out &&
-                        C % 4 == 0 && ldy % 4 == 0 && aligned16(y) && aligned16(vdec),
+        SNN_REQUIRE(neuron == SNN_NEURON_LIF && vdec && !ckpt && !addend && !last_only && !sb && alpha && !out &&
+                        multiples(4, {C, ldy}) && aligned(16, {y, vdec}),
                     "snn_affine_neuron_fwd: SNN_SCAN_SPIKES_FROM_VDEC is for Norm -> LIF with saved potentials, no shortcut, "
                     "all T steps, fp32 tensors, 4-channel groups; out must be NULL");
         ldo = C;   // (unused; keeps the checks below meaningful)
     }
-    SNN_REQUIRE(!last_only || ((neuron == SNN_NEURON_LIF || neuron == SNN_NEURON_LI || neuron == SNN_NEURON_LI_TANH) &&
-                               !addend),
+    SNN_REQUIRE(!last_only || (last_step_neuron(neuron) && !addend),
                 "snn_affine_neuron_fwd: SNN_SCAN_LAST_STEP_ONLY is for LIF / LI / LI+Tanh without a shortcut");
     SNN_REQUIRE(!addend || (ld_addend >= C && neuron != SNN_NEURON_LI_TANH),
                 "snn_affine_neuron_fwd: addend needs ld_addend >= C and is not allowed with LI_TANH");
@@ -1584,74 +1697,27 @@ static int neuron_fwd(int neuron, const float* y, int64_t ldy, const float* alph
     SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "snn_affine_neuron_fwd: alpha/beta must come together");
     SNN_REQUIRE(neuron >= SNN_NEURON_NONE && neuron <= SNN_NEURON_SYNAPSE, "snn_affine_neuron_fwd: bad neuron %d",
                 neuron);
-    int vec = (C % 4 == 0 && ldy % 4 == 0 && ldo % 4 == 0 && aligned16(y) && aligned16(out) && aligned16(alpha) &&
-               aligned16(beta) && aligned16(v0) && aligned16(i0) && aligned16(vT) && aligned16(iT) && aligned16(vdec) &&
-               (!addend || (ld_addend % 4 == 0 && aligned16(addend))))
-                  ? 4
-                  : 1;
-    if (sb) {   // bf16 tensors: 4 elements = 8 bytes per access
-        const bool ok8 = C % 4 == 0 && ldy % 4 == 0 && ldo % 4 == 0 && aligned8(y) && aligned8(out) && aligned8(vdec) &&
-                         aligned16(alpha) && aligned16(beta) && aligned16(v0) && aligned16(i0) && aligned16(vT) &&
-                         aligned16(iT) && (!addend || (ld_addend % 4 == 0 && aligned8(addend)));
-        SNN_REQUIRE(ok8 && !ckpt_mode && (neuron == SNN_NEURON_NONE || neuron == SNN_NEURON_LIF || neuron == SNN_NEURON_LI ||
-                                          neuron == SNN_NEURON_LI_TANH),
-                    "snn_affine_neuron_fwd: bf16 storage covers NONE / LIF / LI / LI+Tanh on channel counts and strides that "
-                    "are multiples of 4 (8-byte aligned tensors), without checkpointing");
-        vec = 4;
-        // 8 channels (16 bytes of bf16) per access when the layout allows: the scan is bound by the number of memory
-        // instructions, not by their bytes (8-byte accesses: 3.3 TB/s of bf16 against 5.1 TB/s with fp32 tensors)
-        static const bool no_v8 = snn_tuning_env("SNN_SCAN_NO_VEC8") != nullptr;   // tuning / bisecting aid
-        if (!no_v8 && C % 8 == 0 && ldy % 8 == 0 && ldo % 8 == 0 && aligned16(y) && aligned16(out) && aligned16(vdec) &&
-            (!addend || (ld_addend % 8 == 0 && aligned16(addend))))
-            vec = 8;
-    }
-    int64_t total = M * (C / vec);
-    // every thread scans the same number of (pixel, channel group) items over all T (grid-stride, tail masked) and
-    // all blocks are resident at once: a capped grid with 1.4 items per thread would run 2 rounds for 1.4 of work
-    const int64_t per_thread = snn_ceil_div(total, (int64_t)snn_max_blocks() * kThreads);
-    int64_t blocks = snn_ceil_div(total, kThreads * per_thread);
-    dim3 grid((unsigned)blocks);
-#define SNN_DISPATCH_FWD_S(NEURON, SAVE)                                                                          \
-    do {                                                                                                          \
-        if (vec == 8)                                                                                             \
-            hipLaunchKernelGGL((k_affine_neuron_fwd<NEURON, 8, SAVE, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, \
-                               y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, T, M, C, *p, last_only); \
-        else                                                                                                      \
-            hipLaunchKernelGGL((k_affine_neuron_fwd<NEURON, 4, SAVE, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, \
-                               y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, T, M, C, *p, last_only); \
-    } while (0)
-    if (sb) {
-        switch (neuron) {
-            case SNN_NEURON_NONE: SNN_DISPATCH_FWD_S(SNN_NEURON_NONE, 0); break;
-            case SNN_NEURON_LIF:
-                if (vdec) SNN_DISPATCH_FWD_S(SNN_NEURON_LIF, 1);
-                else SNN_DISPATCH_FWD_S(SNN_NEURON_LIF, 0);
-                break;
-            case SNN_NEURON_LI: SNN_DISPATCH_FWD_S(SNN_NEURON_LI, 0); break;
-            default: SNN_DISPATCH_FWD_S(SNN_NEURON_LI_TANH, 0); break;
-        }
-        SNN_CHECK_LAUNCH("snn_affine_neuron_fwd");
-        return 0;
-    }
-#undef SNN_DISPATCH_FWD_S
-    switch (neuron) {
-        case SNN_NEURON_NONE: SNN_DISPATCH_FWD(SNN_NEURON_NONE, 0); break;
-        case SNN_NEURON_LIF:
-            if (vdec && ckpt_mode) SNN_DISPATCH_FWD(SNN_NEURON_LIF, 2);
-            else if (vdec) SNN_DISPATCH_FWD(SNN_NEURON_LIF, 1);
-            else SNN_DISPATCH_FWD(SNN_NEURON_LIF, 0);
-            break;
-        case SNN_NEURON_LI: SNN_DISPATCH_FWD(SNN_NEURON_LI, 0); break;
-        case SNN_NEURON_LI_TANH: SNN_DISPATCH_FWD(SNN_NEURON_LI_TANH, 0); break;
-        case SNN_NEURON_SLI:
-            if (vdec) SNN_DISPATCH_FWD(SNN_NEURON_SLI, 1);
-            else SNN_DISPATCH_FWD(SNN_NEURON_SLI, 0);
-            break;
-        default:
-            if (vdec) SNN_DISPATCH_FWD(SNN_NEURON_SYNAPSE, 1);
-            else SNN_DISPATCH_FWD(SNN_NEURON_SYNAPSE, 0);
-            break;
-    }
+    // n channels per access: the activation tensors (bf16: 2 bytes per element) and the fp32 per-pixel / per-channel ones
+    auto lanes_ok = [&](int n, size_t act_bytes) {
+        return multiples(n, {C, ldy, ldo, addend ? ld_addend : 0}) && aligned(act_bytes, {y, out, vdec, addend}) &&
+               aligned(16, {alpha, beta, v0, i0, vT, iT});
+    };
+    SNN_REQUIRE(!sb || (lanes_ok(4, 8) && !ckpt && bf16_neuron(neuron)), "snn_affine_neuron_fwd: %s, without checkpointing", kBf16Covers);
+    const int lanes = sb ? (lanes_ok(8, 16) ? 8 : 4) : (lanes_ok(4, 16) ? 4 : 1);
+    const FwdPlan fp = fwd_plan(neuron, M, C, lanes, vdec != nullptr, ckpt);
+    const bool launched = dispatch(
+        [&](auto NEURON, auto VEC, auto SAVE, auto SB) {
+            if constexpr (fwd_instance(NEURON(), VEC(), SAVE(), SB())) {
+                hipLaunchKernelGGL((k_affine_neuron_fwd<NEURON(), VEC(), SAVE(), SB()>), dim3(fp.blocks), dim3(kThreads), 0,
+                                   (hipStream_t)stream, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT,
+                                   vdec, T, M, C, *p, last_only);
+                return true;
+            } else {
+                return false;
+            }
+        },
+        AnyNeuron{neuron}, OneOf<1, 4, 8>{fp.vec}, OneOf<0, 1, 2>{fp.save}, Flag{sb});
+    SNN_REQUIRE(launched, "snn_affine_neuron_fwd: no kernel instance (neuron %d, vec %d, save %d)", neuron, fp.vec, fp.save);
     SNN_CHECK_LAUNCH("snn_affine_neuron_fwd");
     return 0;
 }
@@ -1660,7 +1726,7 @@ extern "C" int snn_affine_neuron_fwd(int neuron, const float* y, int64_t ldy, co
                                      const float* v0, const float* i0, float* out, int64_t ldo, const float* addend,
                                      int64_t ld_addend, float* vT, float* iT, float* vdec, int T, int64_t M, int C,
                                      const snn_neuron_params* p, int flags, void* stream) {
-    return neuron_fwd(neuron, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, 0, T, M, C, p,
+    return neuron_fwd(neuron, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, false, T, M, C, p,
                       flags, stream);
 }
 
@@ -1671,7 +1737,7 @@ extern "C" int snn_lif_fwd_ckpt(const float* y, int64_t ldy, const float* alpha,
                                 float* vT, float* iT, float* ckpt, int T, int64_t M, int C, const snn_neuron_params* p,
                                 void* stream) {
     SNN_REQUIRE(ckpt, "snn_lif_fwd_ckpt: null checkpoint buffer");
-    return neuron_fwd(SNN_NEURON_LIF, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, ckpt, 1, T, M,
+    return neuron_fwd(SNN_NEURON_LIF, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, ckpt, true, T, M,
                       C, p, 0, stream);
 }
 
@@ -1681,73 +1747,30 @@ extern "C" size_t snn_affine_neuron_bwd_sums_size(int T, int64_t M, int C) {
     return (size_t)pl.gx * T * C * 2;
 }
 
-#define SNN_LAUNCH_BWD_(NEURON, VEC_, MODE_, BUF_, NP_)                                                          \
-    hipLaunchKernelGGL((k_affine_neuron_bwd<NEURON, VEC_, MODE_, BUF_, NP_>), grid, dim3(kThreads), pl.lds_bytes, \
-                       (hipStream_t)stream, g_out, ldg, state, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, \
-                       g_v0, g_i0, sums, T, M, C, pl.cvb, *p, last_only)
-#define SNN_LAUNCH_BWD(NEURON, VEC_, MODE_)                                             \
-    do {                                                                                \
-        if (VEC_ == 4 && buf_ok && pl.rpb == 1) SNN_LAUNCH_BWD_(NEURON, 4, MODE_, true, 1); \
-        else if (VEC_ == 4 && buf_ok) SNN_LAUNCH_BWD_(NEURON, 4, MODE_, true, kBwdNP);  \
-        else SNN_LAUNCH_BWD_(NEURON, VEC_, MODE_, false, kBwdNP);                       \
-    } while (0)
-#define SNN_DISPATCH_BWD(NEURON)                                  \
-    do {                                                          \
-        if (pl.vec == 4) {                                        \
-            if (pl.mode == 0) SNN_LAUNCH_BWD(NEURON, 4, 0);       \
-            else if (pl.mode == 1) SNN_LAUNCH_BWD(NEURON, 4, 1);  \
-            else SNN_LAUNCH_BWD(NEURON, 4, 2);                    \
-        } else {                                                  \
-            if (pl.mode == 0) SNN_LAUNCH_BWD(NEURON, 1, 0);       \
-            else if (pl.mode == 1) SNN_LAUNCH_BWD(NEURON, 1, 1);  \
-            else SNN_LAUNCH_BWD(NEURON, 1, 2);                    \
-        }                                                         \
-    } while (0)
-
-static bool sums_from_state_ok(int neuron, int T, int64_t M, int C, int64_t ldg, const snn_neuron_params* p, int flags) {
-    if (neuron != SNN_NEURON_LIF || !p || T <= 0 || M <= 0 || C <= 0 || ldg < C) return false;
-    if (flags & (SNN_SCAN_WIDE_ADDRESSING | SNN_SCAN_LAST_STEP_ONLY | SNN_SCAN_BF16_STORAGE)) return false;
-    // the rebuilt input divides by c_mem: keep the amplification of the potentials' rounding error bounded
-    if (!(p->c_mem >= 1.0f / 64.0f && p->c_mem <= 1.0f)) return false;
-    const BwdPlan pl = bwd_plan(T, M, C, true);
-    const int64_t ld_max = ldg > C ? ldg : C;
-    return pl.vec == 4 && pl.mode == 1 && ldg % 4 == 0 && M * ld_max * 4 < 0x7fffffffLL;
-}
-
 extern "C" int snn_affine_neuron_bwd_sums_from_state(int neuron, int T, int64_t M, int C, int64_t ldg,
                                                      const snn_neuron_params* p, int flags) {
-    return sums_from_state_ok(neuron, T, M, C, ldg, p, flags) ? 1 : 0;
+    return scan_bwd_plan(neuron, T, M, C, ldg, C, true, p, flags | SNN_SCAN_SUMS_FROM_STATE).refusal ? 0 : 1;
 }
 
-// The instance snn_affine_neuron_bwd launches for this call (host-only; the launch path below takes the same bwd_plan and
-// the same BUF / NP choice).  out[10]: vec, mode, BUF, NP, cvb, gy, gx, rpb, partial last pixel row,
-// LDS bytes.  Returns 0, or 1 (message in snn_last_error) for a call snn_affine_neuron_bwd would refuse by its shape or
-// flags alone.
+// The plan snn_affine_neuron_bwd launches this call with (host-only).  out[10]: vec, mode, BUF, NP, cvb, gy, gx, rpb,
+// partial last pixel row, LDS bytes.  Returns 0, or 1 (message in snn_last_error) for a call snn_affine_neuron_bwd refuses
+// by its shape or flags alone.
 extern "C" int snn_affine_neuron_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, int with_sums,
                                           const snn_neuron_params* p, int flags, int64_t* out) {
     SNN_REQUIRE(out && p, "snn_affine_neuron_bwd_plan: null pointer");
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldg >= C, "snn_affine_neuron_bwd_plan: bad shape");
-    const bool yfree = (flags & SNN_SCAN_SUMS_FROM_STATE) != 0;
-    const int rest = flags & ~(SNN_SCAN_SUMS_FROM_STATE | SNN_SCAN_STATE_LOOKBACK);
-    SNN_REQUIRE(!yfree || (with_sums && sums_from_state_ok(neuron, T, M, C, ldg, p, rest)),
-                "snn_affine_neuron_bwd_plan: SNN_SCAN_SUMS_FROM_STATE not covered");
-    const BwdPlan pl = bwd_plan(T, M, C, with_sums != 0);
-    const int64_t ld_max = ldg > ldy ? (ldg > C ? ldg : C) : (ldy > C ? ldy : C);
-    const bool buf = yfree || (pl.vec == 4 && !(rest & SNN_SCAN_WIDE_ADDRESSING) && M * ld_max * 4 < 0x7fffffffLL);
-    int np;
-    if (yfree) np = pl.rpb == 1 ? 1 : (pl.rpb == 2 ? 2 : 3);
-    else np = (buf && pl.rpb == 1) ? 1 : kBwdNP;
-    const int P = kThreads / pl.cvb;
-    out[0] = pl.vec;
-    out[1] = pl.mode;
-    out[2] = buf ? 1 : 0;
-    out[3] = np;
-    out[4] = pl.cvb;
-    out[5] = pl.gy;
-    out[6] = pl.gx;
-    out[7] = pl.rpb;
+    const ScanBwdPlan sp = scan_bwd_plan(neuron, T, M, C, ldg, ldy, with_sums != 0, p, flags);
+    SNN_REQUIRE(!sp.refusal, "snn_affine_neuron_bwd_plan: %s (neuron %d, flags 0x%x)", sp.refusal, neuron, flags);
+    const int P = kThreads / sp.pl.cvb;
+    out[0] = sp.pl.vec;
+    out[1] = sp.pl.mode;
+    out[2] = sp.buf ? 1 : 0;
+    out[3] = sp.np;
+    out[4] = sp.pl.cvb;
+    out[5] = sp.pl.gy;
+    out[6] = sp.pl.gx;
+    out[7] = sp.pl.rpb;
     out[8] = (M % P) != 0 ? 1 : 0;
-    out[9] = (int64_t)pl.lds_bytes;
+    out[9] = (int64_t)sp.pl.lds_bytes;
     return 0;
 }
 
@@ -1757,118 +1780,45 @@ extern "C" int snn_affine_neuron_bwd(int neuron, const float* g_out, int64_t ldg
                                      double* sums, int T, int64_t M, int C, const snn_neuron_params* p,
                                      int flags, void* stream) {
     SNN_REQUIRE(g_out && gx && p, "snn_affine_neuron_bwd: null pointer");
-    SNN_REQUIRE((flags & ~(SNN_SCAN_WIDE_ADDRESSING | SNN_SCAN_LAST_STEP_ONLY | SNN_SCAN_BF16_STORAGE |
-                           SNN_SCAN_SUMS_FROM_STATE | SNN_SCAN_STATE_LOOKBACK)) == 0,
-                "snn_affine_neuron_bwd: unknown flags 0x%x", flags);
-    const bool yfree = (flags & SNN_SCAN_SUMS_FROM_STATE) != 0;
-    const int lookback = (flags & SNN_SCAN_STATE_LOOKBACK) != 0;
-    SNN_REQUIRE(yfree || !lookback, "snn_affine_neuron_bwd: SNN_SCAN_STATE_LOOKBACK belongs to SNN_SCAN_SUMS_FROM_STATE");
-    flags &= ~(SNN_SCAN_SUMS_FROM_STATE | SNN_SCAN_STATE_LOOKBACK);
-    if (yfree) {
-        SNN_REQUIRE(sums && state && !apply_scale && sums_from_state_ok(neuron, T, M, C, ldg, p, flags),
-                    "snn_affine_neuron_bwd: SNN_SCAN_SUMS_FROM_STATE not covered (ask snn_affine_neuron_bwd_sums_from_state; "
-                    "LIF from the initial state, sums wanted, train-mode BatchNorm)");
-        SNN_REQUIRE(aligned16(g_out) && aligned16(state) && aligned16(g_vT) && aligned16(g_iT) && aligned16(gx) &&
-                    aligned16(g_v0) && aligned16(g_i0), "snn_affine_neuron_bwd: buffers must be 16-byte aligned");
-        const BwdPlan pl = bwd_plan(T, M, C, true);
-        dim3 grid(pl.gx, pl.gy);
-        // three pixels per thread: the four values a pixel keeps for the statistic of two steps later do not fit the
-        // 256 registers of two waves per SIMD beside four pixels' operand sets (287, or 21 spilled)
-#define SNN_LAUNCH_YF(NP_)                                                                                              \
-    hipLaunchKernelGGL((k_affine_neuron_bwd<SNN_NEURON_LIF, 4, 1, true, NP_, false, true>), grid, dim3(kThreads),         \
-                       pl.lds_bytes, (hipStream_t)stream, g_out, ldg, state, g_out, ldg, g_vT, g_iT, alpha, beta, 0, gx, \
-                       g_v0, g_i0, sums, T, M, C, pl.cvb, *p, lookback)
-        if (pl.rpb == 1) SNN_LAUNCH_YF(1);
-        else if (pl.rpb == 2) SNN_LAUNCH_YF(2);
-        else SNN_LAUNCH_YF(3);
-#undef SNN_LAUNCH_YF
-        SNN_CHECK_LAUNCH("snn_affine_neuron_bwd");
-        return 0;
+    const ScanBwdPlan sp = scan_bwd_plan(neuron, T, M, C, ldg, ldy, sums != nullptr, p, flags);
+    SNN_REQUIRE(!sp.refusal, "snn_affine_neuron_bwd: %s (neuron %d, flags 0x%x)", sp.refusal, neuron, flags);
+    const bool reads_y = !sp.yf && (sums || rebuilds_x(neuron));
+    if (sp.yf) {
+        SNN_REQUIRE(state && !apply_scale, "snn_affine_neuron_bwd: %s", kSumsFromStateCovers);
+        y = g_out;   // never read: the kernel's y operand only has to be a valid tensor
+        ldy = ldg;
+    } else {
+        SNN_REQUIRE(!(neuron == SNN_NEURON_LIF || neuron == SNN_NEURON_LI_TANH || rebuilds_x(neuron)) || state,
+                    "snn_affine_neuron_bwd: saved state required");
+        SNN_REQUIRE(!reads_y || (y && ldy >= C), "snn_affine_neuron_bwd: y required");
+        SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "snn_affine_neuron_bwd: alpha/beta must come together");
+        SNN_REQUIRE(!apply_scale || alpha, "snn_affine_neuron_bwd: apply_scale needs alpha");
     }
-    const int last_only = (flags & SNN_SCAN_LAST_STEP_ONLY) != 0;
-    const bool sb = (flags & SNN_SCAN_BF16_STORAGE) != 0;   // g_out, state, y, gx are bf16 tensors
-    SNN_REQUIRE(!last_only || neuron == SNN_NEURON_LIF || neuron == SNN_NEURON_LI || neuron == SNN_NEURON_LI_TANH,
-                "snn_affine_neuron_bwd: SNN_SCAN_LAST_STEP_ONLY is for LIF / LI / LI+Tanh");
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldg >= C, "snn_affine_neuron_bwd: bad shape");
-    SNN_REQUIRE(neuron >= SNN_NEURON_NONE && neuron <= SNN_NEURON_SYNAPSE, "snn_affine_neuron_bwd: bad neuron %d",
-                neuron);
-    const bool needs_x = neuron == SNN_NEURON_SLI || neuron == SNN_NEURON_SYNAPSE;
-    SNN_REQUIRE(!(neuron == SNN_NEURON_LIF || neuron == SNN_NEURON_LI_TANH || needs_x) || state,
-                "snn_affine_neuron_bwd: saved state required");
-    SNN_REQUIRE(!(sums || needs_x) || (y && ldy >= C), "snn_affine_neuron_bwd: y required");
-    SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "snn_affine_neuron_bwd: alpha/beta must come together");
-    SNN_REQUIRE(!apply_scale || alpha, "snn_affine_neuron_bwd: apply_scale needs alpha");
-    BwdPlan pl = bwd_plan(T, M, C, sums != nullptr);
-    if (sb) {
-        const bool ok = pl.vec == 4 && ldg % 4 == 0 && aligned8(g_out) && aligned8(state) && aligned8(gx) && aligned16(g_vT) &&
-                        aligned16(g_iT) && aligned16(alpha) && aligned16(beta) && aligned16(g_v0) && aligned16(g_i0) &&
-                        (!sums || (ldy % 4 == 0 && aligned8(y))) &&
-                        (neuron == SNN_NEURON_NONE || neuron == SNN_NEURON_LIF || neuron == SNN_NEURON_LI ||
-                         neuron == SNN_NEURON_LI_TANH);
-        SNN_REQUIRE(ok, "snn_affine_neuron_bwd: bf16 storage covers NONE / LIF / LI / LI+Tanh on channel counts and strides "
-                        "that are multiples of 4 (8-byte aligned tensors)");
-    } else if (pl.vec == 4) {
-        bool ok = ldg % 4 == 0 && aligned16(g_out) && aligned16(state) && aligned16(g_vT) && aligned16(g_iT) &&
-                  aligned16(alpha) && aligned16(beta) && aligned16(gx) && aligned16(g_v0) && aligned16(g_i0) &&
-                  (!(sums || needs_x) || (ldy % 4 == 0 && aligned16(y)));
-        SNN_REQUIRE(ok, "snn_affine_neuron_bwd: buffers must be 16-byte aligned when C%%4==0");
+    if (sp.pl.vec == 4) {   // 4 channels per access: 16 bytes of fp32, 8 of the bf16 activation tensors
+        const bool ok = ldg % 4 == 0 && (!reads_y || ldy % 4 == 0) &&
+                        aligned(sp.sb ? 8 : 16, {g_out, state, gx, reads_y ? y : nullptr}) &&
+                        aligned(16, {g_vT, g_iT, alpha, beta, g_v0, g_i0});
+        SNN_REQUIRE(ok, "snn_affine_neuron_bwd: %s", sp.sb ? kBf16Covers : "buffers must be 16-byte aligned when C%4==0");
     }
-    dim3 grid(pl.gx, pl.gy);
-    // buffer addressing (see k_affine_neuron_bwd): one timestep of every tensor must fit a 31-bit byte offset
-    const bool no_buf = (flags & SNN_SCAN_WIDE_ADDRESSING) != 0;
-    const int64_t ld_max = ldg > ldy ? (ldg > C ? ldg : C) : (ldy > C ? ldy : C);
-    // (blocks with a single pixel row take the one-pixel-per-thread instance: the three empty pixel slots of the
-    // four-pixel one are computed and issued in straight-line code - measured 58 us against 45 for the branchy kernel)
-    const bool buf_ok = !no_buf && M * ld_max * 4 < 0x7fffffffLL;
-    if (sb) {
-#define SNN_LAUNCH_BWD_S(NEURON, MODE_)                                                                              \
-    do {                                                                                                             \
-        if (buf_ok && pl.rpb == 1)                                                                                   \
-            hipLaunchKernelGGL((k_affine_neuron_bwd<NEURON, 4, MODE_, true, 1, true>), grid, dim3(kThreads), pl.lds_bytes, \
-                               (hipStream_t)stream, g_out, ldg, state, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, \
-                               g_v0, g_i0, sums, T, M, C, pl.cvb, *p, last_only);                                    \
-        else if (buf_ok)                                                                                             \
-            hipLaunchKernelGGL((k_affine_neuron_bwd<NEURON, 4, MODE_, true, kBwdNP, true>), grid, dim3(kThreads),      \
-                               pl.lds_bytes, (hipStream_t)stream, g_out, ldg, state, y, ldy, g_vT, g_iT, alpha, beta,  \
-                               apply_scale, gx, g_v0, g_i0, sums, T, M, C, pl.cvb, *p, last_only);                   \
-        else                                                                                                         \
-            hipLaunchKernelGGL((k_affine_neuron_bwd<NEURON, 4, MODE_, false, kBwdNP, true>), grid, dim3(kThreads),     \
-                               pl.lds_bytes, (hipStream_t)stream, g_out, ldg, state, y, ldy, g_vT, g_iT, alpha, beta,  \
-                               apply_scale, gx, g_v0, g_i0, sums, T, M, C, pl.cvb, *p, last_only);                   \
-    } while (0)
-#define SNN_DISPATCH_BWD_S(NEURON)                        \
-    do {                                                  \
-        if (pl.mode == 0) SNN_LAUNCH_BWD_S(NEURON, 0);    \
-        else if (pl.mode == 1) SNN_LAUNCH_BWD_S(NEURON, 1); \
-        else SNN_LAUNCH_BWD_S(NEURON, 2);                 \
-    } while (0)
-        switch (neuron) {
-            case SNN_NEURON_NONE: SNN_DISPATCH_BWD_S(SNN_NEURON_NONE); break;
-            case SNN_NEURON_LIF: SNN_DISPATCH_BWD_S(SNN_NEURON_LIF); break;
-            case SNN_NEURON_LI: SNN_DISPATCH_BWD_S(SNN_NEURON_LI); break;
-            default: SNN_DISPATCH_BWD_S(SNN_NEURON_LI_TANH); break;
-        }
-#undef SNN_DISPATCH_BWD_S
-#undef SNN_LAUNCH_BWD_S
-        SNN_CHECK_LAUNCH("snn_affine_neuron_bwd");
-        return 0;
-    }
-    switch (neuron) {
-        case SNN_NEURON_NONE: SNN_DISPATCH_BWD(SNN_NEURON_NONE); break;
-        case SNN_NEURON_LIF: SNN_DISPATCH_BWD(SNN_NEURON_LIF); break;
-        case SNN_NEURON_LI: SNN_DISPATCH_BWD(SNN_NEURON_LI); break;
-        case SNN_NEURON_LI_TANH: SNN_DISPATCH_BWD(SNN_NEURON_LI_TANH); break;
-        case SNN_NEURON_SLI: SNN_DISPATCH_BWD(SNN_NEURON_SLI); break;
-        default: SNN_DISPATCH_BWD(SNN_NEURON_SYNAPSE); break;
-    }
+    const bool launched = dispatch(
+        [&](auto NEURON, auto VEC, auto MODE, auto BUF, auto NP, auto SB, auto YF) {
+            if constexpr (bwd_instance(NEURON(), VEC(), MODE(), BUF(), NP(), SB(), YF())) {
+                hipLaunchKernelGGL((k_affine_neuron_bwd<NEURON(), VEC(), MODE(), BUF(), NP(), SB(), YF()>),
+                                   dim3(sp.pl.gx, sp.pl.gy), dim3(kThreads), sp.pl.lds_bytes, (hipStream_t)stream, g_out, ldg,
+                                   state, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, g_v0, g_i0, sums, T, M, C,
+                                   sp.pl.cvb, *p, sp.yf ? sp.lookback : sp.last_only);
+                return true;
+            } else {
+                return false;
+            }
+        },
+        AnyNeuron{neuron}, OneOf<1, 4>{sp.pl.vec}, OneOf<0, 1, 2>{sp.pl.mode}, Flag{sp.buf}, OneOf<1, 2, 3, kBwdNP>{sp.np},
+        Flag{sp.sb}, Flag{sp.yf});
+    SNN_REQUIRE(launched, "snn_affine_neuron_bwd: no kernel instance (neuron %d, vec %d, mode %d, BUF %d, NP %d)", neuron,
+                sp.pl.vec, sp.pl.mode, (int)sp.buf, sp.np);
     SNN_CHECK_LAUNCH("snn_affine_neuron_bwd");
     return 0;
 }
-
-#define SNN_LAUNCH_CKPT(VEC_, MODE_)                                                                              \
-    hipLaunchKernelGGL((k_lif_bwd_ckpt<VEC_, MODE_>), grid, dim3(kThreads), pl.lds_bytes, (hipStream_t)stream, g_out, \
-                       ldg, ckpt, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, g_v0, g_i0, sums, T, M, C, pl.cvb, \
-                       *p)
 
 // LIF backward from the checkpoints of snn_lif_fwd_ckpt; sums / outputs exactly as snn_affine_neuron_bwd(LIF)
 extern "C" int snn_lif_bwd_ckpt(const float* g_out, int64_t ldg, const float* ckpt, const float* y, int64_t ldy,
@@ -1879,51 +1829,47 @@ extern "C" int snn_lif_bwd_ckpt(const float* g_out, int64_t ldg, const float* ck
     SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldg >= C && ldy >= C, "snn_lif_bwd_ckpt: bad shape");
     SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "snn_lif_bwd_ckpt: alpha/beta must come together");
     SNN_REQUIRE(!apply_scale || alpha, "snn_lif_bwd_ckpt: apply_scale needs alpha");
-    BwdPlan pl = bwd_plan(T, M, C, sums != nullptr);
-    if (pl.vec == 4) {
-        bool ok = ldg % 4 == 0 && ldy % 4 == 0 && aligned16(g_out) && aligned16(ckpt) && aligned16(y) &&
-                  aligned16(g_vT) && aligned16(g_iT) && aligned16(alpha) && aligned16(beta) && aligned16(gx) &&
-                  aligned16(g_v0) && aligned16(g_i0);
-        SNN_REQUIRE(ok, "snn_lif_bwd_ckpt: buffers must be 16-byte aligned when C%%4==0");
-    }
-    dim3 grid(pl.gx, pl.gy);
-    if (pl.vec == 4) {
-        if (pl.mode == 0) SNN_LAUNCH_CKPT(4, 0);
-        else if (pl.mode == 1) SNN_LAUNCH_CKPT(4, 1);
-        else SNN_LAUNCH_CKPT(4, 2);
-    } else {
-        if (pl.mode == 0) SNN_LAUNCH_CKPT(1, 0);
-        else if (pl.mode == 1) SNN_LAUNCH_CKPT(1, 1);
-        else SNN_LAUNCH_CKPT(1, 2);
-    }
+    const BwdPlan pl = scan_bwd_plan(SNN_NEURON_LIF, T, M, C, ldg, ldy, sums != nullptr, p, 0).pl;   // (nothing left to refuse)
+    SNN_REQUIRE(pl.vec == 1 || (multiples(4, {ldg, ldy}) && aligned(16, {g_out, ckpt, y, g_vT, g_iT, alpha, beta, gx, g_v0, g_i0})),
+                "snn_lif_bwd_ckpt: buffers must be 16-byte aligned when C%%4==0");
+    dispatch(
+        [&](auto VEC, auto MODE) {
+            hipLaunchKernelGGL((k_lif_bwd_ckpt<VEC(), MODE()>), dim3(pl.gx, pl.gy), dim3(kThreads), pl.lds_bytes,
+                               (hipStream_t)stream, g_out, ldg, ckpt, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, g_v0,
+                               g_i0, sums, T, M, C, pl.cvb, *p);
+            return true;
+        },
+        OneOf<1, 4>{pl.vec}, OneOf<0, 1, 2>{pl.mode});
     SNN_CHECK_LAUNCH("snn_lif_bwd_ckpt");
+    return 0;
+}
+
+// block partials of the reverse scan -> raw (sum gx, sum gx*y) per (t, c); from_state: the scan ran with
+// SNN_SCAN_SUMS_FROM_STATE and its second partial is sum(gx * x)
+static int bn_bwd_reduce(const char* name, int from_state, const double* sums, int T, int64_t M, int C, const float* gamma,
+                         const float* bias, const float* mean, const float* invstd, const float* gx, const float* y,
+                         int64_t ldy, double* raw, void* stream) {
+    SNN_REQUIRE(sums != raw, "%s: raw must not alias the partial sums", name);
+    BwdPlan pl = bwd_plan(T, M, C, true);
+    int n = T * C;
+    hipLaunchKernelGGL(k_bn_bwd_reduce, dim3((n + 7) / 8), dim3(256), 0, (hipStream_t)stream, sums, pl.gx, T, C, raw,
+                       from_state, M, gamma, bias, mean, invstd, gx, y, ldy);
+    SNN_CHECK_LAUNCH(name);
     return 0;
 }
 
 extern "C" int snn_bn_bwd_reduce(const double* sums, int T, int64_t M, int C, double* raw, void* stream) {
     SNN_REQUIRE(sums && raw && T > 0 && M > 0 && C > 0, "snn_bn_bwd_reduce: bad arguments");
-    SNN_REQUIRE(sums != raw, "snn_bn_bwd_reduce: raw must not alias the partial sums");
-    BwdPlan pl = bwd_plan(T, M, C, true);
-    int n = T * C;
-    hipLaunchKernelGGL(k_bn_bwd_reduce, dim3((n + 7) / 8), dim3(256), 0, (hipStream_t)stream, sums, pl.gx, T, C, raw, 0, M,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-    SNN_CHECK_LAUNCH("snn_bn_bwd_reduce");
-    return 0;
+    return bn_bwd_reduce("snn_bn_bwd_reduce", 0, sums, T, M, C, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, raw,
+                         stream);
 }
 
-// the same for sums of a scan that ran with SNN_SCAN_SUMS_FROM_STATE: raw receives (sum gx, sum gx*y) all the same
 extern "C" int snn_bn_bwd_reduce_from_state(const double* sums, int T, int64_t M, int C, const float* gamma, const float* bias,
                                             const float* mean, const float* invstd, const float* gx, const float* y,
                                             int64_t ldy, double* raw, void* stream) {
     SNN_REQUIRE(sums && raw && mean && invstd && gx && y && T > 0 && M > 0 && C > 0 && ldy >= C,
                 "snn_bn_bwd_reduce_from_state: bad arguments");
-    SNN_REQUIRE(sums != raw, "snn_bn_bwd_reduce_from_state: raw must not alias the partial sums");
-    BwdPlan pl = bwd_plan(T, M, C, true);
-    int n = T * C;
-    hipLaunchKernelGGL(k_bn_bwd_reduce, dim3((n + 7) / 8), dim3(256), 0, (hipStream_t)stream, sums, pl.gx, T, C, raw, 1, M,
-                       gamma, bias, mean, invstd, gx, y, ldy);
-    SNN_CHECK_LAUNCH("snn_bn_bwd_reduce_from_state");
-    return 0;
+    return bn_bwd_reduce("snn_bn_bwd_reduce_from_state", 1, sums, T, M, C, gamma, bias, mean, invstd, gx, y, ldy, raw, stream);
 }
 
 extern "C" int snn_bn_bwd_coef(const double* raw, const double* raw_local, double* param_sums, int T, int64_t M_total,
@@ -1945,70 +1891,73 @@ extern "C" int snn_bn_bwd_coef(const double* raw, const double* raw_local, doubl
     return 0;
 }
 
-// single-process form: reduce the block partials in place, then coefficients and parameter gradients
-extern "C" int snn_bn_bwd_finalize(double* sums, int T, int64_t M, int C, const float* gamma, const float* mean,
-                                   const float* invstd, float* coefA, float* coefB, float* coefC, float* dgamma,
-                                   float* dbias, int accumulate, void* stream) {
-    SNN_REQUIRE(sums && mean && invstd && coefA && coefB && coefC, "snn_bn_bwd_finalize: null pointer");
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0, "snn_bn_bwd_finalize: bad shape");
+// single-process form: reduce the block partials in place, then coefficients and parameter gradients; from_state: sums
+// written by a scan that ran with SNN_SCAN_SUMS_FROM_STATE (second partial: sum(gx * x), see the kernel)
+static int bn_bwd_finalize(const char* name, int from_state, double* sums, int T, int64_t M, int C, const float* gamma,
+                           const float* bias, const float* mean, const float* invstd, const float* gx, const float* y,
+                           int64_t ldy, float* coefA, float* coefB, float* coefC, float* dgamma, float* dbias,
+                           int accumulate, void* stream) {
+    SNN_REQUIRE(sums && mean && invstd && coefA && coefB && coefC && (!from_state || (gx && y)), "%s: null pointer", name);
+    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && (!from_state || ldy >= C), "%s: bad shape", name);
     BwdPlan pl = bwd_plan(T, M, C, true);
     hipLaunchKernelGGL(k_bn_bwd_finalize_fused, dim3(C), dim3(1024), 0, (hipStream_t)stream, sums, pl.gx, T, M, C, gamma,
-                       mean, invstd, coefA, coefB, coefC, dgamma, dbias, accumulate, 0, nullptr, nullptr, nullptr, 0);
-    SNN_CHECK_LAUNCH("snn_bn_bwd_finalize");
+                       mean, invstd, coefA, coefB, coefC, dgamma, dbias, accumulate, from_state, bias, gx, y, ldy);
+    SNN_CHECK_LAUNCH(name);
     return 0;
 }
 
-// the same for sums written by a scan that ran with SNN_SCAN_SUMS_FROM_STATE (second partial: sum(gx * x), see the kernel)
+extern "C" int snn_bn_bwd_finalize(double* sums, int T, int64_t M, int C, const float* gamma, const float* mean,
+                                   const float* invstd, float* coefA, float* coefB, float* coefC, float* dgamma,
+                                   float* dbias, int accumulate, void* stream) {
+    return bn_bwd_finalize("snn_bn_bwd_finalize", 0, sums, T, M, C, gamma, nullptr, mean, invstd, nullptr, nullptr, 0, coefA,
+                           coefB, coefC, dgamma, dbias, accumulate, stream);
+}
+
 extern "C" int snn_bn_bwd_finalize_from_state(double* sums, int T, int64_t M, int C, const float* gamma, const float* bias,
                                               const float* mean, const float* invstd, const float* gx, const float* y,
                                               int64_t ldy, float* coefA, float* coefB, float* coefC, float* dgamma,
                                               float* dbias, int accumulate, void* stream) {
-    SNN_REQUIRE(sums && mean && invstd && coefA && coefB && coefC && gx && y, "snn_bn_bwd_finalize_from_state: null pointer");
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C, "snn_bn_bwd_finalize_from_state: bad shape");
-    BwdPlan pl = bwd_plan(T, M, C, true);
-    hipLaunchKernelGGL(k_bn_bwd_finalize_fused, dim3(C), dim3(1024), 0, (hipStream_t)stream, sums, pl.gx, T, M, C, gamma,
-                       mean, invstd, coefA, coefB, coefC, dgamma, dbias, accumulate, 1, bias, gx, y, ldy);
-    SNN_CHECK_LAUNCH("snn_bn_bwd_finalize_from_state");
-    return 0;
+    return bn_bwd_finalize("snn_bn_bwd_finalize_from_state", 1, sums, T, M, C, gamma, bias, mean, invstd, gx, y, ldy, coefA,
+                           coefB, coefC, dgamma, dbias, accumulate, stream);
 }
 
-extern "C" int snn_bn_bwd_apply(const float* gx, const float* y, int64_t ldy, const float* coefA, const float* coefB,
-                                const float* coefC, float* dy, int64_t lddy, int T, int64_t M, int C, int accumulate,
-                                void* stream) {
-    SNN_REQUIRE(gx && y && coefA && coefB && coefC && dy, "snn_bn_bwd_apply: null pointer");
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C && lddy >= C, "snn_bn_bwd_apply: bad shape");
-    int vec = (C % 4 == 0 && ldy % 4 == 0 && lddy % 4 == 0 && aligned16(gx) && aligned16(y) && aligned16(dy) &&
-               aligned16(coefA) && aligned16(coefB) && aligned16(coefC))
-                  ? 4
-                  : 1;
+// dy = A*gx + B*y + C per (t, c); sb: gx, y and dy are bf16 tensors
+static int bn_bwd_apply(const char* name, bool sb, const float* gx, const float* y, int64_t ldy, const float* coefA,
+                        const float* coefB, const float* coefC, float* dy, int64_t lddy, int T, int64_t M, int C,
+                        int accumulate, void* stream) {
+    SNN_REQUIRE(gx && y && coefA && coefB && coefC && dy, "%s: null pointer", name);
+    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C && lddy >= C, "%s: bad shape", name);
+    const int vec = (multiples(4, {C, ldy, lddy}) && aligned(sb ? 8 : 16, {gx, y, dy}) && aligned(16, {coefA, coefB, coefC}))
+                        ? 4
+                        : 1;
+    SNN_REQUIRE(!sb || vec == 4, "%s: bad shape (C and strides multiples of 4, bf16 tensors 8-byte aligned)", name);
     int64_t total = (int64_t)T * M * (C / vec);
     int64_t blocks = snn_ceil_div(total, kThreads);
     if (blocks > snn_max_blocks()) blocks = snn_max_blocks();
     if (const char* force = snn_tuning_env("SNN_APPLY_CAP")) {   // tuning aid: blocks per launch of the apply pass
         if (atoi(force) > 0 && blocks > atoi(force)) blocks = atoi(force);
     }
-    if (vec == 4)
-        hipLaunchKernelGGL(k_bn_bwd_apply<4>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, gx, y,
-                           ldy, coefA, coefB, coefC, dy, lddy, T, M, C, accumulate);
-    else
-        hipLaunchKernelGGL(k_bn_bwd_apply<1>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, gx, y,
-                           ldy, coefA, coefB, coefC, dy, lddy, T, M, C, accumulate);
-    SNN_CHECK_LAUNCH("snn_bn_bwd_apply");
+    dispatch(
+        [&](auto VEC, auto SB) {
+            if constexpr (VEC() == 4 || !SB()) {
+                hipLaunchKernelGGL((k_bn_bwd_apply<VEC(), SB()>), dim3((unsigned)blocks), dim3(kThreads), 0,
+                                   (hipStream_t)stream, gx, y, ldy, coefA, coefB, coefC, dy, lddy, T, M, C, accumulate);
+            }
+            return true;
+        },
+        OneOf<1, 4>{vec}, Flag{sb});
+    SNN_CHECK_LAUNCH(name);
     return 0;
+}
+
+extern "C" int snn_bn_bwd_apply(const float* gx, const float* y, int64_t ldy, const float* coefA, const float* coefB,
+                                const float* coefC, float* dy, int64_t lddy, int T, int64_t M, int C, int accumulate,
+                                void* stream) {
+    return bn_bwd_apply("snn_bn_bwd_apply", false, gx, y, ldy, coefA, coefB, coefC, dy, lddy, T, M, C, accumulate, stream);
 }
 
 extern "C" int snn_bn_bwd_apply_bf16(const float* gx, const float* y, int64_t ldy, const float* coefA, const float* coefB,
                                      const float* coefC, float* dy, int64_t lddy, int T, int64_t M, int C, int accumulate,
                                      void* stream) {
-    SNN_REQUIRE(gx && y && coefA && coefB && coefC && dy, "snn_bn_bwd_apply_bf16: null pointer");
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C && lddy >= C && C % 4 == 0 && ldy % 4 == 0 && lddy % 4 == 0 &&
-                    aligned8(gx) && aligned8(y) && aligned8(dy) && aligned16(coefA) && aligned16(coefB) && aligned16(coefC),
-                "snn_bn_bwd_apply_bf16: bad shape (C and strides multiples of 4, bf16 tensors 8-byte aligned)");
-    int64_t total = (int64_t)T * M * (C / 4);
-    int64_t blocks = snn_ceil_div(total, kThreads);
-    if (blocks > snn_max_blocks()) blocks = snn_max_blocks();
-    hipLaunchKernelGGL((k_bn_bwd_apply<4, true>), dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, gx, y, ldy,
-                       coefA, coefB, coefC, dy, lddy, T, M, C, accumulate);
-    SNN_CHECK_LAUNCH("snn_bn_bwd_apply_bf16");
-    return 0;
+    return bn_bwd_apply("snn_bn_bwd_apply_bf16", true, gx, y, ldy, coefA, coefB, coefC, dy, lddy, T, M, C, accumulate, stream);
 }

@@ -1199,6 +1199,74 @@ USE_SUMS_FROM_STATE = not os.environ.get("SNN_NO_SUMS_FROM_STATE")
 LIF_CHECKPOINT_BYTES: Optional[int] = None
 
 
+def _bn_coefficients(y, ldy, dims, gamma, bias, use_running, eps, momentum, running_mean, running_var, sync_group,
+                     bn_hint, st):
+    """BatchNorm statistics of ``y`` per (t, c) - the running ones, this process's, or the group's (SyncBatchNorm) - and
+    the affine they make with gamma / bias: ``(mean, invstd, alpha, beta)``, each ``[T, C]``."""
+    T, M, C = dims
+    dev = y.device
+    mean, invstd, alpha, beta = (torch.empty((T, C), device=dev, dtype=_F32) for _ in range(4))
+    g_ptr = _ptr(gamma.detach()) if gamma is not None else None
+    b_ptr = _ptr(bias.detach()) if bias is not None else None
+    if use_running:
+        if running_mean is None or running_var is None:
+            raise RuntimeError("BatchNorm in eval mode needs running statistics")
+        _hip.call("snn_bn_stats_finalize", None, 0, 0, T, M, C, g_ptr, b_ptr, eps, momentum,
+                  running_mean.data_ptr(), running_var.data_ptr(), 1, mean.data_ptr(), invstd.data_ptr(),
+                  alpha.data_ptr(), beta.data_ptr(), st)
+        return mean, invstd, alpha, beta
+    if bn_hint is not None and bn_hint.data_ptr == y.data_ptr() and bn_hint.dims == (T, M, C) and USE_CONV_BN_STATS:
+        # the producing convolution summed y and y^2 on the way out (snn_conv2d_fwd bn_partial)
+        partial, chunks, rpc = bn_hint.partial, bn_hint.chunks, bn_hint.rows_per_chunk
+    else:
+        n_part = _hip.query("snn_bn_stats_partial_size", T, M, C)
+        partial = torch.empty((n_part,), device=dev, dtype=torch.float64)
+        chunks = rpc = 0
+        _hip.call("snn_bn_stats_bf16" if y.dtype == _BF16 else "snn_bn_stats", y.data_ptr(), ldy, T, M, C,
+                  partial.data_ptr(), st)
+    if sync_group is None:
+        _hip.call("snn_bn_stats_finalize", partial.data_ptr(), chunks, rpc, T, M, C, g_ptr, b_ptr, eps, momentum,
+                  _ptr(running_mean), _ptr(running_var), 0, mean.data_ptr(), invstd.data_ptr(),
+                  alpha.data_ptr(), beta.data_ptr(), st)
+    else:
+        # SyncBatchNorm (config.yaml:76): ONE all-reduce of [T, C, 2] sums per layer for all timesteps
+        import torch.distributed as dist
+        world = dist.get_world_size(sync_group[0])
+        sums = torch.empty((T, C, 2), device=dev, dtype=torch.float64)
+        _hip.call("snn_bn_stats_reduce", partial.data_ptr(), chunks, rpc, T, M, C, sums.data_ptr(), st)
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=sync_group[0])
+        scratch = torch.empty((T * C,), device=dev, dtype=torch.float64)
+        _hip.call("snn_bn_stats_from_sums", sums.data_ptr(), T, M * world, C, g_ptr, b_ptr, eps, momentum,
+                  _ptr(running_mean), _ptr(running_var), mean.data_ptr(), invstd.data_ptr(),
+                  alpha.data_ptr(), beta.data_ptr(), scratch.data_ptr(), st)
+    return mean, invstd, alpha, beta
+
+
+def _sync_bn_bwd_coefficients(sync_group, sums, from_state, gx, y, ldy, dims, gamma, bn_bias, mean, invstd, coef, dg_ptr,
+                              db_ptr, acc_flag, st):
+    """SyncBatchNorm backward: dy needs the GLOBAL sums (one all-reduce of [T, C, 2]); the parameter gradients use the
+    rank-local sums - the data-parallel all-reduce averages them afterwards."""
+    import torch.distributed as dist
+    T, M, C = dims
+    world = dist.get_world_size(sync_group[0])
+    raw_local = torch.empty((T, C, 2), device=y.device, dtype=torch.float64)
+    if from_state:
+        _hip.call("snn_bn_bwd_reduce_from_state", sums.data_ptr(), T, M, C, _ptr(gamma), _ptr(bn_bias),
+                  mean.data_ptr(), invstd.data_ptr(), gx.data_ptr(), y.data_ptr(), ldy, raw_local.data_ptr(), st)
+    else:
+        _hip.call("snn_bn_bwd_reduce", sums.data_ptr(), T, M, C, raw_local.data_ptr(), st)
+    raw = raw_local.clone()
+    dist.all_reduce(raw, op=dist.ReduceOp.SUM, group=sync_group[0])
+    param_sums = torch.empty((T, C, 2), device=y.device, dtype=torch.float64)
+    _hip.call("snn_bn_bwd_coef", raw.data_ptr(), raw_local.data_ptr(), param_sums.data_ptr(), T, M * world,
+              C, _ptr(gamma), mean.data_ptr(), invstd.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
+              coef[2].data_ptr(), dg_ptr, db_ptr, acc_flag, st)
+
+
+def _ptr_at(t: Optional[torch.Tensor], offset: int) -> Optional[int]:
+    return None if t is None else t.data_ptr() + offset
+
+
 class _AffineNeuron(Function):
     """[BatchNorm2d (per-timestep batch statistics)] -> [LIF | LI | LI+Tanh | nothing], fused.
 
@@ -1231,47 +1299,11 @@ class _AffineNeuron(Function):
         M = B * H * W
         st = _stream()
         dev = y.device
-        alpha = beta = mean = invstd = None
         use_running = has_bn and not training
+        mean = invstd = alpha = beta = None
         if has_bn:
-            mean = torch.empty((T, C), device=dev, dtype=_F32)
-            invstd = torch.empty((T, C), device=dev, dtype=_F32)
-            alpha = torch.empty((T, C), device=dev, dtype=_F32)
-            beta = torch.empty((T, C), device=dev, dtype=_F32)
-            g_ptr = _ptr(gamma.detach()) if gamma is not None else None
-            b_ptr = _ptr(bias.detach()) if bias is not None else None
-            if use_running:
-                if running_mean is None or running_var is None:
-                    raise RuntimeError("BatchNorm in eval mode needs running statistics")
-                _hip.call("snn_bn_stats_finalize", None, 0, 0, T, M, C, g_ptr, b_ptr, eps, momentum,
-                          running_mean.data_ptr(), running_var.data_ptr(), 1, mean.data_ptr(), invstd.data_ptr(),
-                          alpha.data_ptr(), beta.data_ptr(), st)
-            else:
-                if (bn_hint is not None and bn_hint.data_ptr == y.data_ptr() and bn_hint.dims == (T, M, C)
-                        and USE_CONV_BN_STATS):
-                    # the producing convolution summed y and y^2 on the way out (snn_conv2d_fwd bn_partial)
-                    partial, chunks, rpc = bn_hint.partial, bn_hint.chunks, bn_hint.rows_per_chunk
-                else:
-                    n_part = _hip.query("snn_bn_stats_partial_size", T, M, C)
-                    partial = torch.empty((n_part,), device=dev, dtype=torch.float64)
-                    chunks = rpc = 0
-                    _hip.call("snn_bn_stats_bf16" if sb else "snn_bn_stats", y.data_ptr(), ldy, T, M, C,
-                              partial.data_ptr(), st)
-                if sync_group is None:
-                    _hip.call("snn_bn_stats_finalize", partial.data_ptr(), chunks, rpc, T, M, C, g_ptr, b_ptr, eps, momentum,
-                              _ptr(running_mean), _ptr(running_var), 0, mean.data_ptr(), invstd.data_ptr(),
-                              alpha.data_ptr(), beta.data_ptr(), st)
-                else:
-                    # SyncBatchNorm (config.yaml:76): ONE all-reduce of [T, C, 2] sums per layer for all timesteps
-                    import torch.distributed as dist
-                    world = dist.get_world_size(sync_group[0])
-                    sums = torch.empty((T, C, 2), device=dev, dtype=torch.float64)
-                    _hip.call("snn_bn_stats_reduce", partial.data_ptr(), chunks, rpc, T, M, C, sums.data_ptr(), st)
-                    dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=sync_group[0])
-                    scratch = torch.empty((T * C,), device=dev, dtype=torch.float64)
-                    _hip.call("snn_bn_stats_from_sums", sums.data_ptr(), T, M * world, C, g_ptr, b_ptr, eps, momentum,
-                              _ptr(running_mean), _ptr(running_var), mean.data_ptr(), invstd.data_ptr(),
-                              alpha.data_ptr(), beta.data_ptr(), scratch.data_ptr(), st)
+            mean, invstd, alpha, beta = _bn_coefficients(y, ldy, (T, M, C), gamma, bias, use_running, eps, momentum,
+                                                         running_mean, running_var, sync_group, bn_hint, st)
         need_grad = any(ctx.needs_input_grad[:5])
         # spikes_out (a list the caller reads afterwards): the consumer can form the spikes from the saved potentials
         # (snn_conv1x1_spikes_*), so when those are saved anyway no output tensor is written at all
@@ -1390,10 +1422,6 @@ class _AffineNeuron(Function):
         gx = torch.empty((T, B, H, W, C), device=dev, dtype=y.dtype)
         g_v0 = _new_cl((B,), C, H, W, y, _F32) if (has_state and ctx.has_v0 and ctx.needs_input_grad[3]) else None
         g_i0 = _new_cl((B,), C, H, W, y, _F32) if (has_state and ctx.has_i0 and ctx.needs_input_grad[4]) else None
-        sums = None
-        if need_sums:
-            n_sums = _hip.query("snn_affine_neuron_bwd_sums_size", T, M, C)
-            sums = torch.empty((n_sums,), device=dev, dtype=torch.float64)
         # eval-mode BN has no batch coupling: dy = alpha * gx, applied while gx is written
         apply_scale = 1 if (has_bn and use_running) else 0
         dy = dgamma = dbias = None
@@ -1430,90 +1458,61 @@ class _AffineNeuron(Function):
             and not (segmented and T % SCAN_SEGMENT_T == 1)    # (a second segment starting at step 1 has one step to look back on)
             and all(_hip.query("snn_affine_neuron_bwd_sums_from_state", neuron, ts_, M, C, ldg, params, scan_flags)
                     for ts_ in ({SCAN_SEGMENT_T, T % SCAN_SEGMENT_T or SCAN_SEGMENT_T} if segmented else {T})))
-        if segmented:
-            fr_g, fr_y, fr_c = M * ldg * es, M * ldy * es, M * C * es    # bytes per timestep of g_out / y / dense tensors
-            gv_in, gi_in = g_vT, g_iT
-            first = True
-            g_none = None   # last_only: the output gradient of every segment but the last one is zero
-            for t1 in range(T, 0, -SCAN_SEGMENT_T):
-                t0 = max(0, t1 - SCAN_SEGMENT_T)
-                ts = t1 - t0
-                last = t0 == 0
-                gv_out = g_v0 if (last and g_v0 is not None) else torch.empty((B, H, W, C), device=dev, dtype=_F32)
-                gi_out = g_i0 if (last and g_i0 is not None) else torch.empty((B, H, W, C), device=dev, dtype=_F32)
+        # One loop over the segments, last first; an unsegmented scan is the single segment [0, T).
+        seg_T = SCAN_SEGMENT_T if segmented else T
+        fr_g, fr_y, fr_c = M * ldg * es, M * ldy * es, M * C * es    # bytes per timestep of g_out / y / dense tensors
+        gv_in, gi_in = g_vT, g_iT
+        g_none = None   # last_only: the output gradient of every segment but the last one is zero
+        sums = None
+        for t1 in range(T, 0, -seg_T):
+            t0 = max(0, t1 - seg_T)
+            ts, tc = t1 - t0, t0 * C * 4
+            # what a segment hands down: the caller's g_v0 / g_i0 from segment [0, ...), a carry buffer in between
+            gv_out, gi_out = g_v0, g_i0
+            if segmented and (t0 > 0 or g_v0 is None):
+                gv_out = torch.empty((B, H, W, C), device=dev, dtype=_F32)
+            if segmented and (t0 > 0 or g_i0 is None):
+                gi_out = torch.empty((B, H, W, C), device=dev, dtype=_F32)
+            if need_sums:
                 n_sums = _hip.query("snn_affine_neuron_bwd_sums_size", ts, M, C)
-                seg_sums = torch.empty((n_sums,), device=dev, dtype=torch.float64)
-                tc = t0 * C * 4
-                if not ctx.last_only:
-                    g_seg = g_out.data_ptr() + t0 * fr_g
-                elif t1 == T:
-                    g_seg = g_out.data_ptr()          # [B,H,W,C] of the last step = the last step of this segment
-                else:
-                    if g_none is None:
-                        g_none = torch.zeros_like(g_out)
-                    g_seg = g_none.data_ptr()
-                st_off = 0 if (ctx.last_only and neuron == _hip.NEURON_LI_TANH) else t0 * fr_c   # saved output: last step only
+                sums = torch.empty((n_sums,), device=dev, dtype=torch.float64)
+            if not ctx.last_only:
+                g_seg = g_out.data_ptr() + t0 * fr_g
+            elif t1 == T:
+                g_seg = g_out.data_ptr()          # [B,H,W,C] of the last step = the last step of this segment
+            else:
+                if g_none is None:
+                    g_none = torch.zeros_like(g_out)
+                g_seg = g_none.data_ptr()
+            st_off = 0 if (ctx.last_only and neuron == _hip.NEURON_LI_TANH) else t0 * fr_c   # saved output: last step only
+            y_seg, gx_seg = y.data_ptr() + t0 * fr_y, gx.data_ptr() + t0 * fr_c
+            # (sums from the state: y is not read - the statistic comes from the neuron input rebuilt from the saved
+            # potentials; a segment gets the pointer all the same)
+            scan = (g_seg, ldg, _ptr_at(state, st_off), y_seg if (segmented or not sums_from_state) else None, ldy,
+                    _ptr(gv_in), _ptr(gi_in), _ptr_at(alpha, tc), _ptr_at(beta, tc), apply_scale, gx_seg, _ptr(gv_out),
+                    _ptr(gi_out), _ptr(sums), ts, M, C, params)
+            if ctx.ckpt:
+                _hip.call("snn_lif_bwd_ckpt", *scan, st)
+            else:
                 seg_flags = scan_flags
                 if sums_from_state:
                     seg_flags |= _hip.SCAN_SUMS_FROM_STATE | (_hip.SCAN_STATE_LOOKBACK if t0 > 0 else 0)
-                _hip.call("snn_affine_neuron_bwd", neuron, g_seg, ldg,
-                          None if state is None else state.data_ptr() + st_off, y.data_ptr() + t0 * fr_y, ldy,
-                          _ptr(gv_in), _ptr(gi_in), None if alpha is None else alpha.data_ptr() + tc,
-                          None if beta is None else beta.data_ptr() + tc, apply_scale, gx.data_ptr() + t0 * fr_c,
-                          gv_out.data_ptr(), gi_out.data_ptr(), seg_sums.data_ptr(), ts, M, C, params, seg_flags, st)
+                _hip.call("snn_affine_neuron_bwd", neuron, *scan, seg_flags, st)
+            if need_sums and ctx.sync_group is None:
+                # coefficients of this segment's steps; the parameter gradients add up over the segments
+                tail = (coef[0].data_ptr() + tc, coef[1].data_ptr() + tc, coef[2].data_ptr() + tc, dg_ptr, db_ptr,
+                        acc_flag if t1 == T else 1, st)
                 if sums_from_state:
-                    _hip.call("snn_bn_bwd_finalize_from_state", seg_sums.data_ptr(), ts, M, C, _ptr(gamma), _ptr(bn_bias),
-                              mean.data_ptr() + tc, invstd.data_ptr() + tc, gx.data_ptr() + t0 * fr_c,
-                              y.data_ptr() + t0 * fr_y, ldy, coef[0].data_ptr() + tc, coef[1].data_ptr() + tc,
-                              coef[2].data_ptr() + tc, dg_ptr, db_ptr, acc_flag if first else 1, st)
+                    _hip.call("snn_bn_bwd_finalize_from_state", sums.data_ptr(), ts, M, C, _ptr(gamma), _ptr(bn_bias),
+                              mean.data_ptr() + tc, invstd.data_ptr() + tc, gx_seg, y_seg, ldy, *tail)
                 else:
-                    _hip.call("snn_bn_bwd_finalize", seg_sums.data_ptr(), ts, M, C, _ptr(gamma), mean.data_ptr() + tc,
-                              invstd.data_ptr() + tc, coef[0].data_ptr() + tc, coef[1].data_ptr() + tc,
-                              coef[2].data_ptr() + tc, dg_ptr, db_ptr, acc_flag if first else 1, st)
-                gv_in, gi_in, first = gv_out, gi_out, False
-        if segmented:
-            pass
-        elif sums_from_state:
-            # y is not read: the statistic comes from the neuron input rebuilt from the saved potentials
-            _hip.call("snn_affine_neuron_bwd", neuron, g_out.data_ptr(), ldg, _ptr(state), None, ldy,
-                      _ptr(g_vT), _ptr(g_iT), _ptr(alpha), _ptr(beta), 0, gx.data_ptr(), None, None, _ptr(sums), T, M, C,
-                      params, scan_flags | _hip.SCAN_SUMS_FROM_STATE, st)
-        elif ctx.ckpt:
-            _hip.call("snn_lif_bwd_ckpt", g_out.data_ptr(), ldg, state.data_ptr(), y.data_ptr(), ldy, _ptr(g_vT),
-                      _ptr(g_iT), _ptr(alpha), _ptr(beta), apply_scale, gx.data_ptr(), _ptr(g_v0), _ptr(g_i0),
-                      _ptr(sums), T, M, C, params, st)
-        else:
-            _hip.call("snn_affine_neuron_bwd", neuron, g_out.data_ptr(), ldg, _ptr(state), y.data_ptr(), ldy,
-                      _ptr(g_vT), _ptr(g_iT), _ptr(alpha), _ptr(beta), apply_scale, gx.data_ptr(), _ptr(g_v0),
-                      _ptr(g_i0), _ptr(sums), T, M, C, params, scan_flags, st)
+                    _hip.call("snn_bn_bwd_finalize", sums.data_ptr(), ts, M, C, _ptr(gamma), mean.data_ptr() + tc,
+                              invstd.data_ptr() + tc, *tail)
+            gv_in, gi_in = gv_out, gi_out
         if need_sums:
-            if segmented:
-                pass   # coefficients and parameter gradients were finalised per segment
-            elif sums_from_state and ctx.sync_group is None:
-                _hip.call("snn_bn_bwd_finalize_from_state", sums.data_ptr(), T, M, C, _ptr(gamma), _ptr(bn_bias),
-                          mean.data_ptr(), invstd.data_ptr(), gx.data_ptr(), y.data_ptr(), ldy, coef[0].data_ptr(),
-                          coef[1].data_ptr(), coef[2].data_ptr(), dg_ptr, db_ptr, acc_flag, st)
-            elif ctx.sync_group is None and not sums_from_state:
-                _hip.call("snn_bn_bwd_finalize", sums.data_ptr(), T, M, C, _ptr(gamma), mean.data_ptr(),
-                          invstd.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(), dg_ptr,
-                          db_ptr, acc_flag, st)
-            else:
-                # SyncBatchNorm backward: dy needs the GLOBAL sums (one all-reduce of [T, C, 2]); the parameter
-                # gradients use the rank-local sums - the data-parallel all-reduce averages them afterwards
-                import torch.distributed as dist
-                world = dist.get_world_size(ctx.sync_group[0])
-                raw_local = torch.empty((T, C, 2), device=dev, dtype=torch.float64)
-                if sums_from_state:
-                    _hip.call("snn_bn_bwd_reduce_from_state", sums.data_ptr(), T, M, C, _ptr(gamma), _ptr(bn_bias),
-                              mean.data_ptr(), invstd.data_ptr(), gx.data_ptr(), y.data_ptr(), ldy, raw_local.data_ptr(), st)
-                else:
-                    _hip.call("snn_bn_bwd_reduce", sums.data_ptr(), T, M, C, raw_local.data_ptr(), st)
-                raw = raw_local.clone()
-                dist.all_reduce(raw, op=dist.ReduceOp.SUM, group=ctx.sync_group[0])
-                param_sums = torch.empty((T, C, 2), device=dev, dtype=torch.float64)
-                _hip.call("snn_bn_bwd_coef", raw.data_ptr(), raw_local.data_ptr(), param_sums.data_ptr(), T, M * world,
-                          C, _ptr(gamma), mean.data_ptr(), invstd.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
-                          coef[2].data_ptr(), dg_ptr, db_ptr, acc_flag, st)
+            if ctx.sync_group is not None:   # (never segmented: `sums` covers all T steps)
+                _sync_bn_bwd_coefficients(ctx.sync_group, sums, sums_from_state, gx, y, ldy, (T, M, C), gamma, bn_bias, mean,
+                                          invstd, coef, dg_ptr, db_ptr, acc_flag, st)
             if need_y and not use_running and ctx.defer_apply and ctx.sync_group is None:
                 # the producing convolution forms dy itself while it reads gx (see PendingBnApply)
                 _PENDING_APPLY[gx.data_ptr()] = PendingBnApply(gx, y, coef, (T, B, C, H, W))
