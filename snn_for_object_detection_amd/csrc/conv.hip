@@ -146,7 +146,6 @@ __device__ __forceinline__ void stat_flush(double (&s)[TN], double (&q)[TN], dou
     __syncthreads();
 }
 
-static unsigned magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ULL + (unsigned)d - 1) / (unsigned)d); }
 __device__ __forceinline__ int div_magic(int n, int d, unsigned magic) { return d == 1 ? n : (int)__umulhi((unsigned)n, magic); }
 
 // SPLIT = 0: exact fp32 MFMA (v_mfma_f32_32x32x2_f32): an fmaf chain, the reference arithmetic.
@@ -1497,10 +1496,6 @@ __global__ __launch_bounds__(64 * KG) void k_wgrad_reduce_once(const float* __re
     }
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 // Alignment facts a launch derives from its pointers and strides (the `align_bits` of the host-only plan queries): a
 // tensor counts as vectorisable when its pointer is 16-byte (fp32) / 8-byte (bf16 storage) aligned; for an addend the bit
 // also requires a pixel stride that is a multiple of 4 elements.
@@ -1562,29 +1557,31 @@ static GatherPlan gather_plan(const ConvGeom& g, bool dgrad, int split, bool sb,
     return p;
 }
 
-template <bool SB>
 static unsigned gather_align_bits(const void* in, const void* wk, const void* wk_split, const void* out, const void* addend,
                                   int64_t ld_add, const void* addend2, int64_t ld_add2) {
     unsigned a = 0;
-    if (aligned16(in)) a |= kAlignIn16;
-    if (aligned8(in)) a |= kAlignIn8;
-    if (aligned16(wk)) a |= kAlignW16;
-    if (aligned16(out)) a |= kAlignOut16;
-    if (aligned8(out)) a |= kAlignOut8;
-    if (addend && ld_add % 4 == 0 && aligned16(addend)) a |= kAlignAdd16;
-    if (addend && ld_add % 4 == 0 && aligned8(addend)) a |= kAlignAdd8;
-    if (addend2 && ld_add2 % 4 == 0 && aligned16(addend2)) a |= kAlignAdd2_16;
-    if (addend2 && ld_add2 % 4 == 0 && aligned8(addend2)) a |= kAlignAdd2_8;
-    if (wk_split && aligned16(wk_split)) a |= kAlignSplit16;
+    if (aligned(16, {in})) a |= kAlignIn16;
+    if (aligned(8, {in})) a |= kAlignIn8;
+    if (aligned(16, {wk})) a |= kAlignW16;
+    if (aligned(16, {out})) a |= kAlignOut16;
+    if (aligned(8, {out})) a |= kAlignOut8;
+    if (addend && ld_add % 4 == 0 && aligned(16, {addend})) a |= kAlignAdd16;
+    if (addend && ld_add % 4 == 0 && aligned(8, {addend})) a |= kAlignAdd8;
+    if (addend2 && ld_add2 % 4 == 0 && aligned(16, {addend2})) a |= kAlignAdd2_16;
+    if (addend2 && ld_add2 % 4 == 0 && aligned(8, {addend2})) a |= kAlignAdd2_8;
+    if (wk_split && aligned(16, {wk_split})) a |= kAlignSplit16;
     return a;
 }
 
-template <bool DGRAD, int SPLIT, bool SB = false, bool XSP = false>
-static int launch_gather(const float* in, const float* wk, const void* wk_split, float* out, const ConvGeom& g,
-                         const float* addend, int64_t ld_add, const float* addend2, int64_t ld_add2, hipStream_t st,
-                         const char* name) {
-    const GatherPlan p = gather_plan(g, DGRAD, SPLIT, SB, XSP,
-                                     gather_align_bits<SB>(in, wk, wk_split, out, addend, ld_add, addend2, ld_add2),
+constexpr int gather_wm(int bn) { return bn == 32 ? 4 : 2; }   // waves of a block over pixels / over its bn channels
+constexpr int gather_wn(int bn) { return bn == 32 ? 1 : 2; }
+
+// split: the SPLIT of k_conv_gather the precision asks for (snn_conv2d_fwd: 0, 3, 4, 5; snn_conv2d_dgrad: 0, 2, 5)
+static int launch_gather(bool dgrad, int split, bool sb, bool xsp, const float* in, const float* wk, const void* wk_split,
+                         float* out, const ConvGeom& g, const float* addend, int64_t ld_add, const float* addend2,
+                         int64_t ld_add2, hipStream_t st, const char* name) {
+    const GatherPlan p = gather_plan(g, dgrad, split, sb, xsp,
+                                     gather_align_bits(in, wk, wk_split, out, addend, ld_add, addend2, ld_add2),
                                      wk_split != nullptr, addend != nullptr, addend2 != nullptr);
     SNN_REQUIRE(p.why != kGatherTooManyPixels, "%s: too many pixels", name);
     SNN_REQUIRE(p.why != kGatherNotFastSB, "%s: bf16 storage covers the pipelined implicit GEMM only (channels a multiple of 32, pixel "
@@ -1598,38 +1595,25 @@ static int launch_gather(const float* in, const float* wk, const void* wk_split,
     gg.mtiles_per_xcd = p.mtiles_per_xcd;
     gg.ntiles = p.ntiles;
     const dim3 grid((unsigned)p.blocks);
-#define SNN_CONV_LAUNCH(BN_, WM_, WN_)                                                                      \
-    do {                                                                                                    \
-        if constexpr (SB) {                                                                                 \
-            hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, DGRAD, true, 5, true, false, true>), grid,     \
-                               dim3(kThreads), 0, st, in, wk, out, gg, addend, ld_add, addend2, ld_add2);   \
-        } else if constexpr (XSP) {                                                                         \
-            hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, false, true, 4, true, false, false, true>), grid, \
-                               dim3(kThreads), 0, st, in, wk, out, gg, addend, ld_add, addend2, ld_add2);   \
-        } else if (p.loader == kLoadFastPresplit) {                                                         \
-            if constexpr (SPLIT == 2 || SPLIT == 4)                                                         \
-                hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, DGRAD, true, SPLIT, true, true>), grid,    \
-                                   dim3(kThreads), 0, st, in, static_cast<const float*>(wk_split), out, gg, addend, \
-                                   ld_add, addend2, ld_add2);                                               \
-        } else if (p.loader == kLoadFast)                                                                   \
-            hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, DGRAD, true, SPLIT, true>), grid, dim3(kThreads), 0, \
-                               st, in, wk, out, gg, addend, ld_add, addend2, ld_add2);                                        \
-        else if (p.loader == kLoadVec)                                                                      \
-            hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, DGRAD, true, (SPLIT == 4 ? 3 : (SPLIT == 5 ? 2 : SPLIT)), false>), grid, dim3(kThreads), 0, \
-                               st, in, wk, out, gg, addend, ld_add, addend2, ld_add2);                                        \
-        else                                                                                                \
-            hipLaunchKernelGGL((k_conv_gather<BN_, WM_, WN_, DGRAD, false, 0, false>), grid, dim3(kThreads), 0, st, \
-                               in, wk, out, gg, addend, ld_add, addend2, ld_add2);                        \
-    } while (0)
-    if (p.bn == 32) SNN_CONV_LAUNCH(32, 4, 1);
-    else if (p.bn == 64) SNN_CONV_LAUNCH(64, 2, 2);
-    else SNN_CONV_LAUNCH(128, 2, 2);
-#undef SNN_CONV_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snn_set_error("%s: launch failed: %s", name, hipGetErrorString(e));
-        return 2;
-    }
+    const float* wsrc = p.loader == kLoadFastPresplit ? static_cast<const float*>(wk_split) : wk;
+    dispatch(
+        [&](auto BN, auto L, auto DGRAD, auto SPLIT) {
+            constexpr int l = L(), s = SPLIT();
+            constexpr bool vec = l != kLoadScalar, fast = l >= kLoadFast, pre = l == kLoadFastPresplit, sbl = l == kLoadSB,
+                           xspl = l == kLoadXSP;
+            // the vector loader has no two-piece fp16 and no one-product arithmetic (4 -> 3, 5 -> 2); the scalar one is fp32
+            constexpr int ksplit = fast ? s : (vec ? (s == 4 ? 3 : (s == 5 ? 2 : s)) : 0);
+            // SB is SPLIT 5, XSP the forward with SPLIT 4, the pre-split image serves SPLIT 2 and 4
+            if constexpr ((DGRAD() ? s != 3 && s != 4 : s != 2) && (!sbl || s == 5) && (!xspl || (!DGRAD() && s == 4)) &&
+                          (!pre || s == 2 || s == 4)) {
+                hipLaunchKernelGGL((k_conv_gather<BN(), gather_wm(BN()), gather_wn(BN()), DGRAD(), vec, ksplit, fast, pre, sbl, xspl>),
+                                   grid, dim3(kThreads), 0, st, in, wsrc, out, gg, addend, ld_add, addend2, ld_add2);
+                return true;
+            }
+            return false;
+        },
+        OneOf<32, 64, 128>{p.bn}, OneOf<0, 1, 2, 3, 4, 5>{p.loader}, Flag{dgrad}, OneOf<0, 2, 3, 4, 5>{split});
+    SNN_CHECK_LAUNCH(name);
     return 0;
 }
 
@@ -1944,6 +1928,23 @@ extern "C" int snn_conv_first_plan(int64_t N, int H, int W, int Ho, int Wo, int 
     return p.ok ? 0 : 1;
 }
 
+// the one launch of k_conv_first: the forward (out = y), the weight gradient (out = its slabs; bf16 dy with sb) and the
+// weight gradient that applies the BatchNorm backward to its dy operand on the way (fp32 only)
+static int launch_first(bool wgrad, bool bnapply, bool sb, int blocks, size_t lds, const float* x, const float* w,
+                        const float* dy, float* out, const FirstGeom& fg, void* stream, const char* name) {
+    dispatch(
+        [&](auto WGRAD, auto BNAPPLY, auto SB) {
+            if constexpr (!BNAPPLY() || (WGRAD() && !SB())) {
+                hipLaunchKernelGGL((k_conv_first<2, 3, WGRAD(), BNAPPLY(), SB()>), dim3((unsigned)blocks), dim3(kThreads), lds,
+                                   (hipStream_t)stream, x, w, dy, out, fg);
+            }
+            return true;
+        },
+        Flag{wgrad}, Flag{bnapply}, Flag{sb});
+    SNN_CHECK_LAUNCH(name);
+    return 0;
+}
+
 // ---- pre-split weight images (see PRESPLIT of k_conv_gather).  Elementwise over groups of 4 consecutive floats: the
 // group's 16 bytes become (4 hi pieces, 4 lo pieces) with exactly the arithmetic of the in-kernel conversion - fp16
 // pieces of w * 2^8 (forward, SNN_PREC_FP16X3) or bf16 pieces of w (data gradient, SNN_PREC_BF16X3; apply it to the
@@ -1981,18 +1982,19 @@ __global__ void k_weight_presplit(const f32x4* __restrict__ w, u32x4* __restrict
 extern "C" int snn_weight_presplit(const float* w, void* out, int64_t n, int precision, void* stream) {
     SNN_REQUIRE(w && out && n > 0 && n % 4 == 0, "snn_weight_presplit: bad arguments (n = %lld must be a multiple of 4)",
                 (long long)n);
-    SNN_REQUIRE(aligned16(w) && aligned16(out), "snn_weight_presplit: buffers must be 16-byte aligned");
+    SNN_REQUIRE(aligned(16, {w, out}), "snn_weight_presplit: buffers must be 16-byte aligned");
     SNN_REQUIRE(precision == SNN_PREC_FP16X3 || precision == SNN_PREC_BF16X3,
                 "snn_weight_presplit: precision must be SNN_PREC_FP16X3 (forward) or SNN_PREC_BF16X3 (data gradient)");
     const int64_t groups = n / 4;
     int64_t blocks = snn_ceil_div(groups, kThreads);
     if (blocks > 8 * snn_num_cu()) blocks = 8 * snn_num_cu();
-    if (precision == SNN_PREC_FP16X3)
-        hipLaunchKernelGGL(k_weight_presplit<true>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream,
-                           reinterpret_cast<const f32x4*>(w), reinterpret_cast<u32x4*>(out), groups);
-    else
-        hipLaunchKernelGGL(k_weight_presplit<false>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream,
-                           reinterpret_cast<const f32x4*>(w), reinterpret_cast<u32x4*>(out), groups);
+    dispatch(
+        [&](auto F16) {
+            hipLaunchKernelGGL(k_weight_presplit<F16()>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream,
+                               reinterpret_cast<const f32x4*>(w), reinterpret_cast<u32x4*>(out), groups);
+            return true;
+        },
+        Flag{precision == SNN_PREC_FP16X3});
     SNN_CHECK_LAUNCH("snn_weight_presplit");
     return 0;
 }
@@ -2085,7 +2087,6 @@ extern "C" int snn_conv2d_fwd(const float* x, int64_t ldx, const float* w, const
                     precision == SNN_PREC_BF16X1 || precision == SNN_PREC_BF16S,
                 "snn_conv2d_fwd: precision must be SNN_PREC_FP32, _BF16X6, _FP16X3, _BF16X1 or _BF16S (got %d)", precision);
     const bool sbf = precision == SNN_PREC_BF16S;   // x (but for the fp32 event frames), y, addend are bf16
-    const int fwd_split = precision;
     if (check_conv_shape("snn_conv2d_fwd", N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad)) return 1;
     SNN_REQUIRE(ldx >= Cin && ldy >= Cout, "snn_conv2d_fwd: pixel stride smaller than channel count");
     SNN_REQUIRE(!bn_partial || (bn_layout && frames_per_step > 0 && N % frames_per_step == 0),
@@ -2102,18 +2103,11 @@ extern "C" int snn_conv2d_fwd(const float* x, int64_t ldx, const float* w, const
                              ? first_layer_plan(N, H, W, Ho, Wo, Cout, stride, pad, bn_partial ? frames_per_step : 0, false, 0)
                              : FirstPlan{};
     if (fwd_takes_first(fp, addend != nullptr, ldx, ldy, W, Wo, sbf,
-                        gather_align_bits<false>(x, w, nullptr, y, nullptr, 0, nullptr, 0))) {
+                        gather_align_bits(x, w, nullptr, y, nullptr, 0, nullptr, 0))) {
         FirstGeom fg = {ldx, ldy, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, fp.group_rows, fp.group_blocks,
                         bn_partial, nullptr, 0, nullptr, 0, 1, fp.rs};
         if (bn_partial) bn_layout[0] = fp.group_blocks;
-        if (sbf)
-            hipLaunchKernelGGL((k_conv_first<2, 3, false, false, true>), dim3((unsigned)fp.blocks), dim3(kThreads),
-                               fp.lds, (hipStream_t)stream, x, w, nullptr, y, fg);
-        else
-            hipLaunchKernelGGL((k_conv_first<2, 3, false>), dim3((unsigned)fp.blocks), dim3(kThreads),
-                               fp.lds, (hipStream_t)stream, x, w, nullptr, y, fg);
-        SNN_CHECK_LAUNCH("snn_conv2d_fwd");
-        return 0;
+        return launch_first(false, false, sbf, fp.blocks, fp.lds, x, w, nullptr, y, fg, stream, "snn_conv2d_fwd");
     }
     SNN_REQUIRE(!sbf || Cin % 32 == 0, "snn_conv2d_fwd: bf16 storage covers the event-frame layer (fp32 frames, Cin = 2, "
                 "3x3) and layers with a multiple of 32 input channels (got %d)", Cin);
@@ -2124,15 +2118,8 @@ extern "C" int snn_conv2d_fwd(const float* x, int64_t ldx, const float* w, const
         bn_layout[0] = g.bn_chunks;
         bn_layout[1] = BM;
     }
-    if (sbf)
-        return launch_gather<false, 5, true>(x, w, nullptr, y, g, addend, ld_addend, nullptr, 0, (hipStream_t)stream, "snn_conv2d_fwd");
-    if (fwd_split == 5)
-        return launch_gather<false, 5>(x, w, nullptr, y, g, addend, ld_addend, nullptr, 0, (hipStream_t)stream, "snn_conv2d_fwd");
-    if (fwd_split == 4)
-        return launch_gather<false, 4>(x, w, w_split, y, g, addend, ld_addend, nullptr, 0, (hipStream_t)stream, "snn_conv2d_fwd");
-    if (fwd_split == 3)
-        return launch_gather<false, 3>(x, w, nullptr, y, g, addend, ld_addend, nullptr, 0, (hipStream_t)stream, "snn_conv2d_fwd");
-    return launch_gather<false, 0>(x, w, nullptr, y, g, addend, ld_addend, nullptr, 0, (hipStream_t)stream, "snn_conv2d_fwd");
+    return launch_gather(false, sbf ? 5 : precision, sbf, false, x, w, w_split, y, g, addend, ld_addend, nullptr, 0,
+                         (hipStream_t)stream, "snn_conv2d_fwd");
 }
 
 extern "C" int snn_conv2d_dgrad(const float* dy, int64_t lddy, const float* wt, const void* wt_split, float* dx,
@@ -2146,7 +2133,7 @@ extern "C" int snn_conv2d_dgrad(const float* dy, int64_t lddy, const float* wt, 
                     precision == SNN_PREC_BF16S,
                 "snn_conv2d_dgrad: precision must be SNN_PREC_FP32, _BF16X3, _BF16X1 or _BF16S (got %d)", precision);
     const bool sbf = precision == SNN_PREC_BF16S;   // dy, dx and the addends are bf16
-    const int bwd_split = precision;
+    const int bwd_split = (sbf || precision == SNN_PREC_BF16X1) ? 5 : (precision != SNN_PREC_FP32 ? 2 : 0);
     SNN_REQUIRE(!addend2 || ld_addend2 >= Cin, "snn_conv2d_dgrad: addend2 pixel stride smaller than channel count");
     if (check_conv_shape("snn_conv2d_dgrad", N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad)) return 1;
     SNN_REQUIRE(lddy >= Cout && lddx >= Cin, "snn_conv2d_dgrad: pixel stride smaller than channel count");
@@ -2154,20 +2141,12 @@ extern "C" int snn_conv2d_dgrad(const float* dy, int64_t lddy, const float* wt, 
     ConvGeom g = gather_dgrad_geom(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, lddy, lddx);
     SNN_REQUIRE(N * (int64_t)Ho * Wo < 0x7fffffffLL && (int64_t)g.KtotFull * Cout < 0xffffffffLL,
                 "snn_conv2d_dgrad: tensor too large for 32-bit pixel indexing");
-    const bool split = bwd_split != 0;
     // one launch per stride phase: each class multiplies only the taps that can reach it
     for (int ph = 0; ph < stride && ph < H; ++ph)
         for (int pw = 0; pw < stride && pw < W; ++pw) {
             gather_dgrad_phase(g, ph, pw);
-            int rc = sbf ? launch_gather<true, 5, true>(dy, wt, nullptr, dx, g, addend, ld_addend, addend2, ld_addend2,
-                                                        (hipStream_t)stream, "snn_conv2d_dgrad")
-                     : bwd_split == SNN_PREC_BF16X1
-                         ? launch_gather<true, 5>(dy, wt, nullptr, dx, g, addend, ld_addend, addend2, ld_addend2,
-                                                  (hipStream_t)stream, "snn_conv2d_dgrad")
-                         : (split ? launch_gather<true, 2>(dy, wt, wt_split, dx, g, addend, ld_addend, addend2, ld_addend2,
-                                                           (hipStream_t)stream, "snn_conv2d_dgrad")
-                                  : launch_gather<true, 0>(dy, wt, nullptr, dx, g, addend, ld_addend, addend2, ld_addend2,
-                                                           (hipStream_t)stream, "snn_conv2d_dgrad"));
+            const int rc = launch_gather(true, bwd_split, sbf, false, dy, wt, wt_split, dx, g, addend, ld_addend, addend2,
+                                         ld_addend2, (hipStream_t)stream, "snn_conv2d_dgrad");
             if (rc) return rc;
         }
     return 0;
@@ -2235,6 +2214,9 @@ extern "C" int snn_conv2d_gather_plan(int mode, int64_t N, int H, int W, int Cin
 
 namespace {
 struct WgradTile { int bm, bn, id, blocks_per_cu; };
+// the kernels' template arguments of tile `id`: 32-row MFMA tiles per wave (tm x tn) and waves of a block (wm x wn)
+struct WgradShape { int tm, tn, wm, wn; };
+constexpr WgradShape kWgradShapes[6] = {{2, 2, 2, 2}, {2, 2, 1, 4}, {1, 2, 1, 4}, {2, 1, 2, 2}, {1, 1, 2, 2}, {1, 1, 1, 4}};
 // candidate block tiles (out-channels x (tap,ci) columns); pick the one that wastes the least MFMA work on
 // padding, larger tiles first on ties (fewer LDS / L2 bytes per FLOP)
 static WgradTile wgrad_tile(int Cout, int Ktot, bool split, int64_t M) {
@@ -2359,19 +2341,17 @@ static ReducePlan wgrad_reduce_plan(int64_t n, int splitk, bool aligned, int num
 }  // namespace
 
 static int wgrad_reduce_slabs(float* workspace, float* dw, int64_t n, int splitk, int accumulate, hipStream_t st) {
-    const ReducePlan r = wgrad_reduce_plan(n, splitk, aligned16(workspace) && aligned16(dw), snn_num_cu());
+    const ReducePlan r = wgrad_reduce_plan(n, splitk, aligned(16, {workspace, dw}), snn_num_cu());
+    // (the plan gives no other kg than the instances listed: it doubles from 1 up to 16, or is one of four literals)
     if (r.kind == kReduceOnce) {
-#define SNN_REDUCE_ONCE(KG_)                                                                                   \
-    hipLaunchKernelGGL((k_wgrad_reduce_once<KG_>), dim3((unsigned)r.blocks), dim3(64 * KG_), 0, st, workspace, n, splitk, dw, \
-                       accumulate)
-        switch (r.kg) {
-            case 1: SNN_REDUCE_ONCE(1); break;
-            case 2: SNN_REDUCE_ONCE(2); break;
-            case 4: SNN_REDUCE_ONCE(4); break;
-            case 8: SNN_REDUCE_ONCE(8); break;
-            default: SNN_REDUCE_ONCE(16); break;
-        }
-#undef SNN_REDUCE_ONCE
+        const bool launched = dispatch(
+            [&](auto KG) {
+                hipLaunchKernelGGL((k_wgrad_reduce_once<KG()>), dim3((unsigned)r.blocks), dim3(64 * KG()), 0, st, workspace, n,
+                                   splitk, dw, accumulate);
+                return true;
+            },
+            OneOf<1, 2, 4, 8, 16>{r.kg});
+        SNN_REQUIRE(launched, "snn_conv2d_wgrad_reduce: no kernel for %d thread groups", r.kg);
         SNN_CHECK_LAUNCH("snn_conv2d_wgrad_reduce");
         return 0;
     }
@@ -2389,16 +2369,14 @@ static int wgrad_reduce_slabs(float* workspace, float* dw, int64_t n, int splitk
         SNN_CHECK_LAUNCH("snn_conv2d_wgrad_reduce");
         return 0;
     }
-#define SNN_REDUCE_LAUNCH(KG_)                                                                                  \
-    hipLaunchKernelGGL((k_wgrad_reduce<KG_>), dim3((unsigned)r.blocks), dim3(kThreads), 0, st, workspace, dw, n, splitk, \
-                       accumulate)
-    switch (r.kg) {
-        case 1: SNN_REDUCE_LAUNCH(1); break;
-        case 4: SNN_REDUCE_LAUNCH(4); break;
-        case 16: SNN_REDUCE_LAUNCH(16); break;
-        default: SNN_REDUCE_LAUNCH(64); break;
-    }
-#undef SNN_REDUCE_LAUNCH
+    const bool launched = dispatch(
+        [&](auto KG) {
+            hipLaunchKernelGGL((k_wgrad_reduce<KG()>), dim3((unsigned)r.blocks), dim3(kThreads), 0, st, workspace, dw, n, splitk,
+                               accumulate);
+            return true;
+        },
+        OneOf<1, 4, 16, 64>{r.kg});
+    SNN_REQUIRE(launched, "snn_conv2d_wgrad_reduce: no kernel for %d thread groups", r.kg);
     SNN_CHECK_LAUNCH("snn_conv2d_wgrad_reduce");
     return 0;
 }
@@ -2415,8 +2393,8 @@ static FirstPlan first_layer_wgrad_plan(unsigned align, int64_t ldx, int64_t ldd
     return p;
 }
 static unsigned wgrad_align_bits(const void* x, const void* dy) {
-    return (aligned16(x) ? kAlignIn16 : 0u) | (aligned8(x) ? kAlignIn8 : 0u) | (aligned16(dy) ? kAlignDy16 : 0u) |
-           (aligned8(dy) ? kAlignDy8 : 0u);
+    return (aligned(16, {x}) ? kAlignIn16 : 0u) | (aligned(8, {x}) ? kAlignIn8 : 0u) | (aligned(16, {dy}) ? kAlignDy16 : 0u) |
+           (aligned(8, {dy}) ? kAlignDy8 : 0u);
 }
 static FirstPlan first_layer_wgrad_plan(const float* x, int64_t ldx, const float* dy, int64_t lddy, int64_t N, int H, int W,
                                         int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad) {
@@ -2540,14 +2518,13 @@ extern "C" int snn_conv2d_wgrad_bn(const float* x, int64_t ldx, const float* gx,
     SNN_REQUIRE(ldx >= Cin && ldgx >= Cout && ldy >= Cout, "snn_conv2d_wgrad_bn: pixel stride smaller than channel count");
     SNN_REQUIRE(splitk >= 1 && splitk <= 32768, "snn_conv2d_wgrad_bn: bad splitk %d", splitk);
     const FirstPlan fp = first_layer_wgrad_plan(x, ldx, gx, ldgx, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad);
-    SNN_REQUIRE(fp.ok && ldy % 4 == 0 && aligned16(y) && aligned16(coef) && (int64_t)Wo * ldy < 0x7fffffffLL &&
+    SNN_REQUIRE(fp.ok && ldy % 4 == 0 && aligned(16, {y, coef}) && (int64_t)Wo * ldy < 0x7fffffffLL &&
                     (int64_t)Wo * ldgx < 0x7fffffffLL,
                 "snn_conv2d_wgrad_bn: shape / alignment not covered (ask snn_conv2d_wgrad_bn_supported)");
     FirstGeom fg = {ldx, ldgx, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, fp.group_rows, splitk, nullptr,
                     y, ldy, coef, T * Cout, frames_per_step, fp.rs};
-    hipLaunchKernelGGL((k_conv_first<2, 3, true, true>), dim3((unsigned)splitk), dim3(kThreads),
-                       fp.lds, (hipStream_t)stream, x, nullptr, gx, workspace, fg);
-    SNN_CHECK_LAUNCH("snn_conv2d_wgrad_bn");
+    if (const int rc = launch_first(true, true, false, splitk, fp.lds, x, nullptr, gx, workspace, fg, stream, "snn_conv2d_wgrad_bn"))
+        return rc;
     return wgrad_reduce_slabs(workspace, dw, (int64_t)Cout * KH * KW * Cin, splitk, accumulate, (hipStream_t)stream);
 }
 
@@ -2572,19 +2549,14 @@ static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t ld
     g.Ktot = KH * KW * Cin;
     g.x_th = x_th;
     // (the reducer plan in p.r is the one wgrad_reduce_slabs derives again from the same two pointers)
-    const unsigned align = wgrad_align_bits(x, dy) | (aligned16(dw) && aligned16(workspace) ? kAlignDw16 : 0u);
+    const unsigned align = wgrad_align_bits(x, dy) | (aligned(16, {dw, workspace}) ? kAlignDw16 : 0u);
     WgradPlan p = wgrad_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ldx, lddy, align, precision, xsp, 0, splitk);
     if (p.kernel == kWgradFirst) {
         const FirstPlan& fp = p.fp;
         FirstGeom fg = {ldx, lddy, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, fp.group_rows, splitk, nullptr,
                         nullptr, 0, nullptr, 0, 1, fp.rs};
-        if (sbf)
-            hipLaunchKernelGGL((k_conv_first<2, 3, true, false, true>), dim3((unsigned)splitk), dim3(kThreads),
-                               fp.lds, (hipStream_t)stream, x, nullptr, dy, workspace, fg);
-        else
-            hipLaunchKernelGGL((k_conv_first<2, 3, true>), dim3((unsigned)splitk), dim3(kThreads),
-                               fp.lds, (hipStream_t)stream, x, nullptr, dy, workspace, fg);
-        SNN_CHECK_LAUNCH("snn_conv2d_wgrad");
+        if (const int rc = launch_first(true, false, sbf, splitk, fp.lds, x, nullptr, dy, workspace, fg, stream, "snn_conv2d_wgrad"))
+            return rc;
         return wgrad_reduce_slabs(workspace, dw, (int64_t)Cout * g.Ktot, splitk, accumulate, (hipStream_t)stream);
     }
     if (p.kernel == kWgradHalo) {
@@ -2605,9 +2577,6 @@ static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t ld
     SNN_REQUIRE(p.why != kWgradNotPipeXSP, "snn_conv1x1_spikes_wgrad: covers the pipelined bf16 x 3 kernel only (channels and "
                 "strides multiples of 4, 16-byte aligned tensors, < 2 GiB per pixel split)");
     SNN_REQUIRE(p.why != kWgradGridTooLarge, "snn_conv2d_wgrad: grid too large");
-    const WgradTile t = p.t;
-    const int wbk = p.wbk;
-    const bool pipe = p.kernel == kWgradPipe, vec = p.kernel != kWgradScalar, one = p.one;
     g.pix_per_split = p.pix_per_split;
     g.nimg = (int)N;
     g.tiles_m = p.tiles_m;
@@ -2615,46 +2584,19 @@ static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t ld
     g.splitk = splitk;
     dim3 grid((unsigned)((int64_t)g.tiles_m * g.tiles_n * splitk));
     hipStream_t st = (hipStream_t)stream;
-#define SNN_WGRAD_LAUNCH(TM_, TN_, WM_, WN_)                                                                   \
-    do {                                                                                                       \
-        if (xsp && wbk == 64)                                                                                  \
-            hipLaunchKernelGGL((k_conv_wgrad_pipe<TM_, TN_, WM_, WN_, 64, false, false, true>), grid, dim3(kThreads), 0, st, x, \
-                               dy, workspace, g);                                                              \
-        else if (xsp)                                                                                          \
-            hipLaunchKernelGGL((k_conv_wgrad_pipe<TM_, TN_, WM_, WN_, 32, false, false, true>), grid, dim3(kThreads), 0, st, x, \
-                               dy, workspace, g);                                                              \
-        else if (sbf && wbk == 64)                                                                             \
-            hipLaunchKernelGGL((k_conv_wgrad_pipe<TM_, TN_, WM_, WN_, 64, true, true>), grid, dim3(kThreads), 0, st, x, dy, \
-                               workspace, g);                                                                  \
-        else if (sbf)                                                                                          \
-            hipLaunchKernelGGL((k_conv_wgrad_pipe<TM_, TN_, WM_, WN_, 32, true, true>), grid, dim3(kThreads), 0, st, x, dy, \
-                               workspace, g);                                                                  \
-        else if (pipe && one && wbk == 64)                                                                     \
-            hipLaunchKernelGGL((k_conv_wgrad_pipe<TM_, TN_, WM_, WN_, 64, true>), grid, dim3(kThreads), 0, st, x, dy, \
-                               workspace, g);                                                                  \
-        else if (pipe && one)                                                                                  \
-            hipLaunchKernelGGL((k_conv_wgrad_pipe<TM_, TN_, WM_, WN_, 32, true>), grid, dim3(kThreads), 0, st, x, dy, \
-                               workspace, g);                                                                  \
-        else if (pipe && wbk == 64)                                                                            \
-            hipLaunchKernelGGL((k_conv_wgrad_pipe<TM_, TN_, WM_, WN_, 64, false>), grid, dim3(kThreads), 0, st, x, dy, \
-                               workspace, g);                                                                  \
-        else if (pipe)                                                                                         \
-            hipLaunchKernelGGL((k_conv_wgrad_pipe<TM_, TN_, WM_, WN_, 32, false>), grid, dim3(kThreads), 0, st, x, dy, \
-                               workspace, g);                                                                  \
-        else if (vec) hipLaunchKernelGGL((k_conv_wgrad<TM_, TN_, WM_, WN_, true>), grid, dim3(kThreads), 0, st, x,  \
-                                    dy, workspace, g);                                                         \
-        else hipLaunchKernelGGL((k_conv_wgrad<TM_, TN_, WM_, WN_, false>), grid, dim3(kThreads), 0, st, x, dy, \
-                                workspace, g);                                                                 \
-    } while (0)
-    switch (t.id) {
-        case 0: SNN_WGRAD_LAUNCH(2, 2, 2, 2); break;   // 128 x 128
-        case 1: SNN_WGRAD_LAUNCH(2, 2, 1, 4); break;   //  64 x 256
-        case 2: SNN_WGRAD_LAUNCH(1, 2, 1, 4); break;   //  32 x 256
-        case 3: SNN_WGRAD_LAUNCH(2, 1, 2, 2); break;   // 128 x  64
-        case 4: SNN_WGRAD_LAUNCH(1, 1, 2, 2); break;   //  64 x  64
-        default: SNN_WGRAD_LAUNCH(1, 1, 1, 4); break;  //  32 x 128
-    }
-#undef SNN_WGRAD_LAUNCH
+    dispatch(
+        [&](auto ID, auto KERNEL, auto WBK, auto ONE, auto SB, auto XSP) {
+            constexpr WgradShape t = kWgradShapes[ID()];
+            if constexpr (KERNEL() != kWgradPipe) {
+                hipLaunchKernelGGL((k_conv_wgrad<t.tm, t.tn, t.wm, t.wn, KERNEL() == kWgradVec>), grid, dim3(kThreads), 0, st, x, dy,
+                                   workspace, g);
+            } else if constexpr ((!SB() || ONE()) && (!XSP() || (!ONE() && !SB()))) {   // bf16 storage: one product; spikes: three
+                hipLaunchKernelGGL((k_conv_wgrad_pipe<t.tm, t.tn, t.wm, t.wn, WBK(), ONE(), SB(), XSP()>), grid, dim3(kThreads), 0,
+                                   st, x, dy, workspace, g);
+            }
+            return true;
+        },
+        OneOf<0, 1, 2, 3, 4, 5>{p.t.id}, OneOf<0, 1, 2>{p.kernel}, OneOf<32, 64>{p.wbk}, Flag{p.one}, Flag{sbf}, Flag{xsp});
     SNN_CHECK_LAUNCH("snn_conv2d_wgrad");
     return wgrad_reduce_slabs(workspace, dw, (int64_t)Cout * g.Ktot, splitk, accumulate, st);
 }
@@ -2733,8 +2675,8 @@ extern "C" int snn_conv2d_spikes_fwd(const float* vdec, int64_t ld, float v_th, 
         bn_layout[0] = g.bn_chunks;
         bn_layout[1] = BM;
     }
-    return launch_gather<false, 4, false, true>(vdec, w, nullptr, y, g, nullptr, 0, nullptr, 0, (hipStream_t)stream,
-                                                "snn_conv2d_spikes_fwd");
+    return launch_gather(false, 4, false, true, vdec, w, nullptr, y, g, nullptr, 0, nullptr, 0, (hipStream_t)stream,
+                         "snn_conv2d_spikes_fwd");
 }
 
 extern "C" int snn_conv1x1_spikes_fwd(const float* vdec, int64_t ld, float v_th, const float* w, float* y, int64_t ldy,

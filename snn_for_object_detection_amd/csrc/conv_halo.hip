@@ -849,12 +849,6 @@ __global__ void k_weight_frag_image(const float* __restrict__ flat_src, unsigned
     }
 }
 
-static unsigned magic_u32(int d) { return (unsigned)((0x100000000ULL + (unsigned)d - 1) / (unsigned)d); }
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-// 4 consecutive elements of an activation tensor per access: 16 bytes, or 8 with bf16 storage
-static bool out_aligned(const void* p, bool bf16) { return bf16 ? aligned8(p) : aligned16(p); }
-
 // 0: not covered, 1: padded-strip tiles (rows of <= 78 pixels), 2: 4 x 32 rectangles (any width)
 static int halo_mode(int64_t N, int H, int W, int Cin, int Cout) {
     if (N <= 0 || H <= 0 || W <= 0) return 0;
@@ -955,6 +949,32 @@ static int plan_out(const HaloPlan& p, int* out) {
     for (int i = 0; i < 7; ++i) out[i] = v[i];
     return p.mode == 0 ? 1 : 0;
 }
+
+// The kernel argument of a planned launch over the H x W strip grid of `in` (Cin channels, pixel stride ld_in) that
+// produces OH x OW pixels of Cout channels.  bf16: `out` and the addends are bf16 tensors.
+static HaloGeom halo_geom(const HaloPlan& hp, int64_t N, int H, int W, int Cin, int64_t ld_in, int OH, int OW, int Cout,
+                          const void* out, int64_t ld_out, const void* addend, int64_t ld_add, const void* addend2,
+                          int64_t ld_add2, bool bf16, double* bn_partial, float x_th) {
+    HaloGeom g = {};
+    g.ldx = ld_in; g.ldy = ld_out; g.ld_add = ld_add; g.ld_add2 = ld_add2;
+    g.N = (int)N; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout;
+    g.OH = OH; g.OW = OW;
+    g.PW = W + 1; g.PH = H + 1;
+    g.G = hp.G;
+    g.tiles_x = hp.tiles_x;
+    g.tiles_img = hp.tiles_img;
+    g.group_cells = hp.group_cells;
+    g.tiles_per_group = hp.tiles_per_group;
+    g.tiles = hp.tiles;
+    g.ntiles_n = hp.ntiles_n;
+    g.tiles_per_xcd = hp.tiles_per_xcd;
+    g.magic_pw = magic_u32(g.PW); g.magic_ph = magic_u32(g.PH);
+    // 4 consecutive elements of an activation tensor per access: 16 bytes, or 8 with bf16 storage
+    g.out_vec = multiples(4, {ld_out, addend ? ld_add : 0, addend2 ? ld_add2 : 0}) && aligned(bf16 ? 8 : 16, {out, addend, addend2});
+    g.bn_partial = bn_partial;
+    g.x_th = x_th;
+    return g;
+}
 }  // namespace
 
 extern "C" int snn_conv3x3_s2_dgrad_supported(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout) {
@@ -973,7 +993,7 @@ extern "C" int snn_conv3x3_s2_dgrad(const float* dy, int64_t lddy, const void* w
                 "snn_conv3x3_s2_dgrad_supported)", (long long)N, H, W, Ho, Wo, Cin, Cout);
     SNN_REQUIRE(lddy >= Cout && lddx >= Cin && lddy % 4 == 0, "snn_conv3x3_s2_dgrad: bad pixel strides (%lld, %lld)",
                 (long long)lddy, (long long)lddx);
-    SNN_REQUIRE((sbf ? aligned8(dy) : aligned16(dy)) && aligned16(wt_image),
+    SNN_REQUIRE(aligned(sbf ? 8 : 16, {dy}) && aligned(16, {wt_image}),
                 "snn_conv3x3_s2_dgrad: dy (16 bytes; 8 for bf16) and the weight image (16) must be aligned");
     SNN_REQUIRE(!addend || ld_addend >= Cin, "snn_conv3x3_s2_dgrad: addend pixel stride smaller than channel count");
     SNN_REQUIRE(!addend2 || ld_addend2 >= Cin, "snn_conv3x3_s2_dgrad: addend2 pixel stride smaller than channel count");
@@ -984,36 +1004,16 @@ extern "C" int snn_conv3x3_s2_dgrad(const float* dy, int64_t lddy, const void* w
         SNN_REQUIRE((int64_t)Ho * Wo * lddy * 4 < 0x7fffffffLL, "snn_conv3x3_s2_dgrad: a dy image must span less than 2 GiB");
     else
         SNN_REQUIRE((int64_t)4 * Ho * Wo * lddy * 4 < 0x7fffffffLL, "snn_conv3x3_s2_dgrad: four dy images must span less than 2 GiB");
-    HaloGeom g;
-    g.ldx = lddy; g.ldy = lddx; g.ld_add = ld_addend; g.ld_add2 = ld_addend2;
-    g.N = (int)N; g.H = Ho; g.W = Wo;          // the strip grid is dy's
-    g.Cin = Cout;                              // K: dy channels
-    g.Cout = Cin;                              // produced channels: dx
-    g.OH = H; g.OW = W;
-    g.PW = Wo + 1; g.PH = Ho + 1;
-    g.G = hp.G;
-    g.tiles_x = hp.tiles_x;
-    g.tiles_img = hp.tiles_img;
-    g.group_cells = hp.group_cells;
-    g.tiles_per_group = hp.tiles_per_group;
-    g.tiles = hp.tiles;
-    g.ntiles_n = hp.ntiles_n;
-    g.tiles_per_xcd = hp.tiles_per_xcd;
-    g.magic_pw = magic_u32(g.PW); g.magic_ph = magic_u32(g.PH);
-    g.out_vec = (lddx % 4 == 0) && out_aligned(dx, sbf) && (!addend || (ld_addend % 4 == 0 && out_aligned(addend, sbf))) &&
-                (!addend2 || (ld_addend2 % 4 == 0 && out_aligned(addend2, sbf)));
-    g.bn_partial = nullptr;
-    g.x_th = 0.0f;
-    dim3 grid((unsigned)hp.grid);
-    const unsigned char* wi = static_cast<const unsigned char*>(wt_image);
-    if (sbf && rect)
-        hipLaunchKernelGGL((k_conv_s2dgrad3<true, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, dy, wi, dx, g, addend, addend2);
-    else if (sbf)
-        hipLaunchKernelGGL((k_conv_s2dgrad3<true, false>), grid, dim3(kThreads), 0, (hipStream_t)stream, dy, wi, dx, g, addend, addend2);
-    else if (rect)
-        hipLaunchKernelGGL((k_conv_s2dgrad3<false, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, dy, wi, dx, g, addend, addend2);
-    else
-        hipLaunchKernelGGL((k_conv_s2dgrad3<false, false>), grid, dim3(kThreads), 0, (hipStream_t)stream, dy, wi, dx, g, addend, addend2);
+    // the strip grid is dy's, K its channels; the produced tensor is dx
+    const HaloGeom g = halo_geom(hp, N, Ho, Wo, Cout, lddy, H, W, Cin, dx, lddx, addend, ld_addend, addend2, ld_addend2, sbf,
+                                 nullptr, 0.0f);
+    dispatch(
+        [&](auto SBF, auto RECT) {
+            hipLaunchKernelGGL((k_conv_s2dgrad3<SBF(), RECT()>), dim3((unsigned)hp.grid), dim3(kThreads), 0, (hipStream_t)stream,
+                               dy, static_cast<const unsigned char*>(wt_image), dx, g, addend, addend2);
+            return true;
+        },
+        Flag{sbf}, Flag{rect});
     SNN_CHECK_LAUNCH("snn_conv3x3_s2_dgrad");
     return 0;
 }
@@ -1045,16 +1045,17 @@ extern "C" int snn_weight_frag_image_batched(const float* flat_src, void* flat_d
     SNN_REQUIRE(flat_src && flat_dst && table && n > 0 && max_groups > 0, "snn_weight_frag_image_batched: bad arguments");
     SNN_REQUIRE(precision == SNN_PREC_FP16X3 || precision == SNN_PREC_BF16X3,
                 "snn_weight_frag_image: precision must be SNN_PREC_FP16X3 (forward) or SNN_PREC_BF16X3 (data gradient)");
-    SNN_REQUIRE(aligned16(flat_src) && aligned16(flat_dst), "snn_weight_frag_image: buffers must be 16-byte aligned");
+    SNN_REQUIRE(aligned(16, {flat_src, flat_dst}), "snn_weight_frag_image: buffers must be 16-byte aligned");
     int64_t bx = snn_ceil_div(max_groups, kThreads);
     if (bx > 64) bx = 64;
     dim3 grid((unsigned)bx, (unsigned)n);
-    if (precision == SNN_PREC_FP16X3)
-        hipLaunchKernelGGL(k_weight_frag_image<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, flat_src,
-                           static_cast<unsigned char*>(flat_dst), table, flip);
-    else
-        hipLaunchKernelGGL(k_weight_frag_image<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, flat_src,
-                           static_cast<unsigned char*>(flat_dst), table, flip);
+    dispatch(
+        [&](auto F16) {
+            hipLaunchKernelGGL(k_weight_frag_image<F16()>, grid, dim3(kThreads), 0, (hipStream_t)stream, flat_src,
+                               static_cast<unsigned char*>(flat_dst), table, flip);
+            return true;
+        },
+        Flag{precision == SNN_PREC_FP16X3});
     SNN_CHECK_LAUNCH("snn_weight_frag_image_batched");
     return 0;
 }
@@ -1072,7 +1073,7 @@ static int conv3x3_halo_impl(const float* x, int64_t ldx, const void* w_image, f
                 (long long)N, H, W, Cin, Cout);
     SNN_REQUIRE(ldx >= Cin && ldy >= Cout && ldx % 4 == 0, "snn_conv3x3_halo: bad pixel strides (%lld, %lld)",
                 (long long)ldx, (long long)ldy);
-    SNN_REQUIRE((sbf ? aligned8(x) : aligned16(x)) && aligned16(w_image),
+    SNN_REQUIRE(aligned(sbf ? 8 : 16, {x}) && aligned(16, {w_image}),
                 "snn_conv3x3_halo: x (16 bytes; 8 for bf16) and the weight image (16) must be aligned");
     SNN_REQUIRE(!addend || ld_addend >= Cout, "snn_conv3x3_halo: addend pixel stride smaller than channel count");
     SNN_REQUIRE(!addend2 || ld_addend2 >= Cout, "snn_conv3x3_halo: addend2 pixel stride smaller than channel count");
@@ -1086,94 +1087,39 @@ static int conv3x3_halo_impl(const float* x, int64_t ldx, const void* w_image, f
     SNN_REQUIRE(hp.mode != 0, "snn_conv3x3_halo: grid too large");
     const bool rect = hp.mode == 2;
     if (rect) SNN_REQUIRE((int64_t)H * W * ldx * 4 < 0x7fffffffLL, "snn_conv3x3_halo: an image must span less than 2 GiB");
-    HaloGeom g;
-    g.ldx = ldx; g.ldy = ldy; g.ld_add = ld_addend; g.ld_add2 = ld_addend2;
-    g.N = (int)N; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout;
-    g.PW = W + 1; g.PH = H + 1;
-    g.G = hp.G;
-    g.tiles_x = hp.tiles_x;
-    g.tiles_img = hp.tiles_img;
-    g.group_cells = hp.group_cells;
-    g.tiles_per_group = hp.tiles_per_group;
-    const int co_tile = hp.co_tile;
-    g.ntiles_n = hp.ntiles_n;
-    g.tiles = hp.tiles;
-    g.tiles_per_xcd = hp.tiles_per_xcd;
-    g.magic_pw = magic_u32(g.PW); g.magic_ph = magic_u32(g.PH);
-    g.out_vec = (ldy % 4 == 0) && out_aligned(y, sbf) && (!addend || (ld_addend % 4 == 0 && out_aligned(addend, sbf))) &&
-                (!addend2 || (ld_addend2 % 4 == 0 && out_aligned(addend2, sbf)));
-    g.bn_partial = bn_partial;
-    g.OH = H; g.OW = W;
-    g.x_th = x_th;
+    const HaloGeom g = halo_geom(hp, N, H, W, Cin, ldx, H, W, Cout, y, ldy, addend, ld_addend, addend2, ld_addend2, sbf,
+                                 bn_partial, x_th);
     if (bn_partial) bn_layout[0] = g.tiles_per_group;   // every slot of every step is written: rows_per_chunk stays 0
-    dim3 grid((unsigned)hp.grid);
+    const dim3 grid((unsigned)hp.grid);
     const unsigned char* wi = static_cast<const unsigned char*>(w_image);
-    const bool f16 = precision == SNN_PREC_FP16X3;
-#define SNN_HALO_LAUNCH(CO_, F16_)                                                                                   \
-    do {                                                                                                              \
-        if (rect)                                                                                                     \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, F16_, 0, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, wi, \
-                               y, g, addend, addend2);                                                                \
-        else                                                                                                          \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, F16_>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, wi, y, g, addend, \
-                               addend2);                                                                              \
-    } while (0)
 #ifdef SNN_TUNING
     if (const char* e = snn_tuning_env("SNN_HALO_ABL")) {   // timing experiments (tools/halo_abl.py): WRONG results
-        const int abl = atoi(e);
-#define SNN_HALO_ABL_LAUNCH(A_) \
-        if (abl == A_) { \
-            if (co_tile == 128) hipLaunchKernelGGL((k_conv_halo3<128, true, A_>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, wi, y, g, addend, addend2); \
-            else hipLaunchKernelGGL((k_conv_halo3<64, true, A_>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, wi, y, g, addend, addend2); \
-            SNN_CHECK_LAUNCH("snn_conv3x3_halo"); return 0; }
-        SNN_HALO_ABL_LAUNCH(1) SNN_HALO_ABL_LAUNCH(2) SNN_HALO_ABL_LAUNCH(4) SNN_HALO_ABL_LAUNCH(8) SNN_HALO_ABL_LAUNCH(16)
-        SNN_HALO_ABL_LAUNCH(3) SNN_HALO_ABL_LAUNCH(7) SNN_HALO_ABL_LAUNCH(15) SNN_HALO_ABL_LAUNCH(31)
-#undef SNN_HALO_ABL_LAUNCH
+        const bool launched = dispatch(   // (the fp16 strip kernel whatever the call asks for; a 32-channel tile runs the 64 one)
+            [&](auto ABL, auto CO) {
+                hipLaunchKernelGGL((k_conv_halo3<CO(), true, ABL()>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, wi, y, g,
+                                   addend, addend2);
+                return true;
+            },
+            OneOf<1, 2, 4, 8, 16, 3, 7, 15, 31>{atoi(e)}, OneOf<64, 128>{hp.co_tile == 128 ? 128 : 64});
+        if (launched) {
+            SNN_CHECK_LAUNCH("snn_conv3x3_halo");
+            return 0;
+        }
     }
 #endif
-    if (xsp) {   // (precision checked by the caller: the forward arithmetic)
-#define SNN_HALO_LAUNCH_X(CO_)                                                                                       \
-    do {                                                                                                              \
-        if (rect)                                                                                                     \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, true, 0, true, false, true>), grid, dim3(kThreads), 0,              \
-                               (hipStream_t)stream, x, wi, y, g, addend, addend2);                                    \
-        else                                                                                                          \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, true, 0, false, false, true>), grid, dim3(kThreads), 0,             \
-                               (hipStream_t)stream, x, wi, y, g, addend, addend2);                                    \
-    } while (0)
-        if (co_tile == 128) SNN_HALO_LAUNCH_X(128);
-        else if (co_tile == 64) SNN_HALO_LAUNCH_X(64);
-        else SNN_HALO_LAUNCH_X(32);
-#undef SNN_HALO_LAUNCH_X
-        SNN_CHECK_LAUNCH("snn_conv3x3_halo_spikes");
-        return 0;
-    }
-    if (sbf) {
-#define SNN_HALO_LAUNCH_S(CO_)                                                                                       \
-    do {                                                                                                              \
-        if (rect)                                                                                                     \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, false, 0, true, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, x, \
-                               wi, y, g, addend, addend2);                                                            \
-        else                                                                                                          \
-            hipLaunchKernelGGL((k_conv_halo3<CO_, false, 0, false, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, \
-                               x, wi, y, g, addend, addend2);                                                         \
-    } while (0)
-        if (co_tile == 128) SNN_HALO_LAUNCH_S(128);
-        else if (co_tile == 64) SNN_HALO_LAUNCH_S(64);
-        else SNN_HALO_LAUNCH_S(32);
-#undef SNN_HALO_LAUNCH_S
-        SNN_CHECK_LAUNCH("snn_conv3x3_halo");
-        return 0;
-    }
-    if (co_tile == 128) {
-        if (f16) SNN_HALO_LAUNCH(128, true); else SNN_HALO_LAUNCH(128, false);
-    } else if (co_tile == 64) {
-        if (f16) SNN_HALO_LAUNCH(64, true); else SNN_HALO_LAUNCH(64, false);
-    } else {
-        if (f16) SNN_HALO_LAUNCH(32, true); else SNN_HALO_LAUNCH(32, false);
-    }
-#undef SNN_HALO_LAUNCH
-    SNN_CHECK_LAUNCH("snn_conv3x3_halo");
+    // the operand: two fp16 / bf16 pieces of an fp32 x, a bf16 x as it is, or spikes formed from saved potentials
+    enum { kPieces = 0, kBf16Storage = 1, kSpikes = 2 };
+    const bool f16 = precision == SNN_PREC_FP16X3;
+    dispatch(
+        [&](auto CO, auto RECT, auto OPERAND, auto F16) {
+            if constexpr (OPERAND() == kPieces || F16() == (OPERAND() == kSpikes)) {   // spikes: fp16 image; bf16 storage: bf16
+                hipLaunchKernelGGL((k_conv_halo3<CO(), F16(), 0, RECT(), OPERAND() == kBf16Storage, OPERAND() == kSpikes>), grid,
+                                   dim3(kThreads), 0, (hipStream_t)stream, x, wi, y, g, addend, addend2);
+            }
+            return true;
+        },
+        OneOf<32, 64, 128>{hp.co_tile}, Flag{rect}, OneOf<0, 1, 2>{xsp ? kSpikes : (sbf ? kBf16Storage : kPieces)}, Flag{f16});
+    SNN_CHECK_LAUNCH(xsp ? "snn_conv3x3_halo_spikes" : "snn_conv3x3_halo");
     return 0;
 }
 

@@ -9,8 +9,6 @@
 // layer_gen.py:232-235 / 252-254 (norse LIFCell / LICell), tiny_yolo.py:39-44 (LI -> Tanh).
 #include <stdlib.h>
 #include <algorithm>
-#include <initializer_list>
-#include <type_traits>
 #include "snn_common.h"
 
 #ifdef SNN_TUNING
@@ -1455,31 +1453,8 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------- host side: plans and dispatch
-// every pointer of the list (NULL counts as aligned) on a `bytes` boundary / every value a multiple of n
-static bool aligned(size_t bytes, std::initializer_list<const void*> ptrs) {
-    uintptr_t bits = 0;
-    for (const void* q : ptrs) bits |= reinterpret_cast<uintptr_t>(q);
-    return (bits & (bytes - 1)) == 0;
-}
-static bool multiples(int64_t n, std::initializer_list<int64_t> values) {
-    for (int64_t v : values)
-        if (v % n != 0) return false;
-    return true;
-}
-
-// Runtime values -> template arguments.  dispatch(f, OneOf<a, b, ...>{v}, ...) calls f with one std::integral_constant per
-// OneOf, holding the listed value its v equals, and returns what f returns; false when a v is not in its list.  f is a
-// generic lambda that launches under `if constexpr (<the instance exists>)`: what that condition rejects is never
-// instantiated.  (A chain of integer compares, all inlined: nothing is built or allocated per call.)
-template <auto... Vs> struct OneOf { std::common_type_t<decltype(Vs)...> v; };
 using AnyNeuron = OneOf<(int)SNN_NEURON_NONE, (int)SNN_NEURON_LIF, (int)SNN_NEURON_LI, (int)SNN_NEURON_LI_TANH,
                         (int)SNN_NEURON_SLI, (int)SNN_NEURON_SYNAPSE>;
-using Flag = OneOf<false, true>;
-template <class F> static bool dispatch(F&& f) { return f(); }
-template <class F, auto... Vs, class... Rest> static bool dispatch(F&& f, OneOf<Vs...> first, Rest... rest) {
-    return ((first.v == Vs &&
-             dispatch([&](auto... cs) { return f(std::integral_constant<decltype(Vs), Vs>{}, cs...); }, rest...)) || ...);
-}
 
 constexpr bool bf16_neuron(int n) {   // the neurons with a bf16-storage scan
     return n == SNN_NEURON_NONE || n == SNN_NEURON_LIF || n == SNN_NEURON_LI || n == SNN_NEURON_LI_TANH;

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <initializer_list>
+#include <type_traits>
 #include "../../include/snn_hip.h"
 
 void snn_set_error(const char* fmt, ...);
@@ -43,6 +45,34 @@ static inline int snn_num_cu() {
     return 256;
 }
 static inline int snn_max_blocks() { return snn_num_cu() * 8; }
+
+// every pointer of the list (NULL counts as aligned) on a `bytes` boundary / every value a multiple of n
+static bool aligned(size_t bytes, std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* q : ptrs) bits |= reinterpret_cast<uintptr_t>(q);
+    return (bits & (bytes - 1)) == 0;
+}
+static bool multiples(int64_t n, std::initializer_list<int64_t> values) {
+    for (int64_t v : values)
+        if (v % n != 0) return false;
+    return true;
+}
+
+// Runtime values -> template arguments.  dispatch(f, OneOf<a, b, ...>{v}, ...) calls f with one std::integral_constant per
+// OneOf, holding the listed value its v equals, and returns what f returns; false when a v is not in its list.  f is a
+// generic lambda that launches under `if constexpr (<the instance exists>)`: what that condition rejects is never
+// instantiated.  (A chain of integer compares, all inlined: nothing is built or allocated per call.)
+template <auto... Vs> struct OneOf { std::common_type_t<decltype(Vs)...> v; };
+using Flag = OneOf<false, true>;
+template <class F> static bool dispatch(F&& f) { return f(); }
+template <class F, auto... Vs, class... Rest> static bool dispatch(F&& f, OneOf<Vs...> first, Rest... rest) {
+    return ((first.v == Vs &&
+             dispatch([&](auto... cs) { return f(std::integral_constant<decltype(Vs), Vs>{}, cs...); }, rest...)) || ...);
+}
+
+// ceil(2^32 / d): q = umulhi(n, magic) for n * d < 2^32; d = 1 would need 2^32 and gives 0 (the kernels that can meet it
+// add n back)
+static inline unsigned magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ULL + (unsigned)d - 1) / (unsigned)d); }
 
 // Tuning / bisecting knobs exist only in builds made with -DSNN_TUNING (python -m snn_for_object_detection_amd._build
 // --tuning); the product library reads no environment variable.

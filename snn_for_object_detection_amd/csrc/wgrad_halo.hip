@@ -72,7 +72,6 @@ struct HaloGeom {
     float x_th;                         // NPROD 2: x holds saved LIF potentials, the operand is z = (v_dec > x_th)
 };
 
-static unsigned magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ULL + (unsigned)d - 1) / (unsigned)d); }
 __device__ __forceinline__ int div_magic(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
 __device__ __forceinline__ int div_magic2(int n, unsigned m) { return (int)__umulhi((unsigned)n, m); }  // divisor >= 2
 
@@ -370,9 +369,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_halo(const float* __
 #endif
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 }  // namespace
 
 SnnWgradHaloPlan snn_wgrad_halo_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW,
@@ -468,7 +464,7 @@ int snn_wgrad_halo_launch(const SnnWgradHaloPlan& p, const float* x, int64_t ldx
                           int nprod, bool bf16_storage, hipStream_t st, float x_th) {
     // 32-bit byte offsets inside one image (buffer addressing)
     if ((int64_t)H * W * ldx * 4 >= 0x7fffffffLL || (int64_t)Ho * Wo * lddy * 4 >= 0x7fffffffLL) return -1;
-    if (ldx % 4 != 0 || !(bf16_storage ? aligned8(x) : aligned16(x))) return -1;
+    if (ldx % 4 != 0 || !aligned(bf16_storage ? 8 : 16, {x})) return -1;
     if (bf16_storage && ((reinterpret_cast<uintptr_t>(dy) & 1u) || nprod != 1)) return -1;
     HaloGeom g;
     g.H = H; g.W = W; g.Cin = Cin; g.OH = Ho; g.OW = Wo; g.Cout = Cout; g.stride = stride;
@@ -485,29 +481,16 @@ int snn_wgrad_halo_launch(const SnnWgradHaloPlan& p, const float* x, int64_t ldx
     const int64_t nblocks = (int64_t)p.tiles_co * p.tiles_ci * p.splits;
     if (nblocks > 0x7fffffffLL) return -1;
     dim3 grid((unsigned)nblocks);
-#define SNN_HALO_LAUNCH(WCO_, WK_)                                                                                  \
-    do {                                                                                                            \
-        if (bf16_storage && stride == 1)                                                                            \
-            hipLaunchKernelGGL((k_conv_wgrad_halo<WCO_, WK_, 1, 1, true>), grid, dim3(kThreads), 0, st, x, dy, workspace, g); \
-        else if (bf16_storage)                                                                                      \
-            hipLaunchKernelGGL((k_conv_wgrad_halo<WCO_, WK_, 2, 1, true>), grid, dim3(kThreads), 0, st, x, dy, workspace, g); \
-        else if (stride == 1 && nprod == 2)                                                                         \
-            hipLaunchKernelGGL((k_conv_wgrad_halo<WCO_, WK_, 1, 2>), grid, dim3(kThreads), 0, st, x, dy, workspace, g); \
-        else if (nprod == 2)                                                                                        \
-            hipLaunchKernelGGL((k_conv_wgrad_halo<WCO_, WK_, 2, 2>), grid, dim3(kThreads), 0, st, x, dy, workspace, g); \
-        else if (stride == 1 && nprod == 3)                                                                         \
-            hipLaunchKernelGGL((k_conv_wgrad_halo<WCO_, WK_, 1, 3>), grid, dim3(kThreads), 0, st, x, dy, workspace, g); \
-        else if (nprod == 3)                                                                                        \
-            hipLaunchKernelGGL((k_conv_wgrad_halo<WCO_, WK_, 2, 3>), grid, dim3(kThreads), 0, st, x, dy, workspace, g); \
-        else if (stride == 1)                                                                                       \
-            hipLaunchKernelGGL((k_conv_wgrad_halo<WCO_, WK_, 1, 1>), grid, dim3(kThreads), 0, st, x, dy, workspace, g); \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_conv_wgrad_halo<WCO_, WK_, 2, 1>), grid, dim3(kThreads), 0, st, x, dy, workspace, g); \
-    } while (0)
-    if (p.wco == 4) SNN_HALO_LAUNCH(4, 1);
-    else if (p.wco == 2) SNN_HALO_LAUNCH(2, 2);
-    else SNN_HALO_LAUNCH(1, 4);
-#undef SNN_HALO_LAUNCH
+    // (the plan admits strides 1 and 2, the caller passes 1, 2 or 3 products)
+    dispatch(
+        [&](auto WCO, auto STRIDE, auto NPROD, auto SB) {
+            if constexpr (!SB() || NPROD() == 1) {
+                hipLaunchKernelGGL((k_conv_wgrad_halo<WCO(), 4 / WCO(), STRIDE(), NPROD(), SB()>), grid, dim3(kThreads), 0, st, x, dy,
+                                   workspace, g);
+            }
+            return true;
+        },
+        OneOf<4, 2, 1>{p.wco}, OneOf<1, 2>{stride}, OneOf<1, 2, 3>{nprod}, Flag{bf16_storage});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         snn_set_error("snn_conv2d_wgrad: halo kernel launch failed: %s", hipGetErrorString(e));
