@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SNN_ABI_VERSION 17
+#define SNN_ABI_VERSION 18
 
 /* neuron kinds for the fused affine+neuron temporal scan */
 enum {
@@ -543,6 +543,39 @@ int snn_upsample_bwd(const float* gy, float* gx, int64_t N, int H, int W, int C,
 int snn_adamax_step(float* param, const float* grad, float* exp_avg, float* exp_inf,
                     int64_t n, float lr, float beta1, float beta2, float eps, int step,
                     float grad_scale, void* stream);
+
+/* Control record of one optimiser step, in DEVICE memory (16 bytes, 4-byte aligned): written by snn_grad_norm, read on
+ * the device by every snn_adamax_step_ctl launch of that step - the host never has to look at it to issue the step.
+ * The caller zeroes it once; `skipped` then counts for as long as the same record is used. */
+typedef struct snn_step_control {
+    float   norm;     /* 2-norm of grad*grad_scale over the n elements (pre-clip)            */
+    float   scale;    /* extra multiplier: min(1, max_norm / (norm + 1e-6f)), or 1            */
+    int32_t finite;   /* 1 if every element is finite                                         */
+    int32_t skipped;  /* running count of non-finite steps seen through this record           */
+} snn_step_control;
+
+/* 2-norm of a flat gradient and the step's control record (Lightning's gradient_clip_val with
+ * gradient_clip_algorithm="norm" = torch.nn.utils.clip_grad_norm_, norm type 2; detect_anomaly's job for the
+ * gradient).  Squares and sums are formed in fp64.  Block b sums the 8192 elements [8192 b, 8192 b + 8192) of the
+ * buffer counted from the 16-byte boundary at or below `grad`; threads, waves, blocks and block partials are combined
+ * in a fixed order without atomics, so the record is bitwise reproducible and the same on every device.  `grad` needs
+ * 4-byte alignment only (full groups are read as aligned 16-byte loads, the two ragged ends element by element).
+ * Two launches.  Writes  norm = (float)(grad_scale * sqrt(sum g^2)),  scale = min(1, max_norm / (norm + 1e-6f)) in
+ * fp32 (exactly 1.0f when max_norm <= 0: norm only),  finite = isfinite(sum g^2),  skipped += !finite.
+ * ws: snn_grad_norm_workspace_size(n) bytes, 8-byte aligned (host-only helper, callable without a GPU). */
+size_t snn_grad_norm_workspace_size(int64_t n);
+int snn_grad_norm(const float* grad, int64_t n, float grad_scale, float max_norm, void* ws,
+                  snn_step_control* ctl, void* stream);
+
+/* snn_adamax_step with, per element and in this order (clip_grad_norm_ / clip_grad_value_ followed by
+ * torch.optim.Adamax(weight_decay)):  g = grad*grad_scale;  g *= ctl->scale (ctl given);
+ * g = clamp(g, -clip_value, +clip_value) (clip_value > 0);  g += weight_decay * param.
+ * With a ctl whose `finite` is 0 the launch stores nothing: parameters and both moments keep their bits.
+ * ctl NULL, weight_decay 0 and clip_value <= 0 launch snn_adamax_step's kernel: the same bits. */
+int snn_adamax_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_inf,
+                        int64_t n, float lr, float beta1, float beta2, float eps, int step,
+                        float grad_scale, float weight_decay, float clip_value,
+                        const snn_step_control* ctl, void* stream);
 
 /* ---------------------------------------------------------------- event voxelisation
  * utils/datasets.py:378-435: scatter events (t_bin, p, y, x) into binary frames [T][H][W][2]

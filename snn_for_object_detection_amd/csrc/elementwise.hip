@@ -352,16 +352,108 @@ __global__ void k_upsample_bwd(const float* __restrict__ gy, float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------ optimizer
-__global__ void k_adamax(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                         float* __restrict__ u, int64_t n, float w1, float b2, float eps, float clr, float gscale) {
+// One body, two kernels in front of it.  CTL = false is the plain step; CTL = true adds, in the order of clip_grad_* followed
+// by torch.optim.Adamax: the control record's clip factor, the value clamp, the weight decay - and stores NOTHING when the
+// record says the gradient was not finite (the moments would stay non-finite for ever: u = max(b2 * inf, ...) = inf).
+template <bool CTL>
+__device__ __forceinline__ void adamax_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ u, int64_t n, float w1, float b2, float eps, float clr,
+                                            float gscale, float wd, float clip, const snn_step_control* __restrict__ ctl) {
+    float cscale = 1.0f;
+    if constexpr (CTL) {
+        if (ctl) {
+            if (!ctl->finite) return;
+            cscale = ctl->scale;
+        }
+    }
     for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < n; e += (int64_t)gridDim.x * kThreads) {
         float ge = g[e] * gscale;  // gscale = 1/world_size after a SUM all-reduce (exact for powers of two)
+        if constexpr (CTL) {
+            ge *= cscale;                                                      // clip_grad_norm_: grad.mul_(clip_coef)
+            if (clip > 0.0f) ge = ge < -clip ? -clip : (ge > clip ? clip : ge);  // clip_grad_value_ (a NaN stays a NaN)
+            if (wd != 0.0f) ge += wd * p[e];                                   // grad.add(param, alpha=weight_decay)
+        }
         // torch.optim.Adamax single-tensor: exp_avg.lerp_(grad, 1-beta1); exp_inf = max(exp_inf*beta2, |g|+eps)
         float me = m[e] + w1 * (ge - m[e]);
         float ue = fmaxf(u[e] * b2, fabsf(ge) + eps);
         m[e] = me;
         u[e] = ue;
         p[e] = p[e] - clr * (me / ue);
+    }
+}
+__global__ void k_adamax(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                         float* __restrict__ u, int64_t n, float w1, float b2, float eps, float clr, float gscale) {
+    adamax_body<false>(p, g, m, u, n, w1, b2, eps, clr, gscale, 0.0f, 0.0f, nullptr);
+}
+__global__ void k_adamax_ctl(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                             float* __restrict__ u, int64_t n, float w1, float b2, float eps, float clr, float gscale,
+                             float wd, float clip, const snn_step_control* __restrict__ ctl) {
+    adamax_body<true>(p, g, m, u, n, w1, b2, eps, clr, gscale, wd, clip, ctl);
+}
+
+// ------------------------------------------------------------------------------------------ gradient norm
+// sum g^2 over a flat gradient, bitwise reproducible: block b owns the kNormRun elements [b * kNormRun, (b + 1) * kNormRun)
+// of the buffer counted from the 16-byte boundary at or below its first element (`shift` = 0..3 floats in front of it), so
+// every full group of four is one aligned 16-byte load whatever the base pointer is; the groups cut by either end of the
+// buffer (at most two in the whole launch) are read element by element.  A thread adds its squares in index order, the wave
+// and the block combine in a fixed butterfly, and the second kernel adds the block partials in index order: no atomics,
+// and nothing that depends on the device - the run length is a constant, not a function of the CU count.
+constexpr int kNormRun = 8192;
+constexpr int kNormGroups = kNormRun / (4 * kThreads);   // 16-byte groups per thread
+
+__device__ __forceinline__ double block_sum_ordered(double acc) {
+    __shared__ double wave_sum[kThreads / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    double s = wave_sum[0];
+#pragma unroll
+    for (int w = 1; w < kThreads / 64; ++w) s += wave_sum[w];
+    return s;   // the same value in every thread
+}
+
+__global__ void k_grad_norm_partial(const float* __restrict__ g, int64_t n, int shift, double* __restrict__ partial) {
+    const int64_t end = n + shift;   // the buffer is [shift, end) on the aligned grid; g points at element `shift`
+    const int64_t v0 = (int64_t)blockIdx.x * kNormRun;
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < kNormGroups; ++k) {
+        const int64_t v = v0 + ((int64_t)k * kThreads + threadIdx.x) * 4;
+        if (v >= shift && v + 4 <= end) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(g + (v - shift));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc += (double)x[j] * (double)x[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (v + j >= shift && v + j < end) {
+                    const double d = (double)g[v + j - shift];
+                    acc += d * d;
+                }
+        }
+    }
+    const double s = block_sum_ordered(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ void k_grad_norm_finish(const double* __restrict__ partial, int64_t blocks, float grad_scale, float max_norm,
+                                   snn_step_control* __restrict__ ctl) {
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < blocks; i += kThreads) acc += partial[i];
+    const double sum = block_sum_ordered(acc);
+    if (threadIdx.x == 0) {
+        const float norm = (float)((double)grad_scale * sqrt(sum));
+        float scale = 1.0f;
+        if (max_norm > 0.0f) {   // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
+            scale = max_norm / (norm + 1e-6f);
+            if (scale > 1.0f) scale = 1.0f;
+        }
+        const int finite = isfinite(sum) ? 1 : 0;   // an inf or NaN element makes the fp64 sum of squares non-finite
+        ctl->norm = norm;
+        ctl->scale = scale;
+        ctl->finite = finite;
+        ctl->skipped += 1 - finite;
     }
 }
 
@@ -682,6 +774,49 @@ extern "C" int snn_adamax_step(float* param, const float* grad, float* exp_avg, 
     hipLaunchKernelGGL(k_adamax, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, param, grad, exp_avg,
                        exp_inf, n, w1, beta2, eps, clr, grad_scale);
     SNN_CHECK_LAUNCH("snn_adamax_step");
+    return 0;
+}
+
+extern "C" int snn_adamax_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_inf, int64_t n, float lr,
+                                   float beta1, float beta2, float eps, int step, float grad_scale, float weight_decay,
+                                   float clip_value, const snn_step_control* ctl, void* stream) {
+    SNN_REQUIRE(param && grad && exp_avg && exp_inf && n > 0 && step >= 1, "snn_adamax_step_ctl: bad arguments");
+    SNN_REQUIRE(weight_decay >= 0.0f, "snn_adamax_step_ctl: negative weight_decay");   // (false for a NaN too)
+    SNN_REQUIRE(aligned(4, {ctl}), "snn_adamax_step_ctl: the control record must be 4-byte aligned");
+    double bias_corr = 1.0 - pow((double)beta1, (double)step);
+    float clr = (float)((double)lr / bias_corr);
+    float w1 = (float)(1.0 - (double)beta1);
+    if (!ctl && weight_decay == 0.0f && !(clip_value > 0.0f))   // nothing to add: the plain kernel, the same bits
+        hipLaunchKernelGGL(k_adamax, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, param, grad, exp_avg,
+                           exp_inf, n, w1, beta2, eps, clr, grad_scale);
+    else
+        hipLaunchKernelGGL(k_adamax_ctl, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, param, grad, exp_avg,
+                           exp_inf, n, w1, beta2, eps, clr, grad_scale, weight_decay, clip_value, ctl);
+    SNN_CHECK_LAUNCH("snn_adamax_step_ctl");
+    return 0;
+}
+
+static int64_t grad_norm_blocks(int64_t n, int shift) { return snn_ceil_div(n + shift, kNormRun); }
+
+extern "C" size_t snn_grad_norm_workspace_size(int64_t n) {
+    return n > 0 ? (size_t)grad_norm_blocks(n, 3) * sizeof(double) : 0;   // (3: the largest shift of an unaligned base)
+}
+
+extern "C" int snn_grad_norm(const float* grad, int64_t n, float grad_scale, float max_norm, void* ws,
+                             snn_step_control* ctl, void* stream) {
+    SNN_REQUIRE(grad && ws && ctl && n > 0, "snn_grad_norm: bad arguments");
+    SNN_REQUIRE(aligned(4, {grad, ctl}) && aligned(8, {ws}),
+                "snn_grad_norm: grad and ctl must be 4-byte aligned, the workspace 8-byte aligned");
+    const int shift = (int)((reinterpret_cast<uintptr_t>(grad) & 15u) / 4);
+    const int64_t blocks = grad_norm_blocks(n, shift);
+    SNN_REQUIRE(blocks <= 0x7fffffff, "snn_grad_norm: %lld elements are more than one launch covers", (long long)n);
+    double* partial = static_cast<double*>(ws);
+    hipLaunchKernelGGL(k_grad_norm_partial, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, grad, n, shift,
+                       partial);
+    SNN_CHECK_LAUNCH("snn_grad_norm");
+    hipLaunchKernelGGL(k_grad_norm_finish, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, partial, blocks, grad_scale,
+                       max_norm, ctl);
+    SNN_CHECK_LAUNCH("snn_grad_norm");
     return 0;
 }
 

@@ -158,6 +158,10 @@ def work_of(name: str, a):
         return "k_layout", 0.0, 8.0 * n
     if name == "snn_adamax_step":
         return "k_adamax", 8.0 * a[4], 28.0 * a[4]
+    if name == "snn_adamax_step_ctl":
+        return "k_adamax_ctl", 12.0 * a[4], 28.0 * a[4]
+    if name == "snn_grad_norm":   # one read of the flat gradient; a multiply and an add in fp64 per element
+        return "k_grad_norm", 2.0 * a[1], 4.0 * a[1]
     return name, 0.0, 0.0
 
 

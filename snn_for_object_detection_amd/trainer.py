@@ -46,7 +46,21 @@ class FlatTrainer:
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  process_group=None, use_grad_slots: bool = True, broadcast_buffers: bool = False,
                  overlap_grad_exchange: bool = True, exchange_single_rank: bool = False,
-                 find_unused_parameters: bool = True):
+                 find_unused_parameters: bool = True, gradient_clip_val: Optional[float] = None,
+                 gradient_clip_algorithm: str = "norm", skip_nonfinite: bool = False, weight_decay: float = 0.0):
+        # Lightning's ``gradient_clip_val`` / ``gradient_clip_algorithm`` ("norm": clip_grad_norm_, 2-norm over all
+        # parameters; "value": clip_grad_value_), applied to the AVERAGED gradient inside ``step()`` - see ``step()``
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(f"FlatTrainer: gradient_clip_algorithm must be 'norm' or 'value', not "
+                             f"{gradient_clip_algorithm!r}")
+        if gradient_clip_val is not None and not gradient_clip_val > 0:
+            raise ValueError(f"FlatTrainer: gradient_clip_val must be positive (None: no clipping), not {gradient_clip_val}")
+        if not weight_decay >= 0:
+            raise ValueError(f"FlatTrainer: weight_decay must not be negative, not {weight_decay}")
+        self.gradient_clip_val = None if gradient_clip_val is None else float(gradient_clip_val)
+        self.gradient_clip_algorithm = gradient_clip_algorithm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.weight_decay = float(weight_decay)
         self.params: List[torch.nn.Parameter] = [p for p in model.parameters() if p.requires_grad]
         if not self.params:
             raise RuntimeError("model has no trainable parameters")
@@ -62,6 +76,19 @@ class FlatTrainer:
         self.step_count = 0                       # optimiser steps taken by this trainer
         # torch.optim.Adamax keeps ``step`` PER PARAMETER and does not advance it for a parameter without a gradient
         self.param_steps: List[int] = [0] * len(self.params)
+        # The step's control record (snn_step_control: norm, scale, finite, skipped), the norm kernel's workspace and the
+        # pinned word ``finite`` is copied to exist only when norm clipping or ``skip_nonfinite`` needs them: a trainer
+        # built with the defaults issues exactly the launches it always did.
+        self._norm_clip = self.gradient_clip_val is not None and gradient_clip_algorithm == "norm"
+        self._ctl = self._ctl_norm = self._norm_ws = self._finite_host = None
+        self._pending_skip = None   # (event, parameters advanced) of the last step: its ``finite`` word is on its way
+        self._skipped = 0
+        if (self._norm_clip or self.skip_nonfinite) and dev.type == "cuda":
+            self._ctl = torch.zeros(4, device=dev, dtype=torch.int32)
+            self._ctl_norm = self._ctl[:1].view(torch.float32)[0]
+            self._norm_ws = torch.empty(_hip.query("snn_grad_norm_workspace_size", total_padded) // 8, device=dev,
+                                        dtype=torch.float64)
+            self._finite_host = torch.ones(1, dtype=torch.int32).pin_memory()
         self.group = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         # whether the step contains the exchange collectives.  ``exchange_single_rank`` keeps them in a one-rank group
@@ -452,10 +479,50 @@ class FlatTrainer:
                 b.copy_(flat[off:off + n].view(b.shape).to(b.dtype))
                 off += n
 
+    def _reconcile_skip(self) -> None:
+        """Take the last step's ``finite`` word (copied to pinned memory behind its norm kernel) and, if that step was
+        skipped on the device, give the parameters it would have updated their step count back: a skipped step leaves
+        the optimiser as if ``step()`` had not been called, bias correction included.  Waits for that copy only - by
+        the next ``step()`` it is a whole forward and backward pass old."""
+        if self._pending_skip is None:
+            return
+        event, advanced = self._pending_skip
+        self._pending_skip = None
+        event.synchronize()
+        if int(self._finite_host[0]) == 0:
+            self._skipped += 1
+            for k in advanced:
+                self.param_steps[k] -= 1
+
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """2-norm of the averaged gradient of the last ``step()``, before clipping: a 0-dim fp32 DEVICE tensor (a view of
+        the control record - reading it here synchronises nothing; the next ``step()`` overwrites it)."""
+        if self._ctl is None:
+            raise RuntimeError("FlatTrainer.last_grad_norm: the norm is computed only with gradient_clip_val "
+                               "(gradient_clip_algorithm='norm') or skip_nonfinite=True")
+        return self._ctl_norm
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps whose averaged gradient held an inf or a NaN and that therefore changed nothing.  Waits for the last
+        step's flag if it is still on its way."""
+        self._reconcile_skip()
+        return self._skipped
+
     def step(self) -> None:
+        """All-reduce, then the optimiser tail on the AVERAGED gradient, in the order of Lightning's loop
+        (``clip_gradients`` then ``optimizer.step()``): the 2-norm over the whole flat gradient and the step's control
+        record (``snn_grad_norm``: with norm clipping or ``skip_nonfinite``), then the fused Adamax, which reads the clip
+        factor and the finite flag from that record on the device, clamps (``"value"``) and adds the weight decay.
+        Clipping sits here and not in the caller's hands because only here the sum over the ranks is complete; the
+        summed buffer is the same on every rank, so every rank clips by the same factor and skips the same steps
+        without another collective.  A record that says "not finite" makes every Adamax launch of the step store
+        nothing (norm clipping implies it: a clip factor from a non-finite norm means nothing)."""
         if not self.flat_param.is_cuda:
             raise RuntimeError("FlatTrainer.step: parameters are not on a HIP device; the optimiser kernel has no "
                                "CPU fallback")
+        self._reconcile_skip()
         wgrad_stream_sync()  # weight-gradient kernels run on a side stream (functional._Conv2d.backward)
         self._check_bindings()
         self._collect_autograd_grads()
@@ -464,15 +531,33 @@ class FlatTrainer:
             self._flags_work = self._flags = None
         written = self._written_flags()
         self.all_reduce()
-        self.step_count += 1
-        for k, w in enumerate(written):
-            if w:
-                self.param_steps[k] += 1
+        self.step_count += 1                 # counts attempts; a skipped step gives ``param_steps`` back (above)
+        advanced = [k for k, w in enumerate(written) if w]
+        for k in advanced:
+            self.param_steps[k] += 1
         st = torch.cuda.current_stream().cuda_stream
+        grad_scale = 1.0 / self.world
+        ctl = None
+        if self._ctl is not None:
+            ctl = self._ctl.data_ptr()
+            _hip.call("snn_grad_norm", self.flat_grad.data_ptr(), self.flat_grad.numel(), grad_scale,
+                      self.gradient_clip_val if self._norm_clip else 0.0, self._norm_ws.data_ptr(), ctl, st)
+        clip_value = self.gradient_clip_val if (self.gradient_clip_val is not None and not self._norm_clip) else 0.0
+        plain = ctl is None and clip_value == 0.0 and self.weight_decay == 0.0
         for lo, hi, stp in self._ranges(written):
-            _hip.call("snn_adamax_step", self.flat_param.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + 4 * lo,
-                      self.exp_avg.data_ptr() + 4 * lo, self.exp_inf.data_ptr() + 4 * lo, hi - lo, self.lr,
-                      self.betas[0], self.betas[1], self.eps, stp, 1.0 / self.world, st)
+            args = (self.flat_param.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + 4 * lo,
+                    self.exp_avg.data_ptr() + 4 * lo, self.exp_inf.data_ptr() + 4 * lo, hi - lo, self.lr,
+                    self.betas[0], self.betas[1], self.eps, stp, grad_scale)
+            if plain:
+                _hip.call("snn_adamax_step", *args, st)
+            else:
+                _hip.call("snn_adamax_step_ctl", *args, self.weight_decay, clip_value, ctl, st)
+        if ctl is not None:
+            # the host learns whether the step was skipped one step late: no synchronisation here
+            self._finite_host.copy_(self._ctl[2:3], non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+            self._pending_skip = (event, advanced)
         self.refresh_transposed_weights()
         if self.broadcast_buffers:
             self.sync_buffers()
@@ -491,6 +576,7 @@ class FlatTrainer:
         per parameter, as torch does), one param group.  Interchangeable with a
         ``torch.optim.Adamax`` built over the same parameter order (the reference's Lightning checkpoints carry that
         state, ``models/soda.py:135-136``).  Weights and BatchNorm buffers are the model's own ``state_dict()``."""
+        self._reconcile_skip()
         state = {}
         for k, p in enumerate(self.params):
             if self.param_steps[k] == 0:   # torch creates a parameter's state at its first gradient
@@ -498,7 +584,8 @@ class FlatTrainer:
             state[k] = {"step": torch.tensor(float(self.param_steps[k])),
                         "exp_avg": _storage_view(self.exp_avg, self._offsets[k], p.data).clone(),
                         "exp_inf": _storage_view(self.exp_inf, self._offsets[k], p.data).clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "foreach": None,
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+                 "foreach": None,
                  "maximize": False, "differentiable": False, "capturable": False,
                  "params": list(range(len(self.params)))}
         return {"state": state, "param_groups": [group]}
@@ -508,9 +595,14 @@ class FlatTrainer:
         if len(group["params"]) != len(self.params):
             raise RuntimeError(f"optimizer state holds {len(group['params'])} parameters, the model has "
                                f"{len(self.params)}")
-        if group.get("weight_decay", 0) or group.get("maximize", False):
-            raise RuntimeError("FlatTrainer: weight_decay / maximize are not supported by the fused Adamax kernel")
+        if group.get("maximize", False):
+            raise RuntimeError("FlatTrainer: maximize is not supported by the fused Adamax kernel")
+        weight_decay = float(group.get("weight_decay", 0) or 0.0)
+        if not weight_decay >= 0:
+            raise ValueError(f"FlatTrainer: weight_decay must not be negative, not {weight_decay}")
+        self._reconcile_skip()   # (a flag still on its way belongs to the state that is being replaced)
         self.lr, self.betas, self.eps = group["lr"], tuple(group["betas"]), group["eps"]
+        self.weight_decay = weight_decay
         self.param_steps = [0] * len(self.params)
         self.exp_avg.zero_()
         self.exp_inf.zero_()
@@ -530,9 +622,11 @@ class FlatTrainer:
     # ------------------------------------------------------------------ helpers for tests / checkpoints
     def synchronize(self) -> None:
         """Join the weight-gradient side stream AND an early gradient exchange still in flight: after this the current
-        stream may read (or clip, in place) ``flat_grad``.  With the overlapped exchange (N > 1, SODa) the neck / head
+        stream may read ``flat_grad``.  With the overlapped exchange (N > 1, SODa) the neck / head
         part ``flat_grad[early_lo:]`` is then already SUMMED over the ranks while the backbone part is still local until
-        ``step()``; ``FlatTrainer(overlap_grad_exchange=False)`` keeps everything local until ``step()``."""
+        ``step()``; ``FlatTrainer(overlap_grad_exchange=False)`` keeps everything local until ``step()``.  Either way the
+        averaged gradient does not exist yet: clip with ``FlatTrainer(gradient_clip_val=...)``, which acts inside
+        ``step()`` behind the exchange, not on this buffer by hand."""
         if self.flat_grad.is_cuda:
             wgrad_stream_sync()
         self._join_early()

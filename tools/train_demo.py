@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Overfit ONE synthetic GEN1 batch (B=5, T=32) for N steps with the flat-buffer trainer: the loss curve of the full
-path (forward, last-step loss, BPTT, fused Adamax).   usage: train_demo.py [steps]"""
+path (forward, last-step loss, BPTT, fused Adamax).
+usage: train_demo.py [steps] [--clip V] [--clip-algorithm norm|value] [--skip-nonfinite] [--weight-decay D]
+(Lightning's gradient_clip_val / gradient_clip_algorithm / detect_anomaly and Adamax's weight_decay; all off by default)"""
+import argparse
 import os
 import sys
 import time
@@ -12,11 +15,21 @@ import bench  # noqa: E402
 import snn_for_object_detection_amd as S  # noqa: E402
 from snn_for_object_detection_amd.trainer import FlatTrainer  # noqa: E402
 
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 300
+ap = argparse.ArgumentParser(description="Overfit one synthetic GEN1 batch with the flat-buffer trainer")
+ap.add_argument("steps", nargs="?", type=int, default=300)
+ap.add_argument("--clip", type=float, default=None, help="gradient_clip_val (default: no clipping)")
+ap.add_argument("--clip-algorithm", choices=("norm", "value"), default="norm", help="gradient_clip_algorithm")
+ap.add_argument("--skip-nonfinite", action="store_true", help="leave out a step whose gradient holds an inf or a NaN")
+ap.add_argument("--weight-decay", type=float, default=0.0)
+args = ap.parse_args()
+steps = args.steps
 dev = torch.device("cuda")
 torch.manual_seed(2)
 model = S.TinyYolo(num_classes=2, time_window=0).to(dev).train()
-trainer = FlatTrainer(model, lr=model.hparams.learning_rate)
+trainer = FlatTrainer(model, lr=model.hparams.learning_rate, gradient_clip_val=args.clip,
+                      gradient_clip_algorithm=args.clip_algorithm, skip_nonfinite=args.skip_nonfinite,
+                      weight_decay=args.weight_decay)
+with_norm = args.skip_nonfinite or (args.clip is not None and args.clip_algorithm == "norm")
 X, labels = bench.synthetic_batch(32, 5, 240, 304, 2, dev, seed=0)
 t0 = time.perf_counter()
 for k in range(steps):
@@ -25,7 +38,10 @@ for k in range(steps):
     loss.backward()
     trainer.step()
     if k % 20 == 0 or k == steps - 1:
-        print(f"step {k:4d}  loss {float(loss.detach()):.5f}  ({time.perf_counter() - t0:.1f} s)", flush=True)
+        norm = f"  |g| {float(trainer.last_grad_norm):.4g}" if with_norm else ""
+        print(f"step {k:4d}  loss {float(loss.detach()):.5f}{norm}  ({time.perf_counter() - t0:.1f} s)", flush=True)
+if with_norm:
+    print("skipped steps:", trainer.skipped_steps)
 model.eval()
 with torch.no_grad():
     anchors, cls, box = model(X)
