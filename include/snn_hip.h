@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SNN_ABI_VERSION 18
+#define SNN_ABI_VERSION 19
 
 /* neuron kinds for the fused affine+neuron temporal scan */
 enum {
@@ -595,6 +595,25 @@ int snn_detect_decode(const float* cls_prob, const float* offsets, const float* 
  * only while IoU <= iou_threshold against every kept box (so a NaN IoU suppresses, as utils/box.py:95-97 does). */
 int snn_nms_sorted(const float* boxes, const int* order, const int* seg, int num_classes, float iou_threshold,
                    int* kept, int* nkept, unsigned char* kept_flag, int* kept_rank, void* stream);
+/* The same for N frames at once (every timestep of a clip, every sample of a validation batch), rows = N * A.
+ * snn_detect_decode_batched: prob [N][A][K], offsets [N][A][4], anchors [A][4] (the anchor of a row is row % A);
+ *   conf / cls [N][A], boxes [N][A][4].
+ * snn_nms_sorted_batched: one block per (class, frame).  order[N][A]: ROW ids (n * A + anchor) sorted by (frame, class
+ *   ascending, confidence descending, anchor ascending); seg[N][num_classes + 1] counts inside the frame: the members of
+ *   frame n's class c are order[n * A + seg[n][c] .. n * A + seg[n][c + 1]).  kept[N][A] (row ids, frame n's class c from
+ *   n * A + seg[n][c]), nkept[N][num_classes], kept_flag / kept_rank [N][A] as above, zeroed by the caller.
+ * snn_detect_assemble: the output rows (utils/box.py:121-153), one block per frame: out[N][A][6] rows (class, conf, x1,
+ *   y1, x2, y2); kept rows first at class_off[class] + rank (class_off = exclusive sum of nkept[n]), the others behind
+ *   them in anchor order; conf < pos_threshold gives class -1 and confidence 1 - conf, a row that was not kept class -1.
+ *   num_classes <= 1024.  boxes 16-byte, out 8-byte aligned; N * A < 2^31 - 256 in all three. */
+int snn_detect_decode_batched(const float* cls_prob, const float* offsets, const float* anchors, int N, int A, int K,
+                              float* conf, int* cls, float* boxes, void* stream);
+int snn_nms_sorted_batched(const float* boxes, const int* order, const int* seg, int N, int A, int num_classes,
+                           float iou_threshold, int* kept, int* nkept, unsigned char* kept_flag, int* kept_rank,
+                           void* stream);
+int snn_detect_assemble(const float* conf, const int* cls, const float* boxes, const int* nkept,
+                        const unsigned char* kept_flag, const int* kept_rank, int N, int A, int num_classes,
+                        float pos_threshold, float* out, void* stream);
 
 /* ---------------------------------------------------------------- training targets and loss
  * snn_roi_assign: RoI.__call__ (utils/roi.py:18-109) for a whole batch, one block per sample.  anchors [A][4] corner

@@ -2,7 +2,8 @@
 
 Tail of the step (tiny tensors: ``[B, A, C+1]`` / ``[B, A, 4]``).  Target-side helpers are torch tensor ops;
 ``multibox_detection`` on device tensors runs the HIP decode + greedy-NMS kernels of ``csrc/detect.hip`` (SURVEY
-section 8f rank 2), the loop below is the host form the fixtures pin.
+section 8f rank 2) - one frame through ``_multibox_detection_device``, several through ``multibox_detection_batched``
+(no loop over them) - the loop below is the host form the fixtures pin.
 """
 
 import torch
@@ -113,10 +114,51 @@ def _multibox_detection_device(cls_probs: torch.Tensor, offset_preds: torch.Tens
     return torch.stack(out)
 
 
+def multibox_detection_batched(cls_probs: torch.Tensor, offset_preds: torch.Tensor, anchors: torch.Tensor,
+                                nms_threshold: float = 0.1, pos_threshold: float = 0.009999999) -> torch.Tensor:
+    """``_multibox_detection_device`` for ``N`` frames (``cls_probs[N,A,K]``, ``offset_preds[N,A,4]`` on the device)
+    without a loop over them: decode, greedy NMS (one block per class and frame) and the output rows are one HIP launch
+    each (``csrc/detect.hip``), the ordering between them is the same key and the same stable device sort, taken along
+    the anchor dimension of ``[N,A]``.  Element for element the per-frame result; no host synchronisation."""
+    from . import _hip
+    if not cls_probs.is_cuda:
+        raise RuntimeError("multibox_detection_batched runs on device tensors; multibox_detection takes host tensors")
+    N, A, K = cls_probs.shape
+    dev = cls_probs.device
+    st = torch.cuda.current_stream().cuda_stream
+    probs = cls_probs.contiguous().float()
+    offs = offset_preds.contiguous().float()
+    anc = anchors.contiguous().float()
+    conf = torch.empty(N, A, device=dev, dtype=torch.float32)
+    cls = torch.empty(N, A, device=dev, dtype=torch.int32)
+    boxes = torch.empty(N, A, 4, device=dev, dtype=torch.float32)
+    _hip.call("snn_detect_decode_batched", probs.data_ptr(), offs.data_ptr(), anc.data_ptr(), N, A, K, conf.data_ptr(),
+              cls.data_ptr(), boxes.data_ptr(), st)
+    # per frame (class ascending, confidence descending, anchor ascending): the per-frame key, sorted inside each row
+    key = (cls + 1).double() * 2.0 - conf.double()
+    first_row = torch.arange(N, device=dev).unsqueeze(1) * A
+    order = (torch.argsort(key, dim=1, stable=True) + first_row).to(torch.int32)
+    classes = torch.arange(K, device=dev, dtype=torch.int32)
+    counts = (cls.unsqueeze(2) + 1 == classes).sum(1)                           # [N, K]: background, class 0, ...
+    seg = torch.cumsum(counts, 1).to(torch.int32).contiguous()                  # seg[n, c] = first member of class c
+    kept = torch.empty(N, A, device=dev, dtype=torch.int32)
+    nkept = torch.zeros(N, K - 1, device=dev, dtype=torch.int32)
+    flag = torch.zeros(N, A, device=dev, dtype=torch.uint8)
+    rank = torch.zeros(N, A, device=dev, dtype=torch.int32)
+    _hip.call("snn_nms_sorted_batched", boxes.data_ptr(), order.data_ptr(), seg.data_ptr(), N, A, K - 1,
+              float(nms_threshold), kept.data_ptr(), nkept.data_ptr(), flag.data_ptr(), rank.data_ptr(), st)
+    out = torch.empty(N, A, 6, device=dev, dtype=torch.float32)
+    _hip.call("snn_detect_assemble", conf.data_ptr(), cls.data_ptr(), boxes.data_ptr(), nkept.data_ptr(),
+              flag.data_ptr(), rank.data_ptr(), N, A, K - 1, float(pos_threshold), out.data_ptr(), st)
+    return out
+
+
 def multibox_detection(cls_probs: torch.Tensor, offset_preds: torch.Tensor, anchors: torch.Tensor,
                        nms_threshold: float = 0.1, pos_threshold: float = 0.009999999) -> torch.Tensor:
     """``[B, A, 6]`` rows ``(class, conf, x1, y1, x2, y2)``; suppressed / background rows get class -1
     (utils/box.py:102-153)."""
+    if cls_probs.is_cuda and cls_probs.shape[0] > 1:
+        return multibox_detection_batched(cls_probs, offset_preds, anchors, nms_threshold, pos_threshold)
     if cls_probs.is_cuda:
         return _multibox_detection_device(cls_probs, offset_preds, anchors, nms_threshold, pos_threshold)
     device = cls_probs.device

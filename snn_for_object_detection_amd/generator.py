@@ -474,32 +474,35 @@ class Head(nn.Module):
             setattr(self, f"anchor_gen_{idx}", AnchorGenerator(sizes=sizes[idx], ratios=ratios))
             setattr(self, f"model_{idx}", HeadGen(cfg, num_box_out, num_class_out, channels, init_weights))
 
-    def forward(self, X: List[torch.Tensor], state: Optional[ListState]):
+    def forward(self, X: List[torch.Tensor], state: Optional[ListState], all_steps: bool = False):
         """-> ``(anchors[A,4], cls_preds[B,A,C+1], bbox_preds[B,A,4], state)``.
 
         Given sequences the predictions are those of the LAST timestep (all the reference keeps,
-        ``soda.py:141-144``) and ``state`` is the state after the last timestep.
+        ``soda.py:141-144``) and ``state`` is the state after the last timestep.  ``all_steps=True`` keeps every
+        timestep of a sequence instead: ``cls_preds[T,B,A,C+1]``, ``bbox_preds[T,B,A,4]`` (inference over a clip).
         """
         state = [None] * len(X) if state is None else state
         anchors, cls_preds, bbox_preds = [], [], []
         for idx, map in enumerate(X):
             anchors.append(getattr(self, f"anchor_gen_{idx}")(map))
-            boxes, classes, state[idx] = getattr(self, f"model_{idx}")(map, state[idx])
+            boxes, classes, state[idx] = getattr(self, f"model_{idx}")(map, state[idx], all_steps=all_steps)
             bbox_preds.append(boxes)
             cls_preds.append(classes)
         anchors = torch.cat(anchors)
         cls_preds = self._concat_preds(cls_preds)
-        cls_preds = cls_preds.reshape(cls_preds.shape[0], -1, self.num_classes + 1)
+        cls_preds = cls_preds.reshape(*cls_preds.shape[:-1], -1, self.num_classes + 1)
         bbox_preds = self._concat_preds(bbox_preds)
-        bbox_preds = bbox_preds.reshape(bbox_preds.shape[0], -1, 4)
+        bbox_preds = bbox_preds.reshape(*bbox_preds.shape[:-1], -1, 4)
         return anchors, cls_preds, bbox_preds, state
 
     def _flatten_pred(self, pred: torch.Tensor) -> torch.Tensor:
         # channels-last storage makes this permute + flatten a free view
+        if pred.dim() == 5:  # every timestep: [T,B,C,h,w] -> [T,B,h*w*C]
+            return torch.flatten(torch.permute(pred, (0, 1, 3, 4, 2)), start_dim=2)
         return torch.flatten(torch.permute(pred, (0, 2, 3, 1)), start_dim=1)
 
     def _concat_preds(self, preds: List[torch.Tensor]) -> torch.Tensor:
-        return torch.cat([self._flatten_pred(p) for p in preds], dim=1)
+        return torch.cat([self._flatten_pred(p) for p in preds], dim=-1)
 
 
 class HeadGen(ModelGen):
@@ -518,19 +521,21 @@ class HeadGen(ModelGen):
     def _load_cfg(self, cfg) -> ListGen:
         return cfg(self.box_out, self.cls_out)
 
-    def forward(self, X: torch.Tensor, state: Optional[ListState]):
+    def forward(self, X: torch.Tensor, state: Optional[ListState], all_steps: bool = False):
         state = [None] * 3 if state is None else state
-        # sequence input, stateless prediction nets: only the last timestep's predictions survive
-        keep_last = X.dim() == 5 and not (any(_has_state(m) for m in self.box_net.modules())
+        all_steps = all_steps and X.dim() == 5
+        # sequence input, stateless prediction nets: only the last timestep's predictions survive (unless all are asked for)
+        stateless = X.dim() == 5 and not (any(_has_state(m) for m in self.box_net.modules())
                                           or any(_has_state(m) for m in self.cls_net.modules()))
+        keep_last = stateless and not all_steps
         Y, state[0] = self.base_net(X, state[0], last_only=keep_last)
         if Y.dim() == 5 and keep_last:
             Y = Y[-1]
-        if keep_last and Y.dtype == torch.bfloat16:
-            Y = HF.to_float32(Y)   # bf16-storage mode: the last-step read-out (a few frames) and the prediction nets run in fp32
+        if (keep_last or (all_steps and stateless)) and Y.dtype == torch.bfloat16:
+            Y = HF.to_float32(Y)   # bf16-storage mode: the read-out (the last step's few frames, or every step's when all are asked for) and the prediction nets run in fp32
         box, state[1] = self.box_net(Y, state[1])
         cls, state[2] = self.cls_net(Y, state[2])
-        if box.dim() == 5:
+        if box.dim() == 5 and not all_steps:
             box, cls = box[-1], cls[-1]
         if box.dtype == torch.bfloat16:
             box, cls = HF.to_float32(box), HF.to_float32(cls)

@@ -117,7 +117,7 @@ class SODa(nn.Module):
         preds, _ = self._forward_impl(X, None)
         return preds
 
-    def _forward_impl(self, X: torch.Tensor, state: Optional[ListState]):
+    def _forward_impl(self, X: torch.Tensor, state: Optional[ListState], all_steps: bool = False):
         from . import functional as HF
         state = [None] * 3 if state is None else state
         HF.begin_counter_batch()
@@ -126,7 +126,7 @@ class SODa(nn.Module):
             if self._snn_neck_grads_ready is not None and base_out.dim() == 5:
                 base_out = HF.grad_ready_hook(base_out, self._snn_neck_grads_ready)
             neck_out, state[1] = self.neck_net.forward(base_out, state[1])
-            anchors, cls_preds, bbox_preds, state[2] = self.head_net.forward(neck_out, state[2])
+            anchors, cls_preds, bbox_preds, state[2] = self.head_net.forward(neck_out, state[2], all_steps=all_steps)
         finally:
             HF.flush_counter_batch()
         return (anchors, cls_preds, bbox_preds), state
@@ -185,6 +185,39 @@ class SODa(nn.Module):
         prep_pred = prep_pred[prep_pred[:, 0] >= 0]
         prep_pred[:, 2:] = torch.clamp(prep_pred[:, 2:], min=0.0, max=1.0)
         return prep_pred, state
+
+    def predict_sequence(self, X: torch.Tensor, state: Optional[ListState] = None,
+                         skip: int = 0) -> Tuple[torch.Tensor, ListState]:
+        """Detections of EVERY timestep of a clip (or of a window of a live stream) from one pass.
+
+        ``X`` is ``[T,2,H,W]`` (one stream, the frames ``predict`` takes one by one) or ``[T,B,2,H,W]``.  The network runs
+        once, layer-major, over the sequence; softmax, decode and NMS run once over all ``T*B`` frames.  Returns
+        ``(dets, state)`` with ``dets[T,A,6]`` / ``dets[T,B,A,6]`` rows ``(class id, confidence, x1, y1, x2, y2)``, boxes
+        clamped to ``[0,1]``, and the detector state after the last timestep: ``predict_sequence(X[:k])`` followed by
+        ``predict_sequence(X[k:], state)`` continues the stream as ``predict`` does frame by frame.
+
+        The result is padded: the rows ``predict`` drops (suppressed, background, below the confidence threshold) are
+        present with class -1, because dropping them needs their number on the host.  ``dets[t][dets[t][:, 0] >= 0]`` are
+        the rows ``predict`` returns for timestep ``t``, in the same order; ``metrics.MeanAveragePrecision.update_padded``
+        takes the padded form as it is.  The first ``skip`` timesteps get class -1 in every row (the reference's
+        ``idx < time_window`` rule of ``predict_step``: the detector is still warming up).
+        """
+        if X.dim() not in (4, 5):
+            raise ValueError(f"predict_sequence takes X[T,2,H,W] or X[T,B,2,H,W], got a tensor of rank {X.dim()}")
+        if self.training:
+            raise RuntimeError("predict_sequence needs eval mode: a train-mode BatchNorm would normalise every timestep "
+                               "with the statistics of the whole clip")
+        single = X.dim() == 4
+        with torch.no_grad():
+            preds, state = self._forward_impl(X.unsqueeze(1) if single else X, state, all_steps=True)
+            anchors, cls, bbox = preds
+            T, B, A = cls.shape[:3]
+            dets = box.multibox_detection_batched(F.softmax(cls.reshape(T * B, A, -1), dim=2),
+                                                  bbox.reshape(T * B, A, 4), anchors).reshape(T, B, A, 6)
+            dets[..., 2:] = torch.clamp(dets[..., 2:], min=0.0, max=1.0)
+            if skip > 0:
+                dets[:skip, ..., 0] = -1.0
+        return (dets[:, 0] if single else dets), state
 
     def _rand_start_time(self) -> int:
         # soda.py:246-257: drop a random prefix of the sequence; the SAME draw (``requires_grad=False``,
