@@ -621,7 +621,12 @@ int snn_detect_assemble(const float* conf, const int* cls, const float* boxes, c
  * in the greedy phase).  An anchor takes the ground truth of highest IoU when that IoU >= iou_threshold, then every
  * label row claims the globally best remaining anchor (first maximum on ties).  Outputs: bbox_offset [B][A][4] =
  * offset_boxes(anchor, assigned box) * mask (utils/box.py:62-69), bbox_mask [B][A][4] (0 / 1), class_labels [B][A]
- * int64 (0 = background, label + 1 otherwise).  workspace: snn_roi_workspace_size(B, A, N) bytes. */
+ * int64 (0 = background, label + 1 otherwise).  workspace: snn_roi_workspace_size(B, A, N) bytes.
+ * The claimed anchor of a round is trunc((float)flat / (float)N) of the flat argmax index, as upstream forms it
+ * (utils/roi.py:105).  With A * N > 2^24 the fp32 quotient differs from flat / N for some indices; those assignments are
+ * upstream's and are reproduced.  For an index in the last anchor's row it can round up to A, where upstream raises
+ * IndexError; the kernel then takes anchor A - 1 and writes nothing outside the sample's rows.  A * N must stay below
+ * 2^31 - 1024 (refused otherwise). */
 size_t snn_roi_workspace_size(int B, int A, int N);
 int snn_roi_assign(const float* anchors, const float* labels, int B, int A, int N, float iou_threshold,
                    void* workspace, float* bbox_offset, float* bbox_mask, int64_t* class_labels, void* stream);

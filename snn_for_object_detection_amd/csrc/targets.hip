@@ -85,7 +85,12 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_assign(const float* __restr
         }
         __syncthreads();
         const int box_idx = winner.idx % N;
-        const int anc_idx = (int)((float)winner.idx / (float)N);   // float division + truncation, as the reference
+        // float division + truncation, as the reference: once A * N > 2^24 (float)idx rounds, and the quotient differs
+        // from idx / N for some indices - those are the reference's assignments and are kept.  Rounded up it can reach
+        // A for an index in the last anchor's row, where upstream raises IndexError: that one is held inside the
+        // sample's amap / iou rows (the last anchor) instead of writing behind them.
+        int anc_idx = (int)((float)winner.idx / (float)N);
+        if (anc_idx > A - 1) anc_idx = A - 1;
         if (tid == 0) amap[anc_idx] = box_idx;
         for (int a = tid; a < A; a += kRoiThreads) iou[(int64_t)a * N + box_idx] = -1.0f;
         for (int j = tid; j < N; j += kRoiThreads) iou[(int64_t)anc_idx * N + j] = -1.0f;
@@ -144,7 +149,9 @@ __global__ __launch_bounds__(kLossThreads) void k_det_loss_partial(const float* 
         float se = 0.f;
         for (int k = 0; k < K; ++k) se += expf(x[k] - mx);
         const int64_t y = cls[r];
-        const float ce = (mx + logf(se)) - x[y];   // -log_softmax(x)[y]
+        // -log_softmax(x)[y] as torch forms it, log(se) - (x[y] - mx): two terms >= 0.  (mx + log(se)) - x[y] rounds at
+        // the size of mx and loses the loss of a well-classified row with large logits.
+        const float ce = logf(se) - (x[y] - mx);
         if (y > 0) {
             s_pos += ce;
             n_pos += 1;
@@ -231,7 +238,8 @@ extern "C" int snn_roi_assign(const float* anchors, const float* labels, int B, 
                               void* workspace, float* bbox_offset, float* bbox_mask, int64_t* class_labels,
                               void* stream) {
     SNN_REQUIRE(anchors && labels && workspace && bbox_offset && bbox_mask && class_labels, "snn_roi_assign: null pointer");
-    SNN_REQUIRE(B > 0 && A > 0 && N > 0 && (int64_t)A * N < 0x7fffffffLL, "snn_roi_assign: bad shape");
+    // flat IoU indices are int, and the strided argmax loop steps kRoiThreads past the last one before it stops
+    SNN_REQUIRE(B > 0 && A > 0 && N > 0 && (int64_t)A * N < 0x7fffffffLL - kRoiThreads, "snn_roi_assign: bad shape");
     SNN_REQUIRE(aligned16(anchors) && aligned16(bbox_offset) && aligned16(bbox_mask) && aligned16(workspace),
                 "snn_roi_assign: buffers must be 16-byte aligned");
     float* iou = static_cast<float*>(workspace);

@@ -2088,12 +2088,20 @@ class _DetectionLoss(Function):
     def forward(ctx, cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, loss_ratio: float):
         _require_device(cls_preds, "loss: class predictions")
         _require_device(bbox_preds, "loss: box predictions")
+        # the targets go to the kernel as raw pointers: a host or float64 tensor would be read as a wild device address
+        _require_device(bbox_offset, "loss: box offsets")
+        _require_device(bbox_mask, "loss: box mask")
+        for t, what in ((bbox_preds, "box predictions"), (bbox_offset, "box offsets"), (bbox_mask, "box mask"),
+                        (class_labels, "class labels")):
+            if t.device != cls_preds.device:
+                raise RuntimeError(f"loss: {what} are on {t.device}, the class predictions on {cls_preds.device}")
         K = cls_preds.shape[-1]
         logits, boxes = cls_preds.detach().contiguous(), bbox_preds.detach().contiguous()
         off, msk = bbox_offset.contiguous(), bbox_mask.contiguous()
         lab = class_labels.contiguous()
         rows = lab.numel()
-        if logits.numel() != rows * K or boxes.numel() != rows * 4 or off.numel() != rows * 4 or lab.dtype != torch.int64:
+        if logits.numel() != rows * K or boxes.numel() != rows * 4 or off.numel() != rows * 4 or \
+                msk.numel() != rows * 4 or lab.dtype != torch.int64:
             raise RuntimeError("detection loss: predictions and targets differ in shape")
         dev = logits.device
         ws = torch.empty(_hip.query("snn_det_loss_workspace_size", rows), device=dev, dtype=torch.uint8)
