@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SNN_ABI_VERSION 19
+#define SNN_ABI_VERSION 20
 
 /* neuron kinds for the fused affine+neuron temporal scan */
 enum {
@@ -109,6 +109,15 @@ enum { SNN_POOL_AVG = 0, SNN_POOL_MAX = 1, SNN_POOL_SUM = 2 };
 /* pointwise activations, layer_gen.py:257-284 */
 enum { SNN_ACT_RELU = 0, SNN_ACT_SILU = 1, SNN_ACT_TANH = 2 };
 
+/* Surrogate gradient dz/du of the LIF spike z = (u > 0), u = v_dec - v_th, a = alpha; every one has s(0) = 1:
+ *   SNN_SURR_SUPER     1 / (a|u| + 1)^2        (SuperSpike; the default, and the only one that claims to restate norse)
+ *   SNN_SURR_TRIANGLE  max(0, 1 - a|u|)
+ *   SNN_SURR_SIGMOID   4 s(au) (1 - s(au)),  s(x) = 1 / (1 + exp(-x))
+ *   SNN_SURR_ATAN      1 / (1 + (au)^2)
+ * These definitions (normalisation and the meaning of alpha) are THIS project's own: like the rest of the LIF rule they
+ * are "parity unpinned" - no norse source is at hand to compare them with. */
+enum { SNN_SURR_SUPER = 0, SNN_SURR_TRIANGLE = 1, SNN_SURR_SIGMOID = 2, SNN_SURR_ATAN = 3 };
+
 /* neuron constants exactly as norse rounds them in fp32 (oracle/neurons.py:neuron_constants) */
 typedef struct snn_neuron_params {
     float c_mem;   /* dt * tau_mem_inv            (0.1)  */
@@ -116,12 +125,17 @@ typedef struct snn_neuron_params {
     float v_leak;  /* 0 */
     float v_th;    /* 1 */
     float v_reset; /* 0 */
-    float alpha;   /* SuperSpike slope, 100 */
+    float alpha;   /* surrogate slope a (SuperSpike: 100) */
     float v_st;    /* SLI saturation potential, 1 (sli.py:38-39)                              */
     float tau_sec; /* synapse: mediator secretion rate 1/1e-3 (synapse.py:26-27)              */
     float tau_dis; /* synapse: mediator dissociation rate 1/5e-3 (synapse.py:29-30)           */
     float dt;      /* synapse integration step 1e-3 (synapse.py:77)                           */
     float sigma;   /* synapse inhibition, 0 = off (synapse.py:32-36)                          */
+    /* ABI 20, LIF backward only (the forward is the same, bit for bit, whatever they hold).  Zero is the rule of every
+     * earlier ABI, so a caller that zero-fills the tail of the struct computes what it always did. */
+    int surrogate;      /* SNN_SURR_*                                                                              */
+    int reset_detached; /* != 0: the spike inside the reset v = (1-z) v_dec + z v_reset is a constant of the backward
+                           pass:  g_vd = g_v (1-z) + g_out s   instead of   g_v (1-z) + (g_out + g_v (v_reset - v_dec)) s */
 } snn_neuron_params;
 
 int snn_abi_version(void);
@@ -401,15 +415,19 @@ int snn_affine_neuron_fwd(int neuron, const float* y, int64_t ldy,
                           float* vT, float* iT, float* vdec,
                           int T, int64_t M, int C, const snn_neuron_params* p, int flags, void* stream);
 
-/* Reverse-time scan (BPTT through the neuron, SuperSpike surrogate dz/du = 1/(alpha|u|+1)^2,
- * reset path NOT detached).  g_out is dL/d out[t]; g_vT/g_iT (may be NULL = 0) are the
+/* Reverse-time scan (BPTT through the neuron).  LIF: the surrogate dz/du is p->surrogate (default SuperSpike,
+ * 1/(alpha|u|+1)^2) and the reset path is differentiated through the spike unless p->reset_detached (default: NOT
+ * detached); a non-default rule takes a second instance of the same kernel on the same launch plan, on fp32 tensors (with
+ * SNN_SCAN_BF16_STORAGE it is refused), an unknown surrogate code is refused, and so is a non-default rule with a neuron
+ * other than LIF.  g_out is dL/d out[t]; g_vT/g_iT (may be NULL = 0) are the
  * gradients of the final state; writes gx = dL/dx[t] (dense [T][M][C]), g_v0/g_i0 (may be NULL)
  * and, when `sums` != NULL, per-block partial sums of gx and gx*y per (t,c) for the BatchNorm
  * backward (`sums` scratch of snn_affine_neuron_bwd_sums_size() doubles, y must be given).
  * `state` is the forward's vdec buffer for LIF / SLI / SYNAPSE, out (tanh output) for LI_TANH, unused otherwise.
  * alpha/beta (may be NULL = identity): the forward's affine, needed to rebuild x[t] for SLI / SYNAPSE.
  * apply_scale != 0: gx is multiplied by alpha[t,c] before it is written (eval-mode BN: dy = alpha*gx).
- * flags: 0, SNN_SCAN_WIDE_ADDRESSING, SNN_SCAN_LAST_STEP_ONLY (or both). */
+ * flags: any of SNN_SCAN_WIDE_ADDRESSING, SNN_SCAN_LAST_STEP_ONLY (LIF / LI / LI+Tanh), SNN_SCAN_BF16_STORAGE,
+ * SNN_SCAN_SUMS_FROM_STATE [| SNN_SCAN_STATE_LOOKBACK] (see the enum; what a combination does not cover is refused). */
 size_t snn_affine_neuron_bwd_sums_size(int T, int64_t M, int C);
 /* 1 when snn_affine_neuron_bwd(flags | SNN_SCAN_SUMS_FROM_STATE) covers the call (LIF, the ordered-sums plan of the shape,
  * 32-bit buffer addressing, fp32 tensors, all T gradients, c_mem in [1/64, 1]) */
@@ -435,7 +453,8 @@ int snn_affine_neuron_bwd(int neuron, const float* g_out, int64_t ldg, const flo
  *   ckpt[ceil(T/K)][2][M][C]   (2*ceil(T/K)/T of the per-step buffer: half at K = 4)
  * and the backward scan re-runs the K forward steps of a chunk from its checkpoint (it needs y and alpha/beta for
  * that) before walking the chunk in reverse.  An opt-in memory lever for 1280x720-class inputs
- * (functional.LIF_CHECKPOINT_BYTES); speed-neutral. */
+ * (functional.LIF_CHECKPOINT_BYTES); speed-neutral.  Default gradient rule only: snn_lif_bwd_ckpt refuses a struct with
+ * surrogate != SNN_SURR_SUPER or reset_detached != 0 before it launches anything. */
 int snn_lif_ckpt_interval(void);
 int snn_lif_fwd_ckpt(const float* y, int64_t ldy, const float* alpha, const float* beta,
                      const float* v0, const float* i0, float* out, int64_t ldo,

@@ -15,16 +15,18 @@ LIB_PATH = os.environ.get("SNN_HIP_LIB") or os.path.join(_HERE, "libsnn_hip.so")
 NEURON_NONE, NEURON_LIF, NEURON_LI, NEURON_LI_TANH, NEURON_SLI, NEURON_SYNAPSE = 0, 1, 2, 3, 4, 5
 POOL_AVG, POOL_MAX, POOL_SUM = 0, 1, 2
 ACT_RELU, ACT_SILU, ACT_TANH = 0, 1, 2
-ABI_VERSION = 19
+ABI_VERSION = 20
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_FP16X3, PREC_BF16X1, PREC_BF16S = 0, 1, 3, 4, 5, 6   # SNN_PREC_* of include/snn_hip.h
 SCAN_WIDE_ADDRESSING, SCAN_LAST_STEP_ONLY, SCAN_BF16_STORAGE, SCAN_SPIKES_FROM_VDEC, SCAN_SUMS_FROM_STATE = 1, 2, 4, 8, 16
 SCAN_STATE_LOOKBACK = 32
+SURR_SUPER, SURR_TRIANGLE, SURR_SIGMOID, SURR_ATAN = 0, 1, 2, 3   # SNN_SURR_* of include/snn_hip.h
 
 
 class NeuronParams(Structure):
     _fields_ = [("c_mem", c_float), ("c_syn", c_float), ("v_leak", c_float), ("v_th", c_float),
                 ("v_reset", c_float), ("alpha", c_float), ("v_st", c_float), ("tau_sec", c_float),
-                ("tau_dis", c_float), ("dt", c_float), ("sigma", c_float)]
+                ("tau_dis", c_float), ("dt", c_float), ("sigma", c_float),
+                ("surrogate", c_int), ("reset_detached", c_int)]   # (ABI 20; zero = the rule of every earlier ABI)
 
 
 _P, _I, _L, _F = c_void_p, c_int, c_int64, c_float

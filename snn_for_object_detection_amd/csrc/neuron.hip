@@ -647,7 +647,9 @@ static BwdPlan bwd_plan(int T, int64_t M, int C, bool with_sums) {
 // vd[t+1]: it forms i'[t+1], with the i'[t+2] of the step before x[t+2], and adds gx[t+2] * x[t+2] (kept two steps) to the
 // slab row of step t+2; x[1] and x[0] follow after the loop from the initial state.  4 of the 16 bytes per neuron-timestep
 // are never read; the second value of a sums pair is then sum(gx * x) (snn_bn_bwd_finalize_from_state converts).
-template <int NEURON, int VEC, int MODE, bool BUF, int NP, bool SB = false, bool YF = false>
+// GR (LIF, fp32 tensors): the general gradient rule - p.surrogate and p.reset_detached, the same for every lane, are read in
+// the step; false compiles the SuperSpike / reset-not-detached arm alone, the code the default rule has always run.
+template <int NEURON, int VEC, int MODE, bool BUF, int NP, bool SB = false, bool YF = false, bool GR = false>
 __global__ __launch_bounds__(kThreads, YF ? 2 : 1) void k_affine_neuron_bwd(
     const float* __restrict__ g_out, int64_t ldg, const float* __restrict__ state, const float* __restrict__ y,
     int64_t ldy, const float* __restrict__ g_vT, const float* __restrict__ g_iT, const float* __restrict__ alpha,
@@ -679,6 +681,7 @@ __global__ __launch_bounds__(kThreads, YF ? 2 : 1) void k_affine_neuron_bwd(
         __syncthreads();
     }
     static_assert(!YF || (NEURON == SNN_NEURON_LIF && MODE == 1 && BUF && VEC == 4 && !SB), "sums from the saved state: LIF, ordered sums");
+    static_assert(!GR || (NEURON == SNN_NEURON_LIF && !SB), "selectable gradient rule: LIF on fp32 tensors");
     const float one_m_cmem = 1.0f - p.c_mem;
     const float one_p_csyn = 1.0f + p.c_syn;
     [[maybe_unused]] const float inv_cmem = 1.0f / p.c_mem;
@@ -828,12 +831,38 @@ __global__ __launch_bounds__(kThreads, YF ? 2 : 1) void k_affine_neuron_bwd(
                         float vd = lane<VEC>(st_q, j);
                         float u = vd - p.v_th;
                         float z = (u > 0.0f) ? 1.0f : 0.0f;
-                        float den = p.alpha * fabsf(u) + 1.0f;
-                        // bf16 storage: the 1-ulp hardware reciprocal (the result is rounded to 8 bits on its way out; the
-                        // IEEE division is ten VALU instructions and made this instance VALU-bound at 3.3 TB/s)
-                        float sg = SB ? __builtin_amdgcn_rcpf(den * den) : 1.0f / (den * den);
                         float gvj = lane<VEC>(gv[q], j);
-                        float gz = goj + gvj * (p.v_reset - vd);
+                        float sg, gz;
+                        if constexpr (!GR) {
+                            float den = p.alpha * fabsf(u) + 1.0f;
+                            // bf16 storage: the 1-ulp hardware reciprocal (the result is rounded to 8 bits on its way out; the
+                            // IEEE division is ten VALU instructions and made this instance VALU-bound at 3.3 TB/s)
+                            sg = SB ? __builtin_amdgcn_rcpf(den * den) : 1.0f / (den * den);
+                            gz = goj + gvj * (p.v_reset - vd);
+                        } else {
+                            // every surrogate is num / d with s(0) = 1: the branches (scalar: the rule is a kernel argument)
+                            // pick the two, ONE division serves all four.  SUPER: 1 / d, the default arm's value bit for bit.
+                            // SIGMOID: 4 s(x)(1 - s(x)) = 4e / (1 + e)^2 with e = exp(-|x|) - even in x, e in (0, 1]
+                            const float ax = p.alpha * fabsf(u);
+                            float num = 1.0f, d;
+                            if (p.surrogate == SNN_SURR_TRIANGLE) {
+                                num = fmaxf(0.0f, 1.0f - ax);
+                                d = 1.0f;
+                            } else if (p.surrogate == SNN_SURR_SIGMOID) {
+                                const float e = expf(-ax);
+                                const float q1 = 1.0f + e;
+                                num = 4.0f * e;
+                                d = q1 * q1;
+                            } else if (p.surrogate == SNN_SURR_ATAN) {
+                                d = 1.0f + ax * ax;
+                            } else {
+                                const float den = ax + 1.0f;
+                                d = den * den;
+                            }
+                            sg = num / d;
+                            // detached reset: v = (1 - z) v_dec + z v_reset with z a constant - no gradient reaches z through it
+                            gz = p.reset_detached ? goj : goj + gvj * (p.v_reset - vd);
+                        }
                         float g_vd = gvj * (1.0f - z) + gz * sg;
                         float g_in = p.c_mem * g_vd + lane<VEC>(gi[q], j) * one_p_csyn;
                         lane<VEC>(gv[q], j) = g_vd * one_m_cmem;
@@ -1464,6 +1493,11 @@ constexpr bool rebuilds_x(int n) { return n == SNN_NEURON_SLI || n == SNN_NEURON
 const char* const kBf16Covers =
     "bf16 storage covers NONE / LIF / LI / LI+Tanh on channel counts and strides that are multiples of 4 (8-byte aligned "
     "tensors)";
+const char* const kBadSurrogate = "unknown surrogate code (SNN_SURR_SUPER / _TRIANGLE / _SIGMOID / _ATAN)";
+const char* const kGradientRuleCovers =
+    "a non-default gradient rule (surrogate != SNN_SURR_SUPER or reset_detached != 0) is for SNN_NEURON_LIF";
+const char* const kGradientRuleNoBf16 =
+    "a non-default gradient rule (surrogate != SNN_SURR_SUPER or reset_detached != 0) has no bf16-storage scan";
 const char* const kSumsFromStateCovers =
     "SNN_SCAN_SUMS_FROM_STATE not covered (ask snn_affine_neuron_bwd_sums_from_state; LIF from the initial state, sums "
     "wanted, train-mode BatchNorm)";
@@ -1499,7 +1533,7 @@ constexpr bool fwd_instance(int neuron, int vec, int save, bool sb) {
 // instance that really runs.
 struct ScanBwdPlan {
     BwdPlan pl;
-    bool buf, sb, yf;         // BUF / SB / YF of the kernel
+    bool buf, sb, yf, gr;     // BUF / SB / YF / GR of the kernel
     int np;                   // NP: pixel rows per thread
     int lookback, last_only;
     const char* refusal;      // what shape and flags alone rule out (nullptr: nothing)
@@ -1524,6 +1558,10 @@ static ScanBwdPlan scan_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ld
     if (!(T > 0 && M > 0 && C > 0 && ldg >= C)) return refuse("bad shape");
     if (neuron < SNN_NEURON_NONE || neuron > SNN_NEURON_SYNAPSE) return refuse("bad neuron");
     if (sp.last_only && !last_step_neuron(neuron)) return refuse("SNN_SCAN_LAST_STEP_ONLY is for LIF / LI / LI+Tanh");
+    if (p->surrogate < SNN_SURR_SUPER || p->surrogate > SNN_SURR_ATAN) return refuse(kBadSurrogate);
+    sp.gr = p->surrogate != SNN_SURR_SUPER || p->reset_detached != 0;
+    if (sp.gr && neuron != SNN_NEURON_LIF) return refuse(kGradientRuleCovers);
+    if (sp.gr && sp.sb) return refuse(kGradientRuleNoBf16);
     sp.pl = bwd_plan(T, M, C, with_sums);
     if (sp.sb && !(sp.pl.vec == 4 && bf16_neuron(neuron))) return refuse(kBf16Covers);
     // buffer addressing (see k_affine_neuron_bwd): one timestep of every tensor must fit a 31-bit byte offset
@@ -1545,7 +1583,8 @@ static ScanBwdPlan scan_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ld
     }
     return sp;
 }
-constexpr bool bwd_instance(int neuron, int vec, int mode, bool buf, int np, bool sb, bool yf) {
+constexpr bool bwd_instance(int neuron, int vec, int mode, bool buf, int np, bool sb, bool yf, bool gr) {
+    if (gr && (neuron != SNN_NEURON_LIF || sb)) return false;   // one general instance per fp32 LIF instance, no others
     if (yf) return neuron == SNN_NEURON_LIF && vec == 4 && mode == 1 && buf && np <= 3 && !sb;
     return (np == 1 ? buf : np == kBwdNP) && (vec == 4 || !(buf || sb)) && (!sb || bf16_neuron(neuron));
 }
@@ -1776,9 +1815,9 @@ extern "C" int snn_affine_neuron_bwd(int neuron, const float* g_out, int64_t ldg
         SNN_REQUIRE(ok, "snn_affine_neuron_bwd: %s", sp.sb ? kBf16Covers : "buffers must be 16-byte aligned when C%4==0");
     }
     const bool launched = dispatch(
-        [&](auto NEURON, auto VEC, auto MODE, auto BUF, auto NP, auto SB, auto YF) {
-            if constexpr (bwd_instance(NEURON(), VEC(), MODE(), BUF(), NP(), SB(), YF())) {
-                hipLaunchKernelGGL((k_affine_neuron_bwd<NEURON(), VEC(), MODE(), BUF(), NP(), SB(), YF()>),
+        [&](auto NEURON, auto VEC, auto MODE, auto BUF, auto NP, auto SB, auto YF, auto GR) {
+            if constexpr (bwd_instance(NEURON(), VEC(), MODE(), BUF(), NP(), SB(), YF(), GR())) {
+                hipLaunchKernelGGL((k_affine_neuron_bwd<NEURON(), VEC(), MODE(), BUF(), NP(), SB(), YF(), GR()>),
                                    dim3(sp.pl.gx, sp.pl.gy), dim3(kThreads), sp.pl.lds_bytes, (hipStream_t)stream, g_out, ldg,
                                    state, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, g_v0, g_i0, sums, T, M, C,
                                    sp.pl.cvb, *p, sp.yf ? sp.lookback : sp.last_only);
@@ -1788,9 +1827,9 @@ extern "C" int snn_affine_neuron_bwd(int neuron, const float* g_out, int64_t ldg
             }
         },
         AnyNeuron{neuron}, OneOf<1, 4>{sp.pl.vec}, OneOf<0, 1, 2>{sp.pl.mode}, Flag{sp.buf}, OneOf<1, 2, 3, kBwdNP>{sp.np},
-        Flag{sp.sb}, Flag{sp.yf});
-    SNN_REQUIRE(launched, "snn_affine_neuron_bwd: no kernel instance (neuron %d, vec %d, mode %d, BUF %d, NP %d)", neuron,
-                sp.pl.vec, sp.pl.mode, (int)sp.buf, sp.np);
+        Flag{sp.sb}, Flag{sp.yf}, Flag{sp.gr});
+    SNN_REQUIRE(launched, "snn_affine_neuron_bwd: no kernel instance (neuron %d, vec %d, mode %d, BUF %d, NP %d, GR %d)",
+                neuron, sp.pl.vec, sp.pl.mode, (int)sp.buf, sp.np, (int)sp.gr);
     SNN_CHECK_LAUNCH("snn_affine_neuron_bwd");
     return 0;
 }
@@ -1804,6 +1843,9 @@ extern "C" int snn_lif_bwd_ckpt(const float* g_out, int64_t ldg, const float* ck
     SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldg >= C && ldy >= C, "snn_lif_bwd_ckpt: bad shape");
     SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "snn_lif_bwd_ckpt: alpha/beta must come together");
     SNN_REQUIRE(!apply_scale || alpha, "snn_lif_bwd_ckpt: apply_scale needs alpha");
+    SNN_REQUIRE(p->surrogate == SNN_SURR_SUPER && p->reset_detached == 0,
+                "snn_lif_bwd_ckpt: the checkpointed pair has the default gradient rule only (surrogate %d, reset_detached %d): "
+                "use snn_affine_neuron_fwd / _bwd", p->surrogate, p->reset_detached);
     const BwdPlan pl = scan_bwd_plan(SNN_NEURON_LIF, T, M, C, ldg, ldy, sums != nullptr, p, 0).pl;   // (nothing left to refuse)
     SNN_REQUIRE(pl.vec == 1 || (multiples(4, {ldg, ldy}) && aligned(16, {g_out, ckpt, y, g_vT, g_iT, alpha, beta, gx, g_v0, g_i0})),
                 "snn_lif_bwd_ckpt: buffers must be 16-byte aligned when C%%4==0");

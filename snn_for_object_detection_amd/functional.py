@@ -26,12 +26,66 @@ _F32 = torch.float32
 DEFAULT_DT = 0.001
 
 
-def neuron_params(dt: float = DEFAULT_DT) -> NeuronParams:
+# LIF surrogate gradients (SNN_SURR_* of include/snn_hip.h, where they are defined): name -> code
+SURROGATES = {"super": _hip.SURR_SUPER, "triangle": _hip.SURR_TRIANGLE, "sigmoid": _hip.SURR_SIGMOID,
+              "atan": _hip.SURR_ATAN}
+
+
+def _surrogate_code(surrogate: str) -> int:
+    if surrogate not in SURROGATES:
+        raise ValueError(f"unknown surrogate {surrogate!r}: one of {sorted(SURROGATES)}")
+    return SURROGATES[surrogate]
+
+
+def _check_lif_constants(alpha: float, v_th: float, v_reset: float) -> None:
+    if not alpha > 0:
+        raise ValueError(f"the surrogate slope alpha must be positive, got {alpha}")
+    if not v_reset < v_th:
+        raise ValueError(f"v_reset ({v_reset}) must lie below v_th ({v_th})")
+
+
+def neuron_params(dt: float = DEFAULT_DT, *, surrogate: str = "super", alpha: float = 100.0, detach_reset: bool = False,
+                  v_th: float = 1.0, v_reset: float = 0.0, v_leak: float = 0.0) -> NeuronParams:
+    """The constants of one neuron layer.  The keywords are the LIF layer's own: its threshold / reset / leak potentials
+    and its BACKWARD rule - the surrogate ``dz/du`` (``"super"``, ``"triangle"``, ``"sigmoid"``, ``"atan"``, all with
+    value 1 at the threshold and slope parameter ``alpha``) and whether the spike inside the reset term is a constant of
+    the backward pass (``detach_reset``).  The defaults are the norse defaults the reference runs with."""
+    code = _surrogate_code(surrogate)
+    _check_lif_constants(alpha, v_th, v_reset)
     tau_syn_inv = torch.as_tensor(1.0 / 5e-3)
     tau_mem_inv = torch.as_tensor(1.0 / 1e-2)
     # + SLI saturation potential (sli.py:38-39) and the synapse constants (synapse.py:26-36,77)
-    return NeuronParams((dt * tau_mem_inv).item(), (-dt * tau_syn_inv).item(), 0.0, 1.0, 0.0, 100.0,
-                        1.0, torch.as_tensor(1.0 / 1e-3).item(), torch.as_tensor(1.0 / 5e-3).item(), dt, 0.0)
+    return NeuronParams((dt * tau_mem_inv).item(), (-dt * tau_syn_inv).item(), float(v_leak), float(v_th), float(v_reset),
+                        float(alpha), 1.0, torch.as_tensor(1.0 / 1e-3).item(), torch.as_tensor(1.0 / 5e-3).item(), dt, 0.0,
+                        code, int(bool(detach_reset)))
+
+
+def default_gradient_rule(params: NeuronParams) -> bool:
+    """SuperSpike with the reset differentiated through the spike: the rule every scan kernel has."""
+    return params.surrogate == _hip.SURR_SUPER and not params.reset_detached
+
+
+def set_lif_gradient(model, surrogate: Optional[str] = None, alpha: Optional[float] = None,
+                     detach_reset: Optional[bool] = None) -> int:
+    """Rewrite the backward rule of every ``LIFCell`` of ``model`` (``StateStorage``-wrapped ones included); ``None``
+    leaves a field as it is.  Returns the number of cells changed.  The rule lives in each cell's ``params`` - no
+    parameter, buffer or ``state_dict`` key is involved, and the forward pass does not change."""
+    from .layer_gen import LIFCell
+    code = None if surrogate is None else _surrogate_code(surrogate)
+    n = 0
+    for m in model.modules():
+        if not isinstance(m, LIFCell):
+            continue
+        p = m.params
+        _check_lif_constants(p.alpha if alpha is None else alpha, p.v_th, p.v_reset)
+        if code is not None:
+            p.surrogate = code
+        if alpha is not None:
+            p.alpha = float(alpha)
+        if detach_reset is not None:
+            p.reset_detached = int(bool(detach_reset))
+        n += 1
+    return n
 
 
 # ------------------------------------------------------------------------------------------- precision
@@ -1285,6 +1339,14 @@ class _AffineNeuron(Function):
         sb = y.dtype == _BF16   # bf16 storage: y, out, the saved per-step state and the gradients; (v, i) and all sums fp32
         if sb and (neuron not in (_hip.NEURON_NONE, _hip.NEURON_LIF, _hip.NEURON_LI, _hip.NEURON_LI_TANH) or y.shape[-3] % 4):
             raise RuntimeError("bf16 storage: Norm + none / LIF / LI / LI+Tanh with a multiple of 4 channels only")
+        if not default_gradient_rule(params):
+            name = next((k for k, v in SURROGATES.items() if v == params.surrogate), params.surrogate)
+            rule = f"surrogate={name!r}, detach_reset={bool(params.reset_detached)}"
+            if neuron != _hip.NEURON_LIF:
+                raise RuntimeError(f"a non-default gradient rule ({rule}) belongs to LIF layers")
+            if sb:
+                raise RuntimeError(f"bf16 storage has the default LIF gradient rule only, not ({rule}): keep this layer's "
+                                   "tensors fp32 or its rule at surrogate='super', detach_reset=False")
         sb_flag = _hip.SCAN_BF16_STORAGE if sb else 0
         ctx.set_materialize_grads(False)  # unused final-state outputs must arrive as None, not as zero tensors
         y = _raw_to_cl(y)
@@ -1310,7 +1372,8 @@ class _AffineNeuron(Function):
         no_out = (spikes_out is not None and USE_SPIKES_FROM_VDEC and neuron == _hip.NEURON_LIF and need_grad and has_bn
                   and addend is None and dest is None and not last_only and not sb and C % 4 == 0 and ldy % 4 == 0
                   and params.v_th >= 0.0
-                  and not (LIF_CHECKPOINT_BYTES is not None and T * M * C * 4 >= LIF_CHECKPOINT_BYTES))
+                  and not (LIF_CHECKPOINT_BYTES is not None and T * M * C * 4 >= LIF_CHECKPOINT_BYTES
+                           and default_gradient_rule(params)))
         if last_only:
             # only the last timestep's output is kept (snn_affine_neuron_fwd SNN_SCAN_LAST_STEP_ONLY): out is [B,C,H,W]
             if (neuron not in (_hip.NEURON_LIF, _hip.NEURON_LI, _hip.NEURON_LI_TANH) or addend is not None
@@ -1328,8 +1391,9 @@ class _AffineNeuron(Function):
         ckpt = False
         if neuron in _SAVES_STEP and need_grad:
             # (the checkpointed kernels write / read all T outputs: not for the last-step-only read-out)
+            # (... and have the default gradient rule only: a layer with another one takes the plain scan)
             ckpt = (neuron == _hip.NEURON_LIF and LIF_CHECKPOINT_BYTES is not None and not last_only and not sb
-                    and T * M * C * 4 >= LIF_CHECKPOINT_BYTES)
+                    and T * M * C * 4 >= LIF_CHECKPOINT_BYTES and default_gradient_rule(params))
             if ckpt:
                 k = _hip.query("snn_lif_ckpt_interval")
                 vdec = torch.empty(((T + k - 1) // k, 2, B, H, W, C), device=dev, dtype=_F32)
@@ -1370,7 +1434,9 @@ class _AffineNeuron(Function):
         ctx.sb = sb
         ctx.defer_apply = defer_apply
         ctx.last_only = last_only
-        ctx.cfg = (neuron, has_bn, use_running, params, (T, B, C, H, W))
+        # (a copy: the cell's struct is mutable - set_lif_gradient between this forward and its backward must not change
+        # the rule of a graph already recorded, nor ask the checkpointed pair for a rule it refuses)
+        ctx.cfg = (neuron, has_bn, use_running, NeuronParams.from_buffer_copy(params), (T, B, C, H, W))
         ctx.slots = (g_slot, b_slot)
         ctx.sync_group = sync_group if (has_bn and not use_running) else None
         ctx.has_v0 = v0 is not None
