@@ -448,6 +448,48 @@ int snn_affine_neuron_bwd(int neuron, const float* g_out, int64_t ldg, const flo
                           float* gx, float* g_v0, float* g_i0, double* sums,
                           int T, int64_t M, int C, const snn_neuron_params* p, int flags, void* stream);
 
+/* LIF with PER-CHANNEL time constants, and their gradients (additions of ABI 20; `neuron` must be SNN_NEURON_LIF - the
+ * argument is there so that anything else is refused by name).  The forward step is the one above with the struct's
+ * scalars c_mem, c_syn replaced by c_mem[c], c_syn[c] (fp32 [C]; the struct's own two are not read):
+ *   i' = i + x; vd = v + c_mem[c]*((v_leak - v) + i'); i = i' + c_syn[c]*i'; z = (vd - v_th > 0); v = (1-z)*vd + z*v_reset
+ * and the reverse scan is snn_affine_neuron_bwd's with the same replacement, every gradient rule of the struct included.
+ * When tau_partial != NULL it also forms, per pixel block and channel, the partial sums of
+ *   dL/dc_mem[c] = sum_{t,m} g_vd[t] (vd[t] - v[t-1]) / c_mem[c]
+ *   dL/dc_syn[c] = sum_{t,m} g_i[t] i'[t],   i'[t] = (vd[t] - v[t-1]) / c_mem[c] - (v_leak - v[t-1])
+ * (g_i[t]: the gradient arriving at the current after step t; v[t-1] = z[t-1] ? v_reset : vd[t-1], and for t = 0 the
+ * forward's initial potential v0, NULL = v_leak) from the saved potentials alone: nothing else is saved or re-read.
+ * tau_partial: snn_lif_tau_bwd_partial_size(T, M, C, sums != NULL) doubles.  Fixed summation order (bitwise reproducible)
+ * except on the LDS-atomics plan of the shape (mode 2 of snn_affine_neuron_bwd_plan), which adds with LDS float atomics.
+ * The scan reads y for the BatchNorm statistic (`sums`): SNN_SCAN_SUMS_FROM_STATE / _STATE_LOOKBACK are refused, and so are
+ * SNN_SCAN_BF16_STORAGE, a neuron other than LIF, and SNN_SCAN_LAST_STEP_ONLY together with tau_partial.  A sequence is
+ * scanned in one launch (no segment look-back for the two sums).
+ *
+ * snn_lif_tau_param: the parametrisation c_mem = sigmoid(w_mem), 1 + c_syn = sigmoid(w_syn) (so c_mem in (0, 1), c_syn in
+ * (-1, 0)) from n = 1 (per layer) or n = C (per channel) raw values, into c_mem[C], c_syn[C].
+ * snn_lif_tau_finalize: the partials in block order, times c_mem (1 - c_mem) and s (1 - s), s = 1 + c_syn; per_layer: summed
+ * over the channels in order into ONE value each; stored, or added when accumulate != 0 (as dgamma / dbias).  T, M, C and
+ * with_sums are those of the scan that wrote the partials.
+ * snn_lif_tau_bwd_plan (host-only): out[12] = the ten values of snn_affine_neuron_bwd_plan for the instance snn_lif_tau_bwd
+ * launches, then 1 when the two sums are combined in fixed order (0: LDS float atomics) and the LDS bytes of the launch;
+ * returns 1 with the launch's message for what snn_lif_tau_bwd refuses by shape, neuron or flags alone. */
+int snn_lif_tau_param(const float* w_mem, const float* w_syn, int n, int C, float* c_mem, float* c_syn, void* stream);
+int snn_lif_tau_fwd(int neuron, const float* y, int64_t ldy, const float* alpha, const float* beta,
+                    const float* v0, const float* i0, float* out, int64_t ldo,
+                    const float* addend, int64_t ld_addend, float* vT, float* iT, float* vdec,
+                    int T, int64_t M, int C, const snn_neuron_params* p,
+                    const float* c_mem, const float* c_syn, int flags, void* stream);
+size_t snn_lif_tau_bwd_partial_size(int T, int64_t M, int C, int with_sums);
+int snn_lif_tau_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, int with_sums, int with_tau_sums,
+                         const snn_neuron_params* p, int flags, int64_t* out);
+int snn_lif_tau_bwd(int neuron, const float* g_out, int64_t ldg, const float* state, const float* y, int64_t ldy,
+                    const float* g_vT, const float* g_iT, const float* alpha, const float* beta, int apply_scale,
+                    float* gx, float* g_v0, float* g_i0, double* sums,
+                    int T, int64_t M, int C, const snn_neuron_params* p,
+                    const float* c_mem, const float* c_syn, const float* v0, double* tau_partial, int flags, void* stream);
+int snn_lif_tau_finalize(const double* tau_partial, int T, int64_t M, int C, int with_sums,
+                         const float* c_mem, const float* c_syn, int per_layer,
+                         float* d_wmem, float* d_wsyn, int accumulate, void* stream);
+
 /* Memory-saving LIF pair (same results, bit for bit, as the two calls above with neuron = SNN_NEURON_LIF).  Instead
  * of vd[t] for every step, the forward stores the state (v, i) BEFORE every K-th step, K = snn_lif_ckpt_interval():
  *   ckpt[ceil(T/K)][2][M][C]   (2*ceil(T/K)/T of the per-step buffer: half at K = 4)

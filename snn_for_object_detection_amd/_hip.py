@@ -99,6 +99,14 @@ SIGNATURES = {
     "snn_bn_bwd_reduce_from_state": (c_int, [_P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _L, _P, _P]),
     "snn_affine_neuron_bwd_sums_from_state": (c_int, [_I, _I, _L, _I, _L, POINTER(NeuronParams), _I]),
     "snn_affine_neuron_bwd_plan": (c_int, [_I, _I, _L, _I, _L, _L, _I, POINTER(NeuronParams), _I, _P]),
+    "snn_lif_tau_param": (c_int, [_P, _P, _I, _I, _P, _P, _P]),
+    "snn_lif_tau_fwd": (c_int, [_I, _P, _L, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _I, _L, _I,
+                                POINTER(NeuronParams), _P, _P, _I, _P]),
+    "snn_lif_tau_bwd_partial_size": (c_size_t, [_I, _L, _I, _I]),
+    "snn_lif_tau_bwd_plan": (c_int, [_I, _I, _L, _I, _L, _L, _I, _I, POINTER(NeuronParams), _I, _P]),
+    "snn_lif_tau_bwd": (c_int, [_I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _L, _I,
+                                POINTER(NeuronParams), _P, _P, _P, _P, _I, _P]),
+    "snn_lif_tau_finalize": (c_int, [_P, _I, _L, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "snn_bn_bwd_apply": (c_int, [_P, _P, _L, _P, _P, _P, _P, _L, _I, _L, _I, _I, _P]),
     "snn_bn_bwd_apply_bf16": (c_int, [_P, _P, _L, _P, _P, _P, _P, _L, _I, _L, _I, _I, _P]),
     "snn_bn_stats_bf16": (c_int, [_P, _L, _I, _L, _I, _P, _P]),

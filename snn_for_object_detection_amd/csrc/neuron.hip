@@ -354,16 +354,21 @@ constexpr int kCkpt = 4;
 #define SNN_SCAN_PREFETCH 2   // steps of operands in flight ahead of the recurrence (forward scan)
 #endif
 // SB (SNN_SCAN_BF16_STORAGE): y, out, addend and vdec are bf16 tensors (pointers passed as float*, strides in elements)
-template <int NEURON, int VEC, int SAVE, bool SB = false>
+// PC (LIF, fp32 tensors; snn_lif_tau_fwd): the two time constants are per-channel arrays cmem_pc[C] / csyn_pc[C] instead of
+// the struct's scalars; a lane loads its VEC channels' pair once, before the time loop.  The other instances never read the
+// two pointers.
+template <int NEURON, int VEC, int SAVE, bool SB = false, bool PC = false>
 __global__ __launch_bounds__(kThreads) void k_affine_neuron_fwd(
     const float* __restrict__ y, int64_t ldy, const float* __restrict__ alpha, const float* __restrict__ beta,
     const float* __restrict__ v0, const float* __restrict__ i0, float* __restrict__ out, int64_t ldo,
     const float* __restrict__ addend, int64_t ld_add, float* __restrict__ vT, float* __restrict__ iT,
-    float* __restrict__ vdec, int T, int64_t M, int C, snn_neuron_params p, int last_only) {
+    float* __restrict__ vdec, int T, int64_t M, int C, snn_neuron_params p, int last_only,
+    const float* __restrict__ cmem_pc = nullptr, const float* __restrict__ csyn_pc = nullptr) {
     // last_only (SNN_SCAN_LAST_STEP_ONLY): `out` is [M][ldo], only the last timestep's output is kept (the detection
     // head: soda.py:141-144 returns the predictions of the last step) - T-1 of T output stores never happen
     typedef typename Vec<VEC>::type V;
     static_assert(!SB || SAVE != 2, "the checkpointed scan keeps fp32 checkpoints: not combined with bf16 storage");
+    static_assert(!PC || (NEURON == SNN_NEURON_LIF && !SB && SAVE != 2), "per-channel time constants: LIF on fp32 tensors");
     const int cv = C / VEC;
     const int64_t total = M * cv;
     for (int64_t col = (int64_t)blockIdx.x * kThreads + threadIdx.x; col < total;
@@ -371,6 +376,11 @@ __global__ __launch_bounds__(kThreads) void k_affine_neuron_fwd(
         const int64_t m = col / cv;
         const int c = (int)(col % cv) * VEC;
         V v, i;
+        [[maybe_unused]] V cmv, csv;
+        if constexpr (PC) {
+            cmv = Vec<VEC>::load(cmem_pc + c);
+            csv = Vec<VEC>::load(csyn_pc + c);
+        }
         if (NEURON != SNN_NEURON_NONE) {
             if (v0) v = Vec<VEC>::load(v0 + m * C + c);
             else {
@@ -465,9 +475,14 @@ __global__ __launch_bounds__(kThreads) void k_affine_neuron_fwd(
                         lane<VEC>(vd, j) = vj;
                     }
                     float i_new = ij + xin;
-                    float dv = p.c_mem * ((p.v_leak - vj) + i_new);
+                    float c_mem = p.c_mem, c_syn = p.c_syn;
+                    if constexpr (PC) {
+                        c_mem = lane<VEC>(cmv, j);
+                        c_syn = lane<VEC>(csv, j);
+                    }
+                    float dv = c_mem * ((p.v_leak - vj) + i_new);
                     float v_dec = vj + dv;
-                    float di = p.c_syn * i_new;
+                    float di = c_syn * i_new;
                     lane<VEC>(i, j) = i_new + di;
                     if (NEURON == SNN_NEURON_LIF) {
                         float u = v_dec - p.v_th;
@@ -649,13 +664,30 @@ static BwdPlan bwd_plan(int T, int64_t M, int C, bool with_sums) {
 // are never read; the second value of a sums pair is then sum(gx * x) (snn_bn_bwd_finalize_from_state converts).
 // GR (LIF, fp32 tensors): the general gradient rule - p.surrogate and p.reset_detached, the same for every lane, are read in
 // the step; false compiles the SuperSpike / reset-not-detached arm alone, the code the default rule has always run.
-template <int NEURON, int VEC, int MODE, bool BUF, int NP, bool SB = false, bool YF = false, bool GR = false>
-__global__ __launch_bounds__(kThreads, YF ? 2 : 1) void k_affine_neuron_bwd(
+// PC (LIF, fp32 tensors, GR arm, y-reading; snn_lif_tau_bwd): the time constants are the per-channel arrays cmem_pc[C] /
+// csyn_pc[C], loaded once per lane, and (tau_part != NULL) the scan forms their gradients
+//   dL/dc_mem[c] = sum_{t,m} g_vd[t] (vd[t] - v[t-1]) / c_mem[c],   dL/dc_syn[c] = sum_{t,m} g_i[t] i'[t]
+// (g_i[t]: the current's gradient as it ARRIVES at step t; i'[t] = (vd[t] - v[t-1]) / c_mem - (v_leak - v[t-1])) from the
+// potentials it reads anyway.  v[t-1] needs vd[t-1], which the walk meets one step LATER: step t keeps (vd[t], g_vd[t],
+// g_i[t]) and step t-1 adds step t's two terms - no operand of the prefetched set is touched early; step 0's terms follow
+// behind the loop from the initial potential (v0_pc, or v_leak).  A thread's two sums stay in registers over the time loop
+// and over its pixel rows; at the end of the block: the lanes that share channels (wave_sum_channels), the waves in order
+// through LDS, one double pair per (pixel block, channel) into tau_part[gx][C][2].  tau_ordered = 0 (a channel-group count
+// that is not a power of two, the LDS-atomics plan): LDS float atomics on one slab instead.  The other instances never read
+// the five trailing arguments.
+// TS (PC only): the two sums are formed (tau_part is given); without it nothing of them is compiled - a layer with fixed
+// per-channel constants pays no register for them.  The twelve kept registers per pixel do not fit beside four pixels'
+// operand sets in the 256 registers of two waves per SIMD (350 measured, one block per CU where the plan counts on two):
+// the buffer-addressed TS instances take three pixels per thread, as the from-state scan does, and two waves per SIMD.
+template <int NEURON, int VEC, int MODE, bool BUF, int NP, bool SB = false, bool YF = false, bool GR = false, bool PC = false,
+          bool TS = false>
+__global__ __launch_bounds__(kThreads, (YF || (TS && NP <= 3)) ? 2 : 1) void k_affine_neuron_bwd(
     const float* __restrict__ g_out, int64_t ldg, const float* __restrict__ state, const float* __restrict__ y,
     int64_t ldy, const float* __restrict__ g_vT, const float* __restrict__ g_iT, const float* __restrict__ alpha,
     const float* __restrict__ beta, int apply_scale, float* __restrict__ gx, float* __restrict__ g_v0,
     float* __restrict__ g_i0, double* __restrict__ sums, int T, int64_t M, int C, int cvb, snn_neuron_params p,
-    int last_only_or_lookback) {
+    int last_only_or_lookback, const float* __restrict__ cmem_pc = nullptr, const float* __restrict__ csyn_pc = nullptr,
+    const float* __restrict__ v0_pc = nullptr, double* __restrict__ tau_part = nullptr, int tau_ordered = 0) {
     // last_only (SNN_SCAN_LAST_STEP_ONLY; LIF / LI / LI+Tanh): g_out (and LI+Tanh's saved output) are [M][..] tensors of
     // the LAST timestep; the output gradient of every earlier step is zero and nothing is read for it.
     // YF instances (never last_only) take SNN_SCAN_STATE_LOOKBACK in the same argument slot.
@@ -682,9 +714,26 @@ __global__ __launch_bounds__(kThreads, YF ? 2 : 1) void k_affine_neuron_bwd(
     }
     static_assert(!YF || (NEURON == SNN_NEURON_LIF && MODE == 1 && BUF && VEC == 4 && !SB), "sums from the saved state: LIF, ordered sums");
     static_assert(!GR || (NEURON == SNN_NEURON_LIF && !SB), "selectable gradient rule: LIF on fp32 tensors");
+    static_assert(!PC || (GR && !YF), "per-channel time constants: the general-rule arm of the y-reading LIF scan");
+    static_assert(!TS || PC, "the sums of the time constants' gradients belong to the per-channel instances");
     const float one_m_cmem = 1.0f - p.c_mem;
     const float one_p_csyn = 1.0f + p.c_syn;
     [[maybe_unused]] const float inv_cmem = 1.0f / p.c_mem;
+    // PC: this lane's constants (c = 0 for a lane without channels: finite values, its sums stay 0) and its two sums
+    [[maybe_unused]] float pc_cm[VEC], pc_omc[VEC], pc_opc[VEC], pc_icm[VEC], tau_m[VEC], tau_s[VEC];
+    if constexpr (PC) {
+        V cmv = Vec<VEC>::load(cmem_pc + c), csv = Vec<VEC>::load(csyn_pc + c);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            pc_cm[j] = lane<VEC>(cmv, j);
+            pc_omc[j] = 1.0f - pc_cm[j];
+            pc_opc[j] = 1.0f + lane<VEC>(csv, j);
+            if constexpr (TS) {
+                pc_icm[j] = 1.0f / pc_cm[j];
+                tau_m[j] = tau_s[j] = 0.0f;
+            }
+        }
+    }
     const int64_t rows = (M + P - 1) / P;
     const int64_t rpb = (rows + gridDim.x - 1) / gridDim.x;  // pixel rows per block (see bwd_plan)
     const int64_t row_lo = (int64_t)blockIdx.x * rpb;
@@ -695,12 +744,18 @@ __global__ __launch_bounds__(kThreads, YF ? 2 : 1) void k_affine_neuron_bwd(
         V gv[NP], gi[NP];
         // YF: what a step keeps for the statistic of two steps later - vd[t+1], i'[t+2], gx[t+1], gx[t+2]
         [[maybe_unused]] V yf_vd1[YF ? NP : 1], yf_in2[YF ? NP : 1], yf_g1[YF ? NP : 1], yf_g2[YF ? NP : 1];
+        // PC: what a step keeps for the two sums' terms of its own step, formed one step later - vd[t+1], g_vd[t+1], g_i[t+1]
+        [[maybe_unused]] V pc_vd1[TS ? NP : 1], pc_gvd1[TS ? NP : 1], pc_gi1[TS ? NP : 1];
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
             mq[q] = (rb + q) * P + ps;
             ok[q] = lane_ok && rb + q < row_hi && mq[q] < M;
 #pragma unroll
             for (int j = 0; j < VEC; ++j) lane<VEC>(gv[q], j) = lane<VEC>(gi[q], j) = 0.0f;
+            if constexpr (TS) {
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) lane<VEC>(pc_vd1[q], j) = lane<VEC>(pc_gvd1[q], j) = lane<VEC>(pc_gi1[q], j) = 0.0f;
+            }
             if constexpr (YF) {
 #pragma unroll
                 for (int j = 0; j < VEC; ++j)
@@ -864,8 +919,25 @@ __global__ __launch_bounds__(kThreads, YF ? 2 : 1) void k_affine_neuron_bwd(
                             gz = p.reset_detached ? goj : goj + gvj * (p.v_reset - vd);
                         }
                         float g_vd = gvj * (1.0f - z) + gz * sg;
-                        float g_in = p.c_mem * g_vd + lane<VEC>(gi[q], j) * one_p_csyn;
-                        lane<VEC>(gv[q], j) = g_vd * one_m_cmem;
+                        float g_in;
+                        if constexpr (PC) {
+                            const float gi_old = lane<VEC>(gi[q], j);
+                            g_in = pc_cm[j] * g_vd + gi_old * pc_opc[j];
+                            lane<VEC>(gv[q], j) = g_vd * pc_omc[j];
+                            if constexpr (TS) {
+                                // the two terms of step t+1, now that v[t] is known (zero gradients until step t+1 exists)
+                                const float vprev = (u > 0.0f) ? p.v_reset : vd;                       // v[t]
+                                const float dlt = (lane<VEC>(pc_vd1[q], j) - vprev) * pc_icm[j];      // (vd[t+1] - v[t]) / c_mem
+                                tau_m[j] += lane<VEC>(pc_gvd1[q], j) * dlt;
+                                tau_s[j] += lane<VEC>(pc_gi1[q], j) * (dlt - (p.v_leak - vprev));      // g_i[t+1] i'[t+1]
+                                lane<VEC>(pc_vd1[q], j) = vd;
+                                lane<VEC>(pc_gvd1[q], j) = g_vd;
+                                lane<VEC>(pc_gi1[q], j) = gi_old;
+                            }
+                        } else {
+                            g_in = p.c_mem * g_vd + lane<VEC>(gi[q], j) * one_p_csyn;
+                            lane<VEC>(gv[q], j) = g_vd * one_m_cmem;
+                        }
                         lane<VEC>(gi[q], j) = g_in;
                         lane<VEC>(g, j) = g_in;
                         if constexpr (YF) {   // x[t+2] from vd[t+2], vd[t+1], vd[t] (zero gradient slots until t+2 exists)
@@ -1053,6 +1125,23 @@ __global__ __launch_bounds__(kThreads, YF ? 2 : 1) void k_affine_neuron_bwd(
                 }
             }
         }
+        if constexpr (TS) {
+            // step 0's two terms: v[-1] is the initial potential (a pixel slot without a pixel kept zeros: no terms)
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                V v0v;
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) lane<VEC>(v0v, j) = p.v_leak;
+                if (v0_pc && ok[q]) v0v = Vec<VEC>::load(v0_pc + mq[q] * C + c);
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    const float vprev = lane<VEC>(v0v, j);
+                    const float dlt = (lane<VEC>(pc_vd1[q], j) - vprev) * pc_icm[j];
+                    tau_m[j] += lane<VEC>(pc_gvd1[q], j) * dlt;
+                    tau_s[j] += lane<VEC>(pc_gi1[q], j) * (dlt - (p.v_leak - vprev));
+                }
+            }
+        }
         if (NEURON != SNN_NEURON_NONE) {
 #pragma unroll
             for (int q = 0; q < NP; ++q) {
@@ -1087,6 +1176,111 @@ __global__ __launch_bounds__(kThreads, YF ? 2 : 1) void k_affine_neuron_bwd(
             }
         }
     }
+    if constexpr (TS) {
+        {
+            // the block's two sums per channel, through the LDS the BatchNorm sums no longer need (the host sizes it for
+            // both): red[slab][cb][2], one slab per wave (ordered) or one for all (atomics)
+            const int nslab = tau_ordered ? kWaves : 1;
+            __syncthreads();
+            for (int k = tid; k < nslab * cb * 2; k += kThreads) red[k] = 0.0f;
+            __syncthreads();
+            if (tau_ordered) {
+                wave_sum_channels<VEC>(tau_m, tau_s, cvb);
+                if (wave_sum_owner(tid & 63, cvb) && lane_ok) {
+                    float* r = red + ((int64_t)wave * cb + cgl * VEC) * 2;
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) {
+                        r[j * 2 + 0] = tau_m[j];
+                        r[j * 2 + 1] = tau_s[j];
+                    }
+                }
+            } else if (lane_ok) {
+                float* r = red + (int64_t)(cgl * VEC) * 2;
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    atomicAdd(r + j * 2 + 0, tau_m[j]);
+                    atomicAdd(r + j * 2 + 1, tau_s[j]);
+                }
+            }
+            __syncthreads();
+            const int c_lo = blockIdx.y * cb;
+            for (int k = tid; k < cb; k += kThreads) {
+                if (c_lo + k < C) {
+                    double a = 0.0, b = 0.0;
+                    for (int w = 0; w < nslab; ++w) {
+                        a += (double)red[((int64_t)w * cb + k) * 2 + 0];
+                        b += (double)red[((int64_t)w * cb + k) * 2 + 1];
+                    }
+                    double* dst = tau_part + ((int64_t)blockIdx.x * C + c_lo + k) * 2;
+                    dst[0] = a;
+                    dst[1] = b;
+                }
+            }
+        }
+    }
+}
+
+// Second phase of the time constants' gradients (snn_lif_tau_finalize): the per-block partials of k_affine_neuron_bwd<PC>
+// -> dL/dw_mem, dL/dw_syn under c_mem = sigmoid(w_mem), 1 + c_syn = sigmoid(w_syn).  One wave per channel: lane k adds the
+// pixel blocks k, k + 64, ... in order, a fixed xor tree combines the lanes, then the chain rule c (1 - c).  per_layer (one
+// block): a wave adds its channels w, w + waves, ... in order, thread 0 the waves in order - one pair for the layer.
+__global__ __launch_bounds__(1024) void k_lif_tau_finalize(const double* __restrict__ part, int gx_blocks, int C,
+                                                           const float* __restrict__ c_mem, const float* __restrict__ c_syn,
+                                                           int per_layer, float* __restrict__ d_wmem,
+                                                           float* __restrict__ d_wsyn, int accumulate) {
+    __shared__ double sm[16][2];
+    const int ln = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    double tm = 0.0, ts = 0.0;
+    const int c_first = per_layer ? w : blockIdx.x * nw + w;
+    const int c_step = per_layer ? nw : C;   // (per channel: one channel per wave)
+    for (int c = c_first; c < C; c += c_step) {
+        double a = 0.0, b = 0.0;
+        for (int bk = ln; bk < gx_blocks; bk += 64) {
+            const double2 v = *reinterpret_cast<const double2*>(part + ((int64_t)bk * C + c) * 2);
+            a += v.x;
+            b += v.y;
+        }
+        for (int stride = 32; stride >= 1; stride >>= 1) {
+            a += __shfl_xor(a, stride, 64);
+            b += __shfl_xor(b, stride, 64);
+        }
+        const double cm = (double)c_mem[c], s = (double)(1.0f + c_syn[c]);
+        a *= cm * (1.0 - cm);
+        b *= s * (1.0 - s);
+        if (per_layer) {
+            tm += a;
+            ts += b;
+        } else if (ln == 0) {
+            if (d_wmem) d_wmem[c] = accumulate ? d_wmem[c] + (float)a : (float)a;
+            if (d_wsyn) d_wsyn[c] = accumulate ? d_wsyn[c] + (float)b : (float)b;
+        }
+    }
+    if (!per_layer) return;
+    if (ln == 0) {
+        sm[w][0] = tm;
+        sm[w][1] = ts;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a = 0.0, b = 0.0;
+        for (int k = 0; k < nw; ++k) {
+            a += sm[k][0];
+            b += sm[k][1];
+        }
+        if (d_wmem) d_wmem[0] = accumulate ? d_wmem[0] + (float)a : (float)a;
+        if (d_wsyn) d_wsyn[0] = accumulate ? d_wsyn[0] + (float)b : (float)b;
+    }
+}
+
+// The parametrisation (snn_lif_tau_param): c_mem[c] = sigmoid(w_mem), c_syn[c] = sigmoid(w_syn) - 1, from one value per
+// layer (n = 1) or per channel (n = C).
+__global__ void k_lif_tau_param(const float* __restrict__ w_mem, const float* __restrict__ w_syn, int n, int C,
+                                float* __restrict__ c_mem, float* __restrict__ c_syn) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const int k = n == 1 ? 0 : c;
+    c_mem[c] = 1.0f / (1.0f + expf(-w_mem[k]));
+    c_syn[c] = 1.0f / (1.0f + expf(-w_syn[k])) - 1.0f;
 }
 
 // LIF backward scan from checkpoints (forward SAVE mode 2).  Same grid, block roles, reduction order and outputs as
@@ -1523,7 +1717,8 @@ static FwdPlan fwd_plan(int neuron, int64_t M, int C, int lanes, bool saves, boo
     fp.blocks = (unsigned)snn_ceil_div(total, kThreads * per_thread);
     return fp;
 }
-constexpr bool fwd_instance(int neuron, int vec, int save, bool sb) {
+constexpr bool fwd_instance(int neuron, int vec, int save, bool sb, bool pc = false) {
+    if (pc && (neuron != SNN_NEURON_LIF || sb || save == 2)) return false;   // per-channel constants: fp32 LIF, plain scan
     return (sb ? (vec != 1 && bf16_neuron(neuron) && save != 2) : vec != 8) &&
            (save == 0 || neuron == SNN_NEURON_LIF || (save == 1 && rebuilds_x(neuron)));
 }
@@ -1583,7 +1778,46 @@ static ScanBwdPlan scan_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ld
     }
     return sp;
 }
-constexpr bool bwd_instance(int neuron, int vec, int mode, bool buf, int np, bool sb, bool yf, bool gr) {
+const char* const kTauCovers =
+    "per-channel time constants are for SNN_NEURON_LIF on fp32 tensors (no SNN_SCAN_BF16_STORAGE), with the y-reading scan "
+    "(no SNN_SCAN_SUMS_FROM_STATE / SNN_SCAN_STATE_LOOKBACK)";
+const char* const kTauNoLastStep =
+    "SNN_SCAN_LAST_STEP_ONLY is not built together with the sums of the time constants' gradients";
+
+// ---- the scans with per-channel time constants (snn_lif_tau_*): the plan of the plain scan of the shape, on the general
+// gradient-rule arm, and where the block's two extra sums go
+struct TauBwdPlan {
+    ScanBwdPlan sp;
+    bool ordered;        // lanes and waves in fixed order (false: LDS float atomics, the channel-group count is no power of two)
+    size_t lds_bytes;    // the BatchNorm slabs, or the two sums' slabs where those are larger
+};
+static TauBwdPlan tau_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, bool with_sums, bool with_tau,
+                               const snn_neuron_params* p, int flags) {
+    TauBwdPlan tp = {};
+    if (neuron != SNN_NEURON_LIF || (flags & (SNN_SCAN_BF16_STORAGE | SNN_SCAN_SUMS_FROM_STATE | SNN_SCAN_STATE_LOOKBACK))) {
+        tp.sp.refusal = kTauCovers;
+        return tp;
+    }
+    if (with_tau && (flags & SNN_SCAN_LAST_STEP_ONLY)) {
+        tp.sp.refusal = kTauNoLastStep;
+        return tp;
+    }
+    tp.sp = scan_bwd_plan(neuron, T, M, C, ldg, ldy, with_sums, p, flags);
+    if (tp.sp.refusal) return tp;
+    tp.sp.gr = true;   // one family: the general arm serves the default rule too
+    // with the two sums: three pixels per thread where the plain scan takes four (see the kernel's note on TS)
+    if (with_tau && tp.sp.buf && tp.sp.np == kBwdNP) tp.sp.np = 3;
+    const BwdPlan& pl = tp.sp.pl;
+    tp.ordered = pl.mode == 1 || (pl.mode == 0 && (is_pow2(pl.cvb) || pl.cvb >= 64));
+    const size_t tau_bytes = with_tau ? (size_t)(tp.ordered ? kWaves : 1) * pl.cvb * pl.vec * 2 * sizeof(float) : 0;
+    tp.lds_bytes = std::max(pl.lds_bytes, tau_bytes);
+    return tp;
+}
+
+constexpr bool bwd_instance(int neuron, int vec, int mode, bool buf, int np, bool sb, bool yf, bool gr, bool pc = false,
+                            bool ts = false) {
+    if (pc && !(gr && !yf)) return false;                       // per-channel constants: the general arm, y-reading
+    if (ts) return pc && neuron == SNN_NEURON_LIF && !sb && (buf ? (vec == 4 && (np == 1 || np == 3)) : np == kBwdNP);
     if (gr && (neuron != SNN_NEURON_LIF || sb)) return false;   // one general instance per fp32 LIF instance, no others
     if (yf) return neuron == SNN_NEURON_LIF && vec == 4 && mode == 1 && buf && np <= 3 && !sb;
     return (np == 1 ? buf : np == kBwdNP) && (vec == 4 || !(buf || sb)) && (!sb || bf16_neuron(neuron));
@@ -1689,50 +1923,53 @@ extern "C" int snn_bn_stats_from_sums(const double* sums, int T, int64_t M_total
 static int neuron_fwd(int neuron, const float* y, int64_t ldy, const float* alpha, const float* beta, const float* v0,
                       const float* i0, float* out, int64_t ldo, const float* addend, int64_t ld_addend, float* vT,
                       float* iT, float* vdec, bool ckpt, int T, int64_t M, int C, const snn_neuron_params* p,
-                      int flags, void* stream) {
+                      int flags, void* stream, const float* cmem_pc = nullptr, const float* csyn_pc = nullptr) {
+    // cmem_pc / csyn_pc (snn_lif_tau_fwd, which has checked neuron and flags): per-channel time constants
+    const bool pc = cmem_pc != nullptr;
+    const char* const fn = pc ? "snn_lif_tau_fwd" : "snn_affine_neuron_fwd";   // the entry point the messages name
     SNN_REQUIRE((flags & ~(SNN_SCAN_LAST_STEP_ONLY | SNN_SCAN_BF16_STORAGE | SNN_SCAN_SPIKES_FROM_VDEC)) == 0,
-                "snn_affine_neuron_fwd: unknown flags 0x%x", flags);
+                "%s: unknown flags 0x%x", fn, flags);
     const int last_only = (flags & SNN_SCAN_LAST_STEP_ONLY) != 0;
     const bool sb = (flags & SNN_SCAN_BF16_STORAGE) != 0;   // y, out, addend, vdec are bf16 tensors
     const bool no_out = (flags & SNN_SCAN_SPIKES_FROM_VDEC) != 0;   // no output tensor: the consumer thresholds vdec
-    SNN_REQUIRE(y && p && (out || no_out), "snn_affine_neuron_fwd: null pointer");
+    SNN_REQUIRE(y && p && (out || no_out), "%s: null pointer", fn);
     if (no_out) {
         SNN_REQUIRE(neuron == SNN_NEURON_LIF && vdec && !ckpt && !addend && !last_only && !sb && alpha && !out &&
                         multiples(4, {C, ldy}) && aligned(16, {y, vdec}),
-                    "snn_affine_neuron_fwd: SNN_SCAN_SPIKES_FROM_VDEC is for Norm -> LIF with saved potentials, no shortcut, "
-                    "all T steps, fp32 tensors, 4-channel groups; out must be NULL");
+                    "%s: SNN_SCAN_SPIKES_FROM_VDEC is for Norm -> LIF with saved potentials, no shortcut, "
+                    "all T steps, fp32 tensors, 4-channel groups; out must be NULL", fn);
         ldo = C;   // (unused; keeps the checks below meaningful)
     }
     SNN_REQUIRE(!last_only || (last_step_neuron(neuron) && !addend),
-                "snn_affine_neuron_fwd: SNN_SCAN_LAST_STEP_ONLY is for LIF / LI / LI+Tanh without a shortcut");
+                "%s: SNN_SCAN_LAST_STEP_ONLY is for LIF / LI / LI+Tanh without a shortcut", fn);
     SNN_REQUIRE(!addend || (ld_addend >= C && neuron != SNN_NEURON_LI_TANH),
-                "snn_affine_neuron_fwd: addend needs ld_addend >= C and is not allowed with LI_TANH");
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C && ldo >= C, "snn_affine_neuron_fwd: bad shape");
-    SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "snn_affine_neuron_fwd: alpha/beta must come together");
-    SNN_REQUIRE(neuron >= SNN_NEURON_NONE && neuron <= SNN_NEURON_SYNAPSE, "snn_affine_neuron_fwd: bad neuron %d",
+                "%s: addend needs ld_addend >= C and is not allowed with LI_TANH", fn);
+    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C && ldo >= C, "%s: bad shape", fn);
+    SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "%s: alpha/beta must come together", fn);
+    SNN_REQUIRE(neuron >= SNN_NEURON_NONE && neuron <= SNN_NEURON_SYNAPSE, "%s: bad neuron %d", fn,
                 neuron);
     // n channels per access: the activation tensors (bf16: 2 bytes per element) and the fp32 per-pixel / per-channel ones
     auto lanes_ok = [&](int n, size_t act_bytes) {
         return multiples(n, {C, ldy, ldo, addend ? ld_addend : 0}) && aligned(act_bytes, {y, out, vdec, addend}) &&
-               aligned(16, {alpha, beta, v0, i0, vT, iT});
+               aligned(16, {alpha, beta, v0, i0, vT, iT, cmem_pc, csyn_pc});
     };
-    SNN_REQUIRE(!sb || (lanes_ok(4, 8) && !ckpt && bf16_neuron(neuron)), "snn_affine_neuron_fwd: %s, without checkpointing", kBf16Covers);
+    SNN_REQUIRE(!sb || (lanes_ok(4, 8) && !ckpt && bf16_neuron(neuron)), "%s: %s, without checkpointing", fn, kBf16Covers);
     const int lanes = sb ? (lanes_ok(8, 16) ? 8 : 4) : (lanes_ok(4, 16) ? 4 : 1);
     const FwdPlan fp = fwd_plan(neuron, M, C, lanes, vdec != nullptr, ckpt);
     const bool launched = dispatch(
-        [&](auto NEURON, auto VEC, auto SAVE, auto SB) {
-            if constexpr (fwd_instance(NEURON(), VEC(), SAVE(), SB())) {
-                hipLaunchKernelGGL((k_affine_neuron_fwd<NEURON(), VEC(), SAVE(), SB()>), dim3(fp.blocks), dim3(kThreads), 0,
+        [&](auto NEURON, auto VEC, auto SAVE, auto SB, auto PC) {
+            if constexpr (fwd_instance(NEURON(), VEC(), SAVE(), SB(), PC())) {
+                hipLaunchKernelGGL((k_affine_neuron_fwd<NEURON(), VEC(), SAVE(), SB(), PC()>), dim3(fp.blocks), dim3(kThreads), 0,
                                    (hipStream_t)stream, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT,
-                                   vdec, T, M, C, *p, last_only);
+                                   vdec, T, M, C, *p, last_only, cmem_pc, csyn_pc);
                 return true;
             } else {
                 return false;
             }
         },
-        AnyNeuron{neuron}, OneOf<1, 4, 8>{fp.vec}, OneOf<0, 1, 2>{fp.save}, Flag{sb});
-    SNN_REQUIRE(launched, "snn_affine_neuron_fwd: no kernel instance (neuron %d, vec %d, save %d)", neuron, fp.vec, fp.save);
-    SNN_CHECK_LAUNCH("snn_affine_neuron_fwd");
+        AnyNeuron{neuron}, OneOf<1, 4, 8>{fp.vec}, OneOf<0, 1, 2>{fp.save}, Flag{sb}, Flag{pc});
+    SNN_REQUIRE(launched, "%s: no kernel instance (neuron %d, vec %d, save %d)", fn, neuron, fp.vec, fp.save);
+    SNN_CHECK_LAUNCH(fn);
     return 0;
 }
 
@@ -1831,6 +2068,108 @@ extern "C" int snn_affine_neuron_bwd(int neuron, const float* g_out, int64_t ldg
     SNN_REQUIRE(launched, "snn_affine_neuron_bwd: no kernel instance (neuron %d, vec %d, mode %d, BUF %d, NP %d, GR %d)",
                 neuron, sp.pl.vec, sp.pl.mode, (int)sp.buf, sp.np, (int)sp.gr);
     SNN_CHECK_LAUNCH("snn_affine_neuron_bwd");
+    return 0;
+}
+
+// ---- LIF with per-channel time constants (c_mem[C], c_syn[C]) and their gradients
+extern "C" int snn_lif_tau_param(const float* w_mem, const float* w_syn, int n, int C, float* c_mem, float* c_syn,
+                                 void* stream) {
+    SNN_REQUIRE(w_mem && w_syn && c_mem && c_syn, "snn_lif_tau_param: null pointer");
+    SNN_REQUIRE(C > 0 && (n == 1 || n == C), "snn_lif_tau_param: n (%d) must be 1 or C (%d)", n, C);
+    hipLaunchKernelGGL(k_lif_tau_param, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_mem, w_syn, n, C, c_mem,
+                       c_syn);
+    SNN_CHECK_LAUNCH("snn_lif_tau_param");
+    return 0;
+}
+
+extern "C" int snn_lif_tau_fwd(int neuron, const float* y, int64_t ldy, const float* alpha, const float* beta,
+                               const float* v0, const float* i0, float* out, int64_t ldo, const float* addend,
+                               int64_t ld_addend, float* vT, float* iT, float* vdec, int T, int64_t M, int C,
+                               const snn_neuron_params* p, const float* c_mem, const float* c_syn, int flags, void* stream) {
+    SNN_REQUIRE(neuron == SNN_NEURON_LIF && !(flags & SNN_SCAN_BF16_STORAGE), "snn_lif_tau_fwd: %s (neuron %d, flags 0x%x)",
+                kTauCovers, neuron, flags);
+    SNN_REQUIRE(c_mem && c_syn, "snn_lif_tau_fwd: null time constants");
+    // (the forward scan addresses with 64-bit pointers whatever the flag says)
+    return neuron_fwd(neuron, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, false, T, M, C, p,
+                      flags & ~SNN_SCAN_WIDE_ADDRESSING, stream, c_mem, c_syn);
+}
+
+extern "C" size_t snn_lif_tau_bwd_partial_size(int T, int64_t M, int C, int with_sums) {
+    if (T <= 0 || M <= 0 || C <= 0) return 0;
+    return (size_t)bwd_plan(T, M, C, with_sums != 0).gx * C * 2;
+}
+
+// out[12]: the ten values of snn_affine_neuron_bwd_plan, then 1 when the two sums are combined in fixed order (0: LDS float
+// atomics) and the LDS bytes of the launch
+extern "C" int snn_lif_tau_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, int with_sums,
+                                    int with_tau_sums, const snn_neuron_params* p, int flags, int64_t* out) {
+    SNN_REQUIRE(out && p, "snn_lif_tau_bwd_plan: null pointer");
+    const TauBwdPlan tp = tau_bwd_plan(neuron, T, M, C, ldg, ldy, with_sums != 0, with_tau_sums != 0, p, flags);
+    SNN_REQUIRE(!tp.sp.refusal, "snn_lif_tau_bwd_plan: %s (neuron %d, flags 0x%x)", tp.sp.refusal, neuron, flags);
+    const ScanBwdPlan& sp = tp.sp;
+    const int P = kThreads / sp.pl.cvb;
+    out[0] = sp.pl.vec;
+    out[1] = sp.pl.mode;
+    out[2] = sp.buf ? 1 : 0;
+    out[3] = sp.np;
+    out[4] = sp.pl.cvb;
+    out[5] = sp.pl.gy;
+    out[6] = sp.pl.gx;
+    out[7] = sp.pl.rpb;
+    out[8] = (M % P) != 0 ? 1 : 0;
+    out[9] = (int64_t)sp.pl.lds_bytes;
+    out[10] = tp.ordered ? 1 : 0;
+    out[11] = (int64_t)tp.lds_bytes;
+    return 0;
+}
+
+extern "C" int snn_lif_tau_bwd(int neuron, const float* g_out, int64_t ldg, const float* state, const float* y, int64_t ldy,
+                               const float* g_vT, const float* g_iT, const float* alpha, const float* beta, int apply_scale,
+                               float* gx, float* g_v0, float* g_i0, double* sums, int T, int64_t M, int C,
+                               const snn_neuron_params* p, const float* c_mem, const float* c_syn, const float* v0,
+                               double* tau_partial, int flags, void* stream) {
+    SNN_REQUIRE(g_out && gx && p && state && c_mem && c_syn, "snn_lif_tau_bwd: null pointer");
+    const TauBwdPlan tp = tau_bwd_plan(neuron, T, M, C, ldg, ldy, sums != nullptr, tau_partial != nullptr, p, flags);
+    SNN_REQUIRE(!tp.sp.refusal, "snn_lif_tau_bwd: %s (neuron %d, flags 0x%x)", tp.sp.refusal, neuron, flags);
+    const ScanBwdPlan& sp = tp.sp;
+    SNN_REQUIRE(!sums || (y && ldy >= C), "snn_lif_tau_bwd: y required");
+    SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "snn_lif_tau_bwd: alpha/beta must come together");
+    SNN_REQUIRE(!apply_scale || alpha, "snn_lif_tau_bwd: apply_scale needs alpha");
+    if (sp.pl.vec == 4) {
+        const bool ok = ldg % 4 == 0 && (!sums || ldy % 4 == 0) && aligned(16, {g_out, state, gx, sums ? y : nullptr}) &&
+                        aligned(16, {g_vT, g_iT, alpha, beta, g_v0, g_i0, c_mem, c_syn, v0});
+        SNN_REQUIRE(ok, "snn_lif_tau_bwd: buffers must be 16-byte aligned when C%%4==0");
+    }
+    const bool launched = dispatch(
+        [&](auto VEC, auto MODE, auto BUF, auto NP, auto TS) {
+            if constexpr (bwd_instance(SNN_NEURON_LIF, VEC(), MODE(), BUF(), NP(), false, false, true, true, TS())) {
+                hipLaunchKernelGGL((k_affine_neuron_bwd<SNN_NEURON_LIF, VEC(), MODE(), BUF(), NP(), false, false, true, true, TS()>),
+                                   dim3(sp.pl.gx, sp.pl.gy), dim3(kThreads), tp.lds_bytes, (hipStream_t)stream, g_out, ldg,
+                                   state, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, g_v0, g_i0, sums, T, M, C,
+                                   sp.pl.cvb, *p, sp.last_only, c_mem, c_syn, v0, tau_partial, tp.ordered ? 1 : 0);
+                return true;
+            } else {
+                return false;
+            }
+        },
+        OneOf<1, 4>{sp.pl.vec}, OneOf<0, 1, 2>{sp.pl.mode}, Flag{sp.buf}, OneOf<1, 3, kBwdNP>{sp.np}, Flag{tau_partial != nullptr});
+    SNN_REQUIRE(launched, "snn_lif_tau_bwd: no kernel instance (vec %d, mode %d, BUF %d, NP %d)", sp.pl.vec, sp.pl.mode,
+                (int)sp.buf, sp.np);
+    SNN_CHECK_LAUNCH("snn_lif_tau_bwd");
+    return 0;
+}
+
+// per-block partials of snn_lif_tau_bwd -> dL/dw_mem, dL/dw_syn ([C], or [1] with per_layer), stored or accumulated
+extern "C" int snn_lif_tau_finalize(const double* tau_partial, int T, int64_t M, int C, int with_sums, const float* c_mem,
+                                    const float* c_syn, int per_layer, float* d_wmem, float* d_wsyn, int accumulate,
+                                    void* stream) {
+    SNN_REQUIRE(tau_partial && c_mem && c_syn && (d_wmem || d_wsyn), "snn_lif_tau_finalize: null pointer");
+    SNN_REQUIRE(T > 0 && M > 0 && C > 0, "snn_lif_tau_finalize: bad shape");
+    const int gx = bwd_plan(T, M, C, with_sums != 0).gx;
+    constexpr int kFinWaves = 16;
+    hipLaunchKernelGGL(k_lif_tau_finalize, dim3(per_layer ? 1 : (C + kFinWaves - 1) / kFinWaves), dim3(64 * kFinWaves), 0,
+                       (hipStream_t)stream, tau_partial, gx, C, c_mem, c_syn, per_layer ? 1 : 0, d_wmem, d_wsyn, accumulate);
+    SNN_CHECK_LAUNCH("snn_lif_tau_finalize");
     return 0;
 }
 

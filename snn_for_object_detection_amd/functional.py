@@ -44,16 +44,28 @@ def _check_lif_constants(alpha: float, v_th: float, v_reset: float) -> None:
         raise ValueError(f"v_reset ({v_reset}) must lie below v_th ({v_th})")
 
 
-def neuron_params(dt: float = DEFAULT_DT, *, surrogate: str = "super", alpha: float = 100.0, detach_reset: bool = False,
-                  v_th: float = 1.0, v_reset: float = 0.0, v_leak: float = 0.0) -> NeuronParams:
-    """The constants of one neuron layer.  The keywords are the LIF layer's own: its threshold / reset / leak potentials
-    and its BACKWARD rule - the surrogate ``dz/du`` (``"super"``, ``"triangle"``, ``"sigmoid"``, ``"atan"``, all with
-    value 1 at the threshold and slope parameter ``alpha``) and whether the spike inside the reset term is a constant of
-    the backward pass (``detach_reset``).  The defaults are the norse defaults the reference runs with."""
+def _check_time_constants(dt: float, tau_mem: float, tau_syn: float) -> None:
+    """c_mem = dt / tau_mem in (0, 1] (the potential does not overshoot its target), -c_syn = dt / tau_syn in (0, 1) (the
+    current decays without changing sign, and 1 + c_syn has a logit for the learnable layer)."""
+    if not (tau_mem > 0 and 0 < dt / tau_mem <= 1):
+        raise ValueError(f"tau_mem ({tau_mem}) must give 0 < dt/tau_mem <= 1 at dt = {dt}")
+    if not (tau_syn > 0 and 0 < dt / tau_syn < 1):
+        raise ValueError(f"tau_syn ({tau_syn}) must give 0 < dt/tau_syn < 1 at dt = {dt}")
+
+
+def neuron_params(dt: float = DEFAULT_DT, *, tau_mem: float = 1e-2, tau_syn: float = 5e-3, surrogate: str = "super",
+                  alpha: float = 100.0, detach_reset: bool = False, v_th: float = 1.0, v_reset: float = 0.0,
+                  v_leak: float = 0.0) -> NeuronParams:
+    """The constants of one neuron layer.  The keywords are the LIF layer's own: its membrane and synaptic time constants
+    (seconds; the kernels see ``c_mem = dt / tau_mem`` and ``c_syn = -dt / tau_syn``), its threshold / reset / leak
+    potentials and its BACKWARD rule - the surrogate ``dz/du`` (``"super"``, ``"triangle"``, ``"sigmoid"``, ``"atan"``, all
+    with value 1 at the threshold and slope parameter ``alpha``) and whether the spike inside the reset term is a constant
+    of the backward pass (``detach_reset``).  The defaults are the norse defaults the reference runs with."""
     code = _surrogate_code(surrogate)
     _check_lif_constants(alpha, v_th, v_reset)
-    tau_syn_inv = torch.as_tensor(1.0 / 5e-3)
-    tau_mem_inv = torch.as_tensor(1.0 / 1e-2)
+    _check_time_constants(dt, tau_mem, tau_syn)
+    tau_syn_inv = torch.as_tensor(1.0 / tau_syn)
+    tau_mem_inv = torch.as_tensor(1.0 / tau_mem)
     # + SLI saturation potential (sli.py:38-39) and the synapse constants (synapse.py:26-36,77)
     return NeuronParams((dt * tau_mem_inv).item(), (-dt * tau_syn_inv).item(), float(v_leak), float(v_th), float(v_reset),
                         float(alpha), 1.0, torch.as_tensor(1.0 / 1e-3).item(), torch.as_tensor(1.0 / 5e-3).item(), dt, 0.0,
@@ -86,6 +98,62 @@ def set_lif_gradient(model, surrogate: Optional[str] = None, alpha: Optional[flo
             p.reset_detached = int(bool(detach_reset))
         n += 1
     return n
+
+
+LEARN_TAU = (None, "layer", "channel")
+
+
+def set_lif_time_constants(model, tau_mem: Optional[float] = None, tau_syn: Optional[float] = None,
+                           learn_tau: Optional[str] = None) -> int:
+    """Set the time constants of every ``LIFCell`` of ``model`` (``StateStorage``-wrapped ones included) and, with
+    ``learn_tau="layer"`` / ``"channel"``, make them parameters of the cell (``w_mem``, ``w_syn``; see ``LIFCell``); ``None``
+    leaves a field as it is.  Returns the number of cells changed.  For a model built from an unchanged description: a cell
+    records its channel count when its generator builds it (``LIF.get``), and ``learn_tau="channel"`` on a cell that has none
+    raises.  Because it may ADD or REPLACE parameters (new constants re-initialise a learnable cell's raw parameters) it must
+    run before the ``FlatTrainer`` (or any optimiser) is built; a cell whose parameters a ``FlatTrainer`` already holds
+    raises."""
+    from .layer_gen import LIFCell
+    if learn_tau not in LEARN_TAU:
+        raise ValueError(f"learn_tau must be one of {LEARN_TAU}, not {learn_tau!r}")
+    cells = [m for m in model.modules() if isinstance(m, LIFCell)]
+    for m in cells:   # every cell is checked before the first one changes
+        m.check_time_constants(tau_mem, tau_syn, learn_tau)
+    dev = next((q.device for q in model.parameters()), None)
+    for m in cells:
+        m.set_time_constants(tau_mem, tau_syn, learn_tau, device=dev)
+    return len(cells)
+
+
+def lif_time_constants(w_mem: torch.Tensor, w_syn: torch.Tensor, channels: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(c_mem[C], c_syn[C])`` of a learnable LIF layer from its raw parameters (``[1]`` or ``[C]`` each):
+    ``c_mem = sigmoid(w_mem)``, ``1 + c_syn = sigmoid(w_syn)`` (snn_lif_tau_param).  No autograd: the layer's backward
+    applies the chain rule itself."""
+    w_mem, w_syn = w_mem.detach(), w_syn.detach()
+    _require_device(w_mem, "time-constant parameters")
+    n = w_mem.numel()
+    if n not in (1, channels) or w_syn.numel() != n or w_syn.dtype != _F32 or not w_syn.is_cuda:
+        raise RuntimeError(f"time-constant parameters: w_mem and w_syn hold 1 or {channels} fp32 values each on the device, not "
+                           f"{n} and {w_syn.numel()}")
+    c = torch.empty((2, channels), device=w_mem.device, dtype=_F32)
+    _hip.call("snn_lif_tau_param", w_mem.contiguous().data_ptr(), w_syn.contiguous().data_ptr(), n, channels,
+              c[0].data_ptr(), c[1].data_ptr(), _stream())
+    return c[0], c[1]
+
+
+def _tau_refusal(neuron: int, bf16_storage: bool, checkpointed: bool = False) -> None:
+    """What a layer with per-channel / learnable time constants (``affine_neuron(tau=...)``) cannot be combined with: said by
+    name, before any launch.  ``checkpointed`` is there for completeness only: no caller in the package passes True,
+    because ``LIF_CHECKPOINT_BYTES`` never selects such a layer (it stays on the plain scan, ``_AffineNeuron.forward``); the
+    branch states what a caller that forced the checkpointed pair would be told."""
+    if neuron != _hip.NEURON_LIF:
+        raise RuntimeError("per-channel / learnable time constants (tau=...) belong to LIF layers: LI, LI+Tanh, SLI and "
+                           "Synapse scans save no potential to rebuild the current from")
+    if bf16_storage:
+        raise RuntimeError("bf16 storage has no scan with per-channel / learnable time constants (tau=...): keep this layer's "
+                           "tensors fp32")
+    if checkpointed:
+        raise RuntimeError("the checkpointed LIF pair (LIF_CHECKPOINT_BYTES) has the struct's scalar time constants only: a "
+                           "layer with tau=... takes the plain scan")
 
 
 # ------------------------------------------------------------------------------------------- precision
@@ -1332,11 +1400,17 @@ class _AffineNeuron(Function):
     """
 
     @staticmethod
-    def forward(ctx, y, gamma, bias, v0, i0, addend, cfg):
+    def forward(ctx, y, gamma, bias, v0, i0, addend, cfg, w_mem=None, w_syn=None):
         (neuron, has_bn, training, eps, momentum, running_mean, running_var, params, g_slot, b_slot, dest,
-         sync_group, bn_hint, last_only, defer_apply, spikes_out) = cfg
+         sync_group, bn_hint, last_only, defer_apply, spikes_out, tau_slots) = cfg
         _require_device(y, "norm/neuron input", bf16_ok=True)
         sb = y.dtype == _BF16   # bf16 storage: y, out, the saved per-step state and the gradients; (v, i) and all sums fp32
+        # w_mem / w_syn ([1] or [C] each): the raw time-constant parameters of a learnable / per-channel LIF layer
+        tau = w_mem is not None
+        if tau:
+            _tau_refusal(neuron, sb)   # (LIF_CHECKPOINT_BYTES leaves such a layer on the plain scan, see `ckpt`)
+            if last_only and (ctx.needs_input_grad[7] or ctx.needs_input_grad[8]):
+                raise RuntimeError("last_only is not built for a LIF layer whose time constants are learned (tau=...)")
         if sb and (neuron not in (_hip.NEURON_NONE, _hip.NEURON_LIF, _hip.NEURON_LI, _hip.NEURON_LI_TANH) or y.shape[-3] % 4):
             raise RuntimeError("bf16 storage: Norm + none / LIF / LI / LI+Tanh with a multiple of 4 channels only")
         if not default_gradient_rule(params):
@@ -1362,18 +1436,31 @@ class _AffineNeuron(Function):
         st = _stream()
         dev = y.device
         use_running = has_bn and not training
+        if tau:
+            learn = ctx.needs_input_grad[7] or ctx.needs_input_grad[8]
+            nig = ctx.needs_input_grad
+            sums_wanted = has_bn and ((nig[0] and not use_running) or (gamma is not None and nig[1]) or nig[2])
+            if learn and sums_wanted and sync_group is None and SCAN_SEGMENT_T and T > SCAN_SEGMENT_T:
+                # the backward pass of such a sequence runs in segments, and the two sums of a segment behind the first
+                # one would need the potential in front of it (a look-back that is not built)
+                raise RuntimeError(f"learnable time constants (tau=...): a Norm -> LIF sequence of {T} steps is longer than one "
+                                   f"scan segment (SCAN_SEGMENT_T = {SCAN_SEGMENT_T}) and the segment look-back of the two "
+                                   "gradient sums is not built")
         mean = invstd = alpha = beta = None
         if has_bn:
             mean, invstd, alpha, beta = _bn_coefficients(y, ldy, (T, M, C), gamma, bias, use_running, eps, momentum,
                                                          running_mean, running_var, sync_group, bn_hint, st)
-        need_grad = any(ctx.needs_input_grad[:5])
+        need_grad = any(ctx.needs_input_grad[:5]) or (tau and (ctx.needs_input_grad[7] or ctx.needs_input_grad[8]))
+        c_mem = c_syn = None
+        if tau:
+            c_mem, c_syn = lif_time_constants(w_mem, w_syn, C)
         # spikes_out (a list the caller reads afterwards): the consumer can form the spikes from the saved potentials
         # (snn_conv1x1_spikes_*), so when those are saved anyway no output tensor is written at all
         no_out = (spikes_out is not None and USE_SPIKES_FROM_VDEC and neuron == _hip.NEURON_LIF and need_grad and has_bn
                   and addend is None and dest is None and not last_only and not sb and C % 4 == 0 and ldy % 4 == 0
                   and params.v_th >= 0.0
                   and not (LIF_CHECKPOINT_BYTES is not None and T * M * C * 4 >= LIF_CHECKPOINT_BYTES
-                           and default_gradient_rule(params)))
+                           and default_gradient_rule(params) and not tau))
         if last_only:
             # only the last timestep's output is kept (snn_affine_neuron_fwd SNN_SCAN_LAST_STEP_ONLY): out is [B,C,H,W]
             if (neuron not in (_hip.NEURON_LIF, _hip.NEURON_LI, _hip.NEURON_LI_TANH) or addend is not None
@@ -1393,7 +1480,7 @@ class _AffineNeuron(Function):
             # (the checkpointed kernels write / read all T outputs: not for the last-step-only read-out)
             # (... and have the default gradient rule only: a layer with another one takes the plain scan)
             ckpt = (neuron == _hip.NEURON_LIF and LIF_CHECKPOINT_BYTES is not None and not last_only and not sb
-                    and T * M * C * 4 >= LIF_CHECKPOINT_BYTES and default_gradient_rule(params))
+                    and T * M * C * 4 >= LIF_CHECKPOINT_BYTES and default_gradient_rule(params) and not tau)
             if ckpt:
                 k = _hip.query("snn_lif_ckpt_interval")
                 vdec = torch.empty(((T + k - 1) // k, 2, B, H, W, C), device=dev, dtype=_F32)
@@ -1420,11 +1507,15 @@ class _AffineNeuron(Function):
                       out.data_ptr(), cl_stride(out), ad_ptr, ld_ad, _ptr(vT), _ptr(iT), vdec.data_ptr(), T, M, C,
                       params, st)
         else:
-            _hip.call("snn_affine_neuron_fwd", neuron, y.data_ptr(), ldy, _ptr(alpha), _ptr(beta), _ptr(v0), _ptr(i0),
-                      _ptr(out), C if out is None else cl_stride(out), ad_ptr, ld_ad, _ptr(vT) if has_state else None,
-                      _ptr(iT) if has_state else None, _ptr(vdec), T, M, C, params,
-                      (_hip.SCAN_LAST_STEP_ONLY if last_only else 0) | sb_flag
-                      | (_hip.SCAN_SPIKES_FROM_VDEC if no_out else 0), st)
+            head = (neuron, y.data_ptr(), ldy, _ptr(alpha), _ptr(beta), _ptr(v0), _ptr(i0),
+                    _ptr(out), C if out is None else cl_stride(out), ad_ptr, ld_ad, _ptr(vT) if has_state else None,
+                    _ptr(iT) if has_state else None, _ptr(vdec), T, M, C, params)
+            fwd_flags = ((_hip.SCAN_LAST_STEP_ONLY if last_only else 0) | sb_flag
+                         | (_hip.SCAN_SPIKES_FROM_VDEC if no_out else 0))
+            if tau:
+                _hip.call("snn_lif_tau_fwd", *head, c_mem.data_ptr(), c_syn.data_ptr(), fwd_flags, st)
+            else:
+                _hip.call("snn_affine_neuron_fwd", *head, fwd_flags, st)
             if no_out:
                 # what travels to the consumer is an alias of the saved potentials, marked with the threshold that turns
                 # them into this layer's output
@@ -1438,13 +1529,18 @@ class _AffineNeuron(Function):
         # the rule of a graph already recorded, nor ask the checkpointed pair for a rule it refuses)
         ctx.cfg = (neuron, has_bn, use_running, NeuronParams.from_buffer_copy(params), (T, B, C, H, W))
         ctx.slots = (g_slot, b_slot)
+        ctx.tau = tau
+        ctx.tau_slots = tau_slots
+        ctx.tau_n = w_mem.numel() if tau else 0
         ctx.sync_group = sync_group if (has_bn and not use_running) else None
         ctx.has_v0 = v0 is not None
         ctx.has_i0 = i0 is not None
         if neuron == _hip.NEURON_LI_TANH and need_grad and not is_channels_last(out):
             raise RuntimeError("LI+Tanh output placed in a concat slice is not supported for training")
         state = vdec if neuron in _SAVES_STEP else (out if neuron == _hip.NEURON_LI_TANH else None)
-        ctx.save_for_backward(y, gamma, mean, invstd, alpha, beta, state, bias if has_bn else None)
+        # (a learnable layer's backward needs the initial potential for the two sums' terms of step 0)
+        ctx.save_for_backward(y, gamma, mean, invstd, alpha, beta, state, bias if has_bn else None, c_mem, c_syn,
+                              v0 if (tau and need_grad) else None)
         if not has_state:
             ctx.mark_non_differentiable(vT, iT)
         # with a neuron, vT / iT stay differentiable (time-outer BPTT through the carried state)
@@ -1454,7 +1550,7 @@ class _AffineNeuron(Function):
 
     @staticmethod
     def backward(ctx, g_out, g_vT, g_iT):
-        y, gamma, mean, invstd, alpha, beta, state, bn_bias = ctx.saved_tensors
+        y, gamma, mean, invstd, alpha, beta, state, bn_bias, c_mem, c_syn, v0_saved = ctx.saved_tensors
         neuron, has_bn, use_running, params, (T, B, C, H, W) = ctx.cfg
         M = B * H * W
         st = _stream()
@@ -1516,10 +1612,34 @@ class _AffineNeuron(Function):
         # segment boundary through (g_v, g_i), which the kernel already takes and returns: same values bit for bit.
         segmented = (need_sums and has_state and not ctx.ckpt and ctx.sync_group is None and SCAN_SEGMENT_T
                      and T > SCAN_SEGMENT_T)
+        # per-channel / learnable time constants: snn_lif_tau_bwd (the y-reading scan), and the partial sums of the two
+        # gradients when a raw parameter wants one - into its GradSlot when both have one, as dgamma / dbias
+        tau = ctx.tau
+        need_wm, need_ws = (ctx.needs_input_grad[7], ctx.needs_input_grad[8]) if tau else (False, False)
+        d_wmem = d_wsyn = None
+        dwm_ptr = dws_ptr = None
+        tau_acc = 0
+        if need_wm or need_ws:
+            if segmented:   # (the forward refuses what would get here)
+                raise RuntimeError("learnable time constants (tau=...): the segment look-back of the two gradient sums is "
+                                   "not built")
+            m_slot, s_slot = ctx.tau_slots
+            if (m_slot is not None or not need_wm) and (s_slot is not None or not need_ws):
+                tau_acc = 1 if (m_slot or s_slot).written else 0
+                for s_ in (m_slot, s_slot):
+                    if s_ is not None:
+                        s_.claim()
+                dwm_ptr = m_slot.buf.data_ptr() if (m_slot is not None and need_wm) else None
+                dws_ptr = s_slot.buf.data_ptr() if (s_slot is not None and need_ws) else None
+            else:
+                d_wmem = torch.empty((ctx.tau_n,), device=dev, dtype=_F32) if need_wm else None
+                d_wsyn = torch.empty((ctx.tau_n,), device=dev, dtype=_F32) if need_ws else None
+                dwm_ptr, dws_ptr = _ptr(d_wmem), _ptr(d_wsyn)
         # (segments: every segment must be covered; a segment behind the first one finds the neuron state it starts from
         # in the two saved potentials in front of it - SNN_SCAN_STATE_LOOKBACK)
         sums_from_state = bool(
             USE_SUMS_FROM_STATE and need_sums and not ctx.ckpt and not apply_scale and neuron == _hip.NEURON_LIF
+            and not tau    # (its query answers for the struct's scalars only)
             and not ctx.has_v0 and not ctx.has_i0 and g_v0 is None and g_i0 is None
             and not (segmented and T % SCAN_SEGMENT_T == 1)    # (a second segment starting at step 1 has one step to look back on)
             and all(_hip.query("snn_affine_neuron_bwd_sums_from_state", neuron, ts_, M, C, ldg, params, scan_flags)
@@ -1559,6 +1679,16 @@ class _AffineNeuron(Function):
                     _ptr(gi_out), _ptr(sums), ts, M, C, params)
             if ctx.ckpt:
                 _hip.call("snn_lif_bwd_ckpt", *scan, st)
+            elif tau:
+                tau_part = None
+                if need_wm or need_ws:
+                    n_tau = _hip.query("snn_lif_tau_bwd_partial_size", ts, M, C, int(need_sums))
+                    tau_part = torch.empty((n_tau,), device=dev, dtype=torch.float64)
+                _hip.call("snn_lif_tau_bwd", neuron, *scan, _ptr_at(c_mem, 0), _ptr_at(c_syn, 0),
+                          _ptr(v0_saved) if t0 == 0 else None, _ptr(tau_part), scan_flags, st)
+                if tau_part is not None:
+                    _hip.call("snn_lif_tau_finalize", tau_part.data_ptr(), ts, M, C, int(need_sums), c_mem.data_ptr(),
+                              c_syn.data_ptr(), int(ctx.tau_n == 1), dwm_ptr, dws_ptr, tau_acc, st)
             else:
                 seg_flags = scan_flags
                 if sums_from_state:
@@ -1588,7 +1718,7 @@ class _AffineNeuron(Function):
                           coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(), gx.data_ptr(), C, T, M, C, 0, st)
         if need_y:
             dy = _cl_view(gx)
-        return dy, dgamma, dbias, g_v0, g_i0, g_addend, None
+        return dy, dgamma, dbias, g_v0, g_i0, g_addend, None, d_wmem, d_wsyn
 
 
 class BwdPlan(NamedTuple):
@@ -1613,6 +1743,21 @@ def affine_neuron_bwd_plan(neuron: int, T: int, M: int, C: int, ldg: int, ldy: i
     return BwdPlan(*out)
 
 
+class TauBwdPlan(NamedTuple):
+    """The reverse-scan instance snn_lif_tau_bwd launches (include/snn_hip.h, snn_lif_tau_bwd_plan)."""
+    scan: BwdPlan
+    ordered: int      # the two sums of the time constants' gradients are combined in fixed order (0: LDS float atomics)
+    lds_bytes: int
+
+
+def lif_tau_bwd_plan(T: int, M: int, C: int, ldg: int, ldy: int, with_sums: bool, with_tau_sums: bool = True, flags: int = 0,
+                     params: Optional[NeuronParams] = None, neuron: int = _hip.NEURON_LIF) -> TauBwdPlan:
+    out = (ctypes.c_int64 * 12)()
+    _hip.call("snn_lif_tau_bwd_plan", neuron, T, M, C, ldg, ldy, int(bool(with_sums)), int(bool(with_tau_sums)),
+              params or neuron_params(), flags, ctypes.addressof(out))
+    return TauBwdPlan(BwdPlan(*out[:10]), int(out[10]), int(out[11]))
+
+
 def _expand_state(s: torch.Tensor, shape, dev) -> torch.Tensor:
     """State tensors may be 0-dim (LICell's initial v) or NCHW; the kernel wants dense [B,H,W,C]."""
     s = s.detach()
@@ -1623,8 +1768,13 @@ def _expand_state(s: torch.Tensor, shape, dev) -> torch.Tensor:
 
 def affine_neuron(y: torch.Tensor, neuron: int, state: Optional[NeuronState] = None, bn=None,
                   params: Optional[NeuronParams] = None, dest: Optional[Dest] = None,
-                  addend: Optional[torch.Tensor] = None, last_only: bool = False, spikes_ok: bool = False):
+                  addend: Optional[torch.Tensor] = None, last_only: bool = False, spikes_ok: bool = False,
+                  tau: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
     """Fused ``[Norm] -> [neuron] [+ addend]`` over a sequence or a single step.
+
+    ``tau=(w_mem, w_syn)`` (LIF, fp32 tensors): per-channel time constants ``c_mem = sigmoid(w_mem)``, ``1 + c_syn =
+    sigmoid(w_syn)`` in place of ``params.c_mem`` / ``.c_syn``; each holds one value (the whole layer) or one per channel.
+    One that requires a gradient receives it - into its ``GradSlot`` when it has one, through autograd otherwise.
 
     ``spikes_ok`` (LIF on a sequence; the caller guarantees that the ONLY consumer is ``sibling_conv1x1``): the result may be
     the layer's saved potentials instead of its spikes, marked ``_snn_spike_threshold`` - no spike tensor is written.
@@ -1638,6 +1788,8 @@ def affine_neuron(y: torch.Tensor, neuron: int, state: Optional[NeuronState] = N
     if y.dtype == _BF16 and (neuron not in (_hip.NEURON_NONE, _hip.NEURON_LIF, _hip.NEURON_LI, _hip.NEURON_LI_TANH)
                              or y.shape[-3] % 4):
         # no bf16-storage form of this scan (SLI / Synapse, channel counts that are not a multiple of 4): see _through_fp32
+        if tau is not None:
+            _tau_refusal(neuron, True)
         out, new_state = affine_neuron(to_float32(y), neuron, state, bn, params, None,
                                        None if addend is None else to_float32(addend), last_only, False)
         out = out if (last_only and y.dim() == 5) else to_bfloat16(out)
@@ -1680,9 +1832,11 @@ def affine_neuron(y: torch.Tensor, neuron: int, state: Optional[NeuronState] = N
             v0, i0 = state
     sync_group = getattr(bn, "_snn_sync_group", None) if has_bn else None
     spikes_out = [] if (spikes_ok and not single and dest is None and addend is None) else None
+    w_mem, w_syn = tau if tau is not None else (None, None)
     cfg = (neuron, has_bn, training, float(eps), float(momentum), rm, rv, params, _slot_of(gamma), _slot_of(bias),
-           dest, sync_group, bn_hint, bool(last_only) and not single, defer_apply, spikes_out)
-    out, vT, iT = _AffineNeuron.apply(seq, gamma, bias, v0, i0, addend, cfg)
+           dest, sync_group, bn_hint, bool(last_only) and not single, defer_apply, spikes_out,
+           (_slot_of(w_mem), _slot_of(w_syn)))
+    out, vT, iT = _AffineNeuron.apply(seq, gamma, bias, v0, i0, addend, cfg, w_mem, w_syn)
     if spikes_out:
         out._snn_spike_threshold = spikes_out[0]   # `out` holds v_dec: its consumer thresholds on load
     if neuron == _hip.NEURON_NONE:

@@ -316,6 +316,10 @@ class BlockGen(nn.Module):
                     only_last = (last_only and last and zero_copy and len(self.net) == 1 and direct is None
                                  and shortcut is None
                                  and neuron in (_hip.NEURON_LIF, _hip.NEURON_LI, _hip.NEURON_LI_TANH)
+                                 # (time constants that are being LEARNED: all T outputs - the two sums are not built
+                                 # together with the last-step-only scan; fixed or frozen ones, and inference, keep it)
+                                 and not (getattr(cell, "tau", None) is not None and torch.is_grad_enabled()
+                                          and any(w.requires_grad for w in cell.tau))
                                  and not (isinstance(holder, StateStorage) and not self.training))
                     # the only consumer is the fused sibling convolution of the next block (the stage-entry Conv -> Norm -> LIF
                     # in front of a C2f split): it can form the spikes from the saved potentials, none are written
@@ -331,7 +335,8 @@ class BlockGen(nn.Module):
                                           and nxt_l.out_channels % 4 == 0 and nxt_l.kernel_size[0] <= 5
                                           and nxt_l.forward_precision is None and nxt_l.backward_precision is None)))
                     Y, new = HF.affine_neuron(Y, neuron, old, bn=layer, params=cell.params, dest=direct,
-                                              addend=shortcut, last_only=only_last, spikes_ok=spikes_ok)
+                                              addend=shortcut, last_only=only_last, spikes_ok=spikes_ok,
+                                              tau=getattr(cell, "tau", None))
                     if isinstance(holder, StateStorage):
                         holder.record(old, Y, new)
                     branch_state[idx + 1] = new
