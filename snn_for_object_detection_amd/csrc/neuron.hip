@@ -1723,23 +1723,41 @@ constexpr bool fwd_instance(int neuron, int vec, int save, bool sb, bool pc = fa
            (save == 0 || neuron == SNN_NEURON_LIF || (save == 1 && rebuilds_x(neuron)));
 }
 
-// ---- reverse scan: everything snn_affine_neuron_bwd decides from shape and flags, pointer values apart.  The launch
-// consumes it and the host-only query snn_affine_neuron_bwd_plan exports it, so a test that asks the query asserts the
-// instance that really runs.
+const char* const kTauCovers =
+    "per-channel time constants are for SNN_NEURON_LIF on fp32 tensors (no SNN_SCAN_BF16_STORAGE), with the y-reading scan "
+    "(no SNN_SCAN_SUMS_FROM_STATE / SNN_SCAN_STATE_LOOKBACK)";
+const char* const kTauNoLastStep =
+    "SNN_SCAN_LAST_STEP_ONLY is not built together with the sums of the time constants' gradients";
+
+// ---- reverse scan: everything snn_affine_neuron_bwd / snn_lif_tau_bwd decide from shape and flags, pointer values apart.
+// The launch consumes it and the host-only queries snn_affine_neuron_bwd_plan / snn_lif_tau_bwd_plan export it, so a test
+// that asks a query asserts the instance that really runs.
+// The kernel's gradient arm, one chain in which each step compiles more in: the default rule, the general rule (GR), with
+// per-channel time constants (GR, PC), with those and the two sums of their gradients (GR, PC, TS).  A call asks for
+// kRuleDefault (the neuron parameters decide between the first two), kRuleTau or kRuleTauSums.
+enum ScanRule { kRuleDefault = 0, kRuleGeneral, kRuleTau, kRuleTauSums };
 struct ScanBwdPlan {
     BwdPlan pl;
-    bool buf, sb, yf, gr;     // BUF / SB / YF / GR of the kernel
+    bool buf, sb, yf;         // BUF / SB / YF of the kernel
+    ScanRule rule;            // GR / PC / TS of the kernel
     int np;                   // NP: pixel rows per thread
     int lookback, last_only;
+    bool ordered;             // per-channel constants: their two sums combine lanes and waves in fixed order (false: LDS
+                              // float atomics, the channel-group count is no power of two)
+    size_t lds_bytes;         // of the launch: the BatchNorm slabs, or the two sums' slabs where those are larger
     const char* refusal;      // what shape and flags alone rule out (nullptr: nothing)
 };
 static ScanBwdPlan scan_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, bool with_sums,
-                                 const snn_neuron_params* p, int flags) {
+                                 const snn_neuron_params* p, int flags, ScanRule ask = kRuleDefault) {
     ScanBwdPlan sp = {};
     auto refuse = [&sp](const char* why) {
         sp.refusal = why;
         return sp;
     };
+    const bool pc = ask >= kRuleTau, ts = ask == kRuleTauSums;
+    if (pc && (neuron != SNN_NEURON_LIF || (flags & (SNN_SCAN_BF16_STORAGE | SNN_SCAN_SUMS_FROM_STATE | SNN_SCAN_STATE_LOOKBACK))))
+        return refuse(kTauCovers);
+    if (ts && (flags & SNN_SCAN_LAST_STEP_ONLY)) return refuse(kTauNoLastStep);
     if (!p) return refuse("null neuron parameters");
     if (flags & ~(SNN_SCAN_WIDE_ADDRESSING | SNN_SCAN_LAST_STEP_ONLY | SNN_SCAN_BF16_STORAGE | SNN_SCAN_SUMS_FROM_STATE |
                   SNN_SCAN_STATE_LOOKBACK))
@@ -1754,9 +1772,11 @@ static ScanBwdPlan scan_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ld
     if (neuron < SNN_NEURON_NONE || neuron > SNN_NEURON_SYNAPSE) return refuse("bad neuron");
     if (sp.last_only && !last_step_neuron(neuron)) return refuse("SNN_SCAN_LAST_STEP_ONLY is for LIF / LI / LI+Tanh");
     if (p->surrogate < SNN_SURR_SUPER || p->surrogate > SNN_SURR_ATAN) return refuse(kBadSurrogate);
-    sp.gr = p->surrogate != SNN_SURR_SUPER || p->reset_detached != 0;
-    if (sp.gr && neuron != SNN_NEURON_LIF) return refuse(kGradientRuleCovers);
-    if (sp.gr && sp.sb) return refuse(kGradientRuleNoBf16);
+    const bool gr = p->surrogate != SNN_SURR_SUPER || p->reset_detached != 0;
+    if (gr && neuron != SNN_NEURON_LIF) return refuse(kGradientRuleCovers);
+    if (gr && sp.sb) return refuse(kGradientRuleNoBf16);
+    // (the per-channel family is one: its general arm serves the default rule too)
+    sp.rule = pc ? ask : gr ? kRuleGeneral : kRuleDefault;
     sp.pl = bwd_plan(T, M, C, with_sums);
     if (sp.sb && !(sp.pl.vec == 4 && bf16_neuron(neuron))) return refuse(kBf16Covers);
     // buffer addressing (see k_affine_neuron_bwd): one timestep of every tensor must fit a 31-bit byte offset
@@ -1775,43 +1795,14 @@ static ScanBwdPlan scan_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ld
         // (blocks with a single pixel row take the one-pixel-per-thread instance: the three empty pixel slots of the
         // four-pixel one are computed and issued in straight-line code - measured 58 us against 45 for the branchy kernel)
         sp.np = (sp.buf && sp.pl.rpb == 1) ? 1 : kBwdNP;
+        // with the two sums: three pixels per thread where the plain scan takes four (see the kernel's note on TS)
+        if (ts && sp.buf && sp.np == kBwdNP) sp.np = 3;
     }
+    sp.lds_bytes = sp.pl.lds_bytes;
+    const BwdPlan& pl = sp.pl;
+    sp.ordered = pc && (pl.mode == 1 || (pl.mode == 0 && (is_pow2(pl.cvb) || pl.cvb >= 64)));
+    if (ts) sp.lds_bytes = std::max(pl.lds_bytes, (size_t)(sp.ordered ? kWaves : 1) * pl.cvb * pl.vec * 2 * sizeof(float));
     return sp;
-}
-const char* const kTauCovers =
-    "per-channel time constants are for SNN_NEURON_LIF on fp32 tensors (no SNN_SCAN_BF16_STORAGE), with the y-reading scan "
-    "(no SNN_SCAN_SUMS_FROM_STATE / SNN_SCAN_STATE_LOOKBACK)";
-const char* const kTauNoLastStep =
-    "SNN_SCAN_LAST_STEP_ONLY is not built together with the sums of the time constants' gradients";
-
-// ---- the scans with per-channel time constants (snn_lif_tau_*): the plan of the plain scan of the shape, on the general
-// gradient-rule arm, and where the block's two extra sums go
-struct TauBwdPlan {
-    ScanBwdPlan sp;
-    bool ordered;        // lanes and waves in fixed order (false: LDS float atomics, the channel-group count is no power of two)
-    size_t lds_bytes;    // the BatchNorm slabs, or the two sums' slabs where those are larger
-};
-static TauBwdPlan tau_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, bool with_sums, bool with_tau,
-                               const snn_neuron_params* p, int flags) {
-    TauBwdPlan tp = {};
-    if (neuron != SNN_NEURON_LIF || (flags & (SNN_SCAN_BF16_STORAGE | SNN_SCAN_SUMS_FROM_STATE | SNN_SCAN_STATE_LOOKBACK))) {
-        tp.sp.refusal = kTauCovers;
-        return tp;
-    }
-    if (with_tau && (flags & SNN_SCAN_LAST_STEP_ONLY)) {
-        tp.sp.refusal = kTauNoLastStep;
-        return tp;
-    }
-    tp.sp = scan_bwd_plan(neuron, T, M, C, ldg, ldy, with_sums, p, flags);
-    if (tp.sp.refusal) return tp;
-    tp.sp.gr = true;   // one family: the general arm serves the default rule too
-    // with the two sums: three pixels per thread where the plain scan takes four (see the kernel's note on TS)
-    if (with_tau && tp.sp.buf && tp.sp.np == kBwdNP) tp.sp.np = 3;
-    const BwdPlan& pl = tp.sp.pl;
-    tp.ordered = pl.mode == 1 || (pl.mode == 0 && (is_pow2(pl.cvb) || pl.cvb >= 64));
-    const size_t tau_bytes = with_tau ? (size_t)(tp.ordered ? kWaves : 1) * pl.cvb * pl.vec * 2 * sizeof(float) : 0;
-    tp.lds_bytes = std::max(pl.lds_bytes, tau_bytes);
-    return tp;
 }
 
 constexpr bool bwd_instance(int neuron, int vec, int mode, bool buf, int np, bool sb, bool yf, bool gr, bool pc = false,
@@ -2003,25 +1994,82 @@ extern "C" int snn_affine_neuron_bwd_sums_from_state(int neuron, int T, int64_t 
     return scan_bwd_plan(neuron, T, M, C, ldg, C, true, p, flags | SNN_SCAN_SUMS_FROM_STATE).refusal ? 0 : 1;
 }
 
-// The plan snn_affine_neuron_bwd launches this call with (host-only).  out[10]: vec, mode, BUF, NP, cvb, gy, gx, rpb,
-// partial last pixel row, LDS bytes.  Returns 0, or 1 (message in snn_last_error) for a call snn_affine_neuron_bwd refuses
-// by its shape or flags alone.
+// The ten words both plan queries export: vec, mode, BUF, NP, cvb, gy, gx, rpb, partial last pixel row, LDS bytes of the
+// BatchNorm slabs.
+static void export_scan_bwd_plan(const ScanBwdPlan& sp, int64_t M, int64_t* out) {
+    const int P = kThreads / sp.pl.cvb;
+    const int64_t words[10] = {sp.pl.vec, sp.pl.mode, sp.buf, sp.np, sp.pl.cvb, sp.pl.gy, sp.pl.gx, sp.pl.rpb, (M % P) != 0,
+                               (int64_t)sp.pl.lds_bytes};
+    std::copy(words, words + 10, out);
+}
+
+// The plan snn_affine_neuron_bwd launches this call with (host-only), out[10].  Returns 0, or 1 (message in snn_last_error)
+// for a call snn_affine_neuron_bwd refuses by its shape or flags alone.
 extern "C" int snn_affine_neuron_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, int with_sums,
                                           const snn_neuron_params* p, int flags, int64_t* out) {
     SNN_REQUIRE(out && p, "snn_affine_neuron_bwd_plan: null pointer");
     const ScanBwdPlan sp = scan_bwd_plan(neuron, T, M, C, ldg, ldy, with_sums != 0, p, flags);
     SNN_REQUIRE(!sp.refusal, "snn_affine_neuron_bwd_plan: %s (neuron %d, flags 0x%x)", sp.refusal, neuron, flags);
-    const int P = kThreads / sp.pl.cvb;
-    out[0] = sp.pl.vec;
-    out[1] = sp.pl.mode;
-    out[2] = sp.buf ? 1 : 0;
-    out[3] = sp.np;
-    out[4] = sp.pl.cvb;
-    out[5] = sp.pl.gy;
-    out[6] = sp.pl.gx;
-    out[7] = sp.pl.rpb;
-    out[8] = (M % P) != 0 ? 1 : 0;
-    out[9] = (int64_t)sp.pl.lds_bytes;
+    export_scan_bwd_plan(sp, M, out);
+    return 0;
+}
+
+// Every reverse-scan launch.  fn: the entry point the messages name.  c_mem / c_syn / v0 / tau_partial (snn_lif_tau_bwd):
+// per-channel time constants, the initial potential their sums start from, and where those sums go.
+static int scan_bwd(const char* fn, int neuron, const float* g_out, int64_t ldg, const float* state, const float* y,
+                    int64_t ldy, const float* g_vT, const float* g_iT, const float* alpha, const float* beta, int apply_scale,
+                    float* gx, float* g_v0, float* g_i0, double* sums, int T, int64_t M, int C, const snn_neuron_params* p,
+                    int flags, void* stream, const float* c_mem = nullptr, const float* c_syn = nullptr,
+                    const float* v0 = nullptr, double* tau_partial = nullptr) {
+    SNN_REQUIRE(g_out && gx && p, "%s: null pointer", fn);
+    const ScanBwdPlan sp = scan_bwd_plan(neuron, T, M, C, ldg, ldy, sums != nullptr, p, flags,
+                                         !c_mem ? kRuleDefault : tau_partial ? kRuleTauSums : kRuleTau);
+    SNN_REQUIRE(!sp.refusal, "%s: %s (neuron %d, flags 0x%x)", fn, sp.refusal, neuron, flags);
+    const bool reads_y = !sp.yf && (sums || rebuilds_x(neuron));
+    if (sp.yf) {
+        SNN_REQUIRE(state && !apply_scale, "%s: %s", fn, kSumsFromStateCovers);
+        y = g_out;   // never read: the kernel's y operand only has to be a valid tensor
+        ldy = ldg;
+    } else {
+        SNN_REQUIRE(!(neuron == SNN_NEURON_LIF || neuron == SNN_NEURON_LI_TANH || rebuilds_x(neuron)) || state,
+                    "%s: saved state required", fn);
+        SNN_REQUIRE(!reads_y || (y && ldy >= C), "%s: y required", fn);
+        SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "%s: alpha/beta must come together", fn);
+        SNN_REQUIRE(!apply_scale || alpha, "%s: apply_scale needs alpha", fn);
+    }
+    if (sp.pl.vec == 4) {   // 4 channels per access: 16 bytes of fp32, 8 of the bf16 activation tensors
+        const bool ok = ldg % 4 == 0 && (!reads_y || ldy % 4 == 0) &&
+                        aligned(sp.sb ? 8 : 16, {g_out, state, gx, reads_y ? y : nullptr}) &&
+                        aligned(16, {g_vT, g_iT, alpha, beta, g_v0, g_i0, c_mem, c_syn, v0});
+        SNN_REQUIRE(ok, "%s: %s", fn, sp.sb ? kBf16Covers : "buffers must be 16-byte aligned when C%4==0");
+    }
+    // SB, YF and the rule travel as ONE dispatched value: of their sixteen combinations seven have instances (bf16 storage
+    // runs the default rule only, the from-state sums the first two rules), and every combination the dispatcher visits
+    // costs compile time whether bwd_instance keeps it or not (this file: 190 s with three values, 156 s with one).
+    enum { kArmBf16 = kRuleTauSums + 1, kArmFromState, kArmFromStateGeneral };
+    const int arm = sp.sb ? kArmBf16 : sp.yf ? kArmFromState + sp.rule : sp.rule;
+    const bool launched = dispatch(
+        [&](auto NEURON, auto VEC, auto MODE, auto BUF, auto NP, auto ARM) {
+            constexpr bool SB = ARM() == kArmBf16, YF = ARM() >= kArmFromState;
+            constexpr int RULE = SB ? kRuleDefault : YF ? ARM() - kArmFromState : ARM();
+            constexpr bool GR = RULE >= kRuleGeneral, PC = RULE >= kRuleTau, TS = RULE == kRuleTauSums;
+            if constexpr (bwd_instance(NEURON(), VEC(), MODE(), BUF(), NP(), SB, YF, GR, PC, TS)) {
+                // (the instances without per-channel constants never read the five trailing arguments: NULL and 0 there)
+                hipLaunchKernelGGL((k_affine_neuron_bwd<NEURON(), VEC(), MODE(), BUF(), NP(), SB, YF, GR, PC, TS>),
+                                   dim3(sp.pl.gx, sp.pl.gy), dim3(kThreads), sp.lds_bytes, (hipStream_t)stream, g_out, ldg,
+                                   state, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, g_v0, g_i0, sums, T, M, C,
+                                   sp.pl.cvb, *p, sp.yf ? sp.lookback : sp.last_only, c_mem, c_syn, v0, tau_partial,
+                                   sp.ordered ? 1 : 0);
+                return true;
+            } else {
+                return false;
+            }
+        },
+        AnyNeuron{neuron}, OneOf<1, 4>{sp.pl.vec}, OneOf<0, 1, 2>{sp.pl.mode}, Flag{sp.buf}, OneOf<1, 2, 3, kBwdNP>{sp.np},
+        OneOf<0, 1, 2, 3, 4, 5, 6>{arm});
+    SNN_REQUIRE(launched, "%s: no kernel instance (neuron %d, vec %d, mode %d, BUF %d, NP %d, GR %d)", fn, neuron, sp.pl.vec,
+                sp.pl.mode, (int)sp.buf, sp.np, (int)(sp.rule != kRuleDefault));
+    SNN_CHECK_LAUNCH(fn);
     return 0;
 }
 
@@ -2030,45 +2078,8 @@ extern "C" int snn_affine_neuron_bwd(int neuron, const float* g_out, int64_t ldg
                                      const float* beta, int apply_scale, float* gx, float* g_v0, float* g_i0,
                                      double* sums, int T, int64_t M, int C, const snn_neuron_params* p,
                                      int flags, void* stream) {
-    SNN_REQUIRE(g_out && gx && p, "snn_affine_neuron_bwd: null pointer");
-    const ScanBwdPlan sp = scan_bwd_plan(neuron, T, M, C, ldg, ldy, sums != nullptr, p, flags);
-    SNN_REQUIRE(!sp.refusal, "snn_affine_neuron_bwd: %s (neuron %d, flags 0x%x)", sp.refusal, neuron, flags);
-    const bool reads_y = !sp.yf && (sums || rebuilds_x(neuron));
-    if (sp.yf) {
-        SNN_REQUIRE(state && !apply_scale, "snn_affine_neuron_bwd: %s", kSumsFromStateCovers);
-        y = g_out;   // never read: the kernel's y operand only has to be a valid tensor
-        ldy = ldg;
-    } else {
-        SNN_REQUIRE(!(neuron == SNN_NEURON_LIF || neuron == SNN_NEURON_LI_TANH || rebuilds_x(neuron)) || state,
-                    "snn_affine_neuron_bwd: saved state required");
-        SNN_REQUIRE(!reads_y || (y && ldy >= C), "snn_affine_neuron_bwd: y required");
-        SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "snn_affine_neuron_bwd: alpha/beta must come together");
-        SNN_REQUIRE(!apply_scale || alpha, "snn_affine_neuron_bwd: apply_scale needs alpha");
-    }
-    if (sp.pl.vec == 4) {   // 4 channels per access: 16 bytes of fp32, 8 of the bf16 activation tensors
-        const bool ok = ldg % 4 == 0 && (!reads_y || ldy % 4 == 0) &&
-                        aligned(sp.sb ? 8 : 16, {g_out, state, gx, reads_y ? y : nullptr}) &&
-                        aligned(16, {g_vT, g_iT, alpha, beta, g_v0, g_i0});
-        SNN_REQUIRE(ok, "snn_affine_neuron_bwd: %s", sp.sb ? kBf16Covers : "buffers must be 16-byte aligned when C%4==0");
-    }
-    const bool launched = dispatch(
-        [&](auto NEURON, auto VEC, auto MODE, auto BUF, auto NP, auto SB, auto YF, auto GR) {
-            if constexpr (bwd_instance(NEURON(), VEC(), MODE(), BUF(), NP(), SB(), YF(), GR())) {
-                hipLaunchKernelGGL((k_affine_neuron_bwd<NEURON(), VEC(), MODE(), BUF(), NP(), SB(), YF(), GR()>),
-                                   dim3(sp.pl.gx, sp.pl.gy), dim3(kThreads), sp.pl.lds_bytes, (hipStream_t)stream, g_out, ldg,
-                                   state, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, g_v0, g_i0, sums, T, M, C,
-                                   sp.pl.cvb, *p, sp.yf ? sp.lookback : sp.last_only);
-                return true;
-            } else {
-                return false;
-            }
-        },
-        AnyNeuron{neuron}, OneOf<1, 4>{sp.pl.vec}, OneOf<0, 1, 2>{sp.pl.mode}, Flag{sp.buf}, OneOf<1, 2, 3, kBwdNP>{sp.np},
-        Flag{sp.sb}, Flag{sp.yf}, Flag{sp.gr});
-    SNN_REQUIRE(launched, "snn_affine_neuron_bwd: no kernel instance (neuron %d, vec %d, mode %d, BUF %d, NP %d, GR %d)",
-                neuron, sp.pl.vec, sp.pl.mode, (int)sp.buf, sp.np, (int)sp.gr);
-    SNN_CHECK_LAUNCH("snn_affine_neuron_bwd");
-    return 0;
+    return scan_bwd("snn_affine_neuron_bwd", neuron, g_out, ldg, state, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, g_v0,
+                    g_i0, sums, T, M, C, p, flags, stream);
 }
 
 // ---- LIF with per-channel time constants (c_mem[C], c_syn[C]) and their gradients
@@ -2104,22 +2115,12 @@ extern "C" size_t snn_lif_tau_bwd_partial_size(int T, int64_t M, int C, int with
 extern "C" int snn_lif_tau_bwd_plan(int neuron, int T, int64_t M, int C, int64_t ldg, int64_t ldy, int with_sums,
                                     int with_tau_sums, const snn_neuron_params* p, int flags, int64_t* out) {
     SNN_REQUIRE(out && p, "snn_lif_tau_bwd_plan: null pointer");
-    const TauBwdPlan tp = tau_bwd_plan(neuron, T, M, C, ldg, ldy, with_sums != 0, with_tau_sums != 0, p, flags);
-    SNN_REQUIRE(!tp.sp.refusal, "snn_lif_tau_bwd_plan: %s (neuron %d, flags 0x%x)", tp.sp.refusal, neuron, flags);
-    const ScanBwdPlan& sp = tp.sp;
-    const int P = kThreads / sp.pl.cvb;
-    out[0] = sp.pl.vec;
-    out[1] = sp.pl.mode;
-    out[2] = sp.buf ? 1 : 0;
-    out[3] = sp.np;
-    out[4] = sp.pl.cvb;
-    out[5] = sp.pl.gy;
-    out[6] = sp.pl.gx;
-    out[7] = sp.pl.rpb;
-    out[8] = (M % P) != 0 ? 1 : 0;
-    out[9] = (int64_t)sp.pl.lds_bytes;
-    out[10] = tp.ordered ? 1 : 0;
-    out[11] = (int64_t)tp.lds_bytes;
+    const ScanBwdPlan sp =
+        scan_bwd_plan(neuron, T, M, C, ldg, ldy, with_sums != 0, p, flags, with_tau_sums ? kRuleTauSums : kRuleTau);
+    SNN_REQUIRE(!sp.refusal, "snn_lif_tau_bwd_plan: %s (neuron %d, flags 0x%x)", sp.refusal, neuron, flags);
+    export_scan_bwd_plan(sp, M, out);
+    out[10] = sp.ordered ? 1 : 0;
+    out[11] = (int64_t)sp.lds_bytes;
     return 0;
 }
 
@@ -2129,34 +2130,8 @@ extern "C" int snn_lif_tau_bwd(int neuron, const float* g_out, int64_t ldg, cons
                                const snn_neuron_params* p, const float* c_mem, const float* c_syn, const float* v0,
                                double* tau_partial, int flags, void* stream) {
     SNN_REQUIRE(g_out && gx && p && state && c_mem && c_syn, "snn_lif_tau_bwd: null pointer");
-    const TauBwdPlan tp = tau_bwd_plan(neuron, T, M, C, ldg, ldy, sums != nullptr, tau_partial != nullptr, p, flags);
-    SNN_REQUIRE(!tp.sp.refusal, "snn_lif_tau_bwd: %s (neuron %d, flags 0x%x)", tp.sp.refusal, neuron, flags);
-    const ScanBwdPlan& sp = tp.sp;
-    SNN_REQUIRE(!sums || (y && ldy >= C), "snn_lif_tau_bwd: y required");
-    SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "snn_lif_tau_bwd: alpha/beta must come together");
-    SNN_REQUIRE(!apply_scale || alpha, "snn_lif_tau_bwd: apply_scale needs alpha");
-    if (sp.pl.vec == 4) {
-        const bool ok = ldg % 4 == 0 && (!sums || ldy % 4 == 0) && aligned(16, {g_out, state, gx, sums ? y : nullptr}) &&
-                        aligned(16, {g_vT, g_iT, alpha, beta, g_v0, g_i0, c_mem, c_syn, v0});
-        SNN_REQUIRE(ok, "snn_lif_tau_bwd: buffers must be 16-byte aligned when C%%4==0");
-    }
-    const bool launched = dispatch(
-        [&](auto VEC, auto MODE, auto BUF, auto NP, auto TS) {
-            if constexpr (bwd_instance(SNN_NEURON_LIF, VEC(), MODE(), BUF(), NP(), false, false, true, true, TS())) {
-                hipLaunchKernelGGL((k_affine_neuron_bwd<SNN_NEURON_LIF, VEC(), MODE(), BUF(), NP(), false, false, true, true, TS()>),
-                                   dim3(sp.pl.gx, sp.pl.gy), dim3(kThreads), tp.lds_bytes, (hipStream_t)stream, g_out, ldg,
-                                   state, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, g_v0, g_i0, sums, T, M, C,
-                                   sp.pl.cvb, *p, sp.last_only, c_mem, c_syn, v0, tau_partial, tp.ordered ? 1 : 0);
-                return true;
-            } else {
-                return false;
-            }
-        },
-        OneOf<1, 4>{sp.pl.vec}, OneOf<0, 1, 2>{sp.pl.mode}, Flag{sp.buf}, OneOf<1, 3, kBwdNP>{sp.np}, Flag{tau_partial != nullptr});
-    SNN_REQUIRE(launched, "snn_lif_tau_bwd: no kernel instance (vec %d, mode %d, BUF %d, NP %d)", sp.pl.vec, sp.pl.mode,
-                (int)sp.buf, sp.np);
-    SNN_CHECK_LAUNCH("snn_lif_tau_bwd");
-    return 0;
+    return scan_bwd("snn_lif_tau_bwd", neuron, g_out, ldg, state, y, ldy, g_vT, g_iT, alpha, beta, apply_scale, gx, g_v0, g_i0,
+                    sums, T, M, C, p, flags, stream, c_mem, c_syn, v0, tau_partial);
 }
 
 // per-block partials of snn_lif_tau_bwd -> dL/dw_mem, dL/dw_syn ([C], or [1] with per_layer), stored or accumulated

@@ -1389,6 +1389,58 @@ def _ptr_at(t: Optional[torch.Tensor], offset: int) -> Optional[int]:
     return None if t is None else t.data_ptr() + offset
 
 
+class _NeuronCfg(NamedTuple):
+    """The non-tensor arguments of ``_AffineNeuron`` (built by ``affine_neuron``)."""
+    neuron: int
+    has_bn: bool
+    training: bool
+    eps: float
+    momentum: float
+    running_mean: Optional[torch.Tensor]
+    running_var: Optional[torch.Tensor]
+    params: NeuronParams
+    g_slot: Optional[GradSlot]
+    b_slot: Optional[GradSlot]
+    dest: Optional[Dest]
+    sync_group: object
+    bn_hint: object
+    last_only: bool
+    defer_apply: bool
+    spikes_out: Optional[list]
+    tau_slots: Tuple[Optional[GradSlot], Optional[GradSlot]]
+
+
+def _bf16_scan_covers(neuron: int, channels: int) -> bool:
+    """The Norm -> neuron scans have a bf16-storage form for these neurons on a multiple of 4 channels."""
+    return neuron in (_hip.NEURON_NONE, _hip.NEURON_LIF, _hip.NEURON_LI, _hip.NEURON_LI_TANH) and channels % 4 == 0
+
+
+def _takes_checkpointed_pair(neuron: int, nbytes: int, params: NeuronParams, last_only: bool, sb: bool, tau: bool) -> bool:
+    """A layer of ``nbytes`` of saved potentials runs on snn_lif_fwd_ckpt / snn_lif_bwd_ckpt: those write / read all T
+    outputs (not the last-step-only read-out), fp32, and have the default gradient rule and the struct's scalar time
+    constants only - any other layer takes the plain scan."""
+    return (neuron == _hip.NEURON_LIF and LIF_CHECKPOINT_BYTES is not None and not last_only and not sb
+            and nbytes >= LIF_CHECKPOINT_BYTES and default_gradient_rule(params) and not tau)
+
+
+def _grad_pair(slots, needed, n: int, dev):
+    """Where the two gradients of a parameter pair (gamma / bias, w_mem / w_syn) go: ``(ptr_a, ptr_b, accumulate, fresh_a,
+    fresh_b)``.  Straight into the flat gradient buffer when every needed member has a ``GradSlot`` - both slots are then
+    claimed and share one accumulate flag, the first present slot's ``written`` before the claim; into fresh [n] tensors
+    (handed back to autograd, flag 0) otherwise."""
+    if not any(needed):
+        return None, None, 0, None, None
+    if all(s_ is not None or not need for s_, need in zip(slots, needed)):
+        acc = 1 if (slots[0] or slots[1]).written else 0
+        for s_ in slots:
+            if s_ is not None:
+                s_.claim()
+        pa, pb = (s_.buf.data_ptr() if (s_ is not None and need) else None for s_, need in zip(slots, needed))
+        return pa, pb, acc, None, None
+    fa, fb = (torch.empty((n,), device=dev, dtype=_F32) if need else None for need in needed)
+    return _ptr(fa), _ptr(fb), 0, fa, fb
+
+
 class _AffineNeuron(Function):
     """[BatchNorm2d (per-timestep batch statistics)] -> [LIF | LI | LI+Tanh | nothing], fused.
 
@@ -1401,8 +1453,8 @@ class _AffineNeuron(Function):
 
     @staticmethod
     def forward(ctx, y, gamma, bias, v0, i0, addend, cfg, w_mem=None, w_syn=None):
-        (neuron, has_bn, training, eps, momentum, running_mean, running_var, params, g_slot, b_slot, dest,
-         sync_group, bn_hint, last_only, defer_apply, spikes_out, tau_slots) = cfg
+        neuron, has_bn, params, dest, sync_group, last_only = (cfg.neuron, cfg.has_bn, cfg.params, cfg.dest, cfg.sync_group,
+                                                               cfg.last_only)
         _require_device(y, "norm/neuron input", bf16_ok=True)
         sb = y.dtype == _BF16   # bf16 storage: y, out, the saved per-step state and the gradients; (v, i) and all sums fp32
         # w_mem / w_syn ([1] or [C] each): the raw time-constant parameters of a learnable / per-channel LIF layer
@@ -1411,7 +1463,7 @@ class _AffineNeuron(Function):
             _tau_refusal(neuron, sb)   # (LIF_CHECKPOINT_BYTES leaves such a layer on the plain scan, see `ckpt`)
             if last_only and (ctx.needs_input_grad[7] or ctx.needs_input_grad[8]):
                 raise RuntimeError("last_only is not built for a LIF layer whose time constants are learned (tau=...)")
-        if sb and (neuron not in (_hip.NEURON_NONE, _hip.NEURON_LIF, _hip.NEURON_LI, _hip.NEURON_LI_TANH) or y.shape[-3] % 4):
+        if sb and not _bf16_scan_covers(neuron, y.shape[-3]):
             raise RuntimeError("bf16 storage: Norm + none / LIF / LI / LI+Tanh with a multiple of 4 channels only")
         if not default_gradient_rule(params):
             name = next((k for k, v in SURROGATES.items() if v == params.surrogate), params.surrogate)
@@ -1435,7 +1487,7 @@ class _AffineNeuron(Function):
         M = B * H * W
         st = _stream()
         dev = y.device
-        use_running = has_bn and not training
+        use_running = has_bn and not cfg.training
         if tau:
             learn = ctx.needs_input_grad[7] or ctx.needs_input_grad[8]
             nig = ctx.needs_input_grad
@@ -1448,19 +1500,19 @@ class _AffineNeuron(Function):
                                    "gradient sums is not built")
         mean = invstd = alpha = beta = None
         if has_bn:
-            mean, invstd, alpha, beta = _bn_coefficients(y, ldy, (T, M, C), gamma, bias, use_running, eps, momentum,
-                                                         running_mean, running_var, sync_group, bn_hint, st)
+            mean, invstd, alpha, beta = _bn_coefficients(y, ldy, (T, M, C), gamma, bias, use_running, cfg.eps, cfg.momentum,
+                                                         cfg.running_mean, cfg.running_var, sync_group, cfg.bn_hint, st)
         need_grad = any(ctx.needs_input_grad[:5]) or (tau and (ctx.needs_input_grad[7] or ctx.needs_input_grad[8]))
         c_mem = c_syn = None
         if tau:
             c_mem, c_syn = lif_time_constants(w_mem, w_syn, C)
+        ckpt_pair = _takes_checkpointed_pair(neuron, T * M * C * 4, params, last_only, sb, tau)
         # spikes_out (a list the caller reads afterwards): the consumer can form the spikes from the saved potentials
         # (snn_conv1x1_spikes_*), so when those are saved anyway no output tensor is written at all
+        spikes_out = cfg.spikes_out
         no_out = (spikes_out is not None and USE_SPIKES_FROM_VDEC and neuron == _hip.NEURON_LIF and need_grad and has_bn
                   and addend is None and dest is None and not last_only and not sb and C % 4 == 0 and ldy % 4 == 0
-                  and params.v_th >= 0.0
-                  and not (LIF_CHECKPOINT_BYTES is not None and T * M * C * 4 >= LIF_CHECKPOINT_BYTES
-                           and default_gradient_rule(params) and not tau))
+                  and params.v_th >= 0.0 and not ckpt_pair)
         if last_only:
             # only the last timestep's output is kept (snn_affine_neuron_fwd SNN_SCAN_LAST_STEP_ONLY): out is [B,C,H,W]
             if (neuron not in (_hip.NEURON_LIF, _hip.NEURON_LI, _hip.NEURON_LI_TANH) or addend is not None
@@ -1477,10 +1529,7 @@ class _AffineNeuron(Function):
         vdec = None
         ckpt = False
         if neuron in _SAVES_STEP and need_grad:
-            # (the checkpointed kernels write / read all T outputs: not for the last-step-only read-out)
-            # (... and have the default gradient rule only: a layer with another one takes the plain scan)
-            ckpt = (neuron == _hip.NEURON_LIF and LIF_CHECKPOINT_BYTES is not None and not last_only and not sb
-                    and T * M * C * 4 >= LIF_CHECKPOINT_BYTES and default_gradient_rule(params) and not tau)
+            ckpt = ckpt_pair
             if ckpt:
                 k = _hip.query("snn_lif_ckpt_interval")
                 vdec = torch.empty(((T + k - 1) // k, 2, B, H, W, C), device=dev, dtype=_F32)
@@ -1523,14 +1572,14 @@ class _AffineNeuron(Function):
                 spikes_out.append(float(params.v_th))
         ctx.ckpt = ckpt
         ctx.sb = sb
-        ctx.defer_apply = defer_apply
+        ctx.defer_apply = cfg.defer_apply
         ctx.last_only = last_only
         # (a copy: the cell's struct is mutable - set_lif_gradient between this forward and its backward must not change
         # the rule of a graph already recorded, nor ask the checkpointed pair for a rule it refuses)
         ctx.cfg = (neuron, has_bn, use_running, NeuronParams.from_buffer_copy(params), (T, B, C, H, W))
-        ctx.slots = (g_slot, b_slot)
+        ctx.slots = (cfg.g_slot, cfg.b_slot)
         ctx.tau = tau
-        ctx.tau_slots = tau_slots
+        ctx.tau_slots = cfg.tau_slots
         ctx.tau_n = w_mem.numel() if tau else 0
         ctx.sync_group = sync_group if (has_bn and not use_running) else None
         ctx.has_v0 = v0 is not None
@@ -1586,26 +1635,9 @@ class _AffineNeuron(Function):
         g_i0 = _new_cl((B,), C, H, W, y, _F32) if (has_state and ctx.has_i0 and ctx.needs_input_grad[4]) else None
         # eval-mode BN has no batch coupling: dy = alpha * gx, applied while gx is written
         apply_scale = 1 if (has_bn and use_running) else 0
-        dy = dgamma = dbias = None
-        coef = None
-        dg_ptr = db_ptr = None
-        acc_flag = 0
-        if need_sums:
-            coef = torch.empty((3, T, C), device=dev, dtype=_F32)
-            g_slot, b_slot = ctx.slots
-            slotted = (g_slot is not None or not need_gamma) and (b_slot is not None or not need_bias)
-            if slotted and (need_gamma or need_bias):
-                # gradients go straight into the flat gradient buffer; both share one accumulate flag
-                acc_flag = 1 if (g_slot or b_slot).written else 0
-                for s_ in (g_slot, b_slot):
-                    if s_ is not None:
-                        s_.claim()
-                dg_ptr = g_slot.buf.data_ptr() if (g_slot is not None and need_gamma) else None
-                db_ptr = b_slot.buf.data_ptr() if (b_slot is not None and need_bias) else None
-            else:
-                dgamma = torch.empty((C,), device=dev, dtype=_F32) if need_gamma else None
-                dbias = torch.empty((C,), device=dev, dtype=_F32) if need_bias else None
-                dg_ptr, db_ptr = _ptr(dgamma), _ptr(dbias)
+        dy = None
+        coef = torch.empty((3, T, C), device=dev, dtype=_F32) if need_sums else None
+        dg_ptr, db_ptr, acc_flag, dgamma, dbias = _grad_pair(ctx.slots, (need_gamma, need_bias), C, dev)
         # Long sequences in SEGMENTS of SCAN_SEGMENT_T steps, last segment first.  The scan kernel keeps its per-(t, c)
         # BatchNorm sums for ALL T steps in LDS (one slab per wave); at T = 128 that leaves room for 16 channels per
         # block only, i.e. 64-byte runs per pixel - measured 2.6 TB/s against 4.6 at T = 32.  The recurrence crosses a
@@ -1616,25 +1648,10 @@ class _AffineNeuron(Function):
         # gradients when a raw parameter wants one - into its GradSlot when both have one, as dgamma / dbias
         tau = ctx.tau
         need_wm, need_ws = (ctx.needs_input_grad[7], ctx.needs_input_grad[8]) if tau else (False, False)
-        d_wmem = d_wsyn = None
-        dwm_ptr = dws_ptr = None
-        tau_acc = 0
-        if need_wm or need_ws:
-            if segmented:   # (the forward refuses what would get here)
-                raise RuntimeError("learnable time constants (tau=...): the segment look-back of the two gradient sums is "
-                                   "not built")
-            m_slot, s_slot = ctx.tau_slots
-            if (m_slot is not None or not need_wm) and (s_slot is not None or not need_ws):
-                tau_acc = 1 if (m_slot or s_slot).written else 0
-                for s_ in (m_slot, s_slot):
-                    if s_ is not None:
-                        s_.claim()
-                dwm_ptr = m_slot.buf.data_ptr() if (m_slot is not None and need_wm) else None
-                dws_ptr = s_slot.buf.data_ptr() if (s_slot is not None and need_ws) else None
-            else:
-                d_wmem = torch.empty((ctx.tau_n,), device=dev, dtype=_F32) if need_wm else None
-                d_wsyn = torch.empty((ctx.tau_n,), device=dev, dtype=_F32) if need_ws else None
-                dwm_ptr, dws_ptr = _ptr(d_wmem), _ptr(d_wsyn)
+        if (need_wm or need_ws) and segmented:   # (the forward refuses what would get here)
+            raise RuntimeError("learnable time constants (tau=...): the segment look-back of the two gradient sums is "
+                               "not built")
+        dwm_ptr, dws_ptr, tau_acc, d_wmem, d_wsyn = _grad_pair(ctx.tau_slots, (need_wm, need_ws), ctx.tau_n, dev)
         # (segments: every segment must be covered; a segment behind the first one finds the neuron state it starts from
         # in the two saved potentials in front of it - SNN_SCAN_STATE_LOOKBACK)
         sums_from_state = bool(
@@ -1785,8 +1802,7 @@ def affine_neuron(y: torch.Tensor, neuron: int, state: Optional[NeuronState] = N
     T-1 outputs are never written and the backward pass reads no output gradient for them.
     Returns ``(out, NeuronState | None)``.
     """
-    if y.dtype == _BF16 and (neuron not in (_hip.NEURON_NONE, _hip.NEURON_LIF, _hip.NEURON_LI, _hip.NEURON_LI_TANH)
-                             or y.shape[-3] % 4):
+    if y.dtype == _BF16 and not _bf16_scan_covers(neuron, y.shape[-3]):
         # no bf16-storage form of this scan (SLI / Synapse, channel counts that are not a multiple of 4): see _through_fp32
         if tau is not None:
             _tau_refusal(neuron, True)
@@ -1833,9 +1849,10 @@ def affine_neuron(y: torch.Tensor, neuron: int, state: Optional[NeuronState] = N
     sync_group = getattr(bn, "_snn_sync_group", None) if has_bn else None
     spikes_out = [] if (spikes_ok and not single and dest is None and addend is None) else None
     w_mem, w_syn = tau if tau is not None else (None, None)
-    cfg = (neuron, has_bn, training, float(eps), float(momentum), rm, rv, params, _slot_of(gamma), _slot_of(bias),
-           dest, sync_group, bn_hint, bool(last_only) and not single, defer_apply, spikes_out,
-           (_slot_of(w_mem), _slot_of(w_syn)))
+    cfg = _NeuronCfg(neuron=neuron, has_bn=has_bn, training=training, eps=float(eps), momentum=float(momentum),
+                     running_mean=rm, running_var=rv, params=params, g_slot=_slot_of(gamma), b_slot=_slot_of(bias), dest=dest,
+                     sync_group=sync_group, bn_hint=bn_hint, last_only=bool(last_only) and not single,
+                     defer_apply=defer_apply, spikes_out=spikes_out, tau_slots=(_slot_of(w_mem), _slot_of(w_syn)))
     out, vT, iT = _AffineNeuron.apply(seq, gamma, bias, v0, i0, addend, cfg, w_mem, w_syn)
     if spikes_out:
         out._snn_spike_threshold = spikes_out[0]   # `out` holds v_dec: its consumer thresholds on load
