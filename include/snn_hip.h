@@ -588,6 +588,33 @@ int snn_lstm_cell_fwd(const float* gates, const float* c_prev, float* h, float* 
 int snn_lstm_cell_bwd(const float* gates, const float* c_prev, const float* c, const float* gh, const float* gc,
                       float* g_gates, float* g_c_prev, int64_t M, int C, void* stream);
 
+/* ConvLSTM with 1x1 gates over a whole sequence (conv_lstm.py:51-78) as a per-pixel temporal scan: a workgroup keeps a
+ * tile of pixels for all T steps, the gate product [x_t ; h_{t-1}] . w^T runs on the fp32 MFMA (exact fp32 products, fp32
+ * accumulation: no operand split, no range contract), c stays in registers and h in LDS.  Channels-last, time outermost:
+ * x [T][M][ldx >= Cin], w [4Ch][Cin + Ch] = conv.weight in OHWI, gate rows (input, forget, output, candidate).
+ * No atomics and a fixed summation order: the same inputs give the same bits.
+ *
+ * snn_convlstm_seq_supported: host-only (no device needed); the launchers check the same function.  Covered:
+ * Ch % 16 == 0, 16 <= Ch <= 256, 1 <= Cin <= 256, ldx >= Cin; any T, M >= 1.
+ * snn_convlstm_seq_tile: host-only; pixels per workgroup (16 or 32) both kernels use for M pixels, 0 if unsupported.
+ *
+ * fwd: h0 / c0 [M][Ch], NULL = zeros.  Writes hs [T][M][Ch] and cT [M][Ch]; save_gates [T][M][4Ch] (the gate values AFTER
+ * their non-linearity) and save_c [T][M][Ch] (c_t) only when given (both or neither): what the backward reads.
+ *
+ * bwd, t = T-1 .. 0: dh = gh_t + carried dh; the cell backward on the saved gates gives dgates_t (pre-activation
+ * gradients, written to dgates [T][M][4Ch]); d[x ; h] = dgates_t . w: the first Cin columns go to dx_t (pixel stride
+ * lddx; dx NULL = not wanted), the last Ch are the carried dh.  gh [T][M][Ch] may be NULL (loss on the final state
+ * only); ghT / gcT [M][Ch] (NULL = zero) are the gradients of the returned final state (h_T, c_T), added to the carries
+ * before step T-1; c0 as given to the forward.  dh0 / dc0 [M][Ch] receive the carries after step 0 when given.  The
+ * weight gradient is NOT formed here: it is one snn_conv2d_wgrad over the T*B frames of [x ; h_prev] with dy = dgates. */
+int snn_convlstm_seq_supported(int Cin, int Ch, int64_t ldx);
+int snn_convlstm_seq_tile(int Cin, int Ch, int64_t M);
+int snn_convlstm_seq_fwd(const float* x, int64_t ldx, const float* w, const float* h0, const float* c0, float* hs,
+                         float* cT, float* save_gates, float* save_c, int T, int64_t M, int Cin, int Ch, void* stream);
+int snn_convlstm_seq_bwd(const float* w, const float* save_gates, const float* save_c, const float* c0, const float* gh,
+                         const float* ghT, const float* gcT, float* dgates, float* dx, int64_t lddx, float* dh0,
+                         float* dc0, int T, int64_t M, int Cin, int Ch, void* stream);
+
 /* Pool("A"/"M"/"S", k, stride) (layer_gen.py:146-173, common.py:18-49), no padding, floor mode. */
 int snn_pool_fwd(int kind, const float* x, float* y, int64_t N, int H, int W, int C,
                  int Ho, int Wo, int k, int stride, void* stream);

@@ -28,7 +28,7 @@ LIB_NAME = "libsnn_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 STAMP_PATH = LIB_PATH + ".buildstamp"
 SOURCES = ("elementwise.hip", "neuron.hip", "conv.hip", "wgrad_halo.hip", "conv_halo.hip", "detect.hip",
-           "targets.hip", "metrics.hip")
+           "targets.hip", "metrics.hip", "lstm.hip")
 HEADERS = (os.path.join(CSRC, "snn_common.h"), os.path.join(INCLUDE, "snn_hip.h"))
 ARCH = "gfx950"
 # -ffp-contract=off: the pointwise kernels must round like the reference's unfused torch ops.

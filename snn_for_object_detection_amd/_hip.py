@@ -127,6 +127,10 @@ SIGNATURES = {
     "snn_act_bwd": (c_int, [_I, _P, _P, _P, _P, _L, _P]),
     "snn_lstm_cell_fwd": (c_int, [_P, _P, _P, _P, _L, _I, _P]),
     "snn_lstm_cell_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
+    "snn_convlstm_seq_supported": (c_int, [_I, _I, _L]),
+    "snn_convlstm_seq_tile": (c_int, [_I, _I, _L]),
+    "snn_convlstm_seq_fwd": (c_int, [_P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _P]),
+    "snn_convlstm_seq_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _I, _L, _I, _I, _P]),
     "snn_pool_fwd": (c_int, [_I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
     "snn_pool_bwd": (c_int, [_I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
     "snn_upsample_fwd": (c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),

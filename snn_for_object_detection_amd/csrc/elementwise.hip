@@ -212,8 +212,7 @@ __global__ void k_act_bwd(int act, const float* __restrict__ x, const float* __r
 }
 
 // ------------------------------------------------------------------------------------------ ConvLSTM cell
-// gates[m][4C] = (input, forget, output, candidate) pre-activations, conv_lstm.py:66-76
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+// gates[m][4C] = (input, forget, output, candidate) pre-activations, conv_lstm.py:66-76 (sigmoidf_: snn_common.h)
 
 __global__ void k_lstm_fwd(const float* __restrict__ gates, const float* __restrict__ c_prev, float* __restrict__ h,
                            float* __restrict__ c, int64_t M, int C) {

@@ -118,6 +118,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // activation tensor in HBM is fp32, or bf16 = the upper half of the fp32 pattern, rounded to nearest even when stored.
 // Kernels compute in fp32 registers either way; SnnStore<BF> moves 1 or 4 consecutive elements at ELEMENT index i.
 #ifdef __HIPCC__
+// the ConvLSTM gate non-linearity, shared by the cell kernels (elementwise.hip) and the sequence scan (lstm.hip)
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 typedef unsigned snn_u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 snn_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float snn_f32x2 __attribute__((ext_vector_type(2)));

@@ -2292,6 +2292,107 @@ def lstm_cell(gates: torch.Tensor, c_prev: Optional[torch.Tensor]):
     return _LstmCell.apply(gates, c_prev)
 
 
+# One launch per pass over the whole sequence instead of a time-outer loop of concat + gate conv + cell (bisecting aid).
+USE_LSTM_SCAN = not os.environ.get("SNN_NO_LSTM_SCAN")
+
+
+def conv_lstm_scan_covers(in_channels: int, hidden_channels: int, ldx: int) -> bool:
+    """``snn_convlstm_seq_supported``: the function the launchers check (host-only, no device needed)."""
+    return bool(_hip.query("snn_convlstm_seq_supported", int(in_channels), int(hidden_channels), int(ldx)))
+
+
+def conv_lstm_scan_tile(in_channels: int, hidden_channels: int, pixels: int) -> int:
+    """Pixels per workgroup of the two scan kernels for ``pixels = B*H*W`` (``snn_convlstm_seq_tile``; 0: not covered)."""
+    return int(_hip.query("snn_convlstm_seq_tile", int(in_channels), int(hidden_channels), int(pixels)))
+
+
+class _ConvLstmSeq(Function):
+    """ConvLSTM with 1x1 gates over ``[T,B,Cin,H,W]`` (conv_lstm.py:51-78): one scan kernel forward, one backward, and ONE
+    weight-gradient launch over the ``T*B`` frames of ``[x ; h_prev]`` with ``dy = dgates``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, h0, c0, slot, bwd_prec):
+        _require_device(x, "conv_lstm_sequence input")
+        _require_device(weight, "conv_lstm_sequence weight")
+        x = _raw_to_cl(x)
+        T, B, Cin, H, W = _dims5(x)
+        C4, K, KH, KW = weight.shape
+        Ch = C4 // 4
+        if (KH, KW) != (1, 1) or K != Cin + Ch or C4 != 4 * Ch:
+            raise RuntimeError(f"conv_lstm_sequence: weight {tuple(weight.shape)} is no 1x1 gate weight for {Cin} inputs")
+        w = weight.detach()
+        w_ohwi = w if is_channels_last(w) else _raw_dense_cl(w)
+        if h0 is not None:
+            h0, c0 = _raw_dense_cl(h0), _raw_dense_cl(c0)
+        M = B * H * W
+        hs = _new_cl((T, B), Ch, H, W, x)
+        cT = _new_cl((B,), Ch, H, W, x)
+        save_g = save_c = None
+        if any(ctx.needs_input_grad[:4]):   # (eval / no_grad / predict_sequence: nothing but hs and c_T is written)
+            save_g = torch.empty((T, M, C4), device=x.device, dtype=_F32)
+            save_c = torch.empty((T, M, Ch), device=x.device, dtype=_F32)
+        _hip.call("snn_convlstm_seq_fwd", x.data_ptr(), cl_stride(x), w_ohwi.data_ptr(), _ptr(h0), _ptr(c0), hs.data_ptr(),
+                  cT.data_ptr(), _ptr(save_g), _ptr(save_c), T, M, Cin, Ch, _stream())
+        hT = hs[T - 1].clone()
+        ctx.save_for_backward(x, w_ohwi, h0, c0, hs, save_g, save_c)
+        ctx.geom = (T, B, Cin, Ch, H, W)
+        ctx.slot, ctx.prec = slot, bwd_prec
+        ctx.set_materialize_grads(False)
+        return hs, hT, cT
+
+    @staticmethod
+    def backward(ctx, ghs, ghT, gcT):
+        x, w_ohwi, h0, c0, hs, save_g, save_c = ctx.saved_tensors
+        T, B, Cin, Ch, H, W = ctx.geom
+        M, K, C4 = B * H * W, Cin + Ch, 4 * Ch
+        ghs, ghT, gcT = (None if g is None else _raw_dense_cl(g) for g in (ghs, ghT, gcT))
+        st = _stream()
+        dgates = _new_cl((T, B), C4, H, W, x)
+        dx = _new_cl((T, B), Cin, H, W, x) if ctx.needs_input_grad[0] else None
+        dh0 = _new_cl((B,), Ch, H, W, x) if (h0 is not None and ctx.needs_input_grad[2]) else None
+        dc0 = _new_cl((B,), Ch, H, W, x) if (c0 is not None and ctx.needs_input_grad[3]) else None
+        _hip.call("snn_convlstm_seq_bwd", w_ohwi.data_ptr(), save_g.data_ptr(), save_c.data_ptr(), _ptr(c0), _ptr(ghs),
+                  _ptr(ghT), _ptr(gcT), dgates.data_ptr(), _ptr(dx), Cin, _ptr(dh0), _ptr(dc0), T, M, Cin, Ch, st)
+        dw = None
+        if ctx.needs_input_grad[1]:
+            # xh = [x ; h_prev] per frame, h_prev = h0 followed by hs[0 .. T-2]
+            xh = _new_cl((T, B), K, H, W, x)
+            _hip.call("snn_copy_channels", x.data_ptr(), cl_stride(x), xh.data_ptr(), K, T * M, Cin, st)
+            hp = xh.narrow(2, Cin, Ch)
+            if h0 is None:
+                hp[0].zero_()
+            else:
+                _hip.call("snn_copy_channels", h0.data_ptr(), Ch, hp.data_ptr(), K, M, Ch, st)
+            if T > 1:
+                _hip.call("snn_copy_channels", hs.data_ptr(), Ch, hp[1].data_ptr(), K, (T - 1) * M, Ch, st)
+            splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, K, H, W, C4, 1, 1, 1, 0, ctx.prec)
+            slot = ctx.slot
+            with _WgradLaunch(x.device, slot is not None, splitk, C4, K, hold=(xh, dgates)) as (stream, ws, _):
+                if slot is not None:
+                    dst, accumulate = slot.buf, slot.claim()
+                else:
+                    dst, accumulate = torch.empty((C4, 1, 1, K), device=x.device, dtype=_F32), 0
+                _hip.call("snn_conv2d_wgrad", xh.data_ptr(), K, dgates.data_ptr(), C4, dst.data_ptr(), T * B, H, W, K, H, W,
+                          C4, 1, 1, 1, 0, accumulate, ws.data_ptr(), splitk, ctx.prec, stream)
+            if slot is None:
+                dw = dst.permute(0, 3, 1, 2)
+        return dx, dw, dh0, dc0, None, None
+
+
+def conv_lstm_sequence(X: torch.Tensor, weight: torch.Tensor, state: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                       backward_precision: Optional[str] = None):
+    """ConvLSTM with 1x1 gates over a whole sequence ``[T,B,Cin,H,W]`` -> ``(hs, (h_T, c_T))``; ``weight`` is the gate
+    convolution's ``[4Ch, Cin+Ch, 1, 1]`` (gate order input, forget, output, candidate), ``state`` an ``(h0, c0)`` pair of
+    ``[B,Ch,H,W]`` or None for zeros.  The gate products are exact fp32 (fp32 MFMA); ``backward_precision`` is the weight
+    gradient's arithmetic (None = the session default).  Shapes outside ``conv_lstm_scan_covers`` are an error here:
+    ``layer_gen.ConvLSTM`` routes them to the stepwise path."""
+    h0, c0 = (None, None) if state is None else state
+    if (h0 is None) != (c0 is None):
+        raise RuntimeError("conv_lstm_sequence: the state is an (h, c) pair or None")
+    hs, hT, cT = _ConvLstmSeq.apply(X, weight, h0, c0, _slot_of(weight), _prec_codes(None, backward_precision)[1])
+    return hs, (hT, cT)
+
+
 class _StackTime(Function):
     """``torch.stack`` over per-timestep ``[B,C,H,W]`` results into one channels-last ``[T,B,C,H,W]``."""
 

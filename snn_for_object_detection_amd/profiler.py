@@ -140,6 +140,19 @@ def work_of(name: str, a):
         T, M, C = a[14], a[15], a[16]
         elems = float(T) * M * C
         return "k_lif_bwd_ckpt", 28.0 * elems, 4.0 * elems * 3.5
+    # The ConvLSTM sequence scans issue fp32 MFMA.  Their labels deliberately do NOT start with "k_conv": bench.py prices
+    # every k_conv* family against the matrix peak of the session's CONVOLUTION arithmetic, which is not theirs - under
+    # these names the rows carry their FLOPs and bytes and are priced against HBM only.
+    if name == "snn_convlstm_seq_fwd":
+        T, M, Cin, Ch = a[9], a[10], a[11], a[12]
+        px = float(T) * M
+        saved = 5 * Ch if a[7] is not None else 0   # gates after their non-linearity + c_t
+        return "k_lstm_seq_fwd", 2.0 * px * 4 * Ch * (Cin + Ch), 4.0 * (px * (Cin + Ch + saved) + 4 * Ch * (Cin + Ch))
+    if name == "snn_convlstm_seq_bwd":
+        T, M, Cin, Ch = a[12], a[13], a[14], a[15]
+        px = float(T) * M
+        moved = 5 * Ch + 4 * Ch + (Ch if a[4] is not None else 0) + (Cin if a[8] is not None else 0)   # saved, dgates, gh, dx
+        return "k_lstm_seq_bwd", 2.0 * px * 4 * Ch * (Cin + Ch), 4.0 * (px * moved + 4 * Ch * (Cin + Ch))
     if name in ("snn_bn_stats", "snn_bn_stats_bf16"):
         T, M, C = a[2], a[3], a[4]
         sb = name.endswith("_bf16")
