@@ -27,9 +27,17 @@ SCRATCH = os.path.join(os.path.dirname(HERE), "build")   # tuning / stamp / cloc
 LIB_NAME = "libsnn_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 STAMP_PATH = LIB_PATH + ".buildstamp"
-SOURCES = ("elementwise.hip", "neuron.hip", "conv.hip", "wgrad_halo.hip", "conv_halo.hip", "detect.hip",
-           "targets.hip", "metrics.hip", "lstm.hip")
-HEADERS = (os.path.join(CSRC, "snn_common.h"), os.path.join(INCLUDE, "snn_hip.h"))
+# (the two longest compiles first: the pool starts them at once and the short ones fill in around them)
+SOURCES = ("scan_bwd.hip", "conv.hip", "elementwise.hip", "bn_stats.hip", "scan_fwd.hip", "bn_bwd.hip", "wgrad_halo.hip",
+           "conv_halo.hip", "detect.hip", "targets.hip", "metrics.hip", "lstm.hip")
+MAX_WORKERS = 8   # hipcc processes at once: a fixed cap, never the machine's CPU count
+
+
+def headers() -> list:
+    """Every ``csrc/*.h`` (sorted) and ``include/snn_hip.h``: what each object's cache key covers beside its own source -
+    the headers ``source_fingerprint()`` lists, so a new header cannot be left out of the key."""
+    return [os.path.join(CSRC, n) for n in sorted(os.listdir(CSRC)) if n.endswith(".h")] + [os.path.join(INCLUDE, "snn_hip.h")]
+
 ARCH = "gfx950"
 # -ffp-contract=off: the pointwise kernels must round like the reference's unfused torch ops.
 FLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-ffp-contract=off", "-std=c++17", "-Wall",
@@ -93,7 +101,7 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, stam
     if tuning or stamp or clock:
         return _build_tuning(hipcc, verbose, stamp, clock)
     cc = _compiler_id(hipcc)
-    header_bytes = b"".join(open(h, "rb").read() for h in HEADERS)
+    header_bytes = b"".join(open(h, "rb").read() for h in headers())
     objs, jobs = [], []
     for src in SOURCES:
         spath = os.path.join(CSRC, src)
@@ -119,7 +127,7 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, stam
             json.dump({"key": key}, f)
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as pool:
+        with ThreadPoolExecutor(max_workers=min(MAX_WORKERS, len(jobs))) as pool:
             list(pool.map(compile_one, jobs))
     if os.path.exists(STAMP_PATH):
         os.remove(STAMP_PATH)   # never leave a stamp that vouches for a half-written library

@@ -1761,7 +1761,7 @@ __global__ __launch_bounds__(kThreads, WGRAD ? 4 : 1) void k_conv_first(const fl
                 gv = gv_next;
                 const int oxn = ox + PP < g.Wo ? ox + PP : ox;
                 gv_next = St::ld4_last(dy, dyrow + oxn * ldy);
-                if constexpr (BNAPPLY) {   // the statement of k_bn_bwd_apply (neuron.hip): same roundings
+                if constexpr (BNAPPLY) {   // the statement of k_bn_bwd_apply (bn_bwd.hip): same roundings
                     const f32x4 yv = yv_next;
                     yv_next = St::ld4_last(g.bn_y, byrow + oxn * (int)g.bn_ldy);
 #pragma unroll

@@ -1,15 +1,9 @@
-// Fused BatchNorm-apply + spiking-neuron temporal scan, forward and BPTT backward (gfx950).
+// Fused BatchNorm-apply + spiking-neuron temporal scan, BPTT backward (gfx950): the reverse scan, the LIF scan from
+// checkpoints, and the gradients of per-channel time constants.  Forward: scan_fwd.hip; what the two share: scan_common.h.
 //
-// Memory-bound kernels: one thread owns VEC(=4) consecutive channels of one pixel and walks the
-// T timesteps with the membrane state (v, i) in registers; every HBM access is a 16-byte
-// lane-contiguous vector.  Compiled with -ffp-contract=off so each statement rounds like the
-// reference's unfused torch ops (oracle/neurons.py).
-//
-// Reference semantics: layer_gen.py:211-214 (BatchNorm2d, per-timestep batch statistics),
-// layer_gen.py:232-235 / 252-254 (norse LIFCell / LICell), tiny_yolo.py:39-44 (LI -> Tanh).
-#include <stdlib.h>
+// Reference semantics: layer_gen.py:232-235 / 252-254 (norse LIFCell / LICell), tiny_yolo.py:39-44 (LI -> Tanh).
 #include <algorithm>
-#include "snn_common.h"
+#include "scan_common.h"
 
 #ifdef SNN_TUNING
 // tuning builds only: timing experiments on the reverse scan's BatchNorm sums (WRONG results): bit 0 no LDS accumulation,
@@ -22,519 +16,6 @@ extern "C" int snn_debug_set_bwd_abl(int v) { return (int)hipMemcpyToSymbol(HIP_
 #endif
 
 namespace {
-
-constexpr int kThreads = 256;
-#ifndef SNN_SCAN_NT_AUX
-#define SNN_SCAN_NT_AUX 2   // cache-policy operand of the reverse scan's last-use loads (gfx950: bit 1 = nt)
-#endif
-
-template <int VEC> struct Vec;
-template <> struct Vec<4> {
-    typedef f32x4 type;
-    static __device__ __forceinline__ f32x4 load(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-    static __device__ __forceinline__ void store(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-};
-// 8 channels per thread: the bf16-storage scans (16 bytes of bf16 per access; fp32 side tensors as two 16-byte halves)
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-template <> struct Vec<8> {
-    typedef f32x8 type;
-    static __device__ __forceinline__ f32x8 load(const float* p) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-        return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-    static __device__ __forceinline__ void store(float* p, f32x8 v) {
-        *reinterpret_cast<f32x4*>(p) = __builtin_shufflevector(v, v, 0, 1, 2, 3);
-        *reinterpret_cast<f32x4*>(p + 4) = __builtin_shufflevector(v, v, 4, 5, 6, 7);
-    }
-};
-template <> struct Vec<1> {
-    typedef float type;
-    static __device__ __forceinline__ float load(const float* p) { return *p; }
-    static __device__ __forceinline__ void store(float* p, float v) { *p = v; }
-};
-// activation tensors in the storage type (fp32, or bf16 in the bf16-storage mode: snn_common.h SnnStore): element index
-template <int VEC, bool SB> struct VecS;
-template <bool SB> struct VecS<4, SB> {
-    static __device__ __forceinline__ f32x4 load(const float* base, int64_t i) { return SnnStore<SB>::ld4(base, i); }
-    // the same for a tensor nobody reads again soon (non-temporal: what stays in L2 / the memory-side cache should be the
-    // tensors that go from a producer straight to its consumer - conv -> scan -> conv, scan -> apply -> data gradient)
-    static __device__ __forceinline__ f32x4 load_last(const float* base, int64_t i) {
-        if constexpr (SNN_SCAN_NT_AUX == 0) return SnnStore<SB>::ld4(base, i);
-        else if constexpr (SB) return snn_unpack_bf16x4(__builtin_nontemporal_load(
-                                   reinterpret_cast<const snn_u32x2*>(reinterpret_cast<const unsigned short*>(base) + i)));
-        else return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base + i));
-    }
-    static __device__ __forceinline__ void store(float* base, int64_t i, f32x4 v) { SnnStore<SB>::st4(base, i, v); }
-};
-template <> struct VecS<8, true> {   // 8 bf16 values = 16 bytes
-    static __device__ __forceinline__ f32x8 load(const float* base, int64_t i) {
-        typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-        const u32x4_ r = *reinterpret_cast<const u32x4_*>(reinterpret_cast<const unsigned short*>(base) + i);
-        const f32x4 a = snn_unpack_bf16x4(snn_u32x2{r[0], r[1]}), b = snn_unpack_bf16x4(snn_u32x2{r[2], r[3]});
-        return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-    static __device__ __forceinline__ f32x8 load_last(const float* base, int64_t i) {
-        typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-        const u32x4_* src = reinterpret_cast<const u32x4_*>(reinterpret_cast<const unsigned short*>(base) + i);
-        const u32x4_ r = SNN_SCAN_NT_AUX == 0 ? *src : __builtin_nontemporal_load(src);
-        const f32x4 a = snn_unpack_bf16x4(snn_u32x2{r[0], r[1]}), b = snn_unpack_bf16x4(snn_u32x2{r[2], r[3]});
-        return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-    static __device__ __forceinline__ void store(float* base, int64_t i, f32x8 v) {
-        typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-        const snn_u32x2 a = snn_pack_bf16x4(__builtin_shufflevector(v, v, 0, 1, 2, 3));
-        const snn_u32x2 b = snn_pack_bf16x4(__builtin_shufflevector(v, v, 4, 5, 6, 7));
-        *reinterpret_cast<u32x4_*>(reinterpret_cast<unsigned short*>(base) + i) = u32x4_{a[0], a[1], b[0], b[1]};
-    }
-};
-template <bool SB> struct VecS<1, SB> {
-    static __device__ __forceinline__ float load(const float* base, int64_t i) { return SnnStore<SB>::ld1(base, i); }
-    static __device__ __forceinline__ float load_last(const float* base, int64_t i) { return SnnStore<SB>::ld1(base, i); }
-    static __device__ __forceinline__ void store(float* base, int64_t i, float v) { SnnStore<SB>::st1(base, i, v); }
-};
-template <int VEC> __device__ __forceinline__ float& lane(typename Vec<VEC>::type& v, int j);
-template <> __device__ __forceinline__ float& lane<4>(f32x4& v, int j) { return reinterpret_cast<float*>(&v)[j]; }
-template <> __device__ __forceinline__ float& lane<8>(f32x8& v, int j) { return reinterpret_cast<float*>(&v)[j]; }
-template <> __device__ __forceinline__ float& lane<1>(float& v, int) { return v; }
-
-// ------------------------------------------------------------------------------------------
-// BatchNorm statistics: per (t, c) sum and sum of squares over the M pixels of timestep t.
-// grid = (chunks, T, channel blocks); partial[t][c][chunk][2] in fp64.
-// ------------------------------------------------------------------------------------------
-struct StatsPlan {
-    int vec, cvb, zblocks, chunks;
-};
-
-static StatsPlan stats_plan(int T, int64_t M, int C) {
-    StatsPlan pl;
-    pl.vec = (C % 4 == 0) ? 4 : 1;
-    int cv = C / pl.vec;
-    pl.cvb = cv < kThreads ? cv : kThreads;
-    pl.zblocks = (int)snn_ceil_div(cv, pl.cvb);
-    int P = kThreads / pl.cvb;
-    int64_t want = snn_ceil_div(snn_max_blocks(), (int64_t)T * pl.zblocks);
-    int64_t maxc = snn_ceil_div(M, (int64_t)P * 8);  // at least ~8 pixels per thread
-    if (want > maxc) want = maxc;
-    if (want < 1) want = 1;
-    pl.chunks = (int)want;
-    return pl;
-}
-
-template <int VEC, bool SB = false>
-__global__ __launch_bounds__(kThreads) void k_bn_stats(const float* __restrict__ y, int64_t ldy, int64_t M, int C,
-                                                       int cvb, double* __restrict__ partial) {
-    __shared__ double red[kThreads * 2 * VEC];
-    const int chunks = gridDim.x, chunk = blockIdx.x, t = blockIdx.y;
-    const int cv = C / VEC;
-    const int P = kThreads / cvb;
-    const int tid = threadIdx.x;
-    const int cgl = tid % cvb, ps = tid / cvb;
-    const int cg = blockIdx.z * cvb + cgl;
-    const bool active = (ps < P) && (cg < cv);
-    const int64_t per = snn_ceil_div_dev(M, chunks);
-    double s[VEC], q[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) s[j] = q[j] = 0.0;
-    if (active) {
-        const int64_t m0 = (int64_t)chunk * per;
-        int64_t m1 = m0 + per;
-        if (m1 > M) m1 = M;
-        const int64_t base = ((int64_t)t * M) * ldy + (int64_t)cg * VEC;   // element index (y: fp32, or bf16 with SB)
-        for (int64_t m = m0 + ps; m < m1; m += P) {
-            typename Vec<VEC>::type v = VecS<VEC, SB>::load(y, base + m * ldy);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                double d = (double)lane<VEC>(v, j);
-                s[j] += d;
-                q[j] += d * d;
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-        red[(tid * VEC + j) * 2 + 0] = s[j];
-        red[(tid * VEC + j) * 2 + 1] = q[j];
-    }
-    __syncthreads();
-    if (ps == 0 && cg < cv) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            double ss = 0.0, qq = 0.0;
-            for (int k = 0; k < P; ++k) {
-                ss += red[((k * cvb + cgl) * VEC + j) * 2 + 0];
-                qq += red[((k * cvb + cgl) * VEC + j) * 2 + 1];
-            }
-            double* dst = partial + snn_bn_partial_index(t, chunk, (int64_t)cg * VEC + j, chunks, C);
-            dst[0] = ss;
-            dst[1] = qq;
-        }
-    }
-}
-
-__global__ void k_bn_stats_finalize(const double* __restrict__ partial, int chunks, int T, int64_t M, int C,
-                                    const float* __restrict__ gamma, const float* __restrict__ bias, float eps,
-                                    const float* __restrict__ running_mean, const float* __restrict__ running_var,
-                                    int use_running, float* __restrict__ mean, float* __restrict__ invstd,
-                                    float* __restrict__ alpha, float* __restrict__ beta,
-                                    double* __restrict__ var_unbiased) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= T * C) return;
-    int t = idx / C, c = idx % C;
-    float mu, is;
-    if (use_running) {
-        mu = running_mean[c];
-        is = 1.0f / sqrtf(running_var[c] + eps);  // ATen eval path: invstd in fp32
-    } else {
-        double s = 0.0, q = 0.0;
-        for (int k = 0; k < chunks; ++k) {
-            const double* src = partial + snn_bn_partial_index(t, k, c, chunks, C);
-            s += src[0];
-            q += src[1];
-        }
-        double n = (double)M;
-        double m = s / n;
-        double var = q / n - m * m;
-        if (var < 0.0) var = 0.0;
-        mu = (float)m;
-        is = (float)(1.0 / sqrt(var + (double)eps));
-        if (var_unbiased) var_unbiased[idx] = (M > 1) ? var * n / (n - 1.0) : var;
-    }
-    mean[idx] = mu;
-    invstd[idx] = is;
-    float g = gamma ? gamma[c] : 1.0f;
-    float b = bias ? bias[c] : 0.0f;
-    float a = is * g;
-    alpha[idx] = a;
-    beta[idx] = b - mu * a;
-}
-
-// Partials written by a convolution epilogue (conv.hip) come in row tiles of `rows_per_chunk` output pixels that do
-// not line up with the timesteps: chunk k of step t is the part of tile (first tile of t) + k that lies in t, so
-// the number of written slots differs by one between steps.  rows_per_chunk == 0: every one of `chunks` is written.
-__device__ __forceinline__ int chunks_of_step(int chunks, int rows_per_chunk, int t, int64_t M) {
-    if (rows_per_chunk <= 0) return chunks;
-    return (int)((((int64_t)t + 1) * M - 1) / rows_per_chunk - ((int64_t)t * M) / rows_per_chunk) + 1;
-}
-
-// One launch for the whole statistics second phase of a layer (was: finalize + running update, 27 us of two
-// latency-bound kernels 22 times per step).  One block per channel; SUB lanes share the chunk partials of one
-// (t, c) (each sums every SUB-th chunk in order, then a fixed xor tree), 32 timesteps per pass; thread 0 applies the T
-// sequential running-stat updates of one reference forward from LDS.  Fixed summation order: deterministic.
-// SUB = 8 for the few chunks snn_bn_stats writes, 32 for the hundreds of row tiles a convolution epilogue leaves.
-template <int SUB>
-__global__ __launch_bounds__(32 * SUB) void k_bn_stats_finalize_fused(
-    const double* __restrict__ partial, int chunks, int rows_per_chunk, int T, int64_t M, int C,
-    const float* __restrict__ gamma,
-    const float* __restrict__ bias, float eps, float momentum, float* __restrict__ running_mean,
-    float* __restrict__ running_var, int use_running, float* __restrict__ mean, float* __restrict__ invstd,
-    float* __restrict__ alpha, float* __restrict__ beta) {
-    __shared__ float sm_mean[32];
-    __shared__ double sm_var[32];
-    const int c = blockIdx.x;
-    const int sub = threadIdx.x % SUB, tl = threadIdx.x / SUB;
-    const bool update = !use_running && running_mean && running_var;
-    float rm = 0.f, rv = 0.f;
-    if (update && threadIdx.x == 0) {
-        rm = running_mean[c];
-        rv = running_var[c];
-    }
-    const float g = gamma ? gamma[c] : 1.0f;
-    const float b = bias ? bias[c] : 0.0f;
-    const double mom = (double)momentum;
-    for (int tb = 0; tb < T; tb += 32) {
-        const int t = tb + tl;
-        double s = 0.0, q = 0.0;
-        if (!use_running && t < T) {
-            const int nk = chunks_of_step(chunks, rows_per_chunk, t, M);
-            const double* base = partial;
-            int k = sub;
-            constexpr int U = SUB >= 32 ? 8 : 4;   // loads in flight (the loop is latency-bound), added in chunk order
-            for (; k + (U - 1) * SUB < nk; k += U * SUB) {
-                double2 p[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    p[u] = *reinterpret_cast<const double2*>(base + snn_bn_partial_index(t, k + u * SUB, c, chunks, C));
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    s += p[u].x;
-                    q += p[u].y;
-                }
-            }
-            for (; k < nk; k += SUB) {
-                const double2 p0 = *reinterpret_cast<const double2*>(base + snn_bn_partial_index(t, k, c, chunks, C));
-                s += p0.x; q += p0.y;
-            }
-        }
-        for (int stride = SUB / 2; stride >= 1; stride >>= 1) {
-            s += __shfl_xor(s, stride, 64);
-            q += __shfl_xor(q, stride, 64);
-        }
-        if (sub == 0 && t < T) {
-            const int idx = t * C + c;
-            float mu, is;
-            if (use_running) {
-                mu = running_mean[c];
-                is = 1.0f / sqrtf(running_var[c] + eps);  // ATen eval path: invstd in fp32
-            } else {
-                const double n = (double)M;
-                const double m = s / n;
-                double var = q / n - m * m;
-                if (var < 0.0) var = 0.0;
-                mu = (float)m;
-                is = (float)(1.0 / sqrt(var + (double)eps));
-                sm_mean[tl] = mu;
-                sm_var[tl] = (M > 1) ? var * n / (n - 1.0) : var;
-            }
-            mean[idx] = mu;
-            invstd[idx] = is;
-            const float a = is * g;
-            alpha[idx] = a;
-            beta[idx] = b - mu * a;
-        }
-        if (update) {
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const int nt = T - tb < 32 ? T - tb : 32;
-                for (int k = 0; k < nt; ++k) {
-                    rm = (float)(mom * (double)sm_mean[k] + (1.0 - mom) * (double)rm);
-                    rv = (float)(mom * sm_var[k] + (1.0 - mom) * (double)rv);
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (update && threadIdx.x == 0) {
-        running_mean[c] = rm;
-        running_var[c] = rv;
-    }
-}
-
-// chunk partials -> sums[t][c][2] (the quantity a SyncBatchNorm exchange all-reduces, config.yaml:76)
-__global__ void k_bn_stats_reduce(const double* __restrict__ partial, int chunks, int rows_per_chunk, int T, int64_t M,
-                                  int C, double* __restrict__ sums) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= T * C) return;
-    int t = idx / C, c = idx % C;
-    double s = 0.0, q = 0.0;
-    const int nk = chunks_of_step(chunks, rows_per_chunk, t, M);
-    for (int k = 0; k < nk; ++k) {
-        const double* src = partial + snn_bn_partial_index(t, k, c, chunks, C);
-        s += src[0];
-        q += src[1];
-    }
-    sums[(int64_t)idx * 2 + 0] = s;
-    sums[(int64_t)idx * 2 + 1] = q;
-}
-
-// T sequential running-stat updates of one reference forward (one BatchNorm call per timestep).
-__global__ void k_bn_running_update(const float* __restrict__ mean, const double* __restrict__ var_unbiased, int T,
-                                    int C, float momentum, float* __restrict__ running_mean,
-                                    float* __restrict__ running_var) {
-    int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    float rm = running_mean[c], rv = running_var[c];
-    const double mom = (double)momentum;
-    for (int t = 0; t < T; ++t) {
-        rm = (float)(mom * (double)mean[t * C + c] + (1.0 - mom) * (double)rm);
-        rv = (float)(mom * var_unbiased[t * C + c] + (1.0 - mom) * (double)rv);
-    }
-    running_mean[c] = rm;
-    running_var[c] = rv;
-}
-
-// ------------------------------------------------------------------------------------------
-// Forward scan
-// ------------------------------------------------------------------------------------------
-// SAVE: 0 nothing for the backward pass; 1 the per-step state (vdec); 2 (LIF) the state (v, i) BEFORE every kCkpt-th step
-// into vdec = ckpt[chunk][2][M][C]: the backward scan recomputes the steps of a chunk from it (k_lif_bwd_ckpt) instead
-// of reading one saved value per step.  Half the saved-state memory of mode 1 at the same speed (forward faster,
-// backward slower by about as much); opt-in from functional.LIF_CHECKPOINT_BYTES.
-constexpr int kCkpt = 4;
-#ifndef SNN_SCAN_PREFETCH
-#define SNN_SCAN_PREFETCH 2   // steps of operands in flight ahead of the recurrence (forward scan)
-#endif
-// SB (SNN_SCAN_BF16_STORAGE): y, out, addend and vdec are bf16 tensors (pointers passed as float*, strides in elements)
-// PC (LIF, fp32 tensors; snn_lif_tau_fwd): the two time constants are per-channel arrays cmem_pc[C] / csyn_pc[C] instead of
-// the struct's scalars; a lane loads its VEC channels' pair once, before the time loop.  The other instances never read the
-// two pointers.
-template <int NEURON, int VEC, int SAVE, bool SB = false, bool PC = false>
-__global__ __launch_bounds__(kThreads) void k_affine_neuron_fwd(
-    const float* __restrict__ y, int64_t ldy, const float* __restrict__ alpha, const float* __restrict__ beta,
-    const float* __restrict__ v0, const float* __restrict__ i0, float* __restrict__ out, int64_t ldo,
-    const float* __restrict__ addend, int64_t ld_add, float* __restrict__ vT, float* __restrict__ iT,
-    float* __restrict__ vdec, int T, int64_t M, int C, snn_neuron_params p, int last_only,
-    const float* __restrict__ cmem_pc = nullptr, const float* __restrict__ csyn_pc = nullptr) {
-    // last_only (SNN_SCAN_LAST_STEP_ONLY): `out` is [M][ldo], only the last timestep's output is kept (the detection
-    // head: soda.py:141-144 returns the predictions of the last step) - T-1 of T output stores never happen
-    typedef typename Vec<VEC>::type V;
-    static_assert(!SB || SAVE != 2, "the checkpointed scan keeps fp32 checkpoints: not combined with bf16 storage");
-    static_assert(!PC || (NEURON == SNN_NEURON_LIF && !SB && SAVE != 2), "per-channel time constants: LIF on fp32 tensors");
-    const int cv = C / VEC;
-    const int64_t total = M * cv;
-    for (int64_t col = (int64_t)blockIdx.x * kThreads + threadIdx.x; col < total;
-         col += (int64_t)gridDim.x * kThreads) {
-        const int64_t m = col / cv;
-        const int c = (int)(col % cv) * VEC;
-        V v, i;
-        [[maybe_unused]] V cmv, csv;
-        if constexpr (PC) {
-            cmv = Vec<VEC>::load(cmem_pc + c);
-            csv = Vec<VEC>::load(csyn_pc + c);
-        }
-        if (NEURON != SNN_NEURON_NONE) {
-            if (v0) v = Vec<VEC>::load(v0 + m * C + c);
-            else {
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) lane<VEC>(v, j) = p.v_leak;
-            }
-            if (i0) i = Vec<VEC>::load(i0 + m * C + c);
-            else {
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) lane<VEC>(i, j) = 0.0f;
-            }
-        }
-        // The operands of a step - y, the BatchNorm affine (alpha, beta)[t][c], the shortcut - are requested kPrefetch steps
-        // ahead of the recurrence and rotate through registers: with the loads inside the step every iteration waited for
-        // its own alpha / beta loads (s_waitcnt vmcnt(0): a full memory latency per timestep, whatever was prefetched
-        // before them).  Steps past the end re-read the last one.  The pipelined loop must be free of branches around its
-        // memory operations (at a control-flow join the compiler's wait-count pass falls back to vmcnt(0)), so it exists
-        // in the two forms the layer-major step uses - BatchNorm affine, all T outputs, with / without a shortcut - and
-        // everything else (no affine, last step only) takes the plain loop with its run-time checks.
-        auto time_loop = [&](auto piped_c, auto add_c, auto noout_c, auto last_c) {
-        constexpr bool PIPED = decltype(piped_c)::value;       // affine present, ADD known, outputs: all steps or (LAST) one
-        // LAST (PIPED only; SNN_SCAN_LAST_STEP_ONLY, the detection heads' LI + Tanh): nothing is stored inside the loop, the
-        // last step's output once behind it - the plain loop below waited for every step's own loads, 32 dependent memory
-        // round trips (66 us for the 30x38 head at 2.9 TB/s)
-        constexpr bool LAST = decltype(last_c)::value;
-        constexpr bool ADD = decltype(add_c)::value;
-        // NOOUT (SNN_SCAN_SPIKES_FROM_VDEC; LIF without a shortcut, v_dec saved): no output tensor at all - the consumer
-        // forms the spikes itself, z = (v_dec > v_th), while it reads the saved potentials (snn_conv1x1_spikes_*)
-        constexpr bool NOOUT = decltype(noout_c)::value;
-        constexpr int kPrefetch = PIPED ? SNN_SCAN_PREFETCH : 0;
-        struct StepOps { V x, a, b, ad; };
-        auto fetch_step = [&](int t) {
-            const int tc = t < T ? t : T - 1;
-            const int64_t row = (int64_t)tc * M + m;
-            StepOps o;
-            o.x = VecS<VEC, SB>::load_last(y, row * ldy + c);   // (the convolution's output: next read in the backward pass)
-            if (PIPED || alpha) {
-                o.a = Vec<VEC>::load(alpha + (int64_t)tc * C + c);
-                o.b = Vec<VEC>::load(beta + (int64_t)tc * C + c);
-            }
-            if (PIPED ? ADD : addend != nullptr) o.ad = VecS<VEC, SB>::load_last(addend, row * ld_add + c);   // (as y)
-            return o;
-        };
-        StepOps sq[kPrefetch > 0 ? kPrefetch : 1];
-        if constexpr (kPrefetch > 0) {
-#pragma unroll
-            for (int k = 0; k < kPrefetch; ++k) sq[k] = fetch_step(k);
-        }
-        [[maybe_unused]] V o_keep;
-        for (int t = 0; t < T; ++t) {
-            const int64_t row = (int64_t)t * M + m;
-            if (SAVE == 2 && NEURON == SNN_NEURON_LIF && (t % kCkpt) == 0) {
-                float* ck = vdec + ((int64_t)(t / kCkpt) * 2 * M + m) * C + c;
-                Vec<VEC>::store(ck, v);
-                Vec<VEC>::store(ck + M * C, i);
-            }
-            StepOps cur;
-            if constexpr (kPrefetch > 0) {
-                cur = sq[0];
-#pragma unroll
-                for (int k = 0; k + 1 < kPrefetch; ++k) sq[k] = sq[k + 1];
-                sq[kPrefetch - 1] = fetch_step(t + kPrefetch);
-            } else {
-                cur = fetch_step(t);
-            }
-            V x = cur.x;
-            if (PIPED || alpha) {
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) lane<VEC>(x, j) = lane<VEC>(x, j) * lane<VEC>(cur.a, j) + lane<VEC>(cur.b, j);
-            }
-            V o, vd;
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                float xj = lane<VEC>(x, j);
-                if (NEURON == SNN_NEURON_NONE) {
-                    lane<VEC>(o, j) = xj;
-                } else {
-                    float vj = lane<VEC>(v, j), ij = lane<VEC>(i, j);
-                    if (NEURON == SNN_NEURON_SYNAPSE) {
-                        const float tau = (xj > 0.0f) ? p.tau_sec : p.tau_dis;
-                        const float p_new = vj + ((xj - vj) * tau) * p.dt;
-                        float gsyn = p_new;
-                        if (p.sigma != 0.0f) gsyn = (4.0f * p.sigma) * (p_new - p.sigma * (p_new * p_new));
-                        lane<VEC>(v, j) = p_new;
-                        lane<VEC>(o, j) = gsyn < 0.0f ? 0.0f : gsyn;
-                        lane<VEC>(vd, j) = p_new;
-                        continue;
-                    }
-                    float xin = xj;
-                    if (NEURON == SNN_NEURON_SLI) {
-                        xin = xj * (1.0f / (1.0f + expf(-(p.v_st - fabsf(vj)))));
-                        lane<VEC>(vd, j) = vj;
-                    }
-                    float i_new = ij + xin;
-                    float c_mem = p.c_mem, c_syn = p.c_syn;
-                    if constexpr (PC) {
-                        c_mem = lane<VEC>(cmv, j);
-                        c_syn = lane<VEC>(csv, j);
-                    }
-                    float dv = c_mem * ((p.v_leak - vj) + i_new);
-                    float v_dec = vj + dv;
-                    float di = c_syn * i_new;
-                    lane<VEC>(i, j) = i_new + di;
-                    if (NEURON == SNN_NEURON_LIF) {
-                        float u = v_dec - p.v_th;
-                        float z = (u > 0.0f) ? 1.0f : 0.0f;
-                        lane<VEC>(v, j) = (1.0f - z) * v_dec + z * p.v_reset;
-                        lane<VEC>(o, j) = z;
-                        lane<VEC>(vd, j) = v_dec;
-                    } else {
-                        lane<VEC>(v, j) = v_dec;
-                        lane<VEC>(o, j) = (NEURON == SNN_NEURON_LI_TANH) ? tanhf(v_dec) : v_dec;
-                    }
-                }
-            }
-            if (PIPED ? ADD : addend != nullptr) {  // residual shortcut folded into the store
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) lane<VEC>(o, j) += lane<VEC>(cur.ad, j);
-            }
-            if constexpr (LAST) {
-                o_keep = o;   // stored once behind the loop (no branch around a memory operation inside it)
-            } else if constexpr (!NOOUT) {
-                if (PIPED || !last_only) VecS<VEC, SB>::store(out, row * ldo + c, o);
-                else if (t == T - 1) VecS<VEC, SB>::store(out, m * ldo + c, o);
-            }
-            if (SAVE == 1 && (NEURON == SNN_NEURON_LIF || NEURON == SNN_NEURON_SLI || NEURON == SNN_NEURON_SYNAPSE)) {
-                // (non-temporal where the access is one plain 16-byte store: nobody reads v_dec before the backward pass,
-                // while `out` is the next convolution's operand and should be what stays in the caches)
-                if constexpr (VEC == 4 && !SB && SNN_SCAN_NT_AUX != 0) __builtin_nontemporal_store(vd, reinterpret_cast<f32x4*>(vdec + row * C + c));
-                else VecS<VEC, SB>::store(vdec, row * C + c, vd);
-            }
-        }
-        if constexpr (LAST) VecS<VEC, SB>::store(out, m * ldo + c, o_keep);
-        };
-        if constexpr (VEC > 1 && SAVE != 2) {
-            if (alpha && !last_only) {
-                if (addend) time_loop(std::true_type{}, std::true_type{}, std::false_type{}, std::false_type{});
-                else if (SAVE == 1 && NEURON == SNN_NEURON_LIF && !SB && out == nullptr)
-                    time_loop(std::true_type{}, std::false_type{}, std::true_type{}, std::false_type{});
-                else time_loop(std::true_type{}, std::false_type{}, std::false_type{}, std::false_type{});
-            } else if (alpha && last_only && !addend) {
-                time_loop(std::true_type{}, std::false_type{}, std::false_type{}, std::true_type{});
-            } else {
-                time_loop(std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
-            }
-        } else {
-            time_loop(std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
-        }
-        if (NEURON != SNN_NEURON_NONE) {
-            if (vT) Vec<VEC>::store(vT + m * C + c, v);
-            if (iT) Vec<VEC>::store(iT + m * C + c, i);
-        }
-    }
-}
 
 // value of the partner lane l ^ 32 (valid in the UPPER 32 lanes) / l ^ 16 (valid in the odd 16-lane rows)
 __device__ __forceinline__ float swap32_partner(float v) {
@@ -590,62 +71,6 @@ constexpr int kBwdNP = SNN_BWD_NP;
 #ifndef SNN_BWD_SB_DEPTH
 #define SNN_BWD_SB_DEPTH 3   // operand sets in flight in the bf16-storage reverse scan (2 or 3)
 #endif
-constexpr int kWaves = kThreads / 64;
-
-struct BwdPlan {
-    int vec, cvb, gy, gx, mode;  // mode 0: no sums, 1: ordered (shuffle + per-wave slabs), 2: LDS atomics
-    size_t lds_bytes;
-    int64_t rpb;                 // pixel rows per block
-};
-
-static bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
-// (Measured and rejected: a smaller slab budget - 32 / 16 KiB, more blocks of fewer channels - for the mid-size maps whose
-// 64 KiB plan leaves CUs idle.  The 30x38 x 128-channel scan alone went 81 -> 59 us in isolation, but inside the step the
-// family average rose from 98 to 125 us (bf16 storage) and 147 to 151 us (fp32): narrower channel runs per pixel and a
-// second round of blocks on the small maps cost more than the shorter serial chains gain.)
-static BwdPlan bwd_plan(int T, int64_t M, int C, bool with_sums) {
-    constexpr int lds_kib = 64;
-    BwdPlan pl;
-    pl.vec = (C % 4 == 0) ? 4 : 1;
-    int cv = C / pl.vec;
-    int cvb = cv < kThreads ? cv : kThreads;
-    pl.mode = 0;
-    pl.lds_bytes = 0;
-    if (with_sums) {
-        const bool ordered = is_pow2(cvb) || cvb >= 64;
-        pl.mode = ordered ? 1 : 2;
-        const int slabs = ordered ? kWaves : 1;
-        // LDS budget: slabs * T * cb * 2 floats
-        int64_t max_cvb = ((int64_t)lds_kib * 1024) / ((int64_t)slabs * T * 8 * pl.vec);
-        if (max_cvb < 1) max_cvb = 1;
-        if (cvb > max_cvb) {
-            cvb = (int)max_cvb;
-            if (ordered) {  // keep a power of two
-                int p2 = 1;
-                while (p2 * 2 <= cvb) p2 *= 2;
-                cvb = p2;
-            }
-        }
-        pl.lds_bytes = (size_t)slabs * T * cvb * pl.vec * 2 * sizeof(float);
-    }
-    pl.cvb = cvb;
-    pl.gy = (int)snn_ceil_div(cv, cvb);
-    int P = kThreads / cvb;
-    // Every block owns a contiguous run of pixel rows (P pixels each) of EQUAL length, processed kBwdNP rows at a
-    // time with the tail masked: all blocks are resident at once and finish together.  (A grid-stride loop over
-    // kBwdNP-row groups left e.g. 713 groups on 512 blocks: 2 rounds for 1.4 rounds of work.)
-    const int64_t rows = snn_ceil_div(M, (int64_t)P);
-    // blocks resident per CU by LDS (160 KiB per CU; 64 KiB slabs: 2, 32 KiB: 4, 16 KiB: 8 = the wave limit)
-    int64_t cap = with_sums ? (int64_t)(128 / lds_kib) * snn_num_cu() : snn_max_blocks();
-    if (const char* force = snn_tuning_env("SNN_BWD_CAP")) cap = atoi(force) > 0 ? atoi(force) : cap;  // tuning aid
-    cap = cap / pl.gy;
-    if (cap < 1) cap = 1;
-    const int64_t rpb = snn_ceil_div(rows, rows < cap ? rows : cap);
-    pl.gx = (int)snn_ceil_div(rows, rpb);
-    pl.rpb = rpb;
-    return pl;
-}
 
 // BUF (VEC = 4 only): the per-timestep operands are addressed through raw buffer resources - one per tensor and
 // timestep, lane offset -1 for lanes outside the tensor, so loads return zeros and stores are dropped by the hardware
@@ -1490,203 +915,7 @@ __global__ __launch_bounds__(kThreads) void k_lif_bwd_ckpt(
     }
 }
 
-// reduce block partials -> raw[t][c] = (sum gx, sum gx*y).  32 lanes per (t,c): lane k sums blocks k, k+32, ...
-// then a fixed xor tree combines the lanes.  `raw` must not alias the partial buffer (fp32 partials, fp64 result).
-// from_state (the scan ran with SNN_SCAN_SUMS_FROM_STATE): the second partial is sum(gx * x); raw still receives sum(gx * y)
-// = mean * sum(gx) + (sum(gx * x) - bias * sum(gx)) / (gamma * invstd) - what the all-reduce and k_bn_bwd_coef expect - and
-// the sum itself, from gx and y, for a channel whose gamma is exactly 0 (see k_bn_bwd_finalize_fused).
-__device__ __forceinline__ double sum_gx_y_from_state(double s1, double p, double mu, double is, double gam, double bnb) {
-    return mu * s1 + (p - bnb * s1) / (gam * is);
-}
-
-__global__ __launch_bounds__(256) void k_bn_bwd_reduce(const double* __restrict__ sums_, int gx_blocks, int T, int C,
-                                                       double* __restrict__ raw, int from_state, int64_t M,
-                                                       const float* __restrict__ gamma, const float* __restrict__ bn_bias,
-                                                       const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                       const float* __restrict__ gx, const float* __restrict__ y,
-                                                       int64_t ldy) {
-    const float* __restrict__ sums = reinterpret_cast<const float*>(sums_);
-    const int sub = threadIdx.x & 31;
-    const int idx = blockIdx.x * (blockDim.x / 32) + (threadIdx.x >> 5);
-    const bool live = idx < T * C;
-    const int c = live ? idx % C : 0, t = live ? idx / C : 0;
-    const double gam = (double)((from_state && gamma) ? gamma[c] : 1.0f);
-    const bool direct = from_state && gam == 0.0;   // uniform over the 32 lanes of an (t, c)
-    double s1 = 0.0, sy = 0.0;
-    if (live) {
-        for (int b = sub; b < gx_blocks; b += 32) {
-            const float2 v = *reinterpret_cast<const float2*>(sums + ((int64_t)b * T * C + idx) * 2);
-            s1 += (double)v.x;
-            sy += (double)v.y;
-        }
-        if (direct) {
-            sy = 0.0;
-            for (int64_t m = sub; m < M; m += 32)
-                sy += (double)gx[((int64_t)t * M + m) * C + c] * (double)y[((int64_t)t * M + m) * ldy + c];
-        }
-    }
-    for (int stride = 16; stride >= 1; stride >>= 1) {
-        s1 += __shfl_xor(s1, stride, 64);
-        sy += __shfl_xor(sy, stride, 64);
-    }
-    if (!live || sub != 0) return;
-    if (from_state && !direct)
-        sy = sum_gx_y_from_state(s1, sy, (double)mean[idx], (double)invstd[idx], gam, (double)(bn_bias ? bn_bias[c] : 0.0f));
-    raw[(int64_t)idx * 2 + 0] = s1;
-    raw[(int64_t)idx * 2 + 1] = sy;
-}
-
-// raw sums over M pixels (all-reduced over the ranks under SyncBatchNorm) -> backward coefficients;
-// raw_local (this rank's sums) -> (sum gx, sum gx*xhat) for the parameter gradients, written to `param_sums`
-__global__ void k_bn_bwd_coef(const double* __restrict__ raw, const double* __restrict__ raw_local, int T, int64_t M,
-                              int C, const float* __restrict__ gamma, const float* __restrict__ mean,
-                              const float* __restrict__ invstd, float* __restrict__ coefA, float* __restrict__ coefB,
-                              float* __restrict__ coefC, double* __restrict__ param_sums) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= T * C) return;
-    const int c = idx % C;
-    const double mu = (double)mean[idx], is = (double)invstd[idx];
-    const double s1 = raw[(int64_t)idx * 2 + 0], sy = raw[(int64_t)idx * 2 + 1];
-    const double l1 = raw_local[(int64_t)idx * 2 + 0], ly = raw_local[(int64_t)idx * 2 + 1];
-    const double s2 = is * (sy - mu * s1);  // sum gx * xhat
-    const double n = (double)M;
-    const double a = (double)(gamma ? gamma[c] : 1.0f) * is;
-    const double m1 = s1 / n, m2 = s2 / n;
-    coefA[idx] = (float)a;
-    coefB[idx] = (float)(-a * is * m2);
-    coefC[idx] = (float)(-a * m1 + a * is * mu * m2);
-    param_sums[(int64_t)idx * 2 + 0] = l1;
-    param_sums[(int64_t)idx * 2 + 1] = is * (ly - mu * l1);
-}
-
-__global__ void k_bn_bwd_params(const double* __restrict__ sums, int T, int C, float* __restrict__ dgamma,
-                                float* __restrict__ dbias, int accumulate) {
-    int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    double dg = 0.0, db = 0.0;
-    for (int t = 0; t < T; ++t) {
-        db += sums[((int64_t)t * C + c) * 2 + 0];
-        dg += sums[((int64_t)t * C + c) * 2 + 1];
-    }
-    if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)dg : (float)dg;
-    if (dbias) dbias[c] = accumulate ? dbias[c] + (float)db : (float)db;
-}
-
-// One launch for the BatchNorm-backward second phase of a layer (was: reduce + coefficients + parameter gradients).
-// One block per channel; 32 lanes share the block partials of one (t, c) (lane k sums blocks k, k+32, ... in order,
-// then a fixed xor tree), 32 timesteps per pass (1024 threads); thread 0 adds the per-timestep parameter sums in t order.
-__global__ __launch_bounds__(1024) void k_bn_bwd_finalize_fused(
-    const double* __restrict__ sums_, int gx_blocks, int T, int64_t M, int C, const float* __restrict__ gamma,
-    const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ coefA,
-    float* __restrict__ coefB, float* __restrict__ coefC, float* __restrict__ dgamma, float* __restrict__ dbias,
-    int accumulate, int from_state, const float* __restrict__ bn_bias, const float* __restrict__ gx,
-    const float* __restrict__ y, int64_t ldy) {
-    // from_state (the scan ran with SNN_SCAN_SUMS_FROM_STATE): the second partial is sum(gx * x), x = gamma*xhat + bias the
-    // neuron's input, so sum(gx * xhat) = (sum(gx * x) - bias * sum(gx)) / gamma.  A channel whose gamma is exactly 0 carries
-    // no xhat in x: for it (and only for it) the sum is formed here from gx and y - slow, one block per such channel.
-    const float* __restrict__ sums = reinterpret_cast<const float*>(sums_);  // fp32 block partials
-    __shared__ double sm_b[32], sm_g[32];
-    const int c = blockIdx.x;
-    const int sub = threadIdx.x & 31, tl = threadIdx.x >> 5;
-    double dg = 0.0, db = 0.0;
-    const double gam = (double)(gamma ? gamma[c] : 1.0f);
-    const double bnb = (double)((from_state && bn_bias) ? bn_bias[c] : 0.0f);
-    const bool direct = from_state && gam == 0.0;
-    for (int tb = 0; tb < T; tb += 32) {
-        const int t = tb + tl;
-        const int idx = t * C + c;
-        double s1 = 0.0, sy = 0.0;
-        if (t < T) {
-#pragma unroll 4
-            for (int bk = sub; bk < gx_blocks; bk += 32) {
-                const float2 v = *reinterpret_cast<const float2*>(sums + ((int64_t)bk * T * C + idx) * 2);
-                s1 += (double)v.x;
-                sy += (double)v.y;
-            }
-        }
-        if (direct) {   // uniform over the block
-            sy = 0.0;
-            if (t < T) {
-                for (int64_t m = sub; m < M; m += 32)
-                    sy += (double)gx[((int64_t)t * M + m) * C + c] * (double)y[((int64_t)t * M + m) * ldy + c];
-            }
-        }
-        for (int stride = 16; stride >= 1; stride >>= 1) {
-            s1 += __shfl_xor(s1, stride, 64);
-            sy += __shfl_xor(sy, stride, 64);
-        }
-        if (sub == 0 && t < T) {
-            const double mu = (double)mean[idx], is = (double)invstd[idx];
-            if (from_state && !direct) sy = sum_gx_y_from_state(s1, sy, mu, is, gam, bnb);   // (as k_bn_bwd_reduce: same bits)
-            const double s2 = is * (sy - mu * s1);  // sum gx * xhat
-            const double n = (double)M;
-            const double a = gam * is;
-            const double m1 = s1 / n, m2 = s2 / n;
-            coefA[idx] = (float)a;
-            coefB[idx] = (float)(-a * is * m2);
-            coefC[idx] = (float)(-a * m1 + a * is * mu * m2);
-            sm_b[tl] = s1;
-            sm_g[tl] = s2;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int nt = T - tb < 32 ? T - tb : 32;
-            for (int k = 0; k < nt; ++k) {
-                db += sm_b[k];
-                dg += sm_g[k];
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)dg : (float)dg;
-        if (dbias) dbias[c] = accumulate ? dbias[c] + (float)db : (float)db;
-    }
-}
-
-template <int VEC, bool SB = false>
-__global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(const float* __restrict__ gx, const float* __restrict__ y,
-                                                           int64_t ldy, const float* __restrict__ coefA,
-                                                           const float* __restrict__ coefB,
-                                                           const float* __restrict__ coefC, float* __restrict__ dy,
-                                                           int64_t lddy, int T, int64_t M, int C, int accumulate) {
-    typedef typename Vec<VEC>::type V;
-    const int cv = C / VEC;
-    const int64_t total = (int64_t)T * M * cv;
-    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
-        const int64_t row = e / cv;
-        const int c = (int)(e % cv) * VEC;
-        const int64_t t = row / M;
-        V g = VecS<VEC, SB>::load_last(gx, row * C + c);      // last reads of both: dy is what the next kernels want cached
-        V yv = VecS<VEC, SB>::load_last(y, row * ldy + c);
-        V a = Vec<VEC>::load(coefA + t * C + c);
-        V b = Vec<VEC>::load(coefB + t * C + c);
-        V k = Vec<VEC>::load(coefC + t * C + c);
-        V r;
-#pragma unroll
-        for (int j = 0; j < VEC; ++j)
-            lane<VEC>(r, j) = lane<VEC>(a, j) * lane<VEC>(g, j) + lane<VEC>(b, j) * lane<VEC>(yv, j) + lane<VEC>(k, j);
-        if (accumulate) {
-            V old = VecS<VEC, SB>::load(dy, row * lddy + c);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) lane<VEC>(r, j) += lane<VEC>(old, j);
-        }
-        VecS<VEC, SB>::store(dy, row * lddy + c, r);
-    }
-}
-
 // ---------------------------------------------------------------------------------- host side: plans and dispatch
-using AnyNeuron = OneOf<(int)SNN_NEURON_NONE, (int)SNN_NEURON_LIF, (int)SNN_NEURON_LI, (int)SNN_NEURON_LI_TANH,
-                        (int)SNN_NEURON_SLI, (int)SNN_NEURON_SYNAPSE>;
-
-constexpr bool bf16_neuron(int n) {   // the neurons with a bf16-storage scan
-    return n == SNN_NEURON_NONE || n == SNN_NEURON_LIF || n == SNN_NEURON_LI || n == SNN_NEURON_LI_TANH;
-}
-constexpr bool last_step_neuron(int n) { return n == SNN_NEURON_LIF || n == SNN_NEURON_LI || n == SNN_NEURON_LI_TANH; }
-constexpr bool rebuilds_x(int n) { return n == SNN_NEURON_SLI || n == SNN_NEURON_SYNAPSE; }
-const char* const kBf16Covers =
-    "bf16 storage covers NONE / LIF / LI / LI+Tanh on channel counts and strides that are multiples of 4 (8-byte aligned "
-    "tensors)";
 const char* const kBadSurrogate = "unknown surrogate code (SNN_SURR_SUPER / _TRIANGLE / _SIGMOID / _ATAN)";
 const char* const kGradientRuleCovers =
     "a non-default gradient rule (surrogate != SNN_SURR_SUPER or reset_detached != 0) is for SNN_NEURON_LIF";
@@ -1695,37 +924,6 @@ const char* const kGradientRuleNoBf16 =
 const char* const kSumsFromStateCovers =
     "SNN_SCAN_SUMS_FROM_STATE not covered (ask snn_affine_neuron_bwd_sums_from_state; LIF from the initial state, sums "
     "wanted, train-mode BatchNorm)";
-
-// ---- forward scan: which k_affine_neuron_fwd instance on which grid
-struct FwdPlan {
-    int vec, save;   // channels per access (1 / 4, bf16 tensors 4 / 8); SAVE of the kernel
-    unsigned blocks;
-};
-// lanes: the widest channel group (1 / 4 / 8) the strides and pointers of the call allow in one access
-static FwdPlan fwd_plan(int neuron, int64_t M, int C, int lanes, bool saves, bool ckpt) {
-    FwdPlan fp;
-    // 8 channels (16 bytes of bf16) per access when the layout allows: the scan is bound by the number of memory
-    // instructions, not by their bytes (8-byte accesses: 3.3 TB/s of bf16 against 5.1 TB/s with fp32 tensors)
-    static const bool no_v8 = snn_tuning_env("SNN_SCAN_NO_VEC8") != nullptr;   // tuning / bisecting aid
-    fp.vec = (lanes == 8 && no_v8) ? 4 : lanes;   // (8 is offered for bf16 tensors only)
-    const bool step_state = neuron == SNN_NEURON_LIF || rebuilds_x(neuron);   // the others save nothing per step
-    fp.save = (saves && step_state) ? (ckpt ? 2 : 1) : 0;
-    // every thread scans the same number of (pixel, channel group) items over all T (grid-stride, tail masked) and
-    // all blocks are resident at once: a capped grid with 1.4 items per thread would run 2 rounds for 1.4 of work
-    const int64_t total = M * (C / fp.vec);
-    const int64_t per_thread = snn_ceil_div(total, (int64_t)snn_max_blocks() * kThreads);
-    fp.blocks = (unsigned)snn_ceil_div(total, kThreads * per_thread);
-    return fp;
-}
-constexpr bool fwd_instance(int neuron, int vec, int save, bool sb, bool pc = false) {
-    if (pc && (neuron != SNN_NEURON_LIF || sb || save == 2)) return false;   // per-channel constants: fp32 LIF, plain scan
-    return (sb ? (vec != 1 && bf16_neuron(neuron) && save != 2) : vec != 8) &&
-           (save == 0 || neuron == SNN_NEURON_LIF || (save == 1 && rebuilds_x(neuron)));
-}
-
-const char* const kTauCovers =
-    "per-channel time constants are for SNN_NEURON_LIF on fp32 tensors (no SNN_SCAN_BF16_STORAGE), with the y-reading scan "
-    "(no SNN_SCAN_SUMS_FROM_STATE / SNN_SCAN_STATE_LOOKBACK)";
 const char* const kTauNoLastStep =
     "SNN_SCAN_LAST_STEP_ONLY is not built together with the sums of the time constants' gradients";
 
@@ -1817,172 +1015,6 @@ constexpr bool bwd_instance(int neuron, int vec, int mode, bool buf, int np, boo
 }  // namespace
 
 // -------------------------------------------------------------------------------------------- C ABI
-extern "C" size_t snn_bn_stats_partial_size(int T, int64_t M, int C) {
-    if (T <= 0 || M <= 0 || C <= 0) return 0;
-    StatsPlan pl = stats_plan(T, M, C);
-    // partial sums followed by T*C unbiased variances (scratch of the finalize step)
-    return (size_t)T * pl.chunks * C * 2 + (size_t)T * C;
-}
-
-static int bn_stats(const char* name, bool sb, const float* y, int64_t ldy, int T, int64_t M, int C, double* partial,
-                    void* stream) {
-    SNN_REQUIRE(y && partial, "%s: null pointer", name);
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C, "%s: bad shape T=%d M=%lld C=%d ldy=%lld", name, T, (long long)M, C,
-                (long long)ldy);
-    const StatsPlan pl = stats_plan(T, M, C);
-    SNN_REQUIRE(!sb || (pl.vec == 4 && ldy % 4 == 0 && aligned(8, {y})),
-                "%s: bad shape (C and ldy multiples of 4, y 8-byte aligned)", name);
-    SNN_REQUIRE(sb || pl.vec == 1 || (ldy % 4 == 0 && aligned(16, {y})), "%s: y must be 16-byte aligned with ldy%%4==0", name);
-    const dim3 grid(pl.chunks, T, pl.zblocks);
-    dispatch(
-        [&](auto VEC, auto SB) {
-            if constexpr (VEC() == 4 || !SB()) {
-                hipLaunchKernelGGL((k_bn_stats<VEC(), SB()>), grid, dim3(kThreads), 0, (hipStream_t)stream, y, ldy, M, C,
-                                   pl.cvb, partial);
-            }
-            return true;
-        },
-        OneOf<1, 4>{pl.vec}, Flag{sb});
-    SNN_CHECK_LAUNCH(name);
-    return 0;
-}
-
-extern "C" int snn_bn_stats(const float* y, int64_t ldy, int T, int64_t M, int C, double* partial, void* stream) {
-    return bn_stats("snn_bn_stats", false, y, ldy, T, M, C, partial, stream);
-}
-
-extern "C" int snn_bn_stats_bf16(const float* y, int64_t ldy, int T, int64_t M, int C, double* partial, void* stream) {
-    return bn_stats("snn_bn_stats_bf16", true, y, ldy, T, M, C, partial, stream);
-}
-
-extern "C" int snn_bn_stats_finalize(const double* partial, int chunks, int rows_per_chunk, int T, int64_t M, int C,
-                                     const float* gamma,
-                                     const float* bias, float eps, float momentum, float* running_mean,
-                                     float* running_var, int use_running, float* mean, float* invstd, float* alpha,
-                                     float* beta, void* stream) {
-    SNN_REQUIRE(mean && invstd && alpha && beta, "snn_bn_stats_finalize: null output");
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0, "snn_bn_stats_finalize: bad shape");
-    SNN_REQUIRE(use_running ? (running_mean && running_var) : (partial != nullptr),
-                "snn_bn_stats_finalize: missing statistics source");
-    SNN_REQUIRE(chunks >= 0 && rows_per_chunk >= 0 && (chunks > 0 || rows_per_chunk == 0),
-                "snn_bn_stats_finalize: bad partial layout (chunks %d, rows per chunk %d)", chunks, rows_per_chunk);
-    if (chunks == 0) chunks = stats_plan(T, M, C).chunks;   // the layout snn_bn_stats writes
-    dispatch(
-        [&](auto SUB) {
-            hipLaunchKernelGGL(k_bn_stats_finalize_fused<SUB()>, dim3(C), dim3(32 * SUB()), 0, (hipStream_t)stream, partial,
-                               chunks, rows_per_chunk, T, M, C, gamma, bias, eps, momentum, running_mean, running_var,
-                               use_running, mean, invstd, alpha, beta);
-            return true;
-        },
-        OneOf<8, 32>{(chunks > 64 && !use_running) ? 32 : 8});
-    SNN_CHECK_LAUNCH("snn_bn_stats_finalize");
-    return 0;
-}
-
-extern "C" int snn_bn_stats_reduce(const double* partial, int chunks, int rows_per_chunk, int T, int64_t M, int C,
-                                   double* sums, void* stream) {
-    SNN_REQUIRE(partial && sums && T > 0 && M > 0 && C > 0, "snn_bn_stats_reduce: bad arguments");
-    SNN_REQUIRE(chunks >= 0 && rows_per_chunk >= 0 && (chunks > 0 || rows_per_chunk == 0),
-                "snn_bn_stats_reduce: bad partial layout (chunks %d, rows per chunk %d)", chunks, rows_per_chunk);
-    if (chunks == 0) chunks = stats_plan(T, M, C).chunks;
-    int n = T * C;
-    hipLaunchKernelGGL(k_bn_stats_reduce, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, partial, chunks,
-                       rows_per_chunk, T, M, C, sums);
-    SNN_CHECK_LAUNCH("snn_bn_stats_reduce");
-    return 0;
-}
-
-extern "C" int snn_bn_stats_from_sums(const double* sums, int T, int64_t M_total, int C, const float* gamma,
-                                      const float* bias, float eps, float momentum, float* running_mean,
-                                      float* running_var, float* mean, float* invstd, float* alpha, float* beta,
-                                      double* var_scratch, void* stream) {
-    SNN_REQUIRE(sums && mean && invstd && alpha && beta && var_scratch, "snn_bn_stats_from_sums: null pointer");
-    SNN_REQUIRE(T > 0 && M_total > 0 && C > 0, "snn_bn_stats_from_sums: bad shape");
-    int n = T * C;
-    hipLaunchKernelGGL(k_bn_stats_finalize, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, sums, 1, T,
-                       M_total, C, gamma, bias, eps, running_mean, running_var, 0, mean, invstd, alpha, beta,
-                       var_scratch);
-    SNN_CHECK_LAUNCH("snn_bn_stats_from_sums");
-    if (running_mean && running_var) {
-        hipLaunchKernelGGL(k_bn_running_update, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, mean,
-                           var_scratch, T, C, momentum, running_mean, running_var);
-        SNN_CHECK_LAUNCH("snn_bn_running_update");
-    }
-    return 0;
-}
-
-static int neuron_fwd(int neuron, const float* y, int64_t ldy, const float* alpha, const float* beta, const float* v0,
-                      const float* i0, float* out, int64_t ldo, const float* addend, int64_t ld_addend, float* vT,
-                      float* iT, float* vdec, bool ckpt, int T, int64_t M, int C, const snn_neuron_params* p,
-                      int flags, void* stream, const float* cmem_pc = nullptr, const float* csyn_pc = nullptr) {
-    // cmem_pc / csyn_pc (snn_lif_tau_fwd, which has checked neuron and flags): per-channel time constants
-    const bool pc = cmem_pc != nullptr;
-    const char* const fn = pc ? "snn_lif_tau_fwd" : "snn_affine_neuron_fwd";   // the entry point the messages name
-    SNN_REQUIRE((flags & ~(SNN_SCAN_LAST_STEP_ONLY | SNN_SCAN_BF16_STORAGE | SNN_SCAN_SPIKES_FROM_VDEC)) == 0,
-                "%s: unknown flags 0x%x", fn, flags);
-    const int last_only = (flags & SNN_SCAN_LAST_STEP_ONLY) != 0;
-    const bool sb = (flags & SNN_SCAN_BF16_STORAGE) != 0;   // y, out, addend, vdec are bf16 tensors
-    const bool no_out = (flags & SNN_SCAN_SPIKES_FROM_VDEC) != 0;   // no output tensor: the consumer thresholds vdec
-    SNN_REQUIRE(y && p && (out || no_out), "%s: null pointer", fn);
-    if (no_out) {
-        SNN_REQUIRE(neuron == SNN_NEURON_LIF && vdec && !ckpt && !addend && !last_only && !sb && alpha && !out &&
-                        multiples(4, {C, ldy}) && aligned(16, {y, vdec}),
-                    "%s: SNN_SCAN_SPIKES_FROM_VDEC is for Norm -> LIF with saved potentials, no shortcut, "
-                    "all T steps, fp32 tensors, 4-channel groups; out must be NULL", fn);
-        ldo = C;   // (unused; keeps the checks below meaningful)
-    }
-    SNN_REQUIRE(!last_only || (last_step_neuron(neuron) && !addend),
-                "%s: SNN_SCAN_LAST_STEP_ONLY is for LIF / LI / LI+Tanh without a shortcut", fn);
-    SNN_REQUIRE(!addend || (ld_addend >= C && neuron != SNN_NEURON_LI_TANH),
-                "%s: addend needs ld_addend >= C and is not allowed with LI_TANH", fn);
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C && ldo >= C, "%s: bad shape", fn);
-    SNN_REQUIRE((alpha == nullptr) == (beta == nullptr), "%s: alpha/beta must come together", fn);
-    SNN_REQUIRE(neuron >= SNN_NEURON_NONE && neuron <= SNN_NEURON_SYNAPSE, "%s: bad neuron %d", fn,
-                neuron);
-    // n channels per access: the activation tensors (bf16: 2 bytes per element) and the fp32 per-pixel / per-channel ones
-    auto lanes_ok = [&](int n, size_t act_bytes) {
-        return multiples(n, {C, ldy, ldo, addend ? ld_addend : 0}) && aligned(act_bytes, {y, out, vdec, addend}) &&
-               aligned(16, {alpha, beta, v0, i0, vT, iT, cmem_pc, csyn_pc});
-    };
-    SNN_REQUIRE(!sb || (lanes_ok(4, 8) && !ckpt && bf16_neuron(neuron)), "%s: %s, without checkpointing", fn, kBf16Covers);
-    const int lanes = sb ? (lanes_ok(8, 16) ? 8 : 4) : (lanes_ok(4, 16) ? 4 : 1);
-    const FwdPlan fp = fwd_plan(neuron, M, C, lanes, vdec != nullptr, ckpt);
-    const bool launched = dispatch(
-        [&](auto NEURON, auto VEC, auto SAVE, auto SB, auto PC) {
-            if constexpr (fwd_instance(NEURON(), VEC(), SAVE(), SB(), PC())) {
-                hipLaunchKernelGGL((k_affine_neuron_fwd<NEURON(), VEC(), SAVE(), SB(), PC()>), dim3(fp.blocks), dim3(kThreads), 0,
-                                   (hipStream_t)stream, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT,
-                                   vdec, T, M, C, *p, last_only, cmem_pc, csyn_pc);
-                return true;
-            } else {
-                return false;
-            }
-        },
-        AnyNeuron{neuron}, OneOf<1, 4, 8>{fp.vec}, OneOf<0, 1, 2>{fp.save}, Flag{sb}, Flag{pc});
-    SNN_REQUIRE(launched, "%s: no kernel instance (neuron %d, vec %d, save %d)", fn, neuron, fp.vec, fp.save);
-    SNN_CHECK_LAUNCH(fn);
-    return 0;
-}
-
-extern "C" int snn_affine_neuron_fwd(int neuron, const float* y, int64_t ldy, const float* alpha, const float* beta,
-                                     const float* v0, const float* i0, float* out, int64_t ldo, const float* addend,
-                                     int64_t ld_addend, float* vT, float* iT, float* vdec, int T, int64_t M, int C,
-                                     const snn_neuron_params* p, int flags, void* stream) {
-    return neuron_fwd(neuron, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, false, T, M, C, p,
-                      flags, stream);
-}
-
-extern "C" int snn_lif_ckpt_interval(void) { return kCkpt; }
-
-extern "C" int snn_lif_fwd_ckpt(const float* y, int64_t ldy, const float* alpha, const float* beta, const float* v0,
-                                const float* i0, float* out, int64_t ldo, const float* addend, int64_t ld_addend,
-                                float* vT, float* iT, float* ckpt, int T, int64_t M, int C, const snn_neuron_params* p,
-                                void* stream) {
-    SNN_REQUIRE(ckpt, "snn_lif_fwd_ckpt: null checkpoint buffer");
-    return neuron_fwd(SNN_NEURON_LIF, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, ckpt, true, T, M,
-                      C, p, 0, stream);
-}
-
 extern "C" size_t snn_affine_neuron_bwd_sums_size(int T, int64_t M, int C) {
     if (T <= 0 || M <= 0 || C <= 0) return 0;
     BwdPlan pl = bwd_plan(T, M, C, true);
@@ -2045,7 +1077,8 @@ static int scan_bwd(const char* fn, int neuron, const float* g_out, int64_t ldg,
     }
     // SB, YF and the rule travel as ONE dispatched value: of their sixteen combinations seven have instances (bf16 storage
     // runs the default rule only, the from-state sums the first two rules), and every combination the dispatcher visits
-    // costs compile time whether bwd_instance keeps it or not (this file: 190 s with three values, 156 s with one).
+    // costs compile time whether bwd_instance keeps it or not (with the whole scan family in one source: 190 s with three
+    // values, 156 s with one; this file alone, as it is: 104 s).
     enum { kArmBf16 = kRuleTauSums + 1, kArmFromState, kArmFromStateGeneral };
     const int arm = sp.sb ? kArmBf16 : sp.yf ? kArmFromState + sp.rule : sp.rule;
     const bool launched = dispatch(
@@ -2091,18 +1124,6 @@ extern "C" int snn_lif_tau_param(const float* w_mem, const float* w_syn, int n, 
                        c_syn);
     SNN_CHECK_LAUNCH("snn_lif_tau_param");
     return 0;
-}
-
-extern "C" int snn_lif_tau_fwd(int neuron, const float* y, int64_t ldy, const float* alpha, const float* beta,
-                               const float* v0, const float* i0, float* out, int64_t ldo, const float* addend,
-                               int64_t ld_addend, float* vT, float* iT, float* vdec, int T, int64_t M, int C,
-                               const snn_neuron_params* p, const float* c_mem, const float* c_syn, int flags, void* stream) {
-    SNN_REQUIRE(neuron == SNN_NEURON_LIF && !(flags & SNN_SCAN_BF16_STORAGE), "snn_lif_tau_fwd: %s (neuron %d, flags 0x%x)",
-                kTauCovers, neuron, flags);
-    SNN_REQUIRE(c_mem && c_syn, "snn_lif_tau_fwd: null time constants");
-    // (the forward scan addresses with 64-bit pointers whatever the flag says)
-    return neuron_fwd(neuron, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, false, T, M, C, p,
-                      flags & ~SNN_SCAN_WIDE_ADDRESSING, stream, c_mem, c_syn);
 }
 
 extern "C" size_t snn_lif_tau_bwd_partial_size(int T, int64_t M, int C, int with_sums) {
@@ -2173,122 +1194,4 @@ extern "C" int snn_lif_bwd_ckpt(const float* g_out, int64_t ldg, const float* ck
         OneOf<1, 4>{pl.vec}, OneOf<0, 1, 2>{pl.mode});
     SNN_CHECK_LAUNCH("snn_lif_bwd_ckpt");
     return 0;
-}
-
-// block partials of the reverse scan -> raw (sum gx, sum gx*y) per (t, c); from_state: the scan ran with
-// SNN_SCAN_SUMS_FROM_STATE and its second partial is sum(gx * x)
-static int bn_bwd_reduce(const char* name, int from_state, const double* sums, int T, int64_t M, int C, const float* gamma,
-                         const float* bias, const float* mean, const float* invstd, const float* gx, const float* y,
-                         int64_t ldy, double* raw, void* stream) {
-    SNN_REQUIRE(sums != raw, "%s: raw must not alias the partial sums", name);
-    BwdPlan pl = bwd_plan(T, M, C, true);
-    int n = T * C;
-    hipLaunchKernelGGL(k_bn_bwd_reduce, dim3((n + 7) / 8), dim3(256), 0, (hipStream_t)stream, sums, pl.gx, T, C, raw,
-                       from_state, M, gamma, bias, mean, invstd, gx, y, ldy);
-    SNN_CHECK_LAUNCH(name);
-    return 0;
-}
-
-extern "C" int snn_bn_bwd_reduce(const double* sums, int T, int64_t M, int C, double* raw, void* stream) {
-    SNN_REQUIRE(sums && raw && T > 0 && M > 0 && C > 0, "snn_bn_bwd_reduce: bad arguments");
-    return bn_bwd_reduce("snn_bn_bwd_reduce", 0, sums, T, M, C, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, raw,
-                         stream);
-}
-
-extern "C" int snn_bn_bwd_reduce_from_state(const double* sums, int T, int64_t M, int C, const float* gamma, const float* bias,
-                                            const float* mean, const float* invstd, const float* gx, const float* y,
-                                            int64_t ldy, double* raw, void* stream) {
-    SNN_REQUIRE(sums && raw && mean && invstd && gx && y && T > 0 && M > 0 && C > 0 && ldy >= C,
-                "snn_bn_bwd_reduce_from_state: bad arguments");
-    return bn_bwd_reduce("snn_bn_bwd_reduce_from_state", 1, sums, T, M, C, gamma, bias, mean, invstd, gx, y, ldy, raw, stream);
-}
-
-extern "C" int snn_bn_bwd_coef(const double* raw, const double* raw_local, double* param_sums, int T, int64_t M_total,
-                               int C, const float* gamma, const float* mean, const float* invstd, float* coefA,
-                               float* coefB, float* coefC, float* dgamma, float* dbias, int accumulate,
-                               void* stream) {
-    SNN_REQUIRE(raw && raw_local && param_sums && mean && invstd && coefA && coefB && coefC,
-                "snn_bn_bwd_coef: null pointer");
-    SNN_REQUIRE(T > 0 && M_total > 0 && C > 0, "snn_bn_bwd_coef: bad shape");
-    int n = T * C;
-    hipLaunchKernelGGL(k_bn_bwd_coef, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, raw, raw_local, T,
-                       M_total, C, gamma, mean, invstd, coefA, coefB, coefC, param_sums);
-    SNN_CHECK_LAUNCH("snn_bn_bwd_coef");
-    if (dgamma || dbias) {
-        hipLaunchKernelGGL(k_bn_bwd_params, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, param_sums, T, C,
-                           dgamma, dbias, accumulate);
-        SNN_CHECK_LAUNCH("snn_bn_bwd_params");
-    }
-    return 0;
-}
-
-// single-process form: reduce the block partials in place, then coefficients and parameter gradients; from_state: sums
-// written by a scan that ran with SNN_SCAN_SUMS_FROM_STATE (second partial: sum(gx * x), see the kernel)
-static int bn_bwd_finalize(const char* name, int from_state, double* sums, int T, int64_t M, int C, const float* gamma,
-                           const float* bias, const float* mean, const float* invstd, const float* gx, const float* y,
-                           int64_t ldy, float* coefA, float* coefB, float* coefC, float* dgamma, float* dbias,
-                           int accumulate, void* stream) {
-    SNN_REQUIRE(sums && mean && invstd && coefA && coefB && coefC && (!from_state || (gx && y)), "%s: null pointer", name);
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && (!from_state || ldy >= C), "%s: bad shape", name);
-    BwdPlan pl = bwd_plan(T, M, C, true);
-    hipLaunchKernelGGL(k_bn_bwd_finalize_fused, dim3(C), dim3(1024), 0, (hipStream_t)stream, sums, pl.gx, T, M, C, gamma,
-                       mean, invstd, coefA, coefB, coefC, dgamma, dbias, accumulate, from_state, bias, gx, y, ldy);
-    SNN_CHECK_LAUNCH(name);
-    return 0;
-}
-
-extern "C" int snn_bn_bwd_finalize(double* sums, int T, int64_t M, int C, const float* gamma, const float* mean,
-                                   const float* invstd, float* coefA, float* coefB, float* coefC, float* dgamma,
-                                   float* dbias, int accumulate, void* stream) {
-    return bn_bwd_finalize("snn_bn_bwd_finalize", 0, sums, T, M, C, gamma, nullptr, mean, invstd, nullptr, nullptr, 0, coefA,
-                           coefB, coefC, dgamma, dbias, accumulate, stream);
-}
-
-extern "C" int snn_bn_bwd_finalize_from_state(double* sums, int T, int64_t M, int C, const float* gamma, const float* bias,
-                                              const float* mean, const float* invstd, const float* gx, const float* y,
-                                              int64_t ldy, float* coefA, float* coefB, float* coefC, float* dgamma,
-                                              float* dbias, int accumulate, void* stream) {
-    return bn_bwd_finalize("snn_bn_bwd_finalize_from_state", 1, sums, T, M, C, gamma, bias, mean, invstd, gx, y, ldy, coefA,
-                           coefB, coefC, dgamma, dbias, accumulate, stream);
-}
-
-// dy = A*gx + B*y + C per (t, c); sb: gx, y and dy are bf16 tensors
-static int bn_bwd_apply(const char* name, bool sb, const float* gx, const float* y, int64_t ldy, const float* coefA,
-                        const float* coefB, const float* coefC, float* dy, int64_t lddy, int T, int64_t M, int C,
-                        int accumulate, void* stream) {
-    SNN_REQUIRE(gx && y && coefA && coefB && coefC && dy, "%s: null pointer", name);
-    SNN_REQUIRE(T > 0 && M > 0 && C > 0 && ldy >= C && lddy >= C, "%s: bad shape", name);
-    const int vec = (multiples(4, {C, ldy, lddy}) && aligned(sb ? 8 : 16, {gx, y, dy}) && aligned(16, {coefA, coefB, coefC}))
-                        ? 4
-                        : 1;
-    SNN_REQUIRE(!sb || vec == 4, "%s: bad shape (C and strides multiples of 4, bf16 tensors 8-byte aligned)", name);
-    int64_t total = (int64_t)T * M * (C / vec);
-    int64_t blocks = snn_ceil_div(total, kThreads);
-    if (blocks > snn_max_blocks()) blocks = snn_max_blocks();
-    if (const char* force = snn_tuning_env("SNN_APPLY_CAP")) {   // tuning aid: blocks per launch of the apply pass
-        if (atoi(force) > 0 && blocks > atoi(force)) blocks = atoi(force);
-    }
-    dispatch(
-        [&](auto VEC, auto SB) {
-            if constexpr (VEC() == 4 || !SB()) {
-                hipLaunchKernelGGL((k_bn_bwd_apply<VEC(), SB()>), dim3((unsigned)blocks), dim3(kThreads), 0,
-                                   (hipStream_t)stream, gx, y, ldy, coefA, coefB, coefC, dy, lddy, T, M, C, accumulate);
-            }
-            return true;
-        },
-        OneOf<1, 4>{vec}, Flag{sb});
-    SNN_CHECK_LAUNCH(name);
-    return 0;
-}
-
-extern "C" int snn_bn_bwd_apply(const float* gx, const float* y, int64_t ldy, const float* coefA, const float* coefB,
-                                const float* coefC, float* dy, int64_t lddy, int T, int64_t M, int C, int accumulate,
-                                void* stream) {
-    return bn_bwd_apply("snn_bn_bwd_apply", false, gx, y, ldy, coefA, coefB, coefC, dy, lddy, T, M, C, accumulate, stream);
-}
-
-extern "C" int snn_bn_bwd_apply_bf16(const float* gx, const float* y, int64_t ldy, const float* coefA, const float* coefB,
-                                     const float* coefC, float* dy, int64_t lddy, int T, int64_t M, int C, int accumulate,
-                                     void* stream) {
-    return bn_bwd_apply("snn_bn_bwd_apply_bf16", true, gx, y, ldy, coefA, coefB, coefC, dy, lddy, T, M, C, accumulate, stream);
 }

@@ -1,4 +1,5 @@
-"""The fused Norm -> neuron scans (csrc/neuron.hip) against the float64 restatement of tests/norm_neuron_ref.py.
+"""The fused Norm -> neuron scans (csrc/scan_fwd.hip, scan_bwd.hip, with the BatchNorm passes of bn_stats.hip and
+bn_bwd.hip) against the float64 restatement of tests/norm_neuron_ref.py.
 
 Every row of CASES calls ``functional.affine_neuron`` forward and backward and compares outputs, final state, running
 statistics and every gradient with the reference.  Each row states the reverse-scan plan classes it is there for and

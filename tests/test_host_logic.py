@@ -125,6 +125,21 @@ def test_ctypes_signatures_agree_with_the_header():
             assert ctype_of(d) is a, (name, k, d.strip(), a)
 
 
+def test_build_lists_every_kernel_source_and_header():
+    """The build compiles exactly the ``csrc/*.hip`` files, and every ``csrc/*.h`` is part of each object's cache key
+    (a forgotten source fails at link time, a forgotten header leaves stale objects behind).  Needs no library."""
+    from snn_for_object_detection_amd import _build
+    on_disk = os.listdir(_build.CSRC)
+    assert {n for n in on_disk if n.endswith(".hip")} == set(_build.SOURCES)
+    assert len(_build.SOURCES) == len(set(_build.SOURCES))
+    keyed = {os.path.realpath(h) for h in _build.headers()}
+    for name in on_disk:
+        if name.endswith(".h"):
+            assert os.path.realpath(os.path.join(_build.CSRC, name)) in keyed, name
+    assert os.path.realpath(os.path.join(_build.INCLUDE, "snn_hip.h")) in keyed
+    assert 1 <= _build.MAX_WORKERS <= 8
+
+
 def test_neuron_constants_match_oracle():
     from oracle.neurons import neuron_constants
     p = S.functional.neuron_params()

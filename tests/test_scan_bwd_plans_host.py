@@ -1,7 +1,7 @@
 """The reverse-scan plans of ``snn_affine_neuron_bwd_plan`` / ``snn_lif_tau_bwd_plan`` against a recorded table.
 
 ``tests/golden/scan_bwd_plans.json`` was recorded ONCE, from the library of the commit before the two planners and the two
-launchers of ``csrc/neuron.hip`` became one (``ScanBwdPlan`` / ``scan_bwd``) - not from the code under test: that commit
+launchers of ``csrc/neuron.hip`` (now ``csrc/scan_bwd.hip``) became one (``ScanBwdPlan`` / ``scan_bwd``) - not from the code under test: that commit
 was built in a separate worktree and this module run as a script with ``SNN_HIP_LIB`` pointing at its ``libsnn_hip.so``
 (``SNN_HIP_LIB=<old tree>/snn_for_object_detection_amd/libsnn_hip.so python -m tests.test_scan_bwd_plans_host``; the ABI
 is the same, so this tree's binding drives it).  Both queries are host-only, and without a device the planner counts on
