@@ -117,7 +117,7 @@ __global__ void k_bn_stats_finalize(const double* __restrict__ partial, int chun
     beta[idx] = b - mu * a;
 }
 
-// Partials written by a convolution epilogue (conv.hip) come in row tiles of `rows_per_chunk` output pixels that do
+// Partials written by a convolution epilogue (conv_gather.hip) come in row tiles of `rows_per_chunk` output pixels that do
 // not line up with the timesteps: chunk k of step t is the part of tile (first tile of t) + k that lies in t, so
 // the number of written slots differs by one between steps.  rows_per_chunk == 0: every one of `chunks` is written.
 __device__ __forceinline__ int chunks_of_step(int chunks, int rows_per_chunk, int t, int64_t M) {

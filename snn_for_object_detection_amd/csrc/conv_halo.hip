@@ -1,6 +1,6 @@
 // Halo-resident 3x3 / stride 1 / pad 1 convolution for the 64- and 128-channel layers, forward AND data gradient,
 // on the gfx950 matrix cores with 16-bit split products (fp16 x 3 forward, bf16 x 3 backward; fp32 storage and
-// accumulation, same arithmetic per product as conv.hip's k_conv_gather).
+// accumulation, same arithmetic per product as conv_gather.hip's k_conv_gather).
 //
 // Replaces nn.Conv2d(C, C', 3, padding=1, bias=False) forward and its data gradient (reference
 // models/modules/layer_gen.py:129-136) for the layer-major schedule.  The data gradient is the SAME kernel: dx is a
@@ -29,28 +29,15 @@
 // (gradient accumulation), BatchNorm statistics partials of the stored values (forward).
 #include <stdlib.h>
 #include <type_traits>
-#include "snn_common.h"
+#include "conv_common.h"   // kThreads, the 16-bit / 32-bit vector types, the fp16 x 3 pre-scales
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int HBM_ = 128;               // strip cells (GEMM rows) per block
 constexpr int HCELLS = 288;             // halo cells staged per chunk (9 passes of 32): PW <= 79
 constexpr int HPIECE = HCELLS * 64;     // bytes of one piece image [cell][32 ch] x 16 bit
 constexpr int NPASS = HCELLS / 32;      // == taps: one staging pass is requested during every tap of the previous chunk
 static_assert(NPASS == 9, "one halo staging pass per tap");
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kF16WeightScale = 256.0f;   // the fp16 x 3 pre-scales of conv.hip (exact powers of two)
-constexpr float kF16ActScale = 16.0f;
-constexpr float kF16Unscale = 1.0f / (kF16WeightScale * kF16ActScale);
 
 struct HaloGeom {
     int64_t ldx, ldy, ld_add, ld_add2;
@@ -69,7 +56,7 @@ struct HaloGeom {
 
 __device__ __forceinline__ unsigned udiv_small(unsigned n, unsigned magic) { return __umulhi(n, magic); }
 
-// two 16-bit pieces of four fp32 values: fp16 (x * 2^4 = h + l) or bf16 (x = h + l); same arithmetic as conv.hip
+// two 16-bit pieces of four fp32 values: fp16 (x * 2^4 = h + l) or bf16 (x = h + l); same arithmetic as conv_gather.hip
 template <bool F16>
 __device__ __forceinline__ void split4(const f32x4& v, u32x2& hi, u32x2& lo) {
 #pragma unroll

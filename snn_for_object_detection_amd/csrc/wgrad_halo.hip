@@ -3,7 +3,7 @@
 //     dw[co][kh][kw][ci] = sum_{n,oy,ox} dy[n,oy,ox,co] * x[n, oy*s-1+kh, ox*s-1+kw, ci]
 //
 // Replaces ATen's conv backward-weight behind nn.Conv2d (reference models/modules/layer_gen.py:129-136) for the
-// layer-major schedule; called from snn_conv2d_wgrad (conv.hip), results go through the same ordered slab reduction.
+// layer-major schedule; called from snn_conv2d_wgrad (conv_wgrad.hip), results go through the same ordered slab reduction.
 //
 // Why a second kernel.  The implicit-GEMM weight gradient (k_conv_wgrad_pipe) gathers one shifted copy of x PER TAP:
 // every x element is fetched through L1 and split into its bf16 pieces nine times, and the dy tile is re-converted
@@ -29,7 +29,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <type_traits>
-#include "snn_common.h"
+#include "conv_common.h"   // kThreads, the 16-bit / 32-bit vector types, div_magic
 
 #ifdef SNN_TUNING
 // tuning builds only: cycle totals per phase of wave 0 of the first 1024 blocks {prologue, K loops, staging + barriers,
@@ -45,18 +45,11 @@ extern "C" int snn_debug_halo_stamps(unsigned long long* out, int n) {
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int HALO_CAP = 256;          // halo pixels a block can stage
 constexpr int PLANE = HALO_CAP * 64;   // bytes of one piece image: [pixel][32 channels] bf16
 constexpr int NJ = HALO_CAP / 32;      // staging f32x4 per thread
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 struct HaloGeom {
     int H, W, Cin, OH, OW, Cout, stride;
@@ -72,7 +65,6 @@ struct HaloGeom {
     float x_th;                         // NPROD 2: x holds saved LIF potentials, the operand is z = (v_dec > x_th)
 };
 
-__device__ __forceinline__ int div_magic(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
 __device__ __forceinline__ int div_magic2(int n, unsigned m) { return (int)__umulhi((unsigned)n, m); }  // divisor >= 2
 
 __device__ __forceinline__ void split_bf16(float a, float b, unsigned& hi, unsigned& lo) {

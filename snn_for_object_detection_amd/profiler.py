@@ -9,7 +9,7 @@ the work model of SURVEY section 8(d):
   wgrad each count as one forward); bytes = every operand read / written once;
 * fused norm+neuron scans: ``4 B`` per element per tensor the ideal fused kernel touches.
 
-Labels name the kernel template instance that ``csrc/conv.hip`` dispatches for the shape, so the
+Labels name the kernel template instance that ``csrc/conv_gather.hip`` / ``csrc/conv_wgrad.hip`` dispatch for the shape, so the
 rows can be matched with ``rocprofv3 --kernel-trace --stats`` output.
 """
 

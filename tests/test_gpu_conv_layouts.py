@@ -3,7 +3,8 @@
 The zero-copy Dense / C2f merge gives the convolutions channel slices of wider channels-last buffers (pixel stride >
 channel count), outputs at a channel offset inside a concat buffer and data gradients that are slices of a concat
 gradient; FlatTrainer puts every weight into one flat buffer without padding, so a weight starts on any float.  The host
-side of csrc/conv.hip picks a different kernel for each of these (launch_gather: vec / fast / out_vec; wgrad_common: the
+side of csrc/conv_gather.hip and csrc/conv_wgrad.hip picks a different kernel for each of these (launch_gather: vec / fast /
+out_vec; wgrad_common: the
 event-frame row kernels, the halo-resident weight gradient and its drop to the implicit GEMM, pipelined or not), so each
 test here runs ONE set of values through every layout and checks:
 

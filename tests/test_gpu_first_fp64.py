@@ -1,4 +1,4 @@
-"""The event-frame row kernel k_conv_first (csrc/conv.hip: Cin = 2, 3x3, Cout = 4 * 2^k <= 256), one row per plan class,
+"""The event-frame row kernel k_conv_first (csrc/conv_first.hip: Cin = 2, 3x3, Cout = 4 * 2^k <= 256), one row per plan class,
 against fp64 per element.
 
 Its five instances run behind snn_conv2d_fwd (with and without BatchNorm statistics partials; fp32 or bf16-stored y),

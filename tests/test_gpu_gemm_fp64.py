@@ -1,7 +1,7 @@
 """The implicit-GEMM convolutions, one row per plan class, against fp64 per element.
 
-k_conv_gather (forward / data gradient), k_conv_wgrad_pipe / k_conv_wgrad (weight gradient) and the slab reducers
-(k_wgrad_reduce, k_wgrad_reduce_once, k_wgrad_reduce4) of csrc/conv.hip through the C ABI.  Every row
+k_conv_gather (forward / data gradient; csrc/conv_gather.hip), k_conv_wgrad_pipe / k_conv_wgrad (weight gradient) and the
+slab reducers (k_wgrad_reduce, k_wgrad_reduce_once, k_wgrad_reduce4) of csrc/conv_wgrad.hip through the C ABI.  Every row
 * names the plan classes it exists for and asserts them through the host-only queries snn_conv2d_gather_plan /
   snn_conv2d_wgrad_plan with this device's CU count (it is in the row's messages) and the alignment facts of the very
   buffers it passes; test_every_gemm_plan_class_is_reached fails when the tables no longer cover REQUIRED_CLASSES;
