@@ -101,6 +101,9 @@ CASES = [
     Case("li_dest", R.LI, 6, 2, 12, 6, 7, dest=True),
     Case("lif_spikes_ok", R.LIF, 8, 2, 32, 6, 7, spikes_ok=True),
     Case("lif_rpb_gt1", R.LIF, 8, 4, 16, 90, 100, classes=("rpb>1_partial",), variants=("default", "no_yfree", "ckpt")),
+    # ---- one launch over a long sequence (NONE is never segmented): all T slabs in LDS cap the channels per block
+    Case("none_c64_t70", R.NONE, 70, 2, 64, 5, 6, classes=("mode1", "lds_capped", "cvb4", "gy>1")),
+    Case("none_c100_t128", R.NONE, 128, 1, 100, 3, 4, classes=("mode2", "lds_capped")),
     # ---- TinyYolo's LIF layers at 240x304, B = 5, T = 32 (reference on the device)
     Case("prod_lif64_120x152", R.LIF, 32, 5, 64, 120, 152, classes=("mode1", "cvb16"),
          variants=("default", "no_yfree")),
@@ -111,7 +114,7 @@ CASES = [
     Case("prod_litanh256_30x38_last", R.LI_TANH, 32, 5, 256, 30, 38, last_only=True, classes=("gy>1", "rpb>1_partial")),
 ]
 REQUIRED_CLASSES = {"mode0", "mode1", "mode2", "vec1", "vec4", "cvb1", "cvb2", "cvb4", "cvb8", "cvb16", "cvb_np2_lt64",
-                    "cvb_np2_ge64", "gy>1", "rpb1_partial", "rpb>1_partial"}
+                    "cvb_np2_ge64", "gy>1", "rpb1_partial", "rpb>1_partial", "lds_capped"}
 _RECORD = {}
 
 
@@ -129,10 +132,12 @@ def _with_sums(cs):
     return cs.bn in ("train", "eval_grad")
 
 
-def plan_of(HF, cs, variant="default"):
-    """The plan of the (first segment's) reverse scan this row takes."""
+def plan_of(HF, cs, variant="default", one_launch=False):
+    """The plan of the (first segment's) reverse scan this row takes; ``one_launch``: of the scan over all T steps, which
+    a SyncBatchNorm layer launches however long the sequence is."""
     from snn_for_object_detection_amd import _hip
-    segmented = _with_sums(cs) and cs.neuron != R.NONE and HF.SCAN_SEGMENT_T and cs.T > HF.SCAN_SEGMENT_T
+    segmented = (not one_launch and _with_sums(cs) and cs.neuron != R.NONE and HF.SCAN_SEGMENT_T
+                 and cs.T > HF.SCAN_SEGMENT_T)
     T = HF.SCAN_SEGMENT_T if segmented else cs.T
     flags = _hip.SCAN_WIDE_ADDRESSING if variant == "wide" else 0
     return HF.affine_neuron_bwd_plan(cs.neuron, T, cs.B * cs.H * cs.W, cs.C, cs.C, cs.C, _with_sums(cs), flags)
@@ -147,6 +152,10 @@ def plan_classes(pl):
         c.add("cvb_np2_lt64" if pl.cvb < 64 else "cvb_np2_ge64")
     if pl.gy > 1:
         c.add("gy>1")
+    # the slabs of all T steps did not leave room for min(C / vec, 256) channel groups per block: gy = ceil((C / vec) / cvb),
+    # so cvb < C / vec is gy > 1
+    if pl.gy > 1 and pl.cvb < 256:
+        c.add("lds_capped")
     if pl.partial_row:
         c.add("rpb1_partial" if pl.rpb == 1 else "rpb>1_partial")
     return c
@@ -215,7 +224,17 @@ class DevResult(NamedTuple):
     guard_ok: bool
 
 
-def run_device(HF, cs, inp, variant):
+def batch_share(cs, inp, batch):
+    """The row and its inputs restricted to the samples ``batch`` (a slice over B): one rank's share of the batch."""
+    s0 = lambda t: None if t is None else t[batch]        # noqa: E731
+    s1 = lambda t: None if t is None else t[:, batch]     # noqa: E731
+    share = inp._replace(y=s1(inp.y), v0=inp.v0 if cs.v0_scalar else s0(inp.v0), i0=s0(inp.i0), addend=s1(inp.addend),
+                         g_out=s0(inp.g_out) if cs.last_only else s1(inp.g_out), g_vT=s0(inp.g_vT), g_iT=s0(inp.g_iT))
+    return cs._replace(B=len(range(*batch.indices(cs.B)))), share
+
+
+def run_device(HF, cs, inp, variant, sync_group=None, batch=None):
+    """``sync_group``: the layer is a SyncBatchNorm one over that process group; ``batch``: this rank's samples."""
     from snn_for_object_detection_amd import _hip
     from snn_for_object_detection_amd.layer_gen import HipBatchNorm2d
     saved = (HF.USE_SUMS_FROM_STATE, HF.LIF_CHECKPOINT_BYTES, HF.SCAN_FLAGS)
@@ -223,6 +242,8 @@ def run_device(HF, cs, inp, variant):
     HF.LIF_CHECKPOINT_BYTES = 0 if variant == "ckpt" else None
     HF.SCAN_FLAGS = _hip.SCAN_WIDE_ADDRESSING if variant == "wide" else 0
     try:
+        if batch is not None:
+            cs, inp = batch_share(cs, inp, batch)
         T, B, C, H, W = cs.T, cs.B, cs.C, cs.H, cs.W
         bn = None
         if cs.bn is not None:
@@ -235,6 +256,8 @@ def run_device(HF, cs, inp, variant):
             bn.train(cs.bn == "train")
             bn.weight.requires_grad_(cs.bn != "eval")
             bn.bias.requires_grad_(cs.bn != "eval")
+            if sync_group is not None:
+                bn._snn_sync_group = (sync_group,)
         if cs.y_off is None:
             y = _cl(inp.y)
         else:
@@ -497,8 +520,13 @@ def _record(cs, variant, rec):
     _RECORD[f"{cs.id}/{variant}"] = rec
     path = os.environ.get("SNN_FP64_RECORD")
     if path:
+        rows = {}
+        if os.path.exists(path):   # (another test module's rows: tests/test_gpu_syncbn_fp64.py records through here too)
+            with open(path) as f:
+                rows = json.load(f)
+        rows.update(_RECORD)
         with open(path, "w") as f:
-            json.dump(_RECORD, f, indent=1, sort_keys=True)
+            json.dump(rows, f, indent=1, sort_keys=True)
 
 
 @pytest.mark.parametrize("cs", CASES, ids=[c.id for c in CASES])
