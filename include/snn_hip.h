@@ -731,6 +731,50 @@ int snn_det_loss_bwd(const float* cls_logits, const float* bbox_preds, const flo
                      const int64_t* class_labels, int64_t rows, int K, float loss_ratio, const double* stats,
                      const float* g_loss, float* g_logits, float* g_bbox, void* stream);
 
+/* ---- Every labelled timestep of a sequence (multi-target labels; new symbols under ABI v20).  labels [B][N][6] rows
+ * (ts, class, x1, y1, x2, y2): ts the integer-valued timestep of the uncut sequence, -1 in every column = padding row.
+ * The training step drops a prefix of t0 frames; a row belongs to step ts - t0 of the cut sequence of T steps and is
+ * ignored outside [0, T).  K (1 .. 32, <= T) is the number of frame slots per sample.  Nothing here synchronises with
+ * the host or allocates.
+ * snn_label_steps: one block per sample.  steps [K][B] int32: the latest K distinct steps of the sample's real rows
+ * (class >= 0) in ascending order from slot 0, -1 in the unused slots. */
+int snn_label_steps(const float* labels, int B, int N, int T, int K, int t0, int* steps, void* stream);
+/* Channels-last frames [T][B][M pixels][C] with pixel strides ld >= C on both sides (float4 when C, both strides and the
+ * pointers allow, scalar otherwise).  fwd: dst[k][b] = src[steps[k][b]][b], zeros for an empty slot (a step outside
+ * [0, T)).  bwd: writes the C channels of EVERY frame of g_src [T][B] in one pass - the gradient of the slot that
+ * selected the frame (the sum in slot order when several slots of a sample name one step), exact zeros elsewhere; no
+ * memset, no atomics. */
+int snn_gather_steps_fwd(const float* src, int64_t ld_src, const int* steps, float* dst, int64_t ld_dst, int T, int B,
+                         int K, int64_t M, int C, void* stream);
+int snn_gather_steps_bwd(const float* g_dst, int64_t ld_dst, const int* steps, float* g_src, int64_t ld_src, int T, int B,
+                         int K, int64_t M, int C, void* stream);
+/* snn_roi_assign_steps: one block per slot (k, b).  The slot's assignment is snn_roi_assign's for one sample whose label
+ * tensor [n][5] holds, in their order, the real rows of sample b with ts - t0 == steps[k][b] and its padding rows
+ * (which, as there, claim an anchor in the greedy phase; the fp32 quotient of the claimed anchor uses n).  Rows of other
+ * timesteps take no part.  An empty slot gets zero targets.  Outputs bbox_offset [K][B][A][4], bbox_mask [K][B][A][4],
+ * class_labels [K][B][A] int64.  steps is trusted as snn_label_steps writes it (the call carries no T to check it
+ * against): a step >= 0 that no real row of the sample lies on, in a sample without padding rows, leaves n = 0 rows -
+ * the slot then gets zero targets as an empty one does (nothing is read or written out of bounds), but being >= 0 it
+ * still counts as valid in snn_det_loss_steps_*.  workspace: snn_roi_steps_workspace_size(K, B, A, N) bytes, 16-byte
+ * aligned as the anchors and the box outputs; A * N below 2^31 - 1024. */
+size_t snn_roi_steps_workspace_size(int K, int B, int A, int N);
+int snn_roi_assign_steps(const float* anchors, const float* labels, const int* steps, int K, int B, int A, int N,
+                         int t0, float iou_threshold, void* workspace, float* bbox_offset, float* bbox_mask,
+                         int64_t* class_labels, void* stream);
+/* The loss above over the anchors of the V valid slots (steps[k][b] >= 0) of predictions [K][B][A][C] / [K][B][A][4]:
+ *   loss = loss_ratio * mean(CE[pos]) + (1 - loss_ratio) * mean(CE[neg]) + sum |bbox*mask - offset*mask| / (4 A V)
+ * stats[6] = the five sums of snn_det_loss_fwd and V, counted on the device.  V = 0: loss 0 and zero gradients; V > 0
+ * without positives (or negatives): NaN, as snn_det_loss_fwd.  bwd writes all K*B*A rows, exact zeros for empty slots.
+ * workspace: snn_det_loss_steps_workspace_size(K, B, A) bytes. */
+size_t snn_det_loss_steps_workspace_size(int K, int B, int A);
+int snn_det_loss_steps_fwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                           const float* bbox_mask, const int64_t* class_labels, const int* steps, int K, int B, int A,
+                           int C, float loss_ratio, void* workspace, double* stats, float* loss, void* stream);
+int snn_det_loss_steps_bwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                           const float* bbox_mask, const int64_t* class_labels, const int* steps, int K, int B, int A,
+                           int C, float loss_ratio, const double* stats, const float* g_loss, float* g_logits,
+                           float* g_bbox, void* stream);
+
 /* ---------------------------------------------------------------- detection mAP (ABI v12)
  * COCO bounding-box mAP as the reference computes it in validation_step / test_step (models/soda.py:160-182, 283-321:
  * torchmetrics MeanAveragePrecision, iou_type "bbox", area range "all", no crowd boxes).

@@ -118,6 +118,14 @@ SIGNATURES = {
     "snn_det_loss_workspace_size": (c_size_t, [_L]),
     "snn_det_loss_fwd": (c_int, [_P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P]),
     "snn_det_loss_bwd": (c_int, [_P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P]),
+    "snn_label_steps": (c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "snn_gather_steps_fwd": (c_int, [_P, _L, _P, _P, _L, _I, _I, _I, _L, _I, _P]),
+    "snn_gather_steps_bwd": (c_int, [_P, _L, _P, _P, _L, _I, _I, _I, _L, _I, _P]),
+    "snn_roi_steps_workspace_size": (c_size_t, [_I, _I, _I, _I]),
+    "snn_roi_assign_steps": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "snn_det_loss_steps_workspace_size": (c_size_t, [_I, _I, _I]),
+    "snn_det_loss_steps_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "snn_det_loss_steps_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "snn_small_gemm": (c_int, [_P, _L, _I, _P, _L, _I, _P, _L, _I, _I, _I, _I, _P, _L, _P]),
     "snn_small_gemm_batched": (c_int, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "snn_copy_channels_bf16": (c_int, [_P, _L, _P, _L, _L, _I, _P]),

@@ -15,6 +15,7 @@
 namespace {
 
 constexpr int kRoiThreads = 1024;
+constexpr int kMaxLabelSteps = 32;   // frame slots per sample (K) of the *_steps entry points
 
 struct ArgMax {
     float v;
@@ -35,17 +36,16 @@ __device__ __forceinline__ float iou_pair(const float4 p, const float* __restric
     return overlap / (area1 + area2 - overlap);
 }
 
-__global__ __launch_bounds__(kRoiThreads) void k_roi_assign(const float* __restrict__ anchors,
-                                                            const float* __restrict__ labels, int A, int N, float thr,
-                                                            float* __restrict__ iou_ws, int* __restrict__ amap_ws,
-                                                            float* __restrict__ offset, float* __restrict__ mask,
-                                                            int64_t* __restrict__ cls) {
+// The assignment of ONE sample: N label rows [N][5] at lab, the sample's IoU matrix iou [A][N] and map amap [A], targets
+// written to the rows row0 .. row0 + A of offset / mask / cls.  Shared by k_roi_assign (a sample of the batch) and
+// k_roi_assign_steps (a labelled frame of a sample, over the rows that take part): one body, the same roundings.
+__device__ __forceinline__ void roi_assign_sample(const float* __restrict__ anchors, const float* lab, int A, int N,
+                                                  float thr, float* __restrict__ iou, int* __restrict__ amap,
+                                                  float* __restrict__ offset, float* __restrict__ mask,
+                                                  int64_t* __restrict__ cls, int64_t row0) {
     __shared__ ArgMax red[kRoiThreads / 64];
     __shared__ ArgMax winner;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* lab = labels + (int64_t)b * N * 5;
-    float* iou = iou_ws + (int64_t)b * A * N;
-    int* amap = amap_ws + (int64_t)b * A;
+    const int tid = threadIdx.x;
     // ---- IoU matrix; an anchor takes the ground truth of highest IoU when that reaches the threshold (roi.py:78-93)
     for (int a = tid; a < A; a += kRoiThreads) {
         const float4 anc = *reinterpret_cast<const float4*>(anchors + (int64_t)a * 4);
@@ -111,11 +111,90 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_assign(const float* __restr
         o.y = (10 * (tcy - acy) / ah) * m;
         o.z = (5 * logf(1e-6f + tw / aw)) * m;
         o.w = (5 * logf(1e-6f + th / ah)) * m;
-        const int64_t row = (int64_t)b * A + a;
+        const int64_t row = row0 + a;
         *reinterpret_cast<float4*>(offset + row * 4) = o;
         *reinterpret_cast<float4*>(mask + row * 4) = make_float4(m, m, m, m);
         cls[row] = g >= 0 ? (int64_t)gt[0] + 1 : 0;
     }
+}
+
+__global__ __launch_bounds__(kRoiThreads) void k_roi_assign(const float* __restrict__ anchors,
+                                                            const float* __restrict__ labels, int A, int N, float thr,
+                                                            float* __restrict__ iou_ws, int* __restrict__ amap_ws,
+                                                            float* __restrict__ offset, float* __restrict__ mask,
+                                                            int64_t* __restrict__ cls) {
+    const int b = blockIdx.x;
+    roi_assign_sample(anchors, labels + (int64_t)b * N * 5, A, N, thr, iou_ws + (int64_t)b * A * N,
+                      amap_ws + (int64_t)b * A, offset, mask, cls, (int64_t)b * A);
+}
+
+// Step of the cut sequence a six-column label row (ts, class, x1, y1, x2, y2) belongs to, -1 when it is a padding row
+// (class < 0) or falls outside [0, T).  ts is integer valued, so the fp32 difference is exact.
+__device__ __forceinline__ int label_row_step(const float* __restrict__ row, int t0, int T) {
+    const float r = row[0] - (float)t0;
+    return (row[1] >= 0.f && r >= 0.f && r < (float)T) ? (int)r : -1;
+}
+
+// One block per sample: the latest K distinct steps of its real rows, ascending, into steps[0 ..][b]; -1 behind them.
+__global__ __launch_bounds__(64) void k_label_steps(const float* __restrict__ labels, int B, int N, int T, int K, int t0,
+                                                    int* __restrict__ steps) {
+    __shared__ int found[kMaxLabelSteps];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const float* lab = labels + (int64_t)b * N * 6;
+    int bound = T, count = 0;
+    for (; count < K; ++count) {   // the largest step below the one found before; uniform over the wave
+        int best = -1;
+        for (int j = lane; j < N; j += 64) {
+            const int s = label_row_step(lab + j * 6, t0, T);
+            if (s < bound && s > best) best = s;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
+        if (best < 0) break;
+        if (lane == 0) found[count] = best;
+        bound = best;
+    }
+    __syncthreads();
+    if (lane < K) steps[lane * B + b] = lane < count ? found[count - 1 - lane] : -1;
+}
+
+// One block per slot (k, b) = blockIdx.x.  The rows of sample b that take part - real rows of step steps[k][b] and
+// padding rows, in their order - are packed into the slot's [n][5] label tensor, then the assignment is the sample's.
+__global__ __launch_bounds__(kRoiThreads) void k_roi_assign_steps(const float* __restrict__ anchors,
+                                                                  const float* __restrict__ labels6,
+                                                                  const int* __restrict__ steps, int B, int A, int N,
+                                                                  int t0, float thr, float* iou_ws, int* amap_ws,
+                                                                  float* lab_ws, float* __restrict__ offset,
+                                                                  float* __restrict__ mask, int64_t* __restrict__ cls) {
+    __shared__ int n_rows;
+    const int slot = blockIdx.x, b = slot % B, tid = threadIdx.x;
+    const int s = steps[slot];
+    const int64_t row0 = (int64_t)slot * A;
+    if (s < 0) {   // an empty slot: zero targets, nothing else
+        for (int a = tid; a < A; a += kRoiThreads) {
+            *reinterpret_cast<float4*>(offset + (row0 + a) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(mask + (row0 + a) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            cls[row0 + a] = 0;
+        }
+        return;
+    }
+    float* lab = lab_ws + (int64_t)slot * N * 5;
+    if (tid == 0) {
+        const float* src = labels6 + (int64_t)b * N * 6;
+        int n = 0;
+        for (int j = 0; j < N; ++j) {
+            const float* row = src + j * 6;
+            if (row[1] < 0.f || row[0] - (float)t0 == (float)s) {
+                for (int c = 0; c < 5; ++c) lab[n * 5 + c] = row[1 + c];
+                ++n;
+            }
+        }
+        n_rows = n;
+    }
+    __threadfence_block();
+    __syncthreads();
+    roi_assign_sample(anchors, lab, A, n_rows, thr, iou_ws + (int64_t)slot * A * N, amap_ws + (int64_t)slot * A, offset,
+                      mask, cls, row0);
 }
 
 // ------------------------------------------------------------------------------------------ loss
@@ -134,15 +213,19 @@ __device__ __forceinline__ double block_sum(double v, double* scratch) {  // all
 }
 
 // partial[block][5] = {sum CE over positives, positives, sum CE over negatives, negatives, sum |bbox*m - off*m|}
+// kSteps: the rows are [slots][A] and those of an empty slot (steps[slot] < 0) are left out of every sum.
+template <bool kSteps>
 __global__ __launch_bounds__(kLossThreads) void k_det_loss_partial(const float* __restrict__ logits,
                                                                    const float* __restrict__ bbox,
                                                                    const float* __restrict__ offset,
                                                                    const float* __restrict__ mask,
                                                                    const int64_t* __restrict__ cls, int64_t R, int K,
+                                                                   const int* __restrict__ steps, int A,
                                                                    double* __restrict__ partial) {
     __shared__ double scratch[kLossThreads / 64];
     double s_pos = 0, n_pos = 0, s_neg = 0, n_neg = 0, s_l1 = 0;
     for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < R; r += (int64_t)gridDim.x * kLossThreads) {
+        if (kSteps && steps[r / A] < 0) continue;
         const float* x = logits + r * K;
         float mx = x[0];
         for (int k = 1; k < K; ++k) mx = fmaxf(mx, x[k]);
@@ -173,7 +256,13 @@ __global__ __launch_bounds__(kLossThreads) void k_det_loss_partial(const float* 
     }
 }
 
-// stats[5] = totals (block order: reproducible); loss = ratio * pos / n_pos + (1 - ratio) * neg / n_neg + l1 / (4 R)
+// loss = ratio * pos / n_pos + (1 - ratio) * neg / n_neg + l1 / (4 R) of the totals t[5]
+__device__ __forceinline__ float combine_loss(const double* t, int64_t R, float ratio) {
+    const float gt = (float)(t[0] / t[1]), bg = (float)(t[2] / t[3]), l1 = (float)(t[4] / (4.0 * (double)R));
+    return (gt * ratio + bg * (1 - ratio)) + l1;   // soda.py:277-281, same order of the three terms
+}
+
+// stats[5] = totals (block order: reproducible)
 __global__ void k_det_loss_final(const double* __restrict__ partial, int nblocks, int64_t R, float ratio,
                                  double* __restrict__ stats, float* __restrict__ loss) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -181,10 +270,29 @@ __global__ void k_det_loss_final(const double* __restrict__ partial, int nblocks
     for (int b = 0; b < nblocks; ++b)
         for (int k = 0; k < 5; ++k) t[k] += partial[(int64_t)b * 5 + k];
     for (int k = 0; k < 5; ++k) stats[k] = t[k];
-    const float gt = (float)(t[0] / t[1]), bg = (float)(t[2] / t[3]), l1 = (float)(t[4] / (4.0 * (double)R));
-    *loss = (gt * ratio + bg * (1 - ratio)) + l1;   // soda.py:277-281, same order of the three terms
+    *loss = combine_loss(t, R, ratio);
 }
 
+// The same over the anchors of the V valid slots: stats[5] = V, counted here; R = A * V rows; no valid slot: loss 0.
+__global__ void k_det_loss_steps_final(const double* __restrict__ partial, int nblocks, const int* __restrict__ steps,
+                                       int slots, int A, float ratio, double* __restrict__ stats,
+                                       float* __restrict__ loss) {
+    if (blockIdx.x != 0) return;
+    int v = 0;
+    for (int i = threadIdx.x; i < slots; i += 64) v += steps[i] >= 0 ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (threadIdx.x != 0) return;
+    double t[5] = {0, 0, 0, 0, 0};
+    for (int b = 0; b < nblocks; ++b)
+        for (int k = 0; k < 5; ++k) t[k] += partial[(int64_t)b * 5 + k];
+    for (int k = 0; k < 5; ++k) stats[k] = t[k];
+    stats[5] = (double)v;
+    *loss = v > 0 ? combine_loss(t, (int64_t)A * v, ratio) : 0.0f;
+}
+
+// kSteps: rows [slots][A]; R = A * V with V = stats[5]; the rows of an empty slot get exact zeros.
+template <bool kSteps>
 __global__ __launch_bounds__(kLossThreads) void k_det_loss_bwd(const float* __restrict__ logits,
                                                                const float* __restrict__ bbox,
                                                                const float* __restrict__ offset,
@@ -192,11 +300,18 @@ __global__ __launch_bounds__(kLossThreads) void k_det_loss_bwd(const float* __re
                                                                const int64_t* __restrict__ cls, int64_t R, int K,
                                                                const double* __restrict__ stats, float ratio,
                                                                const float* __restrict__ g_loss,
+                                                               const int* __restrict__ steps, int A,
                                                                float* __restrict__ g_logits, float* __restrict__ g_bbox) {
     const float g = *g_loss;
     const float w_pos = g * ratio / (float)stats[1], w_neg = g * (1 - ratio) / (float)stats[3];
-    const float w_l1 = g / (4.0f * (float)R);
+    const int64_t rows_in = kSteps ? (int64_t)A * (int64_t)stats[5] : R;
+    const float w_l1 = g / (4.0f * (float)rows_in);
     for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < R; r += (int64_t)gridDim.x * kLossThreads) {
+        if (kSteps && steps[r / A] < 0) {
+            for (int k = 0; k < K; ++k) g_logits[r * K + k] = 0.f;
+            *reinterpret_cast<float4*>(g_bbox + r * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
         const float* x = logits + r * K;
         float mx = x[0];
         for (int k = 1; k < K; ++k) mx = fmaxf(mx, x[k]);
@@ -221,7 +336,65 @@ __global__ __launch_bounds__(kLossThreads) void k_det_loss_bwd(const float* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------ labelled-frame gather
+// Channels-last frames [T][B][M pixels][C] with pixel strides ld >= C.  An element is one channel (kVec: one channel
+// quad) of one pixel; Cq = elements per pixel.  A step outside [0, T) is an empty slot.
+constexpr int kGatherThreads = 256;
+
+template <bool kVec> struct GatherElem { using type = float; };
+template <> struct GatherElem<true> { using type = float4; };
+__device__ __forceinline__ float zero_of(float) { return 0.f; }
+__device__ __forceinline__ float4 zero_of(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ float sum_of(float a, float b) { return a + b; }
+__device__ __forceinline__ float4 sum_of(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// dst[k][b] = src[steps[k][b]][b]; zeros for an empty slot
+template <bool kVec>
+__global__ __launch_bounds__(kGatherThreads) void k_gather_steps_fwd(const float* __restrict__ src, int64_t ld_src,
+                                                                     const int* __restrict__ steps,
+                                                                     float* __restrict__ dst, int64_t ld_dst, int T,
+                                                                     int B, int64_t M, int Cq, int64_t total) {
+    using E = typename GatherElem<kVec>::type;
+    constexpr int w = kVec ? 4 : 1;
+    for (int64_t i = (int64_t)blockIdx.x * kGatherThreads + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * kGatherThreads) {
+        const int c = (int)(i % Cq);
+        const int64_t pix = i / Cq, m = pix % M, slot = pix / M;
+        const int b = (int)(slot % B), s = steps[slot];
+        E v = zero_of(E());
+        if (s >= 0 && s < T) v = *reinterpret_cast<const E*>(src + (((int64_t)s * B + b) * M + m) * ld_src + c * w);
+        *reinterpret_cast<E*>(dst + (slot * M + m) * ld_dst + c * w) = v;
+    }
+}
+
+// g_src[t][b] = sum over the slots k with steps[k][b] == t of g_dst[k][b], in slot order; zeros where no slot selects it
+template <bool kVec>
+__global__ __launch_bounds__(kGatherThreads) void k_gather_steps_bwd(const float* __restrict__ g_dst, int64_t ld_dst,
+                                                                     const int* __restrict__ steps,
+                                                                     float* __restrict__ g_src, int64_t ld_src, int B,
+                                                                     int K, int64_t M, int Cq, int64_t total) {
+    using E = typename GatherElem<kVec>::type;
+    constexpr int w = kVec ? 4 : 1;
+    for (int64_t i = (int64_t)blockIdx.x * kGatherThreads + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * kGatherThreads) {
+        const int c = (int)(i % Cq);
+        const int64_t pix = i / Cq, m = pix % M, frame = pix / M;
+        const int b = (int)(frame % B), t = (int)(frame / B);
+        E acc = zero_of(E());
+        for (int k = 0; k < K; ++k)
+            if (steps[k * B + b] == t)
+                acc = sum_of(acc, *reinterpret_cast<const E*>(g_dst + (((int64_t)k * B + b) * M + m) * ld_dst + c * w));
+        *reinterpret_cast<E*>(g_src + (frame * M + m) * ld_src + c * w) = acc;
+    }
+}
+
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static int gather_blocks(int64_t total) {
+    int64_t b = snn_ceil_div(total, (int64_t)kGatherThreads);
+    const int64_t cap = (int64_t)snn_num_cu() * 8;
+    if (b > cap) b = cap;
+    return b < 1 ? 1 : (int)b;
+}
 static int loss_blocks(int64_t R) {
     int64_t b = snn_ceil_div(R, (int64_t)kLossThreads * 4);
     if (b > 1024) b = 1024;
@@ -261,8 +434,9 @@ extern "C" int snn_det_loss_fwd(const float* cls_logits, const float* bbox_preds
     SNN_REQUIRE(aligned16(bbox_preds) && aligned16(bbox_offset) && aligned16(bbox_mask),
                 "snn_det_loss_fwd: box tensors must be 16-byte aligned");
     const int nb = loss_blocks(rows);
-    hipLaunchKernelGGL(k_det_loss_partial, dim3((unsigned)nb), dim3(kLossThreads), 0, (hipStream_t)stream, cls_logits,
-                       bbox_preds, bbox_offset, bbox_mask, class_labels, rows, K, static_cast<double*>(workspace));
+    hipLaunchKernelGGL(k_det_loss_partial<false>, dim3((unsigned)nb), dim3(kLossThreads), 0, (hipStream_t)stream,
+                       cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, rows, K, (const int*)nullptr, 1,
+                       static_cast<double*>(workspace));
     hipLaunchKernelGGL(k_det_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream,
                        static_cast<const double*>(workspace), nb, rows, loss_ratio, stats, loss);
     SNN_CHECK_LAUNCH("snn_det_loss_fwd");
@@ -278,9 +452,129 @@ extern "C" int snn_det_loss_bwd(const float* cls_logits, const float* bbox_preds
     SNN_REQUIRE(rows > 0 && K > 1 && K <= kMaxClasses, "snn_det_loss_bwd: bad shape");
     SNN_REQUIRE(aligned16(bbox_preds) && aligned16(bbox_offset) && aligned16(bbox_mask) && aligned16(g_bbox),
                 "snn_det_loss_bwd: box tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(k_det_loss_bwd, dim3((unsigned)loss_blocks(rows)), dim3(kLossThreads), 0, (hipStream_t)stream,
-                       cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, rows, K, stats, loss_ratio, g_loss,
-                       g_logits, g_bbox);
+    hipLaunchKernelGGL(k_det_loss_bwd<false>, dim3((unsigned)loss_blocks(rows)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, rows, K, stats,
+                       loss_ratio, g_loss, (const int*)nullptr, 1, g_logits, g_bbox);
     SNN_CHECK_LAUNCH("snn_det_loss_bwd");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ every labelled timestep
+extern "C" int snn_label_steps(const float* labels, int B, int N, int T, int K, int t0, int* steps, void* stream) {
+    SNN_REQUIRE(labels && steps, "snn_label_steps: null pointer");
+    SNN_REQUIRE(B > 0 && N > 0 && T > 0 && t0 >= 0, "snn_label_steps: bad shape");
+    SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps && K <= T, "snn_label_steps: K must be in 1 .. min(%d, T)", kMaxLabelSteps);
+    hipLaunchKernelGGL(k_label_steps, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, labels, B, N, T, K, t0, steps);
+    SNN_CHECK_LAUNCH("snn_label_steps");
+    return 0;
+}
+
+static bool gather_vec(const float* a, int64_t ld_a, const float* b, int64_t ld_b, int C) {
+    return C % 4 == 0 && ld_a % 4 == 0 && ld_b % 4 == 0 && aligned16(a) && aligned16(b);
+}
+
+extern "C" int snn_gather_steps_fwd(const float* src, int64_t ld_src, const int* steps, float* dst, int64_t ld_dst, int T,
+                                    int B, int K, int64_t M, int C, void* stream) {
+    SNN_REQUIRE(src && steps && dst, "snn_gather_steps_fwd: null pointer");
+    SNN_REQUIRE(T > 0 && B > 0 && M > 0 && C > 0 && ld_src >= C && ld_dst >= C, "snn_gather_steps_fwd: bad shape");
+    SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps && K <= T, "snn_gather_steps_fwd: K must be in 1 .. min(%d, T)",
+                kMaxLabelSteps);
+    const bool vec = gather_vec(src, ld_src, dst, ld_dst, C);
+    const int Cq = vec ? C / 4 : C;
+    const int64_t total = (int64_t)K * B * M * Cq;
+    if (vec)
+        hipLaunchKernelGGL(k_gather_steps_fwd<true>, dim3((unsigned)gather_blocks(total)), dim3(kGatherThreads), 0,
+                           (hipStream_t)stream, src, ld_src, steps, dst, ld_dst, T, B, M, Cq, total);
+    else
+        hipLaunchKernelGGL(k_gather_steps_fwd<false>, dim3((unsigned)gather_blocks(total)), dim3(kGatherThreads), 0,
+                           (hipStream_t)stream, src, ld_src, steps, dst, ld_dst, T, B, M, Cq, total);
+    SNN_CHECK_LAUNCH("snn_gather_steps_fwd");
+    return 0;
+}
+
+extern "C" int snn_gather_steps_bwd(const float* g_dst, int64_t ld_dst, const int* steps, float* g_src, int64_t ld_src,
+                                    int T, int B, int K, int64_t M, int C, void* stream) {
+    SNN_REQUIRE(g_dst && steps && g_src, "snn_gather_steps_bwd: null pointer");
+    SNN_REQUIRE(T > 0 && B > 0 && M > 0 && C > 0 && ld_src >= C && ld_dst >= C, "snn_gather_steps_bwd: bad shape");
+    SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps && K <= T, "snn_gather_steps_bwd: K must be in 1 .. min(%d, T)",
+                kMaxLabelSteps);
+    const bool vec = gather_vec(g_dst, ld_dst, g_src, ld_src, C);
+    const int Cq = vec ? C / 4 : C;
+    const int64_t total = (int64_t)T * B * M * Cq;
+    if (vec)
+        hipLaunchKernelGGL(k_gather_steps_bwd<true>, dim3((unsigned)gather_blocks(total)), dim3(kGatherThreads), 0,
+                           (hipStream_t)stream, g_dst, ld_dst, steps, g_src, ld_src, B, K, M, Cq, total);
+    else
+        hipLaunchKernelGGL(k_gather_steps_bwd<false>, dim3((unsigned)gather_blocks(total)), dim3(kGatherThreads), 0,
+                           (hipStream_t)stream, g_dst, ld_dst, steps, g_src, ld_src, B, K, M, Cq, total);
+    SNN_CHECK_LAUNCH("snn_gather_steps_bwd");
+    return 0;
+}
+
+// bytes: per slot the IoU matrix, the assignment map and the packed [N][5] rows that take part
+extern "C" size_t snn_roi_steps_workspace_size(int K, int B, int A, int N) {
+    return (size_t)K * B * ((size_t)A * ((size_t)N * sizeof(float) + sizeof(int)) + (size_t)N * 5 * sizeof(float));
+}
+
+extern "C" int snn_roi_assign_steps(const float* anchors, const float* labels, const int* steps, int K, int B, int A,
+                                    int N, int t0, float iou_threshold, void* workspace, float* bbox_offset,
+                                    float* bbox_mask, int64_t* class_labels, void* stream) {
+    SNN_REQUIRE(anchors && labels && steps && workspace && bbox_offset && bbox_mask && class_labels,
+                "snn_roi_assign_steps: null pointer");
+    SNN_REQUIRE(B > 0 && A > 0 && N > 0 && t0 >= 0 && (int64_t)A * N < 0x7fffffffLL - kRoiThreads,
+                "snn_roi_assign_steps: bad shape");
+    SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps, "snn_roi_assign_steps: K must be in 1 .. %d", kMaxLabelSteps);
+    SNN_REQUIRE(aligned16(anchors) && aligned16(bbox_offset) && aligned16(bbox_mask) && aligned16(workspace),
+                "snn_roi_assign_steps: buffers must be 16-byte aligned");
+    const size_t slots = (size_t)K * B;
+    float* iou = static_cast<float*>(workspace);
+    int* amap = reinterpret_cast<int*>(iou + slots * A * N);
+    float* lab = reinterpret_cast<float*>(amap + slots * A);
+    hipLaunchKernelGGL(k_roi_assign_steps, dim3((unsigned)slots), dim3(kRoiThreads), 0, (hipStream_t)stream, anchors,
+                       labels, steps, B, A, N, t0, iou_threshold, iou, amap, lab, bbox_offset, bbox_mask, class_labels);
+    SNN_CHECK_LAUNCH("snn_roi_assign_steps");
+    return 0;
+}
+
+extern "C" size_t snn_det_loss_steps_workspace_size(int K, int B, int A) {
+    return (size_t)loss_blocks((int64_t)K * B * A) * 5 * sizeof(double);
+}
+
+extern "C" int snn_det_loss_steps_fwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                                      const float* bbox_mask, const int64_t* class_labels, const int* steps, int K, int B,
+                                      int A, int C, float loss_ratio, void* workspace, double* stats, float* loss,
+                                      void* stream) {
+    SNN_REQUIRE(cls_logits && bbox_preds && bbox_offset && bbox_mask && class_labels && steps && workspace && stats &&
+                    loss, "snn_det_loss_steps_fwd: null pointer");
+    SNN_REQUIRE(B > 0 && A > 0 && C > 1 && C <= kMaxClasses, "snn_det_loss_steps_fwd: bad shape");
+    SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps, "snn_det_loss_steps_fwd: K must be in 1 .. %d", kMaxLabelSteps);
+    SNN_REQUIRE(aligned16(bbox_preds) && aligned16(bbox_offset) && aligned16(bbox_mask),
+                "snn_det_loss_steps_fwd: box tensors must be 16-byte aligned");
+    const int64_t rows = (int64_t)K * B * A;
+    const int nb = loss_blocks(rows);
+    hipLaunchKernelGGL(k_det_loss_partial<true>, dim3((unsigned)nb), dim3(kLossThreads), 0, (hipStream_t)stream,
+                       cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, rows, C, steps, A,
+                       static_cast<double*>(workspace));
+    hipLaunchKernelGGL(k_det_loss_steps_final, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                       static_cast<const double*>(workspace), nb, steps, K * B, A, loss_ratio, stats, loss);
+    SNN_CHECK_LAUNCH("snn_det_loss_steps_fwd");
+    return 0;
+}
+
+extern "C" int snn_det_loss_steps_bwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                                      const float* bbox_mask, const int64_t* class_labels, const int* steps, int K, int B,
+                                      int A, int C, float loss_ratio, const double* stats, const float* g_loss,
+                                      float* g_logits, float* g_bbox, void* stream) {
+    SNN_REQUIRE(cls_logits && bbox_preds && bbox_offset && bbox_mask && class_labels && steps && stats && g_loss &&
+                    g_logits && g_bbox, "snn_det_loss_steps_bwd: null pointer");
+    SNN_REQUIRE(B > 0 && A > 0 && C > 1 && C <= kMaxClasses, "snn_det_loss_steps_bwd: bad shape");
+    SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps, "snn_det_loss_steps_bwd: K must be in 1 .. %d", kMaxLabelSteps);
+    SNN_REQUIRE(aligned16(bbox_preds) && aligned16(bbox_offset) && aligned16(bbox_mask) && aligned16(g_bbox),
+                "snn_det_loss_steps_bwd: box tensors must be 16-byte aligned");
+    const int64_t rows = (int64_t)K * B * A;
+    hipLaunchKernelGGL(k_det_loss_bwd<true>, dim3((unsigned)loss_blocks(rows)), dim3(kLossThreads), 0,
+                       (hipStream_t)stream, cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, rows, C, stats,
+                       loss_ratio, g_loss, steps, A, g_logits, g_bbox);
+    SNN_CHECK_LAUNCH("snn_det_loss_steps_bwd");
     return 0;
 }

@@ -18,6 +18,22 @@ import torch
 from . import _hip
 
 
+def collate_labels(labels: Sequence[torch.Tensor], B: int) -> torch.Tensor:
+    """``_stack_data`` for the label lists (``datasets.py:127-135``): per-sample rows ``[n, 5]`` (``class, x1, y1, x2,
+    y2``) or ``[n, 6]`` (``ts, class, x1, y1, x2, y2``, the multi-target samples) -> host ``[B, n_max, 5 | 6]`` padded
+    with -1.  The width is that of the rows given; a sample without rows (any shape with no row in it) fits either,
+    and a batch without any row is five columns wide.  Mixed widths raise."""
+    n_max = max((int(l.shape[0]) for l in labels), default=0)
+    widths = {int(l.shape[1]) for l in labels if l.dim() == 2 and l.shape[0] > 0}
+    if len(widths) > 1 or not widths <= {5, 6}:
+        raise ValueError(f"EventBatcher: label rows must all have 5 or all have 6 columns, got {sorted(widths)}")
+    lab = torch.full((B, n_max, widths.pop() if widths else 5), -1.0, dtype=torch.float32)
+    for b, l in enumerate(labels):
+        if l.shape[0] > 0:
+            lab[b, : l.shape[0]] = l
+    return lab
+
+
 class EventBatcher:
     def __init__(self, num_steps: int, height: int, width: int, time_step_us: int, device="cuda"):
         self.T, self.H, self.W, self.step = int(num_steps), int(height), int(width), int(time_step_us)
@@ -33,7 +49,8 @@ class EventBatcher:
                  labels: Optional[Sequence[torch.Tensor]] = None):
         """``samples[b] = (t_us, x, y, p, t0_us)`` - 1-D host tensors (int64 / int32; pinned memory makes the copy
         asynchronous) and the time of the first frame.  Returns ``X[T, B, 2, H, W]`` (logical NCHW view of a
-        channels-last buffer) and, when ``labels`` is given, ``labels[B, N, 5]`` padded with -1."""
+        channels-last buffer) and, when ``labels`` is given, ``labels[B, N, 5]`` padded with -1 - ``[B, N, 6]`` when the
+        rows given carry a timestep in front (``(ts, class, x1, y1, x2, y2)``, the multi-target sample format)."""
         B = len(samples)
         T, H, W = self.T, self.H, self.W
         main = torch.cuda.current_stream(self.device)
@@ -65,8 +82,4 @@ class EventBatcher:
         X = buf.permute(0, 1, 4, 2, 3)  # [T, B, 2, H, W], channels-last memory
         if labels is None:
             return X
-        n_max = max(int(l.shape[0]) for l in labels) if labels else 0
-        lab = torch.full((B, n_max, 5), -1.0, dtype=torch.float32)
-        for b, l in enumerate(labels):
-            lab[b, : l.shape[0]] = l
-        return X, lab.to(self.device, non_blocking=True)
+        return X, collate_labels(labels, B).to(self.device, non_blocking=True)

@@ -2469,6 +2469,128 @@ def detection_loss(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox_offse
     return _DetectionLoss.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, loss_ratio)
 
 
+# ------------------------------------------------------------------------------------------- every labelled timestep
+MAX_LABEL_STEPS = 32   # frame slots per sample the *_steps kernels take (csrc/targets.hip)
+
+
+def _require_steps(steps: torch.Tensor, B: int, like: torch.Tensor, what: str) -> Tuple[int, torch.Tensor]:
+    """``steps[K,B]`` as the kernels read it: int32, on ``like``'s device, contiguous.  Returns ``(K, steps)``."""
+    if steps.dim() != 2 or steps.shape[1] != B or steps.dtype != torch.int32 or steps.device != like.device:
+        raise RuntimeError(f"{what}: steps must be an int32 [K, {B}] tensor on {like.device}, got {steps.dtype} "
+                           f"{tuple(steps.shape)} on {steps.device}")
+    return int(steps.shape[0]), steps.contiguous()
+
+
+def select_label_steps(labels: torch.Tensor, T: int, K: int, t0: int = 0) -> torch.Tensor:
+    """The labelled frames of a batch, chosen on the device: ``labels[B,N,6]`` rows ``(ts, class, x1, y1, x2, y2)`` (``ts``
+    counts the steps of the uncut sequence, padding rows are -1) -> ``steps[K,B]`` int32.  For every sample the latest
+    ``K`` distinct steps ``ts - t0`` of its real rows that lie inside the cut sequence ``[0, T)``, in ascending order from
+    slot 0; unused slots hold -1.  One launch, no host synchronisation."""
+    if not labels.is_cuda or labels.dim() != 3 or labels.shape[2] != 6:
+        raise RuntimeError(f"select_label_steps: labels[B,N,6] on a HIP device required, got {tuple(labels.shape)} on "
+                           f"{labels.device}")
+    lab = labels.detach().float().contiguous()
+    B, N, _ = lab.shape
+    if N == 0:
+        return torch.full((int(K), B), -1, device=lab.device, dtype=torch.int32)
+    steps = torch.empty((int(K), B), device=lab.device, dtype=torch.int32)
+    _hip.call("snn_label_steps", lab.data_ptr(), B, N, int(T), int(K), int(t0), steps.data_ptr(), _stream())
+    return steps
+
+
+class _GatherSteps(Function):
+    """``Y[T,B,C,H,W] -> out[K,B,C,H,W]`` with ``out[k][b] = Y[steps[k][b]][b]`` (zeros for an empty slot); the backward
+    writes every frame of the gradient in one pass (zeros where no slot selected the frame)."""
+
+    @staticmethod
+    def forward(ctx, Y, steps):
+        _require_device(Y, "gather_steps")
+        Y = _raw_to_cl(Y)
+        T, B, C, H, W = Y.shape
+        K, steps = _require_steps(steps, B, Y, "gather_steps")
+        out = _new_cl((K, B), C, H, W, Y)
+        _hip.call("snn_gather_steps_fwd", Y.data_ptr(), cl_stride(Y), steps.data_ptr(), out.data_ptr(), C, T, B, K, H * W,
+                  C, _stream())
+        ctx.save_for_backward(steps)
+        ctx.dims = (T, B, C, H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (steps,) = ctx.saved_tensors
+        T, B, C, H, W = ctx.dims
+        g = _raw_to_cl(g)
+        gY = _new_cl((T, B), C, H, W, g)
+        _hip.call("snn_gather_steps_bwd", g.data_ptr(), cl_stride(g), steps.data_ptr(), gY.data_ptr(), C, T, B,
+                  int(steps.shape[0]), H * W, C, _stream())
+        return gY, None
+
+
+def gather_steps(Y: torch.Tensor, steps: torch.Tensor) -> torch.Tensor:
+    """The frames ``steps[K,B]`` names (``select_label_steps``) out of a sequence ``Y[T,B,C,H,W]`` - dense or an aliased
+    channel slice of a wider channels-last buffer - as a dense channels-last ``[K,B,C,H,W]``."""
+    if Y.dim() != 5:
+        raise RuntimeError(f"gather_steps takes a sequence Y[T,B,C,H,W], got a tensor of rank {Y.dim()}")
+    return _GatherSteps.apply(Y, steps)
+
+
+class _DetectionLossSteps(Function):
+    """``_DetectionLoss`` over the anchors of the valid slots only (``steps[k][b] >= 0``); their number ``V`` is counted on
+    the device.  ``V = 0`` gives loss 0 and zero gradients; the gradients of empty slots are exact zeros."""
+
+    @staticmethod
+    def forward(ctx, cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, steps, loss_ratio: float):
+        _require_device(cls_preds, "loss: class predictions")
+        _require_device(bbox_preds, "loss: box predictions")
+        _require_device(bbox_offset, "loss: box offsets")
+        _require_device(bbox_mask, "loss: box mask")
+        for t, what in ((bbox_preds, "box predictions"), (bbox_offset, "box offsets"), (bbox_mask, "box mask"),
+                        (class_labels, "class labels")):
+            if t.device != cls_preds.device:
+                raise RuntimeError(f"loss: {what} are on {t.device}, the class predictions on {cls_preds.device}")
+        if cls_preds.dim() != 4:
+            raise RuntimeError("detection_loss_steps: class predictions [K,B,A,C+1] required")
+        K, B, A, C = cls_preds.shape
+        Ks, steps = _require_steps(steps, B, cls_preds, "detection_loss_steps")
+        logits, boxes = cls_preds.detach().contiguous(), bbox_preds.detach().contiguous()
+        off, msk = bbox_offset.contiguous(), bbox_mask.contiguous()
+        lab = class_labels.contiguous()
+        rows = K * B * A
+        if Ks != K or lab.numel() != rows or boxes.numel() != rows * 4 or off.numel() != rows * 4 or \
+                msk.numel() != rows * 4 or lab.dtype != torch.int64:
+            raise RuntimeError("detection loss: predictions, targets and steps differ in shape")
+        dev = logits.device
+        ws = torch.empty(_hip.query("snn_det_loss_steps_workspace_size", K, B, A), device=dev, dtype=torch.uint8)
+        stats = torch.empty(6, device=dev, dtype=torch.float64)
+        loss = torch.empty((), device=dev, dtype=_F32)
+        _hip.call("snn_det_loss_steps_fwd", logits.data_ptr(), boxes.data_ptr(), off.data_ptr(), msk.data_ptr(),
+                  lab.data_ptr(), steps.data_ptr(), K, B, A, C, float(loss_ratio), ws.data_ptr(), stats.data_ptr(),
+                  loss.data_ptr(), _stream())
+        ctx.save_for_backward(logits, boxes, off, msk, lab, steps, stats)
+        ctx.loss_ratio = float(loss_ratio)
+        ctx.shapes = (cls_preds.shape, bbox_preds.shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, boxes, off, msk, lab, steps, stats = ctx.saved_tensors
+        K, B, A, C = ctx.shapes[0]
+        g = g.detach().to(_F32).contiguous()
+        g_logits, g_boxes = torch.empty_like(logits), torch.empty_like(boxes)
+        _hip.call("snn_det_loss_steps_bwd", logits.data_ptr(), boxes.data_ptr(), off.data_ptr(), msk.data_ptr(),
+                  lab.data_ptr(), steps.data_ptr(), K, B, A, C, ctx.loss_ratio, stats.data_ptr(), g.data_ptr(),
+                  g_logits.data_ptr(), g_boxes.data_ptr(), _stream())
+        return g_logits.view(ctx.shapes[0]), g_boxes.view(ctx.shapes[1]), None, None, None, None, None
+
+
+def detection_loss_steps(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox_offset: torch.Tensor,
+                         bbox_mask: torch.Tensor, class_labels: torch.Tensor, steps: torch.Tensor,
+                         loss_ratio: float) -> torch.Tensor:
+    """``detection_loss`` of ``cls_preds[K,B,A,C+1]`` / ``bbox_preds[K,B,A,4]`` over the valid slots of ``steps[K,B]``:
+    ``r mean(CE[pos]) + (1 - r) mean(CE[neg]) + sum |bbox m - off m| / (4 A V)``."""
+    return _DetectionLossSteps.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, steps, loss_ratio)
+
+
 # ------------------------------------------------------------------------------------------- events
 def events_to_frames(t_bin: torch.Tensor, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, T: int, H: int,
                      W: int) -> torch.Tensor:

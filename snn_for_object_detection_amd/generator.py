@@ -479,18 +479,23 @@ class Head(nn.Module):
             setattr(self, f"anchor_gen_{idx}", AnchorGenerator(sizes=sizes[idx], ratios=ratios))
             setattr(self, f"model_{idx}", HeadGen(cfg, num_box_out, num_class_out, channels, init_weights))
 
-    def forward(self, X: List[torch.Tensor], state: Optional[ListState], all_steps: bool = False):
+    def forward(self, X: List[torch.Tensor], state: Optional[ListState], all_steps: bool = False,
+                steps: Optional[torch.Tensor] = None):
         """-> ``(anchors[A,4], cls_preds[B,A,C+1], bbox_preds[B,A,4], state)``.
 
         Given sequences the predictions are those of the LAST timestep (all the reference keeps,
         ``soda.py:141-144``) and ``state`` is the state after the last timestep.  ``all_steps=True`` keeps every
         timestep of a sequence instead: ``cls_preds[T,B,A,C+1]``, ``bbox_preds[T,B,A,4]`` (inference over a clip).
+        ``steps[K,B]`` (int32, ``functional.select_label_steps``) keeps the frames it names: ``cls_preds[K,B,A,C+1]``,
+        ``bbox_preds[K,B,A,4]``, zeros-in for an empty slot (training on every labelled timestep).
         """
+        if steps is not None and all_steps:
+            raise ValueError("Head.forward: all_steps and steps exclude each other")
         state = [None] * len(X) if state is None else state
         anchors, cls_preds, bbox_preds = [], [], []
         for idx, map in enumerate(X):
             anchors.append(getattr(self, f"anchor_gen_{idx}")(map))
-            boxes, classes, state[idx] = getattr(self, f"model_{idx}")(map, state[idx], all_steps=all_steps)
+            boxes, classes, state[idx] = getattr(self, f"model_{idx}")(map, state[idx], all_steps=all_steps, steps=steps)
             bbox_preds.append(boxes)
             cls_preds.append(classes)
         anchors = torch.cat(anchors)
@@ -526,9 +531,15 @@ class HeadGen(ModelGen):
     def _load_cfg(self, cfg) -> ListGen:
         return cfg(self.box_out, self.cls_out)
 
-    def forward(self, X: torch.Tensor, state: Optional[ListState], all_steps: bool = False):
+    def forward(self, X: torch.Tensor, state: Optional[ListState], all_steps: bool = False,
+                steps: Optional[torch.Tensor] = None):
         state = [None] * 3 if state is None else state
         all_steps = all_steps and X.dim() == 5
+        if steps is not None:
+            if X.dim() != 5:
+                raise ValueError(f"HeadGen.forward: steps select frames of a sequence [T,B,C,H,W], got a map of rank "
+                                 f"{X.dim()}")
+            return self._forward_steps(X, state, steps)
         # sequence input, stateless prediction nets: only the last timestep's predictions survive (unless all are asked for)
         stateless = X.dim() == 5 and not (any(_has_state(m) for m in self.box_net.modules())
                                           or any(_has_state(m) for m in self.cls_net.modules()))
@@ -544,6 +555,24 @@ class HeadGen(ModelGen):
             box, cls = box[-1], cls[-1]
         if box.dtype == torch.bfloat16:
             box, cls = HF.to_float32(box), HF.to_float32(cls)
+        return box, cls, state
+
+    def _forward_steps(self, X: torch.Tensor, state: ListState, steps: torch.Tensor):
+        """The predictions of the frames ``steps[K,B]`` names: the preparation net writes every timestep; stateless
+        prediction nets see the ``K*B`` gathered frames only, others run over the sequence and are gathered behind."""
+        stateless = not (any(_has_state(m) for m in self.box_net.modules())
+                         or any(_has_state(m) for m in self.cls_net.modules()))
+        Y, state[0] = self.base_net(X, state[0])
+        if stateless:
+            if Y.dtype == torch.bfloat16:
+                Y = HF.to_float32(Y)   # bf16-storage mode: the read-out and the prediction nets run in fp32, as for all_steps
+            Y = HF.gather_steps(Y, steps)
+        box, state[1] = self.box_net(Y, state[1])
+        cls, state[2] = self.cls_net(Y, state[2])
+        if box.dtype == torch.bfloat16:
+            box, cls = HF.to_float32(box), HF.to_float32(cls)
+        if not stateless:
+            box, cls = HF.gather_steps(box, steps), HF.gather_steps(cls, steps)
         return box, cls, state
 
 

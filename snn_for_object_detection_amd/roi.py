@@ -54,6 +54,38 @@ class RoI:
                   torch.cuda.current_stream().cuda_stream)
         return offset, mask, cls
 
+    def steps(self, anchors: torch.Tensor, labels: torch.Tensor, steps: torch.Tensor, t0: int = 0):
+        """Targets of every labelled frame (device only): ``labels[B,N,6]`` rows ``(ts, class, x1, y1, x2, y2)``,
+        ``steps[K,B]`` from ``functional.select_label_steps`` ->
+        ``(bbox_offset[K,B,A,4], bbox_mask[K,B,A,4], class_labels[K,B,A])``.
+
+        Slot ``(k, b)`` is ``__call__`` for one sample whose label tensor holds the real rows of sample ``b`` with
+        ``ts - t0 == steps[k][b]`` and its padding rows, in their order; rows of other timesteps take no part, an empty
+        slot (-1) gets zeros.  One launch for all slots."""
+        from . import _hip
+        if not anchors.is_cuda:
+            raise RuntimeError("RoI.steps runs on device tensors only (no CPU fallback)")
+        anchors = anchors.detach().contiguous().float()
+        labels = labels.detach().to(anchors.device).contiguous().float()
+        if labels.dim() != 3 or labels.shape[2] != 6:
+            raise RuntimeError(f"RoI.steps: labels[B,N,6] required, got {tuple(labels.shape)}")
+        B, N, _ = labels.shape
+        if steps.dim() != 2 or steps.shape[1] != B or steps.dtype != torch.int32 or steps.device != anchors.device:
+            raise RuntimeError(f"RoI.steps: steps must be an int32 [K, {B}] tensor on {anchors.device}")
+        steps = steps.contiguous()
+        K, A, dev = int(steps.shape[0]), anchors.shape[0], anchors.device
+        if N == 0:   # no rows at all: every slot is empty
+            return (torch.zeros((K, B, A, 4), device=dev), torch.zeros((K, B, A, 4), device=dev),
+                    torch.zeros((K, B, A), device=dev, dtype=torch.int64))
+        ws = torch.empty(_hip.query("snn_roi_steps_workspace_size", K, B, A, N), device=dev, dtype=torch.uint8)
+        offset = torch.empty((K, B, A, 4), device=dev, dtype=torch.float32)
+        mask = torch.empty((K, B, A, 4), device=dev, dtype=torch.float32)
+        cls = torch.empty((K, B, A), device=dev, dtype=torch.int64)
+        _hip.call("snn_roi_assign_steps", anchors.data_ptr(), labels.data_ptr(), steps.data_ptr(), K, B, A, N, int(t0),
+                  float(self.iou_threshold), ws.data_ptr(), offset.data_ptr(), mask.data_ptr(), cls.data_ptr(),
+                  torch.cuda.current_stream().cuda_stream)
+        return offset, mask, cls
+
     def _assign_anchor_to_box(self, ground_truth: torch.Tensor, anchors: torch.Tensor) -> torch.Tensor:
         num_gt = ground_truth.shape[0]
         iou = box.box_iou(anchors, ground_truth)

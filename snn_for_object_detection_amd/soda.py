@@ -14,6 +14,9 @@ Same constructor, hooks and step logic; what differs:
   ``metrics.MeanAveragePrecision.update_padded`` (no host synchronisation), ``on_validation_epoch_end`` /
   ``on_test_epoch_end`` log ``map, map_50, mar_1, mar_10, mar_100`` through ``log_dict``.  As in the reference
   (``sync_on_compute=False``) each rank's mAP covers the images that rank saw.
+* ``label_steps=K`` trains on every labelled timestep: six-column labels ``(ts, class, x1, y1, x2, y2)`` (the
+  reference's ``one_label: false`` sample format, which nothing there consumes) supervise up to ``K`` labelled frames
+  per sample instead of the last frame only (DESIGN "Every labelled timestep").
 """
 
 from types import SimpleNamespace
@@ -42,12 +45,15 @@ class SODa(nn.Module):
         state_storage: bool = False,
         init_weights: bool = True,
         plotter=None,
+        label_steps: Optional[int] = None,
     ):
         super().__init__()
+        if label_steps is not None and not 1 <= int(label_steps) <= 32:
+            raise ValueError(f"label_steps must be None or in 1 .. 32, got {label_steps}")
         self.hparams = SimpleNamespace(
             num_classes=num_classes, loss_ratio=loss_ratio, time_window=time_window,
             iou_threshold=iou_threshold, learning_rate=learning_rate, state_storage=state_storage,
-            init_weights=init_weights,
+            init_weights=init_weights, label_steps=None if label_steps is None else int(label_steps),
         )
         self.plotter = plotter
         self.logged = {}
@@ -117,7 +123,8 @@ class SODa(nn.Module):
         preds, _ = self._forward_impl(X, None)
         return preds
 
-    def _forward_impl(self, X: torch.Tensor, state: Optional[ListState], all_steps: bool = False):
+    def _forward_impl(self, X: torch.Tensor, state: Optional[ListState], all_steps: bool = False,
+                      steps: Optional[torch.Tensor] = None):
         from . import functional as HF
         state = [None] * 3 if state is None else state
         HF.begin_counter_batch()
@@ -126,16 +133,65 @@ class SODa(nn.Module):
             if self._snn_neck_grads_ready is not None and base_out.dim() == 5:
                 base_out = HF.grad_ready_hook(base_out, self._snn_neck_grads_ready)
             neck_out, state[1] = self.neck_net.forward(base_out, state[1])
-            anchors, cls_preds, bbox_preds, state[2] = self.head_net.forward(neck_out, state[2], all_steps=all_steps)
+            anchors, cls_preds, bbox_preds, state[2] = self.head_net.forward(neck_out, state[2], all_steps=all_steps,
+                                                                                 steps=steps)
         finally:
             HF.flush_counter_batch()
         return (anchors, cls_preds, bbox_preds), state
 
     # ------------------------------------------------------------------ steps
     def _step(self, batch: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        if batch[1].shape[-1] == 6:
+            return self._step_labelled_frames(batch)[0]
         X, labels = batch[0][self._rand_start_time():], batch[1]
         preds = self.forward(X)
         return self._loss(preds, labels)
+
+    def _step_labelled_frames(self, batch: Tuple[torch.Tensor, torch.Tensor]):
+        """Six-column labels ``(ts, class, x1, y1, x2, y2)``: the loss over every labelled frame the ``label_steps`` slots
+        hold.  The random prefix ``t0`` is cut from the frames and subtracted from the rows' timesteps alike; the frames
+        are chosen on the device (``steps[K,B]``), so the step stays free of host synchronisation.
+        -> ``(loss, preds of the K*B frames, steps, t0)``"""
+        from . import functional as HF
+        K = self.hparams.label_steps
+        if K is None:
+            raise ValueError("labels with six columns (ts, class, x1, y1, x2, y2) need the constructor keyword "
+                             "label_steps (the number of labelled frames kept per sample)")
+        t0 = self._rand_start_time()
+        X, labels = batch[0][t0:], batch[1]
+        if X.dim() != 5:
+            raise ValueError(f"six-column labels need a sequence X[T,B,2,H,W], got a tensor of rank {X.dim()}")
+        T = X.shape[0]
+        if K > T:
+            raise ValueError(f"label_steps = {K} exceeds the {T} timesteps left of the sequence")
+        labels = labels.to(X.device)
+        steps = HF.select_label_steps(labels, T, K, t0)
+        preds, _ = self._forward_impl(X, None, steps=steps)
+        anchors, cls_preds, bbox_preds = preds
+        bbox_offset, bbox_mask, class_labels = self.roi_blk.steps(anchors, labels, steps, t0)
+        loss = HF.detection_loss_steps(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, steps,
+                                       self.hparams.loss_ratio)
+        return loss, preds, steps, t0
+
+    def _eval_labelled_frames(self, batch: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """``validation_step`` / ``test_step`` on six-column labels: the loss as in training, and mAP over exactly the
+        valid slots - every labelled frame is one image, with the label rows of its own timestep.  Device ``where`` only."""
+        loss, preds, steps, t0 = self._step_labelled_frames(batch)
+        anchors, cls_preds, bbox_preds = (p.detach() for p in preds)
+        labels = batch[1].to(cls_preds.device).float()
+        K, B, A = cls_preds.shape[:3]
+        dets = box.multibox_detection_batched(F.softmax(cls_preds.reshape(K * B, A, -1), dim=2),
+                                              bbox_preds.reshape(K * B, A, 4), anchors)
+        dets[..., 2:] = torch.clamp(dets[..., 2:], min=0.0, max=1.0)     # the boxes predict_sequence reports
+        valid = (steps >= 0).reshape(K * B, 1)
+        dets[..., 0] = torch.where(valid, dets[..., 0], torch.full_like(dets[..., 0], -1.0))
+        # rows [K*B, N, 5]: the real rows of the slot's own timestep, -1 everywhere else
+        own = (labels[None, :, :, 1] >= 0) & (labels[None, :, :, 0] - float(t0) == steps[:, :, None].float()) \
+            & (steps[:, :, None] >= 0)
+        rows = torch.where(own.unsqueeze(-1), labels[None, :, :, 1:].expand(K, -1, -1, -1),
+                           torch.full((), -1.0, device=labels.device))
+        self.map_metric.update_padded(dets, rows.reshape(K * B, labels.shape[1], 5))
+        return loss
 
     def training_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
         loss = self._step(batch)
@@ -143,6 +199,10 @@ class SODa(nn.Module):
         return loss
 
     def validation_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
+        if batch[1].shape[-1] == 6:
+            loss = self._eval_labelled_frames(batch)
+            self.log("val_loss", loss, batch_size=batch[0].shape[1], sync_dist=True)
+            return loss
         preds = self.forward(batch[0][self._rand_start_time():])
         loss = self._loss(preds, batch[1])
         self.log("val_loss", loss, batch_size=batch[0].shape[1], sync_dist=True)
@@ -153,6 +213,10 @@ class SODa(nn.Module):
         self._map_compute()
 
     def test_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
+        if batch[1].shape[-1] == 6:
+            loss = self._eval_labelled_frames(batch)
+            self.log("test_loss", loss, batch_size=batch[0].shape[1], sync_dist=True)
+            return loss
         preds = self.forward(batch[0][self._rand_start_time():])
         loss = self._loss(preds, batch[1])
         self.log("test_loss", loss, batch_size=batch[0].shape[1], sync_dist=True)
