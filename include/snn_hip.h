@@ -98,10 +98,17 @@ enum { SNN_SCAN_WIDE_ADDRESSING = 1, /* bwd: use 64-bit pointer addressing even 
                                         then go through snn_bn_bwd_finalize_from_state.  Covered cases:
                                         snn_affine_neuron_bwd_sums_from_state().  The sequence must start from the
                                         initial state (v_leak, 0) - or carry the next flag */
-       SNN_SCAN_STATE_LOOKBACK = 32  /* with SNN_SCAN_SUMS_FROM_STATE, for a SEGMENT [t0, t0 + T) of a longer saved
+       SNN_SCAN_STATE_LOOKBACK = 32, /* with SNN_SCAN_SUMS_FROM_STATE, for a SEGMENT [t0, t0 + T) of a longer saved
                                         sequence, t0 >= 2: `state` points at step t0 and state[-1], state[-2] (the two
                                         steps in front of it, same [M][C] layout) are read to rebuild the neuron state
-                                        the segment starts from */ };
+                                        the segment starts from */
+       SNN_SCAN_SPIKE_MASK = 32      /* fwd only (the value is shared with the bwd-only flag above; each direction refuses
+                                        the other's meaning), together with SNN_SCAN_SPIKES_FROM_VDEC, through
+                                        snn_affine_neuron_fwd_mask: the spikes also leave as ONE BIT per neuron,
+                                        mask[T][M][ld_mask] of uint32 - bit (c & 31) of word (c >> 5) of a pixel's row is
+                                        v_dec[t][m][c] > v_th (strict), taken from the value stored to vdec.  C % 32 == 0,
+                                        ld_mask >= C / 32, mask 4-byte aligned; words c >> 5 >= C / 32 of a row are not
+                                        written.  Read by the snn_conv1x1_mask_ entry points */ };
 
 /* pooling kinds, layer_gen.py:139-173 / common.py:18-49 */
 enum { SNN_POOL_AVG = 0, SNN_POOL_MAX = 1, SNN_POOL_SUM = 2 };
@@ -361,6 +368,26 @@ int snn_conv3x3_halo_spikes(const float* vdec, int64_t ld, float v_th, const voi
                             int H, int W, int Cin, int Cout, double* bn_partial, int frames_per_step, int* bn_layout,
                             void* stream);
 
+/* ---- ... and over the spike BIT MASK a scan with SNN_SCAN_SPIKE_MASK wrote: mask[N * H * W][ld_mask] of uint32, bit
+ * (c & 31) of word (c >> 5) of a pixel's row = spike of channel c.  The three calls mirror the snn_conv1x1_spikes_ ones with
+ * (mask, ld_mask) in place of (vdec, ld, v_th); they move 1 bit instead of 32 per input element - one 4-byte load per pixel
+ * and 32-channel chunk, expanded to the matrix-core operand in registers - and run the arithmetic of the potentials-fed
+ * calls in their order: y and dw are bit-identical to theirs (same tile plans, split-K and ordered slab reduction).
+ *   snn_conv1x1_mask_supported : 1 when BOTH launches the non-NULL pointers describe are covered: it checks everything
+ *                              they hard-require - the two default arithmetics, Cin % 32 == 0, ld_mask >= Cin / 32, the mask
+ *                              4-byte aligned and below 2 GiB; forward (w and y given): w 16-byte aligned, ldy >= Cout;
+ *                              weight gradient (dy and dw given): Cout % 4 == 0, lddy % 4 == 0, lddy >= Cout, dy 16-byte
+ *                              aligned, the pixels of a split below 2 GiB of dy.  A NULL w / y (dy / dw) leaves that launch
+ *                              unchecked.  After a 1 the corresponding launch does not refuse; after a 0 the caller takes
+ *                              the potentials (snn_conv1x1_spikes_fwd / _wgrad), which the scan wrote all the same. */
+int snn_conv1x1_mask_supported(int64_t N, int H, int W, int Cin, int Cout, const uint32_t* mask, int64_t ld_mask,
+                               const float* w, const float* y, int64_t ldy, const float* dy, int64_t lddy, const float* dw,
+                               int fwd_precision, int bwd_precision);
+int snn_conv1x1_mask_fwd(const uint32_t* mask, int64_t ld_mask, const float* w, float* y, int64_t ldy, int64_t N, int H, int W,
+                         int Cin, int Cout, void* stream);
+int snn_conv1x1_mask_wgrad(const uint32_t* mask, int64_t ld_mask, const float* dy, int64_t lddy, float* dw, int64_t N, int H,
+                           int W, int Cin, int Cout, int accumulate, float* workspace, int splitk, void* stream);
+
 /* ---------------------------------------------------------------- batch-norm statistics
  * Train-mode nn.BatchNorm2d (layer_gen.py:211-214) applied per TIMESTEP: for every (t,c)
  * the biased mean/var over the M = B*h*w pixels of timestep t (generator.py:190-195 calls the
@@ -414,6 +441,13 @@ int snn_affine_neuron_fwd(int neuron, const float* y, int64_t ldy,
                           float* out, int64_t ldo, const float* addend, int64_t ld_addend,
                           float* vT, float* iT, float* vdec,
                           int T, int64_t M, int C, const snn_neuron_params* p, int flags, void* stream);
+/* The same call with a spike bit mask as a further output: with SNN_SCAN_SPIKE_MASK | SNN_SCAN_SPIKES_FROM_VDEC in flags it
+ * writes vdec, the final state AND mask[T][M][ld_mask] (layout: see the flag); vdec and the state are the bits of the call
+ * without the flag.  Without the flag mask must be NULL and the call is snn_affine_neuron_fwd. */
+int snn_affine_neuron_fwd_mask(int neuron, const float* y, int64_t ldy, const float* alpha, const float* beta,
+                               const float* v0, const float* i0, float* out, int64_t ldo, const float* addend,
+                               int64_t ld_addend, float* vT, float* iT, float* vdec, int T, int64_t M, int C,
+                               const snn_neuron_params* p, int flags, void* stream, uint32_t* mask, int64_t ld_mask);
 
 /* Reverse-time scan (BPTT through the neuron).  LIF: the surrogate dz/du is p->surrogate (default SuperSpike,
  * 1/(alpha|u|+1)^2) and the reset path is differentiated through the spike unless p->reset_detached (default: NOT

@@ -19,6 +19,7 @@ ABI_VERSION = 20
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_FP16X3, PREC_BF16X1, PREC_BF16S = 0, 1, 3, 4, 5, 6   # SNN_PREC_* of include/snn_hip.h
 SCAN_WIDE_ADDRESSING, SCAN_LAST_STEP_ONLY, SCAN_BF16_STORAGE, SCAN_SPIKES_FROM_VDEC, SCAN_SUMS_FROM_STATE = 1, 2, 4, 8, 16
 SCAN_STATE_LOOKBACK = 32
+SCAN_SPIKE_MASK = 32   # forward only (shares its value with the backward-only flag above)
 SURR_SUPER, SURR_TRIANGLE, SURR_SIGMOID, SURR_ATAN = 0, 1, 2, 3   # SNN_SURR_* of include/snn_hip.h
 
 
@@ -73,6 +74,9 @@ SIGNATURES = {
     "snn_conv1x1_spikes_supported": (c_int, [_L, _I, _I, _I, _I, _L, _I, _I]),
     "snn_conv1x1_spikes_fwd": (c_int, [_P, _L, _F, _P, _P, _L, _L, _I, _I, _I, _I, _P]),
     "snn_conv1x1_spikes_wgrad": (c_int, [_P, _L, _F, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "snn_conv1x1_mask_supported": (c_int, [_L, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P, _L, _P, _I, _I]),
+    "snn_conv1x1_mask_fwd": (c_int, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _I, _P]),
+    "snn_conv1x1_mask_wgrad": (c_int, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _I, _P]),
     "snn_conv2d_spikes_supported": (c_int, [_L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _I, _I]),
     "snn_conv2d_spikes_fwd": (c_int, [_P, _L, _F, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "snn_conv2d_spikes_wgrad": (c_int, [_P, _L, _F, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
@@ -86,6 +90,8 @@ SIGNATURES = {
     "snn_bn_bwd_coef": (c_int, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "snn_affine_neuron_fwd": (c_int, [_I, _P, _L, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _I, _L, _I,
                                       POINTER(NeuronParams), _I, _P]),
+    "snn_affine_neuron_fwd_mask": (c_int, [_I, _P, _L, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _I, _L, _I,
+                                           POINTER(NeuronParams), _I, _P, _P, _L]),
     "snn_lif_ckpt_interval": (c_int, []),
     "snn_lif_fwd_ckpt": (c_int, [_P, _L, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _I, _L, _I,
                                  POINTER(NeuronParams), _P]),

@@ -105,3 +105,7 @@ int snn_first_layer_blocks(int64_t rows, int num_cu);
 // the one launch of k_conv_first (see conv_first.hip)
 int snn_launch_first(bool wgrad, bool bnapply, bool sb, int blocks, size_t lds, const float* x, const float* w,
                      const float* dy, float* out, const FirstGeom& fg, void* stream, const char* name);
+
+// what snn_conv1x1_mask_wgrad hard-requires of a call (conv_wgrad.hip), for snn_conv1x1_mask_supported (conv_gather.hip)
+bool snn_wgrad_mask_ok(int64_t N, int H, int W, int Cin, int Cout, const uint32_t* mask, int64_t ld_mask, const float* dy,
+                       int64_t lddy, const float* dw);

@@ -155,8 +155,13 @@ __device__ __forceinline__ void stat_flush(double (&s)[TN], double (&q)[TN], dou
 // is formed here, z = (v_dec > x_th), on the way into LDS.  A spike is exact in ONE fp16 piece (16.0 or 0 after the 2^4
 // pre-scale): no low image is written or read and the product low(x) * high(w) - identically zero - is not issued: two
 // MFMA products per multiply-add, same bits as the three-product kernel fed the stored spikes.
+// XM (XSP only; snn_conv1x1_mask_fwd, 1x1 / stride 1): `in` is the spike BIT MASK the scan wrote next to the potentials
+// (SNN_SCAN_SPIKE_MASK): uint32 [pixel][ldi], bit c & 31 of word c >> 5.  A 32-channel k-step of a pixel is ONE dword: lane
+// (r, h) loads the word of its own fragment row - one 4-byte load instruction per wave and 32 pixels, against four 16-byte
+// ones - and expands byte 2 * ks + h of it into its 8 fp16 values (0x4C00 or 0) in registers.  No A image in LDS, nothing of
+// A is written or read there; the MFMAs, their operands' bits and their order are those of XSP.
 template <int BN, int WM, int WN, bool DGRAD, bool VEC, int SPLIT, bool FAST, bool PRESPLIT = false, bool SB = false,
-          bool XSP = false>
+          bool XSP = false, bool XM = false>
 __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (DGRAD ? 4 : SNN_GATHER_SB_WAVES) : 2)) : SNN_CONV_MIN_WAVES) void k_conv_gather(const float* __restrict__ in, const float* __restrict__ wk,
                                                           float* __restrict__ out, ConvGeom g,
                                                           const float* __restrict__ addend, int64_t ld_add,
@@ -167,6 +172,7 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
     static_assert(WM * WN == 4, "4 waves");
     static_assert(!SB || (FAST && SPLIT == 5 && !PRESPLIT), "bf16 storage: the pipelined one-product kernel");
     static_assert(!XSP || (FAST && SPLIT == 4 && !DGRAD && !PRESPLIT && !SB), "spikes from potentials: fp16 x 3 forward");
+    static_assert(!XM || XSP, "spike bit mask: an instance of the spikes-from-potentials kernel");
     constexpr int ES = SB ? 2 : 4;   // bytes per activation element in HBM
     constexpr int NPIECE = SPLIT == 3 ? 3 : (SPLIT == 5 ? 1 : 2);  // 16-bit images per operand
     constexpr int A_BYTES = SPLIT ? NPIECE * BM * LDB * 2 : BM * LDK * 4;
@@ -258,7 +264,8 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
 
     // A rows on their way to LDS: 4 fp32 values, or (SB) 4 bf16 values as two dwords.  (Integer-typed on purpose: carried
     // in float lanes and bit-cast back element by element, hipcc 7.2 narrows the 8-byte buffer load to 4 bytes.)
-    using AReg = typename std::conditional<SB, u32x2, f32x4>::type;
+    // XM: one mask word per fragment row (TM of the 4 slots are used)
+    using AReg = typename std::conditional<SB, u32x2, typename std::conditional<XM, unsigned, f32x4>::type>::type;
     AReg ra[4];
     f32x4 rb[BROWS];
 
@@ -267,7 +274,22 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
     int a_rel[4];            // byte offset of (row pixel origin, channel kq) from the block's first image
     unsigned a_mask[4];      // bit t: tap t of this row reads inside the image
     unsigned b_rel[BROWS];   // byte offset of (weight row, column kq); >= 2^31 for rows past OC
-    if (FAST) {
+    [[maybe_unused]] int xm_rel[TM];   // XM: byte offset of the mask row of fragment row (wm * TM + i) * 32 + r; -1 past Mtot
+    if constexpr (XM) {
+        // the whole mask is one buffer (host-checked: Mtot * ldi * 4 < 2^31)
+        rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)(g.Mtot * g.ldi * 4), 0x00020000);
+        rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wk), 0, g.OC * g.KtotFull * 4, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int64_t m = m0 + (wm * TM + i) * 32 + r;
+            xm_rel[i] = m < g.Mtot ? (int)(m * g.ldi * 4) : -1;
+        }
+#pragma unroll
+        for (int j = 0; j < BROWS; ++j) {
+            const int n = n0 + lr + 32 * j;
+            b_rel[j] = n < g.OC ? (unsigned)(n * g.KtotFull + kq) * 4u : 0x80000000u;
+        }
+    } else if (FAST) {
         const int ow_ = DGRAD ? g.OWc : g.OW, oh_ = DGRAD ? g.OHc : g.OH;
         const int64_t img0 = (unsigned)m0 / (unsigned)(oh_ * ow_);
         const int64_t ipix = (int64_t)g.IH * g.IW;
@@ -321,7 +343,13 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
             wcol0 = ((g.kh0 + g.stride * th) * g.KW + (g.kw0 + g.stride * tw)) * g.IC + c0;
         }
         const int tbit = kin ? tap : 31;  // bit 31 is never set: a prefetch past the last k-step loads zeros
-        if (which & 1) {
+        if constexpr (XM) {   // 1x1: k0n / 32 is the word of the row (a prefetch past the last k-step loads zeros)
+            if (which & 1) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+                    ra[i] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs_a, (kin && xm_rel[i] >= 0) ? xm_rel[i] + (k0n >> 5) * 4 : -1, 0, 0);
+            }
+        } else if (which & 1) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int voff = ((a_mask[j] >> tbit) & 1u) ? a_rel[j] + toff : -1;
@@ -342,7 +370,7 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
             load_tiles_fast(k0, ra, rb);
             return;
         }
-        if constexpr (!SB) {   // (the generic loaders hold fp32 rows; SB kernels are FAST by construction)
+        if constexpr (!SB && !XM) {   // (the generic loaders hold fp32 rows; SB / XM kernels are FAST by construction)
         const int kk = k0 + kq;
         if (VEC) {
             // Branch-free: every lane always loads from a clamped (valid) address and masks the value afterwards,
@@ -415,7 +443,7 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
         *reinterpret_cast<bf16x4*>(&lo_img[row * LDB + kq]) = lo;
     };
     auto store_tiles = [&]() {
-        if constexpr (SB) return;
+        if constexpr (SB || XM) return;
         else if (SPLIT) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) split_store(ra[j], Ah, Am, Al, lr + 32 * j);
@@ -490,6 +518,7 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
         };
         auto convert_a = [&](const AReg& v, bf16x4* out) {
             if constexpr (SB) out[0] = __builtin_bit_cast(bf16x4, v);   // already the bf16 values
+            else if constexpr (XM) return;   // (expanded per fragment: mfma_group)
             else if constexpr (XSP) {   // z = (v_dec > th) as ONE fp16 piece of z * 2^4: 0x4C00 (16.0) or 0
                 u32x2 hi;
 #pragma unroll
@@ -507,9 +536,21 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
                 convert(v, out, kF16WeightScale);
             }
         };
+        [[maybe_unused]] unsigned xm_cur[TM];   // XM: the mask words of the tile the MFMAs are working on
+        // byte `sel` of a mask word as 8 fp16 values: bit b -> element b = 0x4C00 (16.0, the spike after the 2^4 pre-scale) or 0
+        auto xm_expand = [&](unsigned word, int sel) {
+            const unsigned b = (word >> (8 * sel)) & 0xffu;
+            u32x4 d;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned v = (b >> (2 * q)) & 3u;
+                d[q] = ((v | (v << 15)) & 0x00010001u) * 0x4C00u;
+            }
+            return __builtin_bit_cast(bf16x8, d);
+        };
         auto write_tiles = [&]() {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
+            for (int j = 0; j < (XM ? 0 : 4); ++j) {
                 const int o = (lr + 32 * j) * LDB + kq;
                 *reinterpret_cast<bf16x4*>(&Ah[o]) = pa[j][0];
                 if constexpr (NP >= 2 && !XSP) *reinterpret_cast<bf16x4*>(&Al[o]) = pa[j][1];
@@ -528,6 +569,10 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int off = ((wm * TM + i) * 32 + r) * LDB + ks * 16 + 8 * h;
+                if constexpr (XM) {
+                    ah[i] = xm_expand(xm_cur[i], 2 * ks + h);
+                    continue;
+                }
                 ah[i] = *reinterpret_cast<const bf16x8*>(&Ah[off]);
                 if constexpr (NP >= 2 && !XSP) al[i] = *reinterpret_cast<const bf16x8*>(&Al[off]);
                 if constexpr (NP >= 3) am[i] = *reinterpret_cast<const bf16x8*>(&Am[off]);
@@ -573,9 +618,9 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
                 }
         };
         constexpr int NM = TM * TN * (XSP ? 2 : NPROD);  // MFMAs per k16 group
-        constexpr int NREAD = XSP ? TM + TN * NP : (TM + TN) * NP;   // ds_read_b128 per k16 group
+        constexpr int NREAD = XM ? TN * NP : (XSP ? TM + TN * NP : (TM + TN) * NP);   // ds_read_b128 per k16 group
         constexpr int CONV_OPS = SPLIT == 3 ? 24 : (SPLIT == 5 ? 2 : 14);   // VALU per converted f32x4 (approx.)
-        constexpr int VPG_A = ((XSP ? 4 * 8 : 4 * CONV_OPS) + NM - 1) / NM;
+        constexpr int VPG_A = ((XM ? TM * 18 : (XSP ? 4 * 8 : 4 * CONV_OPS)) + NM - 1) / NM;
         constexpr int VPG_B = PRESPLIT ? 1 : (BROWS * CONV_OPS + NM - 1) / NM;   // pre-split: only register moves
         if (g.Ktot > 0) {
             // both first tiles are requested back to back (the accumulators are not live yet, registers are free):
@@ -584,6 +629,10 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
             f32x4 rb0[BROWS];
             load_tiles_fast(0, ra0, rb0);
             load_tiles_fast(BK, ra, rb);
+            if constexpr (XM) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i) xm_cur[i] = ra0[i];
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) convert_a(ra0[j], pa[j]);
 #pragma unroll
@@ -621,6 +670,10 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
             }
             __builtin_amdgcn_sched_barrier(0);
             STAMP(1);
+            if constexpr (XM) {   // the words of tile k + 1 (requested one k-step ago) become the current ones
+#pragma unroll
+                for (int i = 0; i < TM; ++i) xm_cur[i] = ra[i];
+            }
             load_tiles_fast(k0 + 2 * BK, ra, rb);   // (requesting the A rows one MFMA group earlier: measured neutral)
             STAMP(2);
             __syncthreads();
@@ -838,7 +891,7 @@ __global__ __launch_bounds__(kThreads, (FAST && SPLIT) ? (PRESPLIT ? 3 : (SB ? (
 
 // The launch plan of k_conv_gather for one ConvGeom (the forward, or one stride phase of a data gradient), read by
 // launch_gather and by snn_conv2d_gather_plan.  ok = 0: the launch refuses the call (why: the reason).
-enum GatherLoader { kLoadScalar = 0, kLoadVec = 1, kLoadFast = 2, kLoadFastPresplit = 3, kLoadSB = 4, kLoadXSP = 5 };
+enum GatherLoader { kLoadScalar = 0, kLoadVec = 1, kLoadFast = 2, kLoadFastPresplit = 3, kLoadSB = 4, kLoadXSP = 5, kLoadXM = 6 };
 enum GatherRefusal { kGatherOk = 0, kGatherTooManyPixels, kGatherNotFastSB, kGatherNotFastXSP, kGatherGridTooLarge };
 struct GatherPlan {
     int ok, why;
@@ -848,10 +901,12 @@ struct GatherPlan {
     int mtiles, mtiles_per_xcd, ntiles;
     int64_t blocks;  // mtiles_per_xcd * 8 * ntiles: the blocks past the last pixel tile of an XCD share return at once
 };
+// xm (with xsp): the gathered tensor is a spike bit mask (uint32 words, g.ldi words per pixel; kAlignIn16 then stands for
+// its 4-byte alignment)
 static GatherPlan gather_plan(const ConvGeom& g, bool dgrad, int split, bool sb, bool xsp, unsigned align, bool has_split,
-                              bool has_add, bool has_add2) {
+                              bool has_add, bool has_add2, bool xm = false) {
     GatherPlan p = {};
-    const bool vec = (g.IC % 4 == 0) && (g.ldi % 4 == 0) && (align & (sb ? kAlignIn8 : kAlignIn16)) && (align & kAlignW16);
+    const bool vec = (g.IC % 4 == 0) && (xm || g.ldi % 4 == 0) && (align & (sb ? kAlignIn8 : kAlignIn16)) && (align & kAlignW16);
     const int64_t gm = snn_ceil_div(g.Mtot, BM);
     if (!(g.Mtot < 0x7fffffffLL && (int64_t)g.IH * g.IW < 0x7fffffffLL)) {
         p.why = kGatherTooManyPixels;
@@ -861,7 +916,8 @@ static GatherPlan gather_plan(const ConvGeom& g, bool dgrad, int split, bool sb,
     const int ntaps = nth * ntw;
     static const bool no_fast = snn_tuning_env("SNN_CONV_NO_FAST") != nullptr;  // tuning / bisecting aid
     const bool fast = vec && !no_fast && g.IC % BK == 0 && ntaps >= 1 && ntaps <= 31 && nth <= 6 && ntw <= 6 &&
-                      (int64_t)g.IH * g.IW * g.ldi * 16 < 0x7fffffffLL && (int64_t)g.OC * g.KtotFull * 4 < 0x7fffffffLL;
+                      (int64_t)g.IH * g.IW * g.ldi * 16 < 0x7fffffffLL && (int64_t)g.OC * g.KtotFull * 4 < 0x7fffffffLL &&
+                      (!xm || (ntaps == 1 && g.stride == 1 && g.pad == 0 && g.ldi * 32 >= g.IC && g.Mtot * g.ldi * 4 < 0x7fffffffLL));
     p.out_vec = (g.ldo % 4 == 0) && (align & (sb ? kAlignOut8 : kAlignOut16)) &&
                 (!has_add || (align & (sb ? kAlignAdd8 : kAlignAdd16))) &&
                 (!has_add2 || (align & (sb ? kAlignAdd2_8 : kAlignAdd2_16)));
@@ -875,7 +931,7 @@ static GatherPlan gather_plan(const ConvGeom& g, bool dgrad, int split, bool sb,
     }
     // the pre-split weight image serves the pipelined kernel in its two-piece modes; every other path converts wk itself
     const bool presplit = has_split && (split == 2 || split == 4) && (align & kAlignSplit16);
-    p.loader = sb ? kLoadSB : xsp ? kLoadXSP : (fast && presplit) ? kLoadFastPresplit : fast ? kLoadFast : vec ? kLoadVec : kLoadScalar;
+    p.loader = sb ? kLoadSB : xm ? kLoadXM : xsp ? kLoadXSP : (fast && presplit) ? kLoadFastPresplit : fast ? kLoadFast : vec ? kLoadVec : kLoadScalar;
     p.bn = g.OC <= 32 ? 32 : (g.OC <= 64 ? 64 : 128);
     p.mtiles = (int)gm;
     p.mtiles_per_xcd = (int)snn_ceil_div(gm, 8);
@@ -911,10 +967,11 @@ constexpr int gather_wn(int bn) { return bn == 32 ? 1 : 2; }
 // split: the SPLIT of k_conv_gather the precision asks for (snn_conv2d_fwd: 0, 3, 4, 5; snn_conv2d_dgrad: 0, 2, 5)
 static int launch_gather(bool dgrad, int split, bool sb, bool xsp, const float* in, const float* wk, const void* wk_split,
                          float* out, const ConvGeom& g, const float* addend, int64_t ld_add, const float* addend2,
-                         int64_t ld_add2, hipStream_t st, const char* name) {
-    const GatherPlan p = gather_plan(g, dgrad, split, sb, xsp,
-                                     gather_align_bits(in, wk, wk_split, out, addend, ld_add, addend2, ld_add2),
-                                     wk_split != nullptr, addend != nullptr, addend2 != nullptr);
+                         int64_t ld_add2, hipStream_t st, const char* name, bool xm = false) {
+    unsigned align = gather_align_bits(in, wk, wk_split, out, addend, ld_add, addend2, ld_add2);
+    if (xm) align = (align & ~(kAlignIn16 | kAlignIn8)) | (aligned(4, {in}) ? kAlignIn16 : 0u);
+    const GatherPlan p = gather_plan(g, dgrad, split, sb, xsp, align, wk_split != nullptr, addend != nullptr,
+                                     addend2 != nullptr, xm);
     SNN_REQUIRE(p.why != kGatherTooManyPixels, "%s: too many pixels", name);
     SNN_REQUIRE(p.why != kGatherNotFastSB, "%s: bf16 storage covers the pipelined implicit GEMM only (channels a multiple of 32, pixel "
                 "stride a multiple of 4, 8-byte aligned tensors): %d channels, stride %lld", name, g.IC, (long long)g.ldi);
@@ -932,19 +989,19 @@ static int launch_gather(bool dgrad, int split, bool sb, bool xsp, const float* 
         [&](auto BN, auto L, auto DGRAD, auto SPLIT) {
             constexpr int l = L(), s = SPLIT();
             constexpr bool vec = l != kLoadScalar, fast = l >= kLoadFast, pre = l == kLoadFastPresplit, sbl = l == kLoadSB,
-                           xspl = l == kLoadXSP;
+                           xml = l == kLoadXM, xspl = l == kLoadXSP || xml;
             // the vector loader has no two-piece fp16 and no one-product arithmetic (4 -> 3, 5 -> 2); the scalar one is fp32
             constexpr int ksplit = fast ? s : (vec ? (s == 4 ? 3 : (s == 5 ? 2 : s)) : 0);
             // SB is SPLIT 5, XSP the forward with SPLIT 4, the pre-split image serves SPLIT 2 and 4
             if constexpr ((DGRAD() ? s != 3 && s != 4 : s != 2) && (!sbl || s == 5) && (!xspl || (!DGRAD() && s == 4)) &&
                           (!pre || s == 2 || s == 4)) {
-                hipLaunchKernelGGL((k_conv_gather<BN(), gather_wm(BN()), gather_wn(BN()), DGRAD(), vec, ksplit, fast, pre, sbl, xspl>),
+                hipLaunchKernelGGL((k_conv_gather<BN(), gather_wm(BN()), gather_wn(BN()), DGRAD(), vec, ksplit, fast, pre, sbl, xspl, xml>),
                                    grid, dim3(kThreads), 0, st, in, wsrc, out, gg, addend, ld_add, addend2, ld_add2);
                 return true;
             }
             return false;
         },
-        OneOf<32, 64, 128>{p.bn}, OneOf<0, 1, 2, 3, 4, 5>{p.loader}, Flag{dgrad}, OneOf<0, 2, 3, 4, 5>{split});
+        OneOf<32, 64, 128>{p.bn}, OneOf<0, 1, 2, 3, 4, 5, 6>{p.loader}, Flag{dgrad}, OneOf<0, 2, 3, 4, 5>{split});
     SNN_CHECK_LAUNCH(name);
     return 0;
 }
@@ -1255,4 +1312,43 @@ extern "C" int snn_conv2d_spikes_fwd(const float* vdec, int64_t ld, float v_th, 
 extern "C" int snn_conv1x1_spikes_fwd(const float* vdec, int64_t ld, float v_th, const float* w, float* y, int64_t ldy,
                                       int64_t N, int H, int W, int Cin, int Cout, void* stream) {
     return snn_conv2d_spikes_fwd(vdec, ld, v_th, w, y, ldy, N, H, W, Cin, H, W, Cout, 1, 1, 1, 0, nullptr, 0, nullptr, stream);
+}
+
+// ---- the 1x1 convolution over the spike bit mask of a scan with SNN_SCAN_SPIKE_MASK (see k_conv_gather XM, include/snn_hip.h)
+namespace {
+// the forward launch's own requirements, shared by the query and the call: shape, stride, plan and pointer alignment
+static bool mask_fwd_ok(int64_t N, int H, int W, int Cin, int Cout, const uint32_t* mask, int64_t ld_mask, const float* w,
+                        const float* y, int64_t ldy) {
+    if (!(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && ld_mask >= Cin / 32 && ldy >= Cout &&
+          N * (int64_t)H * W < 0x7fffffffLL && (int64_t)Cin * Cin < 0xffffffffLL && mask && w && y))
+        return false;
+    const ConvGeom g = gather_fwd_geom(N, H, W, Cin, H, W, Cout, 1, 1, 1, 0, ld_mask, ldy);
+    unsigned align = gather_align_bits(mask, w, nullptr, y, nullptr, 0, nullptr, 0) & ~(kAlignIn16 | kAlignIn8);
+    if (aligned(4, {mask})) align |= kAlignIn16;
+    const GatherPlan p = gather_plan(g, false, 4, false, true, align, false, false, false, true);
+    return p.ok && p.loader == kLoadXM;
+}
+}  // namespace
+
+extern "C" int snn_conv1x1_mask_supported(int64_t N, int H, int W, int Cin, int Cout, const uint32_t* mask, int64_t ld_mask,
+                                          const float* w, const float* y, int64_t ldy, const float* dy, int64_t lddy,
+                                          const float* dw, int fwd_precision, int bwd_precision) {
+    if (fwd_precision != SNN_PREC_FP16X3 || bwd_precision != SNN_PREC_BF16X3 || !mask) return 0;
+    if (!(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && ld_mask >= Cin / 32 && aligned(4, {mask}) &&
+          N * (int64_t)H * W * ld_mask * 4 < 0x7fffffffLL))
+        return 0;
+    if ((w || y) && !mask_fwd_ok(N, H, W, Cin, Cout, mask, ld_mask, w, y, ldy)) return 0;
+    if ((dy || dw) && !snn_wgrad_mask_ok(N, H, W, Cin, Cout, mask, ld_mask, dy, lddy, dw)) return 0;
+    return 1;
+}
+
+extern "C" int snn_conv1x1_mask_fwd(const uint32_t* mask, int64_t ld_mask, const float* w, float* y, int64_t ldy, int64_t N,
+                                    int H, int W, int Cin, int Cout, void* stream) {
+    SNN_REQUIRE(mask && w && y, "snn_conv1x1_mask_fwd: null pointer");
+    if (check_conv_shape("snn_conv1x1_mask_fwd", N, H, W, Cin, H, W, Cout, 1, 1, 1, 0)) return 1;
+    SNN_REQUIRE(mask_fwd_ok(N, H, W, Cin, Cout, mask, ld_mask, w, y, ldy),
+                "snn_conv1x1_mask_fwd: call not covered (ask snn_conv1x1_mask_supported)");
+    const ConvGeom g = gather_fwd_geom(N, H, W, Cin, H, W, Cout, 1, 1, 1, 0, ld_mask, ldy);
+    return launch_gather(false, 4, false, true, reinterpret_cast<const float*>(mask), w, nullptr, y, g, nullptr, 0, nullptr, 0,
+                         (hipStream_t)stream, "snn_conv1x1_mask_fwd", true);
 }

@@ -232,7 +232,12 @@ __global__ __launch_bounds__(kThreads, SNN_CONV_MIN_WAVES) void k_conv_wgrad(con
 // XSP (bf16 x 3 only; snn_conv1x1_spikes_wgrad): x holds the saved potentials v_dec of a LIF layer that wrote no spike tensor
 // (see k_conv_gather XSP); the operand z = (v_dec > x_th) is formed in the conversion - one exact bf16 piece (0x3F80 or 0),
 // no low image, and the product high(dy) * low(x) is not issued: two MFMA products per multiply-add.
-template <int TM, int TN, int WM, int WN, int WBK, bool ONE, bool SB = false, bool XSP = false>   // ONE: bf16 x 1 (hi pieces only, one product)
+// XM (XSP only; snn_conv1x1_mask_wgrad, 1x1 / stride 1): x is the spike BIT MASK of the scan (SNN_SCAN_SPIKE_MASK): uint32
+// [pixel][ldx], bit ci & 31 of word ci >> 5.  A stage's x operand is WBK words per 32-column group - ONE 4-byte load per
+// thread (at most one load instruction per wave and stage, against 4 * XQ 16-byte ones), staged as words (Xw[group][pixel]);
+// lane (r, h) reads the 8 words of its 8 pixels (two broadcast ds_read_b128) and takes bit r of each as a bf16 1.0 / 0.  The
+// MFMAs, their operands' bits and their order are those of XSP.
+template <int TM, int TN, int WM, int WN, int WBK, bool ONE, bool SB = false, bool XSP = false, bool XM = false>   // ONE: bf16 x 1 (hi pieces only, one product)
 __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __restrict__ x,
                                                                  const float* __restrict__ dy,
                                                                  float* __restrict__ ws, WgradGeom g) {
@@ -244,6 +249,8 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
     static_assert(WBK == 32 || WBK == 64, "stage length");
     static_assert(!SB || ONE, "bf16 storage: one product");
     static_assert(!XSP || (!ONE && !SB), "spikes from potentials: the bf16 x 3 kernel");
+    static_assert(!XM || XSP, "spike bit mask: an instance of the spikes-from-potentials kernel");
+    constexpr int XW = ((BNk / 32) * WBK + kThreads - 1) / kThreads;   // XM: mask words per thread and stage (1, 2 for the widest tile)
     constexpr int ES = SB ? 2 : 4;   // bytes per activation element in HBM
     constexpr int LDW = WBK + 8;      // bf16 row pitch: 80 / 144 bytes, conflict-free ds_read_b128 fragments
     constexpr int NQ = WBK / 4;       // pixel quads per stage
@@ -251,8 +258,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
     constexpr int DQ = (DG + GPP - 1) / GPP, XQ = (XG + GPP - 1) / GPP;
     __shared__ __attribute__((aligned(16))) __bf16 Dh[BMc * LDW];
     __shared__ __attribute__((aligned(16))) __bf16 Dl[ONE ? 8 : BMc * LDW];
-    __shared__ __attribute__((aligned(16))) __bf16 Xh[BNk * LDW];
+    __shared__ __attribute__((aligned(16))) __bf16 Xh[XM ? 8 : BNk * LDW];
     __shared__ __attribute__((aligned(16))) __bf16 Xl[(ONE || XSP) ? 8 : BNk * LDW];
+    __shared__ __attribute__((aligned(16))) unsigned Xw[XM ? XW * kThreads : 4];   // XM: [32-column group][WBK pixels] = [tid + kThreads * k]
     __shared__ __attribute__((aligned(16))) int Pinfo[2][WBK][4];  // {byte offset of the pixel origin, y0, x0, valid}
 
     const int tid = threadIdx.x;
@@ -331,6 +339,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
         d_img = (int)(im - img_lo);
     }
     auto decode = [&](int slot) {
+        if constexpr (XM) return;   // (1x1 / stride 1: a pixel's mask row is at pixel * ldx)
         if (tid < WBK) {
             const int y0 = d_oy * g.stride - g.pad, x0 = d_ox * g.stride - g.pad;
             int4 info;
@@ -354,22 +363,40 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
     // operand quads on their way to LDS: 4 fp32 values, or (SB) 4 bf16 values as two dwords (integer-typed: see k_conv_gather)
     using OReg = typename std::conditional<SB, u32x2, f32x4>::type;
     OReg rd[DQ][4], rx[XQ][4];
+    // XM: word k of a thread -> (pixel tid % WBK of the stage, 32-column group tid / WBK + k * (kThreads / WBK)); past the
+    // tile / Cin / the split: zeros
+    [[maybe_unused]] unsigned rxw[XW] = {}, pxw[XW] = {};
+    [[maybe_unused]] const int xm_pl = tid % WBK;
+    [[maybe_unused]] const int xm_word = kc0 / 32 + tid / WBK;
+    [[maybe_unused]] bool xm_ok[XW];
+#pragma unroll
+    for (int k = 0; k < XW; ++k)
+        xm_ok[k] = tid / WBK + k * (kThreads / WBK) < BNk / 32 && (xm_word + k * (kThreads / WBK)) * 32 < g.Cin;
+    if constexpr (XM)   // the whole mask is one buffer (host-checked: Mtot * ldx * 4 < 2^31)
+        rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)(g.Mtot * g.ldx * 4), 0x00020000);
     auto load_tiles = [&](unsigned p0, int slot) {
         const int dstage = (int)(p0 - p_lo) * (int)g.lddy * ES;  // scalar
         auto fetch = [&](__amdgpu_buffer_rsrc_t rs, int voff) -> OReg {
             if constexpr (SB) return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0));
             else return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0));
         };
+        if constexpr (XM) {
+            const unsigned p = p0 + (unsigned)xm_pl;
+#pragma unroll
+            for (int k = 0; k < XW; ++k)
+                rxw[k] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(
+                    rs_x, (xm_ok[k] && p < p_hi) ? (int)((p * (unsigned)g.ldx + (unsigned)(xm_word + k * (kThreads / WBK))) * 4u) : -1, 0, 0);
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int4 info = *reinterpret_cast<const int4*>(&Pinfo[slot][quad * 4 + e][0]);
+            const int4 info = XM ? int4{0, 0, 0, 0} : *reinterpret_cast<const int4*>(&Pinfo[slot][quad * 4 + e][0]);
 #pragma unroll
             for (int q = 0; q < DQ; ++q) {
                 const int voff = d_off[q] < 0 ? -1 : d_off[q] + e * (int)g.lddy * ES + dstage;
                 rd[q][e] = fetch(rs_d, voff);
             }
 #pragma unroll
-            for (int q = 0; q < XQ; ++q) {
+            for (int q = 0; q < (XM ? 0 : XQ); ++q) {
                 const int iy = info.y + x_kh[q], ix = info.z + x_kw[q];
                 const bool ok = (info.w != 0) & x_ok[q] & ((unsigned)iy < (unsigned)g.H) & ((unsigned)ix < (unsigned)g.W);
                 const int voff = ok ? info.x + x_tapoff[q] : -1;
@@ -429,8 +456,12 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
                     if constexpr (!ONE) *reinterpret_cast<bf16x4*>(&Dl[(d_cq[q] + c) * LDW + quad * 4]) = pd[q][c][1];
                 }
             }
+        if constexpr (XM) {
 #pragma unroll
-        for (int q = 0; q < XQ; ++q)
+            for (int k = 0; k < XW; ++k) Xw[tid + kThreads * k] = pxw[k];
+        }
+#pragma unroll
+        for (int q = 0; q < (XM ? 0 : XQ); ++q)
             if (grp0 + GPP * q < XG) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
@@ -458,6 +489,17 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
+            if constexpr (XM) {   // bit r of the words of pixels 16 ks + 8 h .. + 7: bf16 1.0 (0x3F80) or 0
+                const u32x4 w0 = *reinterpret_cast<const u32x4*>(&Xw[(wn * TN + j) * WBK + ks * 16 + 8 * h]);
+                const u32x4 w1 = *reinterpret_cast<const u32x4*>(&Xw[(wn * TN + j) * WBK + ks * 16 + 8 * h + 4]);
+                u32x4 d;
+                d[0] = (((w0[0] >> r) & 1u) | (((w0[1] >> r) & 1u) << 16)) * 0x3F80u;
+                d[1] = (((w0[2] >> r) & 1u) | (((w0[3] >> r) & 1u) << 16)) * 0x3F80u;
+                d[2] = (((w1[0] >> r) & 1u) | (((w1[1] >> r) & 1u) << 16)) * 0x3F80u;
+                d[3] = (((w1[2] >> r) & 1u) | (((w1[3] >> r) & 1u) << 16)) * 0x3F80u;
+                bh[j] = __builtin_bit_cast(bf16x8, d);
+                continue;
+            }
             const int off = ((wn * TN + j) * 32 + r) * LDW + ks * 16 + 8 * h;
             bh[j] = *reinterpret_cast<const bf16x8*>(&Xh[off]);
             if constexpr (!ONE && !XSP) bl[j] = *reinterpret_cast<const bf16x8*>(&Xl[off]);
@@ -474,9 +516,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
             }
     };
     constexpr int NM = TM * TN * (ONE ? 1 : (XSP ? 2 : 3));
-    constexpr int NREAD = XSP ? 2 * TM + TN : (TM + TN) * (ONE ? 1 : 2);
+    constexpr int NREAD = XM ? 2 * TM + 2 * TN : (XSP ? 2 * TM + TN : (TM + TN) * (ONE ? 1 : 2));
     constexpr int CQ_OPS = SB ? 12 : 56;   // VALU per converted quad (approx.)
-    constexpr int VPG_D = (DQ * CQ_OPS + NM - 1) / NM, VPG_X = (XQ * (XSP ? 24 : CQ_OPS) + NM - 1) / NM;
+    constexpr int VPG_D = (DQ * CQ_OPS + NM - 1) / NM, VPG_X = XM ? (TN * 20 + NM - 1) / NM : (XQ * (XSP ? 24 : CQ_OPS) + NM - 1) / NM;
 
     decode(0);
     __syncthreads();
@@ -486,8 +528,11 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
 #pragma unroll
     for (int q = 0; q < DQ; ++q) convert_quad(rd[q], pd[q]);
 #pragma unroll
+    for (int k = 0; k < XW; ++k) pxw[k] = rxw[k];
+#pragma unroll
     for (int q = 0; q < XQ; ++q) {
-        if constexpr (XSP) convert_spikes(rx[q], px[q]);
+        if constexpr (XM) continue;
+        else if constexpr (XSP) convert_spikes(rx[q], px[q]);
         else convert_quad(rx[q], px[q]);
     }
     write_tiles();
@@ -510,8 +555,11 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
         __builtin_amdgcn_sched_barrier(0);
         mfma_group(1);
 #pragma unroll
+        for (int k = 0; k < XW; ++k) pxw[k] = rxw[k];   // (XM: the words of tile k + 1 as they were loaded; rxw takes tile k + 2 below)
+#pragma unroll
         for (int q = 0; q < XQ; ++q) {
-            if constexpr (XSP) convert_spikes(rx[q], px[q]);
+            if constexpr (XM) continue;
+            else if constexpr (XSP) convert_spikes(rx[q], px[q]);
             else convert_quad(rx[q], px[q]);
         }
         __builtin_amdgcn_sched_group_barrier(0x100, NREAD, 0);
@@ -858,7 +906,9 @@ struct WgradPlan {
 };
 static WgradPlan wgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
                             int64_t ldx, int64_t lddy, unsigned align, int precision, bool xsp, int num_cu, int splitk,
-                            bool halo = true) {
+                            bool halo = true, bool xm = false) {
+    // xm (with xsp, 1x1 / stride 1): x is a spike bit mask of ldx uint32 words per pixel; kAlignIn16 stands for its 4-byte
+    // alignment
     WgradPlan p = {};
     if (num_cu <= 0) num_cu = snn_num_cu();
     const int bwd_split = precision;
@@ -884,7 +934,7 @@ static WgradPlan wgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, in
             return p;
         }
     }
-    const bool vec = (Cin % 4 == 0) && (Cout % 4 == 0) && (ldx % 4 == 0) && (lddy % 4 == 0) &&
+    const bool vec = (Cin % 4 == 0) && (Cout % 4 == 0) && (xm || ldx % 4 == 0) && (lddy % 4 == 0) &&
                      (sbf ? (align & kAlignIn8) && (align & kAlignDy8) : (align & kAlignIn16) && (align & kAlignDy16));
     p.t = wgrad_tile(Cout, Ktot, bwd_split && Cin % 4 == 0 && Cout % 4 == 0, M);
     // small tiles (64 x 64, 32 x 128) run 64-pixel stages in the pipelined kernel (latency cover), the others 32
@@ -895,7 +945,8 @@ static WgradPlan wgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, in
     const int64_t span_pix = p.pix_per_split * (int64_t)stride * stride + 3 * (int64_t)H * W;
     static const bool no_pipe = snn_tuning_env("SNN_WGRAD_NO_PIPE") != nullptr;  // tuning / bisecting aid
     const bool pipe = vec && bwd_split && !no_pipe && M < 0x7fffffffLL && span_pix * ldx * 4 < 0x7fffffffLL &&
-                      p.pix_per_split * lddy * 4 < 0x7fffffffLL && (int64_t)H * W * ldx * 4 < 0x7fffffffLL;
+                      p.pix_per_split * lddy * 4 < 0x7fffffffLL && (int64_t)H * W * ldx * 4 < 0x7fffffffLL &&
+                      (!xm || (Cin % 32 == 0 && ldx * 32 >= Cin && M * ldx * 4 < 0x7fffffffLL));
     p.one = precision == SNN_PREC_BF16X1 || sbf;
     p.kernel = pipe ? kWgradPipe : (vec ? kWgradVec : kWgradScalar);
     if (sbf && !pipe) {
@@ -923,14 +974,15 @@ static WgradPlan wgrad_plan(int64_t N, int H, int W, int Cin, int Ho, int Wo, in
 // xsp: x holds saved LIF potentials, the operand is z = (x > x_th) (snn_conv1x1_spikes_wgrad; pipelined bf16 x 3 kernel only)
 static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t lddy, float* dw, int64_t N,
                         int H, int W, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad,
-                        int accumulate, float* workspace, int splitk, int precision, void* stream, bool xsp, float x_th) {
+                        int accumulate, float* workspace, int splitk, int precision, void* stream, bool xsp, float x_th,
+                        bool xm = false) {
     SNN_REQUIRE(x && dy && dw && workspace, "snn_conv2d_wgrad: null pointer");
     SNN_REQUIRE(precision == SNN_PREC_FP32 || precision == SNN_PREC_BF16X3 || precision == SNN_PREC_BF16X1 ||
                     precision == SNN_PREC_BF16S,
                 "snn_conv2d_wgrad: precision must be SNN_PREC_FP32, _BF16X3, _BF16X1 or _BF16S (got %d)", precision);
     const bool sbf = precision == SNN_PREC_BF16S;   // x (but for the fp32 event frames) and dy are bf16
     if (check_conv_shape("snn_conv2d_wgrad", N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad)) return 1;
-    SNN_REQUIRE(ldx >= Cin && lddy >= Cout, "snn_conv2d_wgrad: pixel stride smaller than channel count");
+    SNN_REQUIRE((xm || ldx >= Cin) && lddy >= Cout, "snn_conv2d_wgrad: pixel stride smaller than channel count");
     SNN_REQUIRE(splitk >= 1 && splitk <= 32768, "snn_conv2d_wgrad: bad splitk %d", splitk);
     SNN_REQUIRE(N * (int64_t)H * W < 0x7fffffffLL, "snn_conv2d_wgrad: more than 2^31 input pixels");
     WgradGeom g;
@@ -941,8 +993,9 @@ static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t ld
     g.Ktot = KH * KW * Cin;
     g.x_th = x_th;
     // (the reducer plan in p.r is the one wgrad_reduce_slabs derives again from the same two pointers)
-    const unsigned align = wgrad_align_bits(x, dy) | (aligned(16, {dw, workspace}) ? kAlignDw16 : 0u);
-    WgradPlan p = wgrad_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ldx, lddy, align, precision, xsp, 0, splitk);
+    unsigned align = wgrad_align_bits(x, dy) | (aligned(16, {dw, workspace}) ? kAlignDw16 : 0u);
+    if (xm) align = (align & ~(kAlignIn16 | kAlignIn8)) | (aligned(4, {x}) ? kAlignIn16 : 0u);
+    WgradPlan p = wgrad_plan(N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ldx, lddy, align, precision, xsp, 0, splitk, !xm, xm);
     if (p.kernel == kWgradFirst) {
         const FirstPlan& fp = p.fp;
         FirstGeom fg = {ldx, lddy, (int)(N * Ho), H, W, Ho, Wo, Cout, stride, pad, fp.group_rows, splitk, nullptr,
@@ -977,18 +1030,18 @@ static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t ld
     dim3 grid((unsigned)((int64_t)g.tiles_m * g.tiles_n * splitk));
     hipStream_t st = (hipStream_t)stream;
     dispatch(
-        [&](auto ID, auto KERNEL, auto WBK, auto ONE, auto SB, auto XSP) {
+        [&](auto ID, auto KERNEL, auto WBK, auto ONE, auto SB, auto XSP, auto XM) {
             constexpr WgradShape t = kWgradShapes[ID()];
             if constexpr (KERNEL() != kWgradPipe) {
                 hipLaunchKernelGGL((k_conv_wgrad<t.tm, t.tn, t.wm, t.wn, KERNEL() == kWgradVec>), grid, dim3(kThreads), 0, st, x, dy,
                                    workspace, g);
-            } else if constexpr ((!SB() || ONE()) && (!XSP() || (!ONE() && !SB()))) {   // bf16 storage: one product; spikes: three
-                hipLaunchKernelGGL((k_conv_wgrad_pipe<t.tm, t.tn, t.wm, t.wn, WBK(), ONE(), SB(), XSP()>), grid, dim3(kThreads), 0,
+            } else if constexpr ((!SB() || ONE()) && (!XSP() || (!ONE() && !SB())) && (!XM() || XSP())) {   // bf16 storage: one product; spikes: three
+                hipLaunchKernelGGL((k_conv_wgrad_pipe<t.tm, t.tn, t.wm, t.wn, WBK(), ONE(), SB(), XSP(), XM()>), grid, dim3(kThreads), 0,
                                    st, x, dy, workspace, g);
             }
             return true;
         },
-        OneOf<0, 1, 2, 3, 4, 5>{p.t.id}, OneOf<0, 1, 2>{p.kernel}, OneOf<32, 64>{p.wbk}, Flag{p.one}, Flag{sbf}, Flag{xsp});
+        OneOf<0, 1, 2, 3, 4, 5>{p.t.id}, OneOf<0, 1, 2>{p.kernel}, OneOf<32, 64>{p.wbk}, Flag{p.one}, Flag{sbf}, Flag{xsp}, Flag{xm});
     SNN_CHECK_LAUNCH("snn_conv2d_wgrad");
     return wgrad_reduce_slabs(workspace, dw, (int64_t)Cout * g.Ktot, splitk, accumulate, st);
 }
@@ -1084,4 +1137,30 @@ extern "C" int snn_conv1x1_spikes_wgrad(const float* vdec, int64_t ld, float v_t
                                         int splitk, void* stream) {
     return snn_conv2d_spikes_wgrad(vdec, ld, v_th, dy, lddy, dw, N, H, W, Cin, H, W, Cout, 1, 1, 1, 0, accumulate, workspace,
                                    splitk, stream);
+}
+
+// ---- the 1x1 weight gradient over the spike bit mask of a scan with SNN_SCAN_SPIKE_MASK (see k_conv_wgrad_pipe XM)
+bool snn_wgrad_mask_ok(int64_t N, int H, int W, int Cin, int Cout, const uint32_t* mask, int64_t ld_mask, const float* dy,
+                       int64_t lddy, const float* dw) {
+    if (!(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && mask && dy && dw && Cin % 32 == 0 && Cout % 4 == 0 &&
+          ld_mask >= Cin / 32 && lddy >= Cout && lddy % 4 == 0 && aligned(4, {mask, dw}) && aligned(16, {dy}) &&
+          (int64_t)Cin * Cout < (1LL << 26)))
+        return false;
+    // whatever slab count the caller brings, a pixel split is at most the 64-rounded pixel count
+    const int64_t M = N * H * (int64_t)W;
+    if (!(M < 0x7fffffffLL - 64 && (M + 64 + 3 * (int64_t)H * W) * ld_mask * 4 < 0x7fffffffLL && (M + 64) * lddy * 4 < 0x7fffffffLL))
+        return false;
+    const unsigned align = kAlignIn16 | kAlignDy16 | kAlignDy8 | (aligned(16, {dw}) ? kAlignDw16 : 0u);
+    const WgradPlan p = wgrad_plan(N, H, W, Cin, H, W, Cout, 1, 1, 1, 0, ld_mask, lddy, align, SNN_PREC_BF16X3, true, 0, 0, false, true);
+    return p.ok && p.kernel == kWgradPipe;
+}
+
+extern "C" int snn_conv1x1_mask_wgrad(const uint32_t* mask, int64_t ld_mask, const float* dy, int64_t lddy, float* dw, int64_t N,
+                                      int H, int W, int Cin, int Cout, int accumulate, float* workspace, int splitk,
+                                      void* stream) {
+    SNN_REQUIRE(mask && dy && dw && workspace, "snn_conv1x1_mask_wgrad: null pointer");
+    SNN_REQUIRE(snn_wgrad_mask_ok(N, H, W, Cin, Cout, mask, ld_mask, dy, lddy, dw),
+                "snn_conv1x1_mask_wgrad: call not covered (ask snn_conv1x1_mask_supported)");
+    return wgrad_common(reinterpret_cast<const float*>(mask), ld_mask, dy, lddy, dw, N, H, W, Cin, H, W, Cout, 1, 1, 1, 0,
+                        accumulate, workspace, splitk, SNN_PREC_BF16X3, stream, true, 0.0f, true);
 }

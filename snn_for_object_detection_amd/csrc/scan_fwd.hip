@@ -27,7 +27,8 @@ __global__ __launch_bounds__(kThreads) void k_affine_neuron_fwd(
     const float* __restrict__ v0, const float* __restrict__ i0, float* __restrict__ out, int64_t ldo,
     const float* __restrict__ addend, int64_t ld_add, float* __restrict__ vT, float* __restrict__ iT,
     float* __restrict__ vdec, int T, int64_t M, int C, snn_neuron_params p, int last_only,
-    const float* __restrict__ cmem_pc = nullptr, const float* __restrict__ csyn_pc = nullptr) {
+    const float* __restrict__ cmem_pc = nullptr, const float* __restrict__ csyn_pc = nullptr,
+    uint32_t* __restrict__ mask = nullptr, int64_t ld_mask = 0) {
     // last_only (SNN_SCAN_LAST_STEP_ONLY): `out` is [M][ldo], only the last timestep's output is kept (the detection
     // head: soda.py:141-144 returns the predictions of the last step) - T-1 of T output stores never happen
     typedef typename Vec<VEC>::type V;
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(kThreads) void k_affine_neuron_fwd(
         // memory operations (at a control-flow join the compiler's wait-count pass falls back to vmcnt(0)), so it exists
         // in the two forms the layer-major step uses - BatchNorm affine, all T outputs, with / without a shortcut - and
         // everything else (no affine, last step only) takes the plain loop with its run-time checks.
-        auto time_loop = [&](auto piped_c, auto add_c, auto noout_c, auto last_c) {
+        auto time_loop = [&](auto piped_c, auto add_c, auto noout_c, auto last_c, auto mask_c) {
         constexpr bool PIPED = decltype(piped_c)::value;       // affine present, ADD known, outputs: all steps or (LAST) one
         // LAST (PIPED only; SNN_SCAN_LAST_STEP_ONLY, the detection heads' LI + Tanh): nothing is stored inside the loop, the
         // last step's output once behind it - the plain loop below waited for every step's own loads, 32 dependent memory
@@ -74,6 +75,12 @@ __global__ __launch_bounds__(kThreads) void k_affine_neuron_fwd(
         // NOOUT (SNN_SCAN_SPIKES_FROM_VDEC; LIF without a shortcut, v_dec saved): no output tensor at all - the consumer
         // forms the spikes itself, z = (v_dec > v_th), while it reads the saved potentials (snn_conv1x1_spikes_*)
         constexpr bool NOOUT = decltype(noout_c)::value;
+        // MASK (NOOUT only; SNN_SCAN_SPIKE_MASK): the spikes z = (v_dec > v_th) additionally leave as one bit per neuron,
+        // mask[t][m][c >> 5] bit c & 31 - what snn_conv1x1_mask_* read instead of 32 bits of potential.  A lane holds 4
+        // channels, 8 neighbouring lanes (one pixel: C % 32 == 0, so a group of 8 never straddles a row or the tail of the
+        // grid-stride loop) make one word: three DPP OR steps inside the group, then all 8 lanes store the same word to the
+        // same address - no branch around the store (see above), and one wave instruction per 64 * 4 neurons.
+        constexpr bool MASK = decltype(mask_c)::value;
         constexpr int kPrefetch = PIPED ? SNN_SCAN_PREFETCH : 0;
         struct StepOps { V x, a, b, ad; };
         auto fetch_step = [&](int t) {
@@ -176,22 +183,36 @@ __global__ __launch_bounds__(kThreads) void k_affine_neuron_fwd(
                 if constexpr (VEC == 4 && !SB && SNN_SCAN_NT_AUX != 0) __builtin_nontemporal_store(vd, reinterpret_cast<f32x4*>(vdec + row * C + c));
                 else VecS<VEC, SB>::store(vdec, row * C + c, vd);
             }
+            if constexpr (MASK && VEC == 4) {
+                unsigned wd = 0;   // taken from the very values stored to vdec; strict comparison, like the consumers'
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) wd |= (lane<VEC>(vd, j) > p.v_th ? 1u : 0u) << j;
+                wd <<= (c & 31);
+                wd |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)wd, 0xB1, 0xf, 0xf, true);    // quad_perm [1,0,3,2]: lane ^ 1
+                wd |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)wd, 0x4E, 0xf, 0xf, true);    // quad_perm [2,3,0,1]: lane ^ 2
+                wd |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)wd, 0x141, 0xf, 0xf, true);   // row_half_mirror: the other quad
+                // (one lane of the 8 storing it, under a lane test, compiles to a branch and s_waitcnt vmcnt(0) at the loop top)
+                mask[row * ld_mask + (c >> 5)] = wd;
+            }
         }
         if constexpr (LAST) VecS<VEC, SB>::store(out, m * ldo + c, o_keep);
         };
         if constexpr (VEC > 1 && SAVE != 2) {
             if (alpha && !last_only) {
-                if (addend) time_loop(std::true_type{}, std::true_type{}, std::false_type{}, std::false_type{});
-                else if (SAVE == 1 && NEURON == SNN_NEURON_LIF && !SB && out == nullptr)
-                    time_loop(std::true_type{}, std::false_type{}, std::true_type{}, std::false_type{});
-                else time_loop(std::true_type{}, std::false_type{}, std::false_type{}, std::false_type{});
+                constexpr std::true_type yes{};
+                constexpr std::false_type no{};
+                if (addend) time_loop(yes, yes, no, no, no);
+                else if (SAVE == 1 && NEURON == SNN_NEURON_LIF && !SB && !PC && VEC == 4 && out == nullptr && mask != nullptr)
+                    time_loop(yes, no, yes, no, yes);
+                else if (SAVE == 1 && NEURON == SNN_NEURON_LIF && !SB && out == nullptr) time_loop(yes, no, yes, no, no);
+                else time_loop(yes, no, no, no, no);
             } else if (alpha && last_only && !addend) {
-                time_loop(std::true_type{}, std::false_type{}, std::false_type{}, std::true_type{});
+                time_loop(std::true_type{}, std::false_type{}, std::false_type{}, std::true_type{}, std::false_type{});
             } else {
-                time_loop(std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
+                time_loop(std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
             }
         } else {
-            time_loop(std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
+            time_loop(std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{}, std::false_type{});
         }
         if (NEURON != SNN_NEURON_NONE) {
             if (vT) Vec<VEC>::store(vT + m * C + c, v);
@@ -234,12 +255,16 @@ constexpr bool fwd_instance(int neuron, int vec, int save, bool sb, bool pc = fa
 static int neuron_fwd(int neuron, const float* y, int64_t ldy, const float* alpha, const float* beta, const float* v0,
                       const float* i0, float* out, int64_t ldo, const float* addend, int64_t ld_addend, float* vT,
                       float* iT, float* vdec, bool ckpt, int T, int64_t M, int C, const snn_neuron_params* p,
-                      int flags, void* stream, const float* cmem_pc = nullptr, const float* csyn_pc = nullptr) {
+                      int flags, void* stream, const float* cmem_pc = nullptr, const float* csyn_pc = nullptr,
+                      uint32_t* mask = nullptr, int64_t ld_mask = 0) {
     // cmem_pc / csyn_pc (snn_lif_tau_fwd, which has checked neuron and flags): per-channel time constants
     const bool pc = cmem_pc != nullptr;
-    const char* const fn = pc ? "snn_lif_tau_fwd" : "snn_affine_neuron_fwd";   // the entry point the messages name
-    SNN_REQUIRE((flags & ~(SNN_SCAN_LAST_STEP_ONLY | SNN_SCAN_BF16_STORAGE | SNN_SCAN_SPIKES_FROM_VDEC)) == 0,
+    const char* const fn = pc ? "snn_lif_tau_fwd" : (mask ? "snn_affine_neuron_fwd_mask" : "snn_affine_neuron_fwd");   // the entry point the messages name
+    SNN_REQUIRE((flags & ~(SNN_SCAN_LAST_STEP_ONLY | SNN_SCAN_BF16_STORAGE | SNN_SCAN_SPIKES_FROM_VDEC | SNN_SCAN_SPIKE_MASK)) == 0,
                 "%s: unknown flags 0x%x", fn, flags);
+    const bool with_mask = (flags & SNN_SCAN_SPIKE_MASK) != 0;   // the spikes also leave as one bit per neuron
+    SNN_REQUIRE(with_mask == (mask != nullptr) && (!with_mask || !pc),
+                "%s: SNN_SCAN_SPIKE_MASK comes with a mask buffer, through snn_affine_neuron_fwd_mask only", fn);
     const int last_only = (flags & SNN_SCAN_LAST_STEP_ONLY) != 0;
     const bool sb = (flags & SNN_SCAN_BF16_STORAGE) != 0;   // y, out, addend, vdec are bf16 tensors
     const bool no_out = (flags & SNN_SCAN_SPIKES_FROM_VDEC) != 0;   // no output tensor: the consumer thresholds vdec
@@ -266,13 +291,16 @@ static int neuron_fwd(int neuron, const float* y, int64_t ldy, const float* alph
     };
     SNN_REQUIRE(!sb || (lanes_ok(4, 8) && !ckpt && bf16_neuron(neuron)), "%s: %s, without checkpointing", fn, kBf16Covers);
     const int lanes = sb ? (lanes_ok(8, 16) ? 8 : 4) : (lanes_ok(4, 16) ? 4 : 1);
+    SNN_REQUIRE(!with_mask || (no_out && C % 32 == 0 && ld_mask >= C / 32 && aligned(4, {mask}) && lanes == 4),
+                "%s: SNN_SCAN_SPIKE_MASK needs SNN_SCAN_SPIKES_FROM_VDEC, C a multiple of 32, ld_mask >= C / 32 and 16-byte "
+                "aligned operands", fn);
     const FwdPlan fp = fwd_plan(neuron, M, C, lanes, vdec != nullptr, ckpt);
     const bool launched = dispatch(
         [&](auto NEURON, auto VEC, auto SAVE, auto SB, auto PC) {
             if constexpr (fwd_instance(NEURON(), VEC(), SAVE(), SB(), PC())) {
                 hipLaunchKernelGGL((k_affine_neuron_fwd<NEURON(), VEC(), SAVE(), SB(), PC()>), dim3(fp.blocks), dim3(kThreads), 0,
                                    (hipStream_t)stream, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT,
-                                   vdec, T, M, C, *p, last_only, cmem_pc, csyn_pc);
+                                   vdec, T, M, C, *p, last_only, cmem_pc, csyn_pc, mask, ld_mask);
                 return true;
             } else {
                 return false;
@@ -290,6 +318,18 @@ extern "C" int snn_affine_neuron_fwd(int neuron, const float* y, int64_t ldy, co
                                      const snn_neuron_params* p, int flags, void* stream) {
     return neuron_fwd(neuron, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, false, T, M, C, p,
                       flags, stream);
+}
+
+// the same scan; with SNN_SCAN_SPIKE_MASK (and SNN_SCAN_SPIKES_FROM_VDEC) it also writes the spike bit mask (include/snn_hip.h)
+extern "C" int snn_affine_neuron_fwd_mask(int neuron, const float* y, int64_t ldy, const float* alpha, const float* beta,
+                                          const float* v0, const float* i0, float* out, int64_t ldo, const float* addend,
+                                          int64_t ld_addend, float* vT, float* iT, float* vdec, int T, int64_t M, int C,
+                                          const snn_neuron_params* p, int flags, void* stream, uint32_t* mask,
+                                          int64_t ld_mask) {
+    SNN_REQUIRE(((flags & SNN_SCAN_SPIKE_MASK) != 0) == (mask != nullptr),
+                "snn_affine_neuron_fwd_mask: SNN_SCAN_SPIKE_MASK and the mask buffer come together");
+    return neuron_fwd(neuron, y, ldy, alpha, beta, v0, i0, out, ldo, addend, ld_addend, vT, iT, vdec, false, T, M, C, p,
+                      flags, stream, nullptr, nullptr, mask, ld_mask);
 }
 
 extern "C" int snn_lif_ckpt_interval(void) { return kCkpt; }

@@ -640,6 +640,13 @@ USE_SIBLING_FUSION = not os.environ.get("SNN_NO_SIBLING_FUSION")
 # a Norm -> LIF layer whose only consumer is such a convolution writes NO spike tensor: the consumer thresholds the saved
 # potentials itself (snn_conv1x1_spikes_*; SNN_NO_SPIKES_FROM_VDEC: tuning / bisecting aid)
 USE_SPIKES_FROM_VDEC = not os.environ.get("SNN_NO_SPIKES_FROM_VDEC")
+# ... and such a layer also writes its spikes as one bit per neuron, which the consumer reads instead of the 32-bit
+# potentials where snn_conv1x1_mask_supported covers the call (SNN_NO_SPIKE_MASK: tuning / bisecting aid - no mask is
+# written, the consumer thresholds the potentials)
+USE_SPIKE_MASK = not os.environ.get("SNN_NO_SPIKE_MASK")
+# The mask pays where the potentials are HBM traffic.  A layer whose saved potentials are smaller than one XCD's L2 (4 MiB)
+# is served from cache and its convolutions are bound by launch latency: it keeps the potentials path and allocates nothing.
+SPIKE_MASK_MIN_BYTES = 4 << 20
 
 
 class GradAccumulator:
@@ -1112,9 +1119,10 @@ class _SiblingConv1x1(Function):
     ``composed_conv1x1``."""
 
     @staticmethod
-    def forward(ctx, x, w1, dest, acc, prec, slot1, slots2, x_th, *w2s):
+    def forward(ctx, x, w1, dest, acc, prec, slot1, slots2, x_th, x_mask, *w2s):
         """``x_th`` (not None): ``x`` holds the saved potentials of the LIF layer in front (``affine_neuron(spikes_ok=True)``),
-        the operand is ``z = (x > x_th)``."""
+        the operand is ``z = (x > x_th)``; ``x_mask`` (not None): the same spikes as the bit mask that layer's scan wrote
+        (``[T,B,H,W,ceil(C/32)]`` int32), read instead of the potentials where ``snn_conv1x1_mask_supported`` says so."""
         _require_device(x, "conv2d input", bf16_ok=True)
         fwd_prec, bwd_prec = _conv_precs(prec, x.dtype == _BF16)
         T, B, Cin, H, W = _dims5(x)
@@ -1155,7 +1163,14 @@ class _SiblingConv1x1(Function):
         x, x_th = _spikes_fwd_operand(x, x_th, lambda: _spikes_fwd_ok(
             _hip.query("snn_conv1x1_spikes_supported", T * B, H, W, Cin, Ct, cl_stride(x), fwd_prec, bwd_prec), False,
             x.data_ptr(), wc.data_ptr()))
-        if x_th is not None:
+        if x_th is None:
+            x_mask = None
+        if x_mask is not None and _hip.query("snn_conv1x1_mask_supported", T * B, H, W, Cin, Ct, x_mask.data_ptr(),
+                                             x_mask.shape[-1], wc.data_ptr(), y.data_ptr(), cl_stride(y), None, 0, None,
+                                             fwd_prec, bwd_prec):
+            _hip.call("snn_conv1x1_mask_fwd", x_mask.data_ptr(), x_mask.shape[-1], wc.data_ptr(), y.data_ptr(), cl_stride(y),
+                      T * B, H, W, Cin, Ct, _stream())
+        elif x_th is not None:
             _hip.call("snn_conv1x1_spikes_fwd", x.data_ptr(), cl_stride(x), x_th, wc.data_ptr(), y.data_ptr(), cl_stride(y),
                       T * B, H, W, Cin, Ct, _stream())
         else:
@@ -1163,6 +1178,8 @@ class _SiblingConv1x1(Function):
                       H, W, Cin, H, W, Ct, 1, 1, 1, 0, None, 0, None, 0, None, fwd_prec, _stream())
         ctx.prec = bwd_prec
         ctx.x_th = x_th
+        ctx.x_mask = x_mask
+        ctx.fwd_prec = fwd_prec
         ctx.save_for_backward(x, w1m, *w2ms)
         ctx.wct = wct
         ctx.geom = (T, B, Cin, H, W, Ct, 1, 1, H, W, 1, 0)
@@ -1183,13 +1200,20 @@ class _SiblingConv1x1(Function):
         dw2s = [None] * len(widths)
         if ctx.needs_input_grad[0]:
             dx = _dgrad_accumulate(ctx.acc, gy, ldg, ctx.wct, x, ctx.geom, _stream(), ctx.prec)
-        if any(ctx.needs_input_grad[8:]) or (composed and ctx.needs_input_grad[1]):
+        if any(ctx.needs_input_grad[9:]) or (composed and ctx.needs_input_grad[1]):
             slot1, slots2 = ctx.slot1, ctx.slots2
             slotted = all(s_ is not None for s_ in slots2) and (slot1 is not None or not composed)
             splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, H, W, Ct, 1, 1, 1, 0, ctx.prec)
             xw, ldxw, x_th = _spikes_wgrad_operand(x, ldx, ctx.x_th, gy, ldg)
-            with _WgradLaunch(x.device, slotted, splitk, Ct, Cin, hold=(x, xw, gy), with_g=True) as (stream, ws, G):
-                if x_th is not None:   # x holds the potentials of the LIF layer in front: thresholded on load
+            x_mask = ctx.x_mask
+            with _WgradLaunch(x.device, slotted, splitk, Ct, Cin, hold=(x, xw, gy, x_mask), with_g=True) as (stream, ws, G):
+                if x_mask is not None and _hip.query("snn_conv1x1_mask_supported", T * B, H, W, Cin, Ct, x_mask.data_ptr(),
+                                                     x_mask.shape[-1], None, None, 0, gy.data_ptr(), ldg, G.data_ptr(),
+                                                     ctx.fwd_prec, ctx.prec):
+                    # the spikes of the LIF layer in front as its bit mask; otherwise its potentials, which are always there
+                    _hip.call("snn_conv1x1_mask_wgrad", x_mask.data_ptr(), x_mask.shape[-1], gy.data_ptr(), ldg, G.data_ptr(),
+                              T * B, H, W, Cin, Ct, 0, ws.data_ptr(), splitk, stream)
+                elif x_th is not None:   # x holds the potentials of the LIF layer in front: thresholded on load
                     _hip.call("snn_conv1x1_spikes_wgrad", xw.data_ptr(), ldxw, x_th, gy.data_ptr(), ldg, G.data_ptr(),
                               T * B, H, W, Cin, Ct, 0, ws.data_ptr(), splitk, stream)
                 else:
@@ -1220,7 +1244,7 @@ class _SiblingConv1x1(Function):
                         dw2s[b] = g2.view(c, C1, 1, 1)
                 if composed and not slotted:
                     dw1 = g1.view(C1, Cin, 1, 1)
-        return (dx, dw1, None, None, None, None, None, None, *dw2s)
+        return (dx, dw1, None, None, None, None, None, None, None, *dw2s)
 
 
 def sibling_conv1x1(x: torch.Tensor, w1: Optional[torch.Tensor], w2s: Sequence[torch.Tensor], dest: Optional[Dest] = None,
@@ -1229,7 +1253,7 @@ def sibling_conv1x1(x: torch.Tensor, w1: Optional[torch.Tensor], w2s: Sequence[t
     convolution; ``x`` is a sequence ``[T,B,C,H,W]``."""
     return _SiblingConv1x1.apply(x, w1, dest, _acc_of(x), _prec_codes(forward_precision, backward_precision),
                                  _slot_of(w1), tuple(_slot_of(w) for w in w2s), getattr(x, "_snn_spike_threshold", None),
-                                 *w2s)
+                                 getattr(x, "_snn_spike_mask", None), *w2s)
 
 
 def composed_conv1x1(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, dest: Optional[Dest] = None,
@@ -1242,7 +1266,7 @@ def composed_conv1x1(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, dest: 
         return place(y, dest) if dest is not None else y
     seq, single = as_sequence(x)
     y = _SiblingConv1x1.apply(seq, w1, dest, _acc_of(seq), _prec_codes(forward_precision, backward_precision),
-                              _slot_of(w1), (_slot_of(w2),), None, w2)
+                              _slot_of(w1), (_slot_of(w2),), None, None, w2)
     return y[0] if single else y
 
 
@@ -1408,6 +1432,7 @@ class _NeuronCfg(NamedTuple):
     defer_apply: bool
     spikes_out: Optional[list]
     tau_slots: Tuple[Optional[GradSlot], Optional[GradSlot]]
+    spike_mask: bool = False   # the consumer is sibling_conv1x1, which can read the spikes as a bit mask
 
 
 def _bf16_scan_covers(neuron: int, channels: int) -> bool:
@@ -1561,8 +1586,15 @@ class _AffineNeuron(Function):
                     _ptr(iT) if has_state else None, _ptr(vdec), T, M, C, params)
             fwd_flags = ((_hip.SCAN_LAST_STEP_ONLY if last_only else 0) | sb_flag
                          | (_hip.SCAN_SPIKES_FROM_VDEC if no_out else 0))
+            # ... and the spikes as one bit per neuron next to the potentials (snn_conv1x1_mask_*: 32 channels per word)
+            mask = None
+            if no_out and cfg.spike_mask and USE_SPIKE_MASK and not tau and C % 32 == 0 and T * M * C * 4 >= SPIKE_MASK_MIN_BYTES and all(
+                    t is None or t.data_ptr() % 16 == 0 for t in (y, alpha, beta, v0, i0, vT, iT, vdec)):
+                mask = torch.empty((T, B, H, W, C // 32), device=dev, dtype=torch.int32)
             if tau:
                 _hip.call("snn_lif_tau_fwd", *head, c_mem.data_ptr(), c_syn.data_ptr(), fwd_flags, st)
+            elif mask is not None:
+                _hip.call("snn_affine_neuron_fwd_mask", *head, fwd_flags | _hip.SCAN_SPIKE_MASK, st, mask.data_ptr(), C // 32)
             else:
                 _hip.call("snn_affine_neuron_fwd", *head, fwd_flags, st)
             if no_out:
@@ -1570,6 +1602,8 @@ class _AffineNeuron(Function):
                 # them into this layer's output
                 out = _alias(vdec, vdec.storage_offset(), T, B, C, H, W, C)
                 spikes_out.append(float(params.v_th))
+                if mask is not None:
+                    spikes_out.append(mask)
         ctx.ckpt = ckpt
         ctx.sb = sb
         ctx.defer_apply = cfg.defer_apply
@@ -1786,7 +1820,7 @@ def _expand_state(s: torch.Tensor, shape, dev) -> torch.Tensor:
 def affine_neuron(y: torch.Tensor, neuron: int, state: Optional[NeuronState] = None, bn=None,
                   params: Optional[NeuronParams] = None, dest: Optional[Dest] = None,
                   addend: Optional[torch.Tensor] = None, last_only: bool = False, spikes_ok: bool = False,
-                  tau: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+                  tau: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, spike_mask_ok: bool = False):
     """Fused ``[Norm] -> [neuron] [+ addend]`` over a sequence or a single step.
 
     ``tau=(w_mem, w_syn)`` (LIF, fp32 tensors): per-channel time constants ``c_mem = sigmoid(w_mem)``, ``1 + c_syn =
@@ -1795,6 +1829,8 @@ def affine_neuron(y: torch.Tensor, neuron: int, state: Optional[NeuronState] = N
 
     ``spikes_ok`` (LIF on a sequence; the caller guarantees that the ONLY consumer is ``sibling_conv1x1``): the result may be
     the layer's saved potentials instead of its spikes, marked ``_snn_spike_threshold`` - no spike tensor is written.
+    ``spike_mask_ok`` (with ``spikes_ok``; the consumer IS ``sibling_conv1x1``): the scan may also write the spikes as one bit
+    per neuron (``_snn_spike_mask``, ``[T,B,H,W,C/32]`` int32), which that convolution reads instead of the potentials.
 
     ``bn`` is an ``nn.BatchNorm2d``-like module (weight, bias, running stats, eps, momentum, training)
     or None; ``addend`` (same shape as the output) is a residual shortcut added in the output store.
@@ -1852,10 +1888,13 @@ def affine_neuron(y: torch.Tensor, neuron: int, state: Optional[NeuronState] = N
     cfg = _NeuronCfg(neuron=neuron, has_bn=has_bn, training=training, eps=float(eps), momentum=float(momentum),
                      running_mean=rm, running_var=rv, params=params, g_slot=_slot_of(gamma), b_slot=_slot_of(bias), dest=dest,
                      sync_group=sync_group, bn_hint=bn_hint, last_only=bool(last_only) and not single,
-                     defer_apply=defer_apply, spikes_out=spikes_out, tau_slots=(_slot_of(w_mem), _slot_of(w_syn)))
+                     defer_apply=defer_apply, spikes_out=spikes_out, tau_slots=(_slot_of(w_mem), _slot_of(w_syn)),
+                     spike_mask=bool(spike_mask_ok))
     out, vT, iT = _AffineNeuron.apply(seq, gamma, bias, v0, i0, addend, cfg, w_mem, w_syn)
     if spikes_out:
         out._snn_spike_threshold = spikes_out[0]   # `out` holds v_dec: its consumer thresholds on load
+        if len(spikes_out) > 1:
+            out._snn_spike_mask = spikes_out[1]    # ... or reads the same spikes as one bit per neuron
     if neuron == _hip.NEURON_NONE:
         new_state = None
     elif neuron == _hip.NEURON_SYNAPSE:

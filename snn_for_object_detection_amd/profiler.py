@@ -80,6 +80,16 @@ def work_of(name: str, a):
             return WGRAD_LABELS[0], flops, byts
         tile = "32, 4, 1" if cout <= 32 else ("64, 2, 2" if cout <= 64 else "128, 2, 2")
         return f"k_conv_gather<{tile}, false, true>", flops, byts
+    if name in ("snn_conv1x1_mask_fwd", "snn_conv1x1_mask_wgrad"):   # 1x1 over the spike bit mask of the scan in front
+        # (mask, ld_mask, w | dy, y | lddy, ldy | dw, N, H, W, Cin, Cout, ...); the mask costs 1/8 byte per element
+        fwd = name.endswith("_fwd")
+        n, h, w, cin, cout = (a[5], a[6], a[7], a[8], a[9])
+        flops = 2.0 * n * h * w * cout * cin
+        byts = n * h * w * cin / 8.0 + 4.0 * (n * h * w * cout + cout * cin)
+        if not fwd:
+            return WGRAD_LABELS[0] + ", mask, spikes", flops, byts
+        tile = "32, 4, 1" if cout <= 32 else ("64, 2, 2" if cout <= 64 else "128, 2, 2")
+        return f"k_conv_gather<{tile}, false, true>, mask, spikes", flops, byts
     if name in ("snn_conv2d_spikes_fwd", "snn_conv2d_spikes_wgrad"):   # any kernel size over spikes formed from saved potentials
         # (vdec, ld, v_th, w | dy, y | lddy, ldy | dw, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ...)
         fwd = name.endswith("_fwd")
@@ -113,7 +123,7 @@ def work_of(name: str, a):
         flops = 2.0 * n * ho * wo * cout * kh * kw * cin
         byts = 4.0 * (n * h * w * cin + 2 * n * ho * wo * cout + cout * kh * kw * cin)   # x, gx and y are read
         return WGRAD_LABELS[2], flops, byts
-    if name == "snn_affine_neuron_fwd":
+    if name in ("snn_affine_neuron_fwd", "snn_affine_neuron_fwd_mask"):   # (_mask: the same kernel family and argument order)
         neuron, T, M, C = a[0], a[14], a[15], a[16]
         last_only = bool(a[18] & 2)   # SNN_SCAN_LAST_STEP_ONLY: the output of ONE step is written
         elems = float(T) * M * C
@@ -121,7 +131,9 @@ def work_of(name: str, a):
         wrote_out = 0 if a[7] is None else (1.0 / T if last_only else 1)   # (SNN_SCAN_SPIKES_FROM_VDEC: no output tensor)
         tensors = 1 + wrote_out + (1 if a[13] is not None else 0) + (1 if a[9] is not None else 0)
         sb = bool(a[18] & SCAN_BF16_STORAGE)
-        return f"k_affine_neuron_fwd<{neuron}>" + (", bf16s" if sb else ""), 12.0 * elems, (2.0 if sb else 4.0) * elems * tensors
+        mask_bytes = elems / 8.0 if (name.endswith("_mask") and a[20] is not None) else 0.0   # + one bit per neuron-timestep
+        return (f"k_affine_neuron_fwd<{neuron}>" + (", bf16s" if sb else ""), 12.0 * elems,
+                (2.0 if sb else 4.0) * elems * tensors + mask_bytes)
     if name == "snn_affine_neuron_bwd":
         neuron, T, M, C = a[0], a[15], a[16], a[17]
         last_only = bool(a[19] & 2)   # output gradient (and a saved OUTPUT, LI+Tanh) exist for the last step only
@@ -187,7 +199,7 @@ class KernelProfiler:
 
     def before(self, name, args):
         label, flops, byts = work_of(name, args)
-        if name in ("snn_affine_neuron_fwd", "snn_lif_fwd_ckpt"):
+        if name in ("snn_affine_neuron_fwd", "snn_affine_neuron_fwd_mask", "snn_lif_fwd_ckpt"):
             self.neuron_steps += flops / 12.0   # work_of counts 12 FLOP per neuron-timestep
         start = torch.cuda.Event(enable_timing=True)
         end = torch.cuda.Event(enable_timing=True)

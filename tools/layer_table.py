@@ -31,7 +31,13 @@ def shape_of(name, a):
         return f"N{a[5]} {a[6]}x{a[7]} {a[8]}->{a[9]} {'fwd' if a[17] == 4 else 'dgrad'}{' +add' if a[10] is not None else ''}{' +add2' if a[12] is not None else ''}"
     if name == "snn_conv3x3_s2_dgrad":
         return f"N{a[5]} {a[6]}x{a[7]} {a[8]}->{a[11]}"
-    if name == "snn_affine_neuron_fwd":
+    if name in ("snn_conv1x1_spikes_fwd", "snn_conv1x1_spikes_wgrad"):   # (vdec, ld, v_th, w | dy, y | lddy, ldy | dw, N, H, W, Cin, Cout)
+        return f"N{a[6]} {a[7]}x{a[8]} {a[9]}->{a[10]}"
+    if name in ("snn_conv1x1_mask_fwd", "snn_conv1x1_mask_wgrad"):       # (mask, ld_mask, w | dy, y | lddy, ldy | dw, N, H, W, Cin, Cout)
+        return f"N{a[5]} {a[6]}x{a[7]} {a[8]}->{a[9]}"
+    if name in ("snn_affine_neuron_fwd", "snn_affine_neuron_fwd_mask"):
+        if a[7] is None:   # no output tensor (SNN_SCAN_SPIKES_FROM_VDEC); + the spike bit mask
+            return f"n{a[0]} T{a[14]} M{a[15]} C{a[16]} no-out{' +mask' if name.endswith('_mask') else ''}"
         return f"n{a[0]} T{a[14]} M{a[15]} C{a[16]}{' +shortcut' if a[9] is not None else ''}"
     if name == "snn_affine_neuron_bwd":
         return f"n{a[0]} T{a[15]} M{a[16]} C{a[17]}"
