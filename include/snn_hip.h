@@ -705,6 +705,35 @@ int snn_adamax_step_ctl(float* param, const float* grad, float* exp_avg, float* 
 int snn_events_to_frames(const int32_t* t_bin, const int32_t* x, const int32_t* y, const int32_t* p,
                          int64_t n_events, float* frames, int T, int H, int W, void* stream);
 
+/* Augmented event feed: the scatter with the binning of the raw timestamps and a per-sample horizontal flip, zoom,
+ * shift and random event drop inside it.  aug is int32 [B][8] in device memory, one row per sample:
+ *   {flip (0 | 1), a_q16 (zoom s = a_q16 / 65536; 65536 = identity; callers keep it in [2^14, 2^18]), ox, oy (pixel
+ *    shift after the zoom), drop_bits (a uint32 threshold floor(p_drop 2^32); 0 = keep all), seed_bits (uint32), 0, 0}.
+ * The events of sample b are offsets[b] .. offsets[b+1] (offsets int64 [B+1], offsets[0] = 0), t0 int64 [B] its window
+ * start, frames [T][B][H][W][2] (zero-filled here).  Event e of sample b, j = e - offsets[b]:
+ *   1. t_bin = floor((t_us - t0[b]) / step_us) (a true floor); skipped unless 0 <= t_bin < T;
+ *   2. skipped unless 0 <= y < H and p in {0, 1}; x clipped into [0, W-1] (the contract of snn_events_to_frames);
+ *   3. skipped if fmix32((uint32)j ^ fmix32(seed + 0x9E3779B9 * (uint32)(j >> 32))) < drop (fmix32: the murmur3
+ *      finaliser) - a function of the event's index inside its sample, not of what else the batch holds;
+ *   4. flip: x = W - 1 - x;   5. x' = (((2x + 1) a_q16) >> 17) + ox = floor((x + 0.5) s) + ox, y' likewise with oy;
+ *   6. skipped unless (x', y') is inside the frame (dropped, not clipped: for ANY table contents nothing is written
+ *      outside the buffer);   7. frames[t_bin][b][y'][x'][p] = 1.
+ * Zooming in does not interpolate: a factor above 1 leaves the gaps sparse events leave.  n_events = 0 and empty
+ * samples are fine.  Refused: null pointers, step_us <= 0, a frame buffer of 2^31 elements or more. */
+int snn_events_to_frames_aug(const int64_t* t_us, const int32_t* x, const int32_t* y, const int32_t* p,
+                             const int64_t* offsets, const int64_t* t0, const int32_t* aug, int64_t n_events,
+                             float* frames, int T, int B, int H, int W, int64_t step_us, void* stream);
+
+/* The boxes of the same transform.  labels_in / labels_out: fp32 [B][N][width], width 5 (class, x1, y1, x2, y2) or 6
+ * (ts in front, copied untouched), boxes normalised to [0, 1]; a row whose class is below 0 is padding and stays
+ * padding.  A valid row, s = a_q16 2^-16:  flip (x1, x2) = (1 - x2, 1 - x1);  x' = x s + ox / W, y' = y s + oy / H;
+ * A0 = area of that box, A1 = area of it clipped to [0, 1]; the row is kept, with the CLIPPED box, when
+ * A1 >= min_visible A0 and the clipped extents are at least min_size_px pixels wide and high; otherwise it becomes all
+ * -1.  Kept rows are written to the front of their sample in their order, the -1 rows behind them (the layout a collate
+ * that pads at the end produces); N never changes.  One block per sample.  labels_out must not be labels_in. */
+int snn_labels_augment(const float* labels_in, float* labels_out, const int32_t* aug, int B, int N, int width, int W,
+                       int H, float min_visible, float min_size_px, void* stream);
+
 /* ---------------------------------------------------------------- detection decode
  * Tail of SODa.predict (models/soda.py:202-233): per anchor conf = max_k prob[k], class = argmax - 1 (background -1),
  * box = offset_inverse(anchor, offsets) (utils/box.py:72-79, 102-119).  prob [A][K], offsets / anchors / boxes [A][4]. */
