@@ -861,6 +861,27 @@ int snn_map_accumulate(const int* order, const unsigned* match_mask, const int* 
                        int slots, const int* max_dets, int num_max_dets, const double* rec_thresholds, int num_rec,
                        int num_iou, int t50, int t75, void* workspace, float* out, void* stream);
 
+/* ---------------------------------------------------------------- activity counts (ABI v20, symbols added)
+ * Per-channel counts of the elements of a channels-last tensor src[T][M][ld] that satisfy a predicate: the spikes of a
+ * LIF layer from whatever its forward scan left (spike tensor, saved potentials, bit mask) and the non-zero operands of
+ * a convolution.  Counts are exact integers: per-lane 32-bit counters, one 64-bit integer atomic add per (block,
+ * timestep, channel); nothing is accumulated in floating point. */
+enum { SNN_ACT_NONZERO_F32 = 0, SNN_ACT_NONZERO_BF16 = 1,   /* x != 0 (-0.0 is zero; NaN and denormals are non-zero) */
+       SNN_ACT_ABOVE_F32 = 2,   SNN_ACT_ABOVE_BF16 = 3,     /* x > threshold, strict - the comparison of the scans and of
+                                                               the snn_conv*_spikes_* consumers; NaN is not above */
+       SNN_ACT_MASK = 4 };                                  /* uint32 words, layout of SNN_SCAN_SPIKE_MASK; C % 32 == 0 */
+/* ld: pixel stride of src in elements (SNN_ACT_MASK: in words), ld >= C (mask: >= C / 32); any C >= 1, any ld and any
+ * pointer alignment are taken: 4 channels per access where C % 4 == 0, ld % 4 == 0 and src is 16-byte (bf16: 8-byte)
+ * aligned, one channel per access otherwise; the mask is read one word per lane.  Channels >= C of a row - the bits of
+ * mask words past C / 32 included - never reach a count.  counts: int64 [T][C] with per_step != 0, else [C] (summed over
+ * the timesteps); accumulate == 0 overwrites the buffer, != 0 adds to it.  Refused by name (nothing launched): an
+ * unknown kind, a non-positive shape, ld too small, a mask with C % 32 != 0, a null pointer. */
+int snn_activity_count(const void* src, int kind, int64_t ld, float threshold, int T, int64_t M, int C,
+                       int per_step, int64_t* counts, int accumulate, void* stream);
+/* Host only: out[4] = {channels per access (4 / 1; mask: 32), pixel rows per block, grid x, grid y} of exactly the
+ * instance snn_activity_count launches for these arguments; `aligned` != 0: src is 16-byte (bf16: 8-byte) aligned. */
+int snn_activity_count_plan(int kind, int T, int64_t M, int C, int64_t ld, int aligned, int64_t* out /*[4]*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ All arithmetic of the hot path runs in ``libsnn_hip.so`` (hand-written gfx950 ke
 raises if the library is missing - there is no CPU / eager fallback.
 """
 
-from . import box, functional  # noqa: F401
+from . import activity, box, functional  # noqa: F401
 from .anchors import AnchorGenerator  # noqa: F401
 from .data import EventAugment, EventBatcher  # noqa: F401
 from .generator import BackboneGen, BlockGen, Head, HeadGen, ListGen, ListState, ModelGen, NeckGen  # noqa: F401

@@ -21,6 +21,8 @@ SCAN_WIDE_ADDRESSING, SCAN_LAST_STEP_ONLY, SCAN_BF16_STORAGE, SCAN_SPIKES_FROM_V
 SCAN_STATE_LOOKBACK = 32
 SCAN_SPIKE_MASK = 32   # forward only (shares its value with the backward-only flag above)
 SURR_SUPER, SURR_TRIANGLE, SURR_SIGMOID, SURR_ATAN = 0, 1, 2, 3   # SNN_SURR_* of include/snn_hip.h
+# SNN_ACT_* of include/snn_hip.h (snn_activity_count; not the ACT_* activations above)
+ACTIVITY_NONZERO_F32, ACTIVITY_NONZERO_BF16, ACTIVITY_ABOVE_F32, ACTIVITY_ABOVE_BF16, ACTIVITY_MASK = 0, 1, 2, 3, 4
 
 
 class NeuronParams(Structure):
@@ -159,6 +161,8 @@ SIGNATURES = {
     "snn_map_match":(c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "snn_map_workspace_size": (c_size_t, [_I, _I, _I]),
     "snn_map_accumulate": (c_int, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "snn_activity_count": (c_int, [_P, _I, _L, _F, _I, _L, _I, _I, _P, _I, _P]),
+    "snn_activity_count_plan": (c_int, [_I, _I, _L, _I, _L, _I, _P]),
 }
 
 _lib = None

@@ -591,6 +591,70 @@ def _dims5(x: torch.Tensor):
 
 
 # ------------------------------------------------------------------------------------------- gradient slots
+# ------------------------------------------------------------------------------------------- activity counts
+_ACTIVITY = None   # the ``activity.Recorder`` of the enclosing ``activity.record(...)`` block, else None: nothing is counted
+
+
+def _activity_launch(ptr: int, kind: int, ld: int, threshold: float, T: int, M: int, C: int, per_step: bool,
+                     counts: torch.Tensor, accumulate: bool) -> None:
+    _hip.call("snn_activity_count", ptr, kind, ld, float(threshold), T, M, C, int(bool(per_step)), counts.data_ptr(),
+              int(bool(accumulate)), _stream())
+
+
+def activity_plan(kind: int, T: int, M: int, C: int, ld: int, aligned: bool) -> Tuple[int, int, int, int]:
+    """``(channels per access, pixel rows per block, grid x, grid y)`` of the launch ``snn_activity_count`` takes (host only)."""
+    out = (ctypes.c_int64 * 4)()
+    _hip.call("snn_activity_count_plan", kind, T, M, C, ld, int(bool(aligned)), out)
+    return tuple(int(v) for v in out)
+
+
+def spike_count(x: Optional[torch.Tensor], threshold: Optional[float] = None, mask: Optional[torch.Tensor] = None,
+                per_step: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact per-channel element counts of a sequence, int64 ``[C]`` (``per_step``: ``[T,C]``), by one launch of
+    ``snn_activity_count``; nothing is synchronised.
+
+    ``x`` is ``[T,B,C,H,W]`` channels-last, or a channel slice of such a tensor (``cl_stride``), fp32 or bf16: counted is
+    ``x != 0`` (-0.0 is zero; NaN and denormals are not), or, with ``threshold``, ``x > threshold`` (strict, the scans'
+    comparison: ``x`` holds saved potentials).  ``mask`` (int32 ``[T,B,H,W,words]``, the spike bit mask of a stage-entry LIF
+    scan, possibly the first ``words`` columns of wider rows) is counted instead of ``x``, which then only tells the channel
+    count (``x=None``: ``32 * words``).  ``out``: an int64 tensor of the result's shape that the counts are ADDED to."""
+    if mask is not None:
+        if not mask.is_cuda:   # (_require_device also checks for a float type)
+            raise RuntimeError(f"spike_count mask: tensor is on {mask.device}; the MI355X path has no CPU fallback "
+                               "(move the model and its inputs to a HIP device)")
+        if mask.dim() != 5 or mask.dtype != torch.int32:
+            raise RuntimeError("spike_count: the mask is int32 [T,B,H,W,words]")
+        T, B, H, W, words = mask.shape
+        C = int(x.shape[-3]) if x is not None else 32 * words
+        ld = mask.stride(3)
+        want = (B * H * W * ld, H * W * ld, W * ld, ld, 1)
+        if C % 32 or C // 32 > words or ld < words or any(n > 1 and s != w for n, s, w in zip(mask.shape, mask.stride(), want)):
+            raise RuntimeError("spike_count: the mask rows hold C / 32 words (C a multiple of 32) at one pixel stride")
+        src, kind, th = mask, _hip.ACTIVITY_MASK, 0.0
+    else:
+        _require_device(x, "spike_count input", bf16_ok=True)
+        if x.dim() != 5 or cl_stride(x) is None:
+            raise RuntimeError("spike_count takes a channels-last sequence [T,B,C,H,W] (functional.to_channels_last) or a "
+                               "channel slice of one")
+        T, B, C, H, W = _dims5(x)
+        ld = cl_stride(x)
+        bf = x.dtype == _BF16
+        if threshold is None:
+            kind, th = (_hip.ACTIVITY_NONZERO_BF16 if bf else _hip.ACTIVITY_NONZERO_F32), 0.0
+        else:
+            kind, th = (_hip.ACTIVITY_ABOVE_BF16 if bf else _hip.ACTIVITY_ABOVE_F32), float(threshold)
+        src = x
+    shape = (T, C) if per_step else (C,)
+    if out is None:
+        counts = torch.empty(shape, device=src.device, dtype=torch.int64)
+    else:
+        if out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != src.device:
+            raise RuntimeError(f"spike_count: out must be a contiguous int64 tensor of shape {shape} on {src.device}")
+        counts = out
+    _activity_launch(src.data_ptr(), kind, ld, th, T, B * H * W, C, per_step, counts, out is not None)
+    return counts
+
+
 class GradSlot:
     """Destination of a parameter's gradient inside a flat gradient buffer (``trainer.FlatTrainer``).
 
@@ -907,6 +971,8 @@ class _Conv2d(Function):
             _hip.query("snn_conv2d_spikes_supported", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, cl_stride(x),
                        fwd_prec, bwd_prec),
             _halo_ok(T * B, H, W, Cin, Cout, KH, KW, stride, pad), x.data_ptr(), w_ohwi.data_ptr()))
+        if _ACTIVITY is not None:
+            _ACTIVITY.count_conv((weight,), x, x_th, None, Cout, KH, KW, stride)
         y = _out_tensor(dest, T, B, Cout, Ho, Wo, x, _BF16 if sb else None)
         partial = layout = None
         if bn_out is not None:  # a train-mode BatchNorm follows: its statistics come out of this kernel's epilogue
@@ -1165,9 +1231,13 @@ class _SiblingConv1x1(Function):
             x.data_ptr(), wc.data_ptr()))
         if x_th is None:
             x_mask = None
-        if x_mask is not None and _hip.query("snn_conv1x1_mask_supported", T * B, H, W, Cin, Ct, x_mask.data_ptr(),
-                                             x_mask.shape[-1], wc.data_ptr(), y.data_ptr(), cl_stride(y), None, 0, None,
-                                             fwd_prec, bwd_prec):
+        reads_mask = x_mask is not None and bool(_hip.query(
+            "snn_conv1x1_mask_supported", T * B, H, W, Cin, Ct, x_mask.data_ptr(), x_mask.shape[-1], wc.data_ptr(),
+            y.data_ptr(), cl_stride(y), None, 0, None, fwd_prec, bwd_prec))
+        if _ACTIVITY is not None:
+            _ACTIVITY.count_conv(((w1,) if w1 is not None else ()) + tuple(w2s), x, x_th, x_mask if reads_mask else None,
+                                 Ct, 1, 1, 1)
+        if reads_mask:
             _hip.call("snn_conv1x1_mask_fwd", x_mask.data_ptr(), x_mask.shape[-1], wc.data_ptr(), y.data_ptr(), cl_stride(y),
                       T * B, H, W, Cin, Ct, _stream())
         elif x_th is not None:
@@ -1560,6 +1630,17 @@ class _AffineNeuron(Function):
                 vdec = torch.empty(((T + k - 1) // k, 2, B, H, W, C), device=dev, dtype=_F32)
             else:
                 vdec = torch.empty((T, B, H, W, C), device=dev, dtype=y.dtype)
+        count_only = False
+        if _ACTIVITY is not None and neuron == _hip.NEURON_LIF and (addend is not None or last_only):
+            # the recorder counts this layer's spikes, and the scan leaves none to count: `out` is z + shortcut, or the last
+            # step alone.  Potentials are saved anyway when a backward pass follows; otherwise the scan writes them for this
+            # one pass, into a buffer that is free again once the count has been enqueued.
+            if ckpt:
+                raise RuntimeError("activity.record: a LIF layer on the checkpointed scan (LIF_CHECKPOINT_BYTES) with a fused "
+                                   "shortcut keeps neither spikes nor potentials to count")
+            if vdec is None:
+                vdec = torch.empty((T, B, H, W, C), device=dev, dtype=y.dtype)
+                count_only = True
         if v0 is not None:
             v0 = _expand_state(v0, (B, C, H, W), dev)
         if i0 is not None:
@@ -1576,6 +1657,7 @@ class _AffineNeuron(Function):
             if addend.dtype != y.dtype:
                 raise RuntimeError("Residual merge: shortcut and branch are stored in different types (fp32 / bf16)")
             ad_ptr, ld_ad = addend.data_ptr(), cl_stride(addend)
+        mask = None
         if ckpt:
             _hip.call("snn_lif_fwd_ckpt", y.data_ptr(), ldy, _ptr(alpha), _ptr(beta), _ptr(v0), _ptr(i0),
                       out.data_ptr(), cl_stride(out), ad_ptr, ld_ad, _ptr(vT), _ptr(iT), vdec.data_ptr(), T, M, C,
@@ -1587,7 +1669,6 @@ class _AffineNeuron(Function):
             fwd_flags = ((_hip.SCAN_LAST_STEP_ONLY if last_only else 0) | sb_flag
                          | (_hip.SCAN_SPIKES_FROM_VDEC if no_out else 0))
             # ... and the spikes as one bit per neuron next to the potentials (snn_conv1x1_mask_*: 32 channels per word)
-            mask = None
             if no_out and cfg.spike_mask and USE_SPIKE_MASK and not tau and C % 32 == 0 and T * M * C * 4 >= SPIKE_MASK_MIN_BYTES and all(
                     t is None or t.data_ptr() % 16 == 0 for t in (y, alpha, beta, v0, i0, vT, iT, vdec)):
                 mask = torch.empty((T, B, H, W, C // 32), device=dev, dtype=torch.int32)
@@ -1604,6 +1685,15 @@ class _AffineNeuron(Function):
                 spikes_out.append(float(params.v_th))
                 if mask is not None:
                     spikes_out.append(mask)
+        if _ACTIVITY is not None and neuron == _hip.NEURON_LIF:
+            # what this forward produced, cheapest first: the bit mask; the spike tensor, unless a shortcut is folded into
+            # its store or only the last step was written; the saved potentials with v_th.  In bf16 storage the last are the
+            # STORED (rounded) potentials - the spikes the reverse scan sees, which the scan's own comparison on the
+            # unrounded value can differ from for a potential within one bf16 step of the threshold.
+            spikes = None if (no_out or addend is not None or last_only) else out
+            _ACTIVITY.count_lif(params, mask, spikes, None if ckpt else vdec, float(params.v_th), (T, B, C, H, W))
+            if count_only:
+                vdec = None
         ctx.ckpt = ckpt
         ctx.sb = sb
         ctx.defer_apply = cfg.defer_apply

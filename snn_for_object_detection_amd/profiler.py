@@ -185,6 +185,10 @@ def work_of(name: str, a):
         return "k_adamax", 8.0 * a[4], 28.0 * a[4]
     if name == "snn_adamax_step_ctl":
         return "k_adamax_ctl", 12.0 * a[4], 28.0 * a[4]
+    if name == "snn_activity_count":   # one read of the source: fp32 / bf16 elements, or one bit per neuron (kind 4)
+        kind, T, M, C = a[1], a[4], a[5], a[6]
+        label = "k_activity_count" + (", mask" if kind == 4 else (", bf16s" if kind in (1, 3) else ""))
+        return label, 0.0, float(T) * M * C * (0.125 if kind == 4 else (2.0 if kind in (1, 3) else 4.0))
     if name == "snn_grad_norm":   # one read of the flat gradient; a multiply and an add in fp64 per element
         return "k_grad_norm", 2.0 * a[1], 4.0 * a[1]
     return name, 0.0, 0.0

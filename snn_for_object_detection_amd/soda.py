@@ -307,6 +307,21 @@ class SODa(nn.Module):
         background_loss = cls[~mask].mean()
         return (gt_loss * self.hparams.loss_ratio + background_loss * (1 - self.hparams.loss_ratio) + bbox.mean())
 
+    def activity_report(self, X: torch.Tensor, state: Optional[ListState] = None, per_step: bool = False,
+                        process_group=None) -> dict:
+        """Firing rates of every LIF layer and the synaptic operations of every convolution over the clip ``X[T,B,2,H,W]``
+        (``activity.make_report``): one eval-mode, ``no_grad``, layer-major pass under ``activity.record``, continuing from
+        ``state`` when given.  ``per_step``: the LIF counts per timestep."""
+        from . import activity
+        if X.dim() != 5:
+            raise ValueError(f"activity_report takes X[T,B,2,H,W], got a tensor of rank {X.dim()}")
+        if self.training:
+            raise RuntimeError("activity_report needs eval mode (model.eval()); a training step is recorded with "
+                               "`with activity.record(model) as rec: model.training_step(batch)`")
+        with torch.no_grad(), activity.record(self, per_step=per_step) as rec:
+            self._forward_impl(X, state)
+        return rec.report(process_group)
+
     def spike_taps(self):
         """``{module path: spikes[T,B,C,h,w]}`` of every ``StateStorage`` (``state_storage=True``, eval mode)."""
         from .layer_gen import StateStorage
