@@ -724,6 +724,18 @@ int snn_events_to_frames_aug(const int64_t* t_us, const int32_t* x, const int32_
                              const int64_t* offsets, const int64_t* t0, const int32_t* aug, int64_t n_events,
                              float* frames, int T, int B, int H, int W, int64_t step_us, void* stream);
 
+/* The same feed from the 8-byte records of a Prophesee DAT recording, unpacked in the kernel: words is uint32 [n][2] in
+ * device memory, 8-byte aligned (sample slices may start at any event), event e = {ts_us, data}:
+ *   t_us = words[2e] zero-extended to 64 bits;  d = words[2e+1]:  x = d & 0x3FFF, y = (d >> 14) & 0x3FFF,
+ *   p = (d >> 28) & 1; bits 29-31 are ignored.
+ * Everything else - offsets, t0, the table, binning, x clipped to [0, W-1], y >= H dropped, the drop hash on the index
+ * inside the sample, flip, zoom, shift, the frame test, zero-fill, the refusals - is snn_events_to_frames_aug's.  aug NULL
+ * is the identity and reads no table.  For ANY word contents and ANY table contents nothing is written outside frames.
+ * n_events = 0 zero-fills and launches nothing.  Timestamps do not wrap inside a recording (2^32 us = 71 minutes). */
+int snn_events_to_frames_packed(const uint32_t* words, const int64_t* offsets, const int64_t* t0, const int32_t* aug,
+                                int64_t n_events, float* frames, int T, int B, int H, int W, int64_t step_us,
+                                void* stream);
+
 /* The boxes of the same transform.  labels_in / labels_out: fp32 [B][N][width], width 5 (class, x1, y1, x2, y2) or 6
  * (ts in front, copied untouched), boxes normalised to [0, 1]; a row whose class is below 0 is padding and stays
  * padding.  A valid row, s = a_q16 2^-16:  flip (x1, x2) = (1 - x2, 1 - x1);  x' = x s + ox / W, y' = y s + oy / H;

@@ -16,6 +16,8 @@ from .data import EventAugment, EventBatcher  # noqa: F401
 from .generator import BackboneGen, BlockGen, Head, HeadGen, ListGen, ListState, ModelGen, NeckGen  # noqa: F401
 from .layer_gen import *  # noqa: F401,F403
 from .metrics import MeanAveragePrecision  # noqa: F401
+from .recordings import (DatRecording, MTSampler, PropheseeFeed, STSampler, load_boxes, pack_events,  # noqa: F401
+                         unpack_events, write_dat)
 from .roi import RoI  # noqa: F401
 from .soda import SODa  # noqa: F401
 from .tiny_yolo import TinyYolo  # noqa: F401

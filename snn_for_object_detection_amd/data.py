@@ -14,9 +14,14 @@ layout the first convolution reads, so the NCHW -> NHWC pass over the input disa
 ``EventAugment`` (not in the reference) adds the usual event-camera augmentations - horizontal flip, zoom with a shift,
 random event drop - inside the scatter: a batcher that has one hands the raw int64 timestamps to
 ``snn_events_to_frames_aug``, which bins and transforms them in one launch, and the boxes to ``snn_labels_augment``.
+
+A sample may also be ``(words, t0_us)`` - the 8-byte records of a Prophesee DAT recording as they lie in the file
+(``recordings.DatRecording``): the slices go through one of two persistent pinned staging buffers, one copy carries
+8 bytes per event, and ``snn_events_to_frames_packed`` unpacks the words inside the scatter.
 """
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _hip
@@ -134,6 +139,9 @@ class EventBatcher:
         from . import functional as _HF
         dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
         self._copy_stream = _HF.concurrent_stream(torch.cuda.current_stream(dev), avoid=tuple(_HF._SIDE_STREAMS.values()))
+        # packed samples: two pinned staging slots used in turn, each with the HIP event recorded behind its last copies
+        self._slots = [{"words": None, "words_np": None, "meta": None, "done": None} for _ in range(2)]
+        self._slot = 1
 
     def __call__(self, samples: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, int]],
                  labels: Optional[Sequence[torch.Tensor]] = None, *, augment: bool = True,
@@ -142,21 +150,105 @@ class EventBatcher:
         asynchronous) and the time of the first frame.  Returns ``X[T, B, 2, H, W]`` (logical NCHW view of a
         channels-last buffer) and, when ``labels`` is given, ``labels[B, N, 5]`` padded with -1 - ``[B, N, 6]`` when the
         rows given carry a timestep in front (``(ts, class, x1, y1, x2, y2)``, the multi-target sample format).
+        Or ``samples[b] = (words, t0_us)`` with ``words`` the DAT records of the sample, host ``uint32[n, 2]`` (``_packed``);
+        all samples of a call have the same form.
 
         A batcher built with an ``EventAugment`` draws one transform per sample and applies it to events and boxes
         (``augment=False``: the identity, for validation batches); ``aug_table`` (host ``int32[B, 8]``) replaces the
         draw, with or without an ``EventAugment`` - for a test, or for the same transform on two modalities.  The table
         used is kept as ``last_aug_table``.  Boxes the transform pushes out of the frame become -1 rows behind the kept
         ones; ``N`` stays that of the collate."""
+        forms = {len(s) for s in samples}
+        if 2 in forms and forms != {2}:
+            raise ValueError("EventBatcher: packed (words, t0_us) samples and (t_us, x, y, p, t0_us) samples mixed in one "
+                             "call")
+        packed = forms == {2}
         if aug_table is None and self.augment is None:
-            return self._plain(samples, labels)
+            return self._packed(samples, labels, None) if packed else self._plain(samples, labels)
         from . import functional as _HF
         B = len(samples)
         if aug_table is not None:
             table = _HF.check_aug_table(aug_table, B)
         else:
             table = self.augment.draw(B) if augment else EventAugment.identity(B)
-        return self._augmented(samples, labels, table)
+        return self._packed(samples, labels, table) if packed else self._augmented(samples, labels, table)
+
+    def _staging(self, n: int, meta_len: int) -> dict:
+        """The next of the two pinned staging slots, free to be written: its last H2D copies have completed (the HIP event
+        recorded behind them is waited on here, on the host), and it holds at least ``n`` records and ``meta_len`` int64."""
+        self._slot ^= 1
+        slot = self._slots[self._slot]
+        if slot["done"] is not None:
+            slot["done"].synchronize()
+        if slot["words"] is None or slot["words"].shape[0] < n:
+            cap = max(n, 2 * (0 if slot["words"] is None else int(slot["words"].shape[0])), 1 << 16)
+            slot["words"] = torch.empty((cap, 2), dtype=torch.int32, pin_memory=True)
+            slot["words_np"] = slot["words"].numpy().view(np.uint32)
+        if slot["meta"] is None or slot["meta"].numel() < meta_len:
+            slot["meta"] = torch.empty(meta_len, dtype=torch.int64, pin_memory=True)
+        return slot
+
+    def _packed(self, samples, labels, table: Optional[torch.Tensor]):
+        """Packed samples ``(words, t0_us)`` - ``words`` the 8-byte records of a DAT recording as host ``uint32[n, 2]``
+        (numpy, a memory map included, or torch): the slices are copied into a persistent pinned staging buffer, one H2D
+        copy carries the events (8 bytes each) and one ``offsets | t0 | table``, one ``snn_events_to_frames_packed`` launch
+        unpacks, bins and transforms.  ``table`` None: the kernel reads no table."""
+        from . import functional as _HF
+        B = len(samples)
+        T, H, W = self.T, self.H, self.W
+        if self.step <= 0:
+            raise ValueError(f"EventBatcher: time_step_us must be positive, got {self.step}")
+        words = []
+        for w, _ in samples:
+            w = w.numpy() if isinstance(w, torch.Tensor) else np.asarray(w)
+            if w.dtype.kind not in "ui" or w.dtype.itemsize != 4 or w.ndim != 2 or w.shape[1] != 2:
+                raise ValueError(f"EventBatcher: packed events must be uint32 [n, 2], got {w.dtype} {tuple(w.shape)}")
+            words.append(w.view(np.uint32) if w.dtype != np.uint32 else w)
+        counts = [int(w.shape[0]) for w in words]
+        n = sum(counts)
+        meta_len = (2 * B + 1) + (4 * B if table is not None else 0)   # offsets[B + 1] | t0[B] | table[B][8] (int32)
+        slot = self._staging(n, meta_len)
+        at = 0
+        for w, c in zip(words, counts):
+            if c:
+                slot["words_np"][at:at + c] = w
+                at += c
+        meta = slot["meta"][:meta_len]
+        meta[0] = 0
+        meta[1:B + 1] = torch.tensor(counts, dtype=torch.int64).cumsum(0)
+        meta[B + 1:2 * B + 1] = torch.tensor([int(s[1]) for s in samples], dtype=torch.int64)
+        if table is not None:
+            meta[2 * B + 1:].view(torch.int32).copy_(table.reshape(-1))
+        main = torch.cuda.current_stream(self.device)
+        buf = torch.empty((T, B, H, W, 2), device=self.device, dtype=torch.float32)   # [T][B][H][W][C]
+        meta_dev = torch.empty(meta_len, device=self.device, dtype=torch.int64)
+        self._copy_stream.wait_stream(main)
+        with torch.cuda.stream(self._copy_stream):
+            ev = torch.empty((max(n, 1), 2), device=self.device, dtype=torch.int32)
+            if n:
+                ev[:n].copy_(slot["words"][:n], non_blocking=True)
+            meta_dev.copy_(meta, non_blocking=True)
+            if slot["done"] is None:
+                slot["done"] = torch.cuda.Event()
+            slot["done"].record(self._copy_stream)   # behind both copies: the slot is rewritten only after it
+            aug_dev = meta_dev[2 * B + 1:].view(torch.int32) if table is not None else None
+            _hip.call("snn_events_to_frames_packed", ev.data_ptr(), meta_dev.data_ptr(), meta_dev[B + 1:].data_ptr(),
+                      aug_dev.data_ptr() if aug_dev is not None else None, n, buf.data_ptr(), T, B, H, W, self.step,
+                      self._copy_stream.cuda_stream)
+            buf.record_stream(self._copy_stream)
+            meta_dev.record_stream(self._copy_stream)
+        main.wait_stream(self._copy_stream)
+        if table is not None:
+            self.last_aug_table = table.clone()
+        X = buf.permute(0, 1, 4, 2, 3)
+        if labels is None:
+            return X
+        with torch.cuda.stream(main):
+            lab = collate_labels(labels, B).to(self.device, non_blocking=True)
+            if table is not None:
+                a = self.augment
+                lab = _HF.labels_augment(lab, aug_dev, W, H, *((a.min_visible, a.min_size_px) if a is not None else ()))
+        return X, lab
 
     def _augmented(self, samples, labels, table: torch.Tensor):
         """Four copies per sample into slices of the batch's event arrays, ``offsets | t0 | table`` in one small pinned

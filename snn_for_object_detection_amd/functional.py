@@ -2770,6 +2770,33 @@ def events_to_frames_aug(t_us: torch.Tensor, x: torch.Tensor, y: torch.Tensor, p
     return buf.permute(0, 1, 4, 2, 3)
 
 
+def events_to_frames_packed(words: torch.Tensor, offsets: torch.Tensor, t0: torch.Tensor, aug: Optional[torch.Tensor],
+                            T: int, B: int, H: int, W: int, step_us: int) -> torch.Tensor:
+    """``snn_events_to_frames_packed`` on device tensors: the DAT records of a whole batch (``words`` uint32 or int32
+    ``[n, 2]`` rows ``ts_us, data``, any storage offset that is a whole record; sample ``b`` at
+    ``offsets[b]:offsets[b+1]``, window starts ``t0[B]``) unpacked, binned, transformed by the rows of ``aug`` (``None``: the
+    identity, no table is read) and scattered -> ``[T, B, 2, H, W]``, channels-last memory."""
+    T, B, H, W = int(T), int(B), int(H), int(W)
+    if int(step_us) <= 0:
+        raise ValueError(f"events_to_frames_packed: step_us must be positive, got {step_us}")
+    if min(T, B, H, W) <= 0:
+        raise ValueError(f"events_to_frames_packed: T, B, H, W must be positive, got {(T, B, H, W)}")
+    word_types = tuple(d for d in (getattr(torch, "uint32", None), torch.int32) if d is not None)
+    if (not words.is_cuda or words.dtype not in word_types or words.dim() != 2 or words.shape[1] != 2
+            or not words.is_contiguous() or words.data_ptr() % 8):
+        raise ValueError("events_to_frames_packed: words must be a contiguous 8-byte aligned HIP tensor uint32[n, 2]")
+    want = ((offsets, torch.int64, B + 1), (t0, torch.int64, B)) + (((aug, torch.int32, 8 * B),) if aug is not None else ())
+    for v, dtype, n in want:
+        if not v.is_cuda or v.dtype != dtype or v.numel() != n or not v.is_contiguous():
+            raise ValueError("events_to_frames_packed: contiguous HIP tensors offsets int64[B + 1], t0 int64[B], aug "
+                             "int32[B, 8] or None required")
+    buf = torch.empty((T, B, H, W, 2), device=words.device, dtype=_F32)
+    _hip.call("snn_events_to_frames_packed", words.data_ptr(), offsets.data_ptr(), t0.data_ptr(),
+              aug.data_ptr() if aug is not None else None, int(words.shape[0]), buf.data_ptr(), T, B, H, W, int(step_us),
+              _stream())
+    return buf.permute(0, 1, 4, 2, 3)
+
+
 def labels_augment(labels: torch.Tensor, aug: torch.Tensor, W: int, H: int, min_visible: float = 0.25,
                    min_size_px: float = 2.0) -> torch.Tensor:
     """``snn_labels_augment``: the boxes of device ``labels[B, N, 5 | 6]`` under the rows of the device table ``aug`` -

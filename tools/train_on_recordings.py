@@ -1,0 +1,49 @@
+#!/usr/bin/env python3
+"""Train TinyYolo on Prophesee recordings: ``PropheseeFeed`` -> ``TinyYolo`` -> ``FlatTrainer``, one loss per step.
+
+    python tools/train_on_recordings.py --data-dir ./data --dataset gen1 --steps 100 --batch-size 4 --num-steps 42
+
+expects ``<data-dir>/<dataset>/train/*_bbox.npy`` with their ``*_td.dat``.  ``--augment`` switches the event augmentation
+on (flip, zoom with shift, random drop); ``--label-steps K`` trains on every labelled timestep (multi-target samples and
+``SODa(label_steps=K)``).  The feed of step n+1 is queued while step n runs.  No checkpoint logic beyond FlatTrainer's."""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import snn_for_object_detection_amd as S  # noqa: E402
+from snn_for_object_detection_amd.trainer import FlatTrainer  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--data-dir", required=True)
+    ap.add_argument("--dataset", default="gen1", choices=("gen1", "1mpx"))
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--batch-size", type=int, default=4)
+    ap.add_argument("--num-steps", type=int, default=42)
+    ap.add_argument("--augment", action="store_true")
+    ap.add_argument("--label-steps", type=int, default=None, metavar="K")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+
+    augment = S.EventAugment(hflip=0.5, zoom=(0.75, 1.25), drop=(0.0, 0.1), seed=args.seed) if args.augment else None
+    feed = S.PropheseeFeed(args.data_dir, dataset=args.dataset, split="train", batch_size=args.batch_size,
+                           num_steps=args.num_steps, one_label=args.label_steps is None, seed=args.seed, augment=augment)
+    torch.manual_seed(args.seed)
+    model = S.TinyYolo(num_classes=len(feed.get_labels()), label_steps=args.label_steps).cuda().train()
+    trainer = FlatTrainer(model)
+    batch = next(feed)
+    for step in range(args.steps):
+        trainer.zero_grad()
+        loss = model.training_step(batch)
+        loss.backward()
+        trainer.step()
+        batch = next(feed)          # queued behind the step that is still running
+        print(f"step {step:5d}  loss {float(loss.detach()):.6f}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
