@@ -850,6 +850,38 @@ int snn_det_loss_steps_bwd(const float* cls_logits, const float* bbox_preds, con
                            int C, float loss_ratio, const double* stats, const float* g_loss, float* g_logits,
                            float* g_bbox, void* stream);
 
+/* ---- Selectable detection loss (new symbols under ABI v20; snn_det_loss_* above are unchanged).  The same rows, with
+ * anchors [A][4] corner boxes (row r uses anchor r % A; rows is a multiple of A) and steps [rows / A] int32 or NULL:
+ * with steps, the rows of a frame with steps[frame] < 0 are left out of every sum and get exact zeros as gradients, and
+ * V counts the other frames on the device; without, V = rows / A.
+ *   cls  = loss_ratio * sum_pos f / max(n_pos, 1) + (1 - loss_ratio) * sum_neg f / max(n_neg, 1)
+ *          f = ce = -log softmax(x)[y] (SNN_LOSS_CLS_CE) or (1 - p_y)^gamma * ce (SNN_LOSS_CLS_FOCAL); pos: label > 0
+ *   box  = box_weight * sum |bbox*mask - offset*mask| / (4 A V)                              (SNN_LOSS_BOX_L1)
+ *        = box_weight * sum over box rows of (1 - IoU + penalty) / max(n_pos, 1)             (GIOU, DIOU, CIOU)
+ *   loss = cls + box; without any positive row the means over them are 0 (not NaN); V = 0: loss 0, zero gradients.
+ * Box rows have label > 0 and all four mask entries equal to 1.  Their boxes are offset_inverse (utils/box.py:72-79) of
+ * the anchor with bbox_preds and with bbox_offset, the exponent argument o / 5 clamped above at log(1000 / 16) (zero
+ * gradient past the clamp).  IoU = I / (U + eps); GIoU penalty (C - U) / (C + eps) of the enclosing box's area C;
+ * DIoU rho^2 / (c^2 + eps), squared centre distance over squared enclosing diagonal; CIoU adds alpha * v with
+ * v = 4 / pi^2 (atan(wg / (hg + eps)) - atan(w / (h + eps)))^2 and alpha = v / (1 - IoU + v + eps) held constant in the
+ * gradient; eps = 1e-7.  Rows that are no box rows get exact zeros in g_bbox under the IoU modes.
+ * stats[9] = {sum f pos, n_pos, sum f neg, n_neg, box sum, V, pos term, neg term, box term}: the last three are the fp32
+ * terms of the loss, loss = (pos term + neg term) + box term.  Refused before any launch: null pointers (steps may be
+ * NULL), K outside 1 .. 64, rows not a positive multiple of A, unknown modes, gamma < 0, bbox_preds / bbox_offset /
+ * bbox_mask / anchors / g_bbox not 16-byte aligned.  workspace: snn_det_loss_ext_workspace_size(rows) bytes. */
+enum { SNN_LOSS_CLS_CE = 0, SNN_LOSS_CLS_FOCAL = 1 };
+enum { SNN_LOSS_BOX_L1 = 0, SNN_LOSS_BOX_GIOU = 1, SNN_LOSS_BOX_DIOU = 2, SNN_LOSS_BOX_CIOU = 3 };
+size_t snn_det_loss_ext_workspace_size(int64_t rows);
+int snn_det_loss_ext_fwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                         const float* bbox_mask, const int64_t* class_labels, const float* anchors, const int* steps,
+                         int64_t rows, int A, int K, float loss_ratio, int cls_mode, float gamma, int box_mode,
+                         float box_weight, void* workspace, double* stats, float* loss, void* stream);
+int snn_det_loss_ext_bwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                         const float* bbox_mask, const int64_t* class_labels, const float* anchors, const int* steps,
+                         int64_t rows, int A, int K, float loss_ratio, int cls_mode, float gamma, int box_mode,
+                         float box_weight, const double* stats, const float* g_loss, float* g_logits, float* g_bbox,
+                         void* stream);
+
 /* ---------------------------------------------------------------- detection mAP (ABI v12)
  * COCO bounding-box mAP as the reference computes it in validation_step / test_step (models/soda.py:160-182, 283-321:
  * torchmetrics MeanAveragePrecision, iou_type "bbox", area range "all", no crowd boxes).

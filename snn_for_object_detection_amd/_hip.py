@@ -23,6 +23,8 @@ SCAN_SPIKE_MASK = 32   # forward only (shares its value with the backward-only f
 SURR_SUPER, SURR_TRIANGLE, SURR_SIGMOID, SURR_ATAN = 0, 1, 2, 3   # SNN_SURR_* of include/snn_hip.h
 # SNN_ACT_* of include/snn_hip.h (snn_activity_count; not the ACT_* activations above)
 ACTIVITY_NONZERO_F32, ACTIVITY_NONZERO_BF16, ACTIVITY_ABOVE_F32, ACTIVITY_ABOVE_BF16, ACTIVITY_MASK = 0, 1, 2, 3, 4
+LOSS_CLS_MODES = {"ce": 0, "focal": 1}                        # SNN_LOSS_CLS_* of include/snn_hip.h
+LOSS_BOX_MODES = {"l1": 0, "giou": 1, "diou": 2, "ciou": 3}   # SNN_LOSS_BOX_*
 
 
 class NeuronParams(Structure):
@@ -134,6 +136,9 @@ SIGNATURES = {
     "snn_det_loss_steps_workspace_size": (c_size_t, [_I, _I, _I]),
     "snn_det_loss_steps_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "snn_det_loss_steps_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "snn_det_loss_ext_workspace_size": (c_size_t, [_L]),
+    "snn_det_loss_ext_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _I, _F, _I, _F, _P, _P, _P, _P]),
+    "snn_det_loss_ext_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _I, _F, _I, _F, _P, _P, _P, _P, _P]),
     "snn_small_gemm": (c_int, [_P, _L, _I, _P, _L, _I, _P, _L, _I, _I, _I, _I, _P, _L, _P]),
     "snn_small_gemm_batched": (c_int, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "snn_copy_channels_bf16": (c_int, [_P, _L, _P, _L, _L, _I, _P]),

@@ -2720,6 +2720,117 @@ def detection_loss_steps(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox
     return _DetectionLossSteps.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, steps, loss_ratio)
 
 
+# ------------------------------------------------------------------------------------------- selectable detection loss
+def check_loss_options(cls_loss: str, focal_gamma: float, box_loss: str, box_loss_weight: float) -> Tuple[int, float, int, float]:
+    """The loss options by name -> ``(cls_mode, gamma, box_mode, box_weight)`` as the kernels take them, or ``ValueError``."""
+    if cls_loss not in _hip.LOSS_CLS_MODES:
+        raise ValueError(f"cls_loss must be one of {sorted(_hip.LOSS_CLS_MODES)}, got {cls_loss!r}")
+    if box_loss not in _hip.LOSS_BOX_MODES:
+        raise ValueError(f"box_loss must be one of {sorted(_hip.LOSS_BOX_MODES)}, got {box_loss!r}")
+    if not float(focal_gamma) >= 0.0:
+        raise ValueError(f"focal_gamma must be >= 0, got {focal_gamma}")
+    if not float(box_loss_weight) >= 0.0:
+        raise ValueError(f"box_loss_weight must be >= 0, got {box_loss_weight}")
+    return _hip.LOSS_CLS_MODES[cls_loss], float(focal_gamma), _hip.LOSS_BOX_MODES[box_loss], float(box_loss_weight)
+
+
+class _DetectionLossExt(Function):
+    """``_DetectionLoss`` / ``_DetectionLossSteps`` (``steps`` None or ``[K,B]``) with a selectable classification term
+    (cross entropy | focal) and box term (L1 | GIoU | DIoU | CIoU) (``csrc/det_loss_ext.hip``): two launches forward, one
+    backward, no host round trip.  Returns the loss and ``stats[9]``, whose last three entries are the terms of the loss."""
+
+    @staticmethod
+    def forward(ctx, cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, loss_ratio: float,
+                modes: Tuple[int, float, int, float]):
+        _require_device(cls_preds, "loss: class predictions")
+        _require_device(bbox_preds, "loss: box predictions")
+        # the targets and anchors go to the kernel as raw pointers: a host or float64 tensor would be a wild address
+        _require_device(bbox_offset, "loss: box offsets")
+        _require_device(bbox_mask, "loss: box mask")
+        _require_device(anchors, "loss: anchors")
+        for t, what in ((bbox_preds, "box predictions"), (bbox_offset, "box offsets"), (bbox_mask, "box mask"),
+                        (class_labels, "class labels"), (anchors, "anchors")):
+            if t.device != cls_preds.device:
+                raise RuntimeError(f"loss: {what} are on {t.device}, the class predictions on {cls_preds.device}")
+        if anchors.dim() != 2 or anchors.shape[1] != 4 or cls_preds.dim() < 2 or cls_preds.shape[-2] != anchors.shape[0]:
+            raise RuntimeError(f"detection loss: anchors [A,4] and class predictions [..., A, C+1] required, got "
+                               f"{tuple(anchors.shape)} and {tuple(cls_preds.shape)}")
+        A, C = int(anchors.shape[0]), int(cls_preds.shape[-1])
+        logits, boxes = cls_preds.detach().contiguous(), bbox_preds.detach().contiguous()
+        off, msk = bbox_offset.contiguous(), bbox_mask.contiguous()
+        lab, anc = class_labels.contiguous(), anchors.detach().contiguous()
+        rows = lab.numel()
+        if rows == 0 or logits.numel() != rows * C or boxes.numel() != rows * 4 or off.numel() != rows * 4 or \
+                msk.numel() != rows * 4 or lab.dtype != torch.int64:
+            raise RuntimeError("detection loss: predictions and targets differ in shape")
+        if steps is not None:
+            if cls_preds.dim() != 4:
+                raise RuntimeError("detection_loss_steps_ext: class predictions [K,B,A,C+1] required")
+            Ks, steps = _require_steps(steps, int(cls_preds.shape[1]), cls_preds, "detection_loss_steps_ext")
+            if Ks != cls_preds.shape[0]:
+                raise RuntimeError("detection loss: predictions, targets and steps differ in shape")
+        dev = logits.device
+        ws = torch.empty(_hip.query("snn_det_loss_ext_workspace_size", rows), device=dev, dtype=torch.uint8)
+        stats = torch.empty(9, device=dev, dtype=torch.float64)
+        loss = torch.empty((), device=dev, dtype=_F32)
+        ctx.args = (rows, A, C, float(loss_ratio), int(modes[0]), float(modes[1]), int(modes[2]), float(modes[3]))
+        _hip.call("snn_det_loss_ext_fwd", logits.data_ptr(), boxes.data_ptr(), off.data_ptr(), msk.data_ptr(),
+                  lab.data_ptr(), anc.data_ptr(), None if steps is None else steps.data_ptr(), *ctx.args, ws.data_ptr(),
+                  stats.data_ptr(), loss.data_ptr(), _stream())
+        ctx.has_steps = steps is not None
+        ctx.save_for_backward(logits, boxes, off, msk, lab, anc, stats, *(() if steps is None else (steps,)))
+        ctx.shapes = (cls_preds.shape, bbox_preds.shape)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, g, _g_stats):
+        logits, boxes, off, msk, lab, anc, stats = ctx.saved_tensors[:7]
+        steps = ctx.saved_tensors[7] if ctx.has_steps else None
+        g = g.detach().to(_F32).contiguous()
+        g_logits, g_boxes = torch.empty_like(logits), torch.empty_like(boxes)
+        _hip.call("snn_det_loss_ext_bwd", logits.data_ptr(), boxes.data_ptr(), off.data_ptr(), msk.data_ptr(),
+                  lab.data_ptr(), anc.data_ptr(), None if steps is None else steps.data_ptr(), *ctx.args, stats.data_ptr(),
+                  g.data_ptr(), g_logits.data_ptr(), g_boxes.data_ptr(), _stream())
+        return (g_logits.view(ctx.shapes[0]), g_boxes.view(ctx.shapes[1])) + (None,) * 7
+
+
+def _loss_ext(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, loss_ratio, cls_loss,
+              focal_gamma, box_loss, box_loss_weight, return_terms):
+    modes = check_loss_options(cls_loss, focal_gamma, box_loss, box_loss_weight)
+    loss, stats = _DetectionLossExt.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps,
+                                          loss_ratio, modes)
+    if not return_terms:
+        return loss
+    terms = stats[6:9].to(_F32)       # the kernel's own fp32 terms: (terms[0] + terms[1]) + terms[2] is the loss, bit for bit
+    return loss, terms[0] + terms[1], terms[2]
+
+
+def detection_loss_ext(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox_offset: torch.Tensor,
+                       bbox_mask: torch.Tensor, class_labels: torch.Tensor, anchors: torch.Tensor, loss_ratio: float,
+                       cls_loss: str = "ce", focal_gamma: float = 2.0, box_loss: str = "l1",
+                       box_loss_weight: float = 1.0, return_terms: bool = False):
+    """``detection_loss`` with a selectable objective: ``cls_loss`` ``"ce"`` or ``"focal"`` (``(1 - p_y)^gamma ce``, same
+    ``loss_ratio`` weighting, means over ``max(n, 1)`` rows), ``box_loss`` ``"l1"`` (the term of ``detection_loss``) or
+    ``"giou" | "diou" | "ciou"`` of the boxes decoded from ``anchors[A,4]`` with the predicted and the target offsets,
+    summed over the positive rows and divided by ``max(n_pos, 1)``; the box term is scaled by ``box_loss_weight``.
+    ``return_terms``: ``(loss, classification term, box term)`` - device scalars, ``loss`` is their fp32 sum."""
+    return _loss_ext(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, None, loss_ratio, cls_loss,
+                     focal_gamma, box_loss, box_loss_weight, return_terms)
+
+
+def detection_loss_steps_ext(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox_offset: torch.Tensor,
+                             bbox_mask: torch.Tensor, class_labels: torch.Tensor, anchors: torch.Tensor,
+                             steps: torch.Tensor, loss_ratio: float, cls_loss: str = "ce", focal_gamma: float = 2.0,
+                             box_loss: str = "l1", box_loss_weight: float = 1.0, return_terms: bool = False):
+    """``detection_loss_ext`` of ``cls_preds[K,B,A,C+1]`` / ``bbox_preds[K,B,A,4]`` over the valid slots of ``steps[K,B]``
+    (their number ``V`` is counted on the device; the L1 term divides by ``4 A V``); no valid slot: loss 0, zero gradients."""
+    if steps is None:
+        raise RuntimeError("detection_loss_steps_ext: steps[K,B] required")
+    return _loss_ext(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, loss_ratio, cls_loss,
+                     focal_gamma, box_loss, box_loss_weight, return_terms)
+
+
 # ------------------------------------------------------------------------------------------- events
 def events_to_frames(t_bin: torch.Tensor, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, T: int, H: int,
                      W: int) -> torch.Tensor:

@@ -17,8 +17,12 @@ Same constructor, hooks and step logic; what differs:
 * ``label_steps=K`` trains on every labelled timestep: six-column labels ``(ts, class, x1, y1, x2, y2)`` (the
   reference's ``one_label: false`` sample format, which nothing there consumes) supervise up to ``K`` labelled frames
   per sample instead of the last frame only (DESIGN "Every labelled timestep").
+* ``cls_loss`` / ``focal_gamma`` / ``box_loss`` / ``box_loss_weight`` select the objective: focal classification and a
+  GIoU / DIoU / CIoU term on the decoded boxes next to the reference's cross entropy + L1, which stays the default and
+  runs exactly as before (DESIGN "Selectable detection loss").
 """
 
+import math
 from types import SimpleNamespace
 from typing import Optional, Tuple
 
@@ -30,6 +34,77 @@ from . import box
 from .metrics import MeanAveragePrecision
 from .generator import BackboneGen, Head, ListGen, ListState, NeckGen
 from .roi import RoI
+
+LOSS_CLS_NAMES = ("ce", "focal")
+LOSS_BOX_NAMES = ("l1", "giou", "diou", "ciou")
+_EXP_CLAMP = math.log(1000.0 / 16.0)   # upper clamp of the exponent argument of a decoded box side
+_IOU_EPS = 1e-7
+
+
+def _decode_corners(anchors: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """``box.offset_inverse`` with the exponent argument clamped above (zero gradient past the clamp)."""
+    anc = box.box_corner_to_center(anchors)
+    xy = (offsets[:, :2] * anc[:, 2:] / 10) + anc[:, :2]
+    wh = torch.exp(torch.clamp(offsets[:, 2:] / 5, max=_EXP_CLAMP)) * anc[:, 2:]
+    return box.box_center_to_corner(torch.cat((xy, wh), dim=1))
+
+
+def iou_box_loss(pred: torch.Tensor, target: torch.Tensor, mode: str) -> torch.Tensor:
+    """``1 - IoU + penalty`` per row of corner boxes ``pred[n,4]`` / ``target[n,4]``: GIoU ``(C - U) / C`` of the enclosing
+    box, DIoU ``rho^2 / c^2``, CIoU DIoU ``+ alpha v`` (``alpha`` detached); ``eps = 1e-7`` in every denominator."""
+    eps = _IOU_EPS
+    px1, py1, px2, py2 = pred.unbind(-1)
+    gx1, gy1, gx2, gy2 = target.unbind(-1)
+    inter = torch.clamp(torch.minimum(px2, gx2) - torch.maximum(px1, gx1), min=0) * \
+        torch.clamp(torch.minimum(py2, gy2) - torch.maximum(py1, gy1), min=0)
+    union = (px2 - px1) * (py2 - py1) + (gx2 - gx1) * (gy2 - gy1) - inter
+    iou = inter / (union + eps)
+    cw = torch.maximum(px2, gx2) - torch.minimum(px1, gx1)
+    ch = torch.maximum(py2, gy2) - torch.minimum(py1, gy1)
+    if mode == "giou":
+        area = cw * ch
+        return (1 - iou) + (area - union) / (area + eps)
+    rho2 = ((px1 + px2) / 2 - (gx1 + gx2) / 2) ** 2 + ((py1 + py2) / 2 - (gy1 + gy2) / 2) ** 2
+    pen = rho2 / ((cw * cw + ch * ch) + eps)
+    if mode == "ciou":
+        v = (4 / math.pi ** 2) * (torch.atan((gx2 - gx1) / ((gy2 - gy1) + eps))
+                                  - torch.atan((px2 - px1) / ((py2 - py1) + eps))) ** 2
+        alpha = (v / (((1 - iou) + v) + eps)).detach()
+        pen = pen + alpha * v
+    return (1 - iou) + pen
+
+
+def detection_loss_host(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, loss_ratio: float,
+                        cls_loss: str = "ce", focal_gamma: float = 2.0, box_loss: str = "l1",
+                        box_loss_weight: float = 1.0, valid: Optional[torch.Tensor] = None):
+    """The selectable detection loss (``functional.detection_loss_ext`` / ``detection_loss_steps_ext``) as a plain torch
+    expression in the dtype of its operands: predictions ``[..., A, C+1]`` / ``[..., A, 4]``, ``anchors[A,4]``, ``valid``
+    a boolean per frame (the valid slots; None: every frame).  -> ``(classification term, box term)``; the loss is their
+    sum.  Means run over ``max(n, 1)`` rows; no valid frame gives zeros."""
+    A, C = anchors.shape[0], cls_preds.shape[-1]
+    x, bb = cls_preds.reshape(-1, A, C), bbox_preds.reshape(-1, A, 4)
+    off, msk, y = bbox_offset.reshape(-1, A, 4), bbox_mask.reshape(-1, A, 4), class_labels.reshape(-1, A)
+    if valid is not None:
+        keep = valid.reshape(-1).bool()
+        x, bb, off, msk, y = x[keep], bb[keep], off[keep], msk[keep], y[keep]
+    V = x.shape[0]
+    if V == 0:
+        zero = cls_preds.sum() * 0
+        return zero, zero
+    x, bb, off, msk, y = x.reshape(-1, C), bb.reshape(-1, 4), off.reshape(-1, 4), msk.reshape(-1, 4), y.reshape(-1)
+    ce = F.cross_entropy(x, y, reduction="none")
+    if cls_loss == "focal":
+        p_y = F.softmax(x, dim=1).gather(1, y[:, None])[:, 0]
+        ce = (1 - p_y) ** focal_gamma * ce
+    pos = y > 0
+    n_pos, n_neg = max(int(pos.sum()), 1), max(int((~pos).sum()), 1)
+    cls = (ce[pos].sum() / n_pos) * loss_ratio + (ce[~pos].sum() / n_neg) * (1 - loss_ratio)
+    if box_loss == "l1":
+        return cls, F.l1_loss(bb * msk, off * msk) * box_loss_weight
+    rows = pos & (msk == 1).all(dim=1)
+    anc = anchors.repeat(V, 1)[rows]
+    per_row = iou_box_loss(_decode_corners(anc, bb[rows]), _decode_corners(anc, off[rows]), box_loss)
+    return cls, (per_row.sum() / n_pos) * box_loss_weight
 
 
 class SODa(nn.Module):
@@ -46,14 +121,28 @@ class SODa(nn.Module):
         init_weights: bool = True,
         plotter=None,
         label_steps: Optional[int] = None,
+        cls_loss: str = "ce",
+        focal_gamma: float = 2.0,
+        box_loss: str = "l1",
+        box_loss_weight: float = 1.0,
     ):
         super().__init__()
         if label_steps is not None and not 1 <= int(label_steps) <= 32:
             raise ValueError(f"label_steps must be None or in 1 .. 32, got {label_steps}")
+        if cls_loss not in LOSS_CLS_NAMES:
+            raise ValueError(f"cls_loss must be one of {LOSS_CLS_NAMES}, got {cls_loss!r}")
+        if box_loss not in LOSS_BOX_NAMES:
+            raise ValueError(f"box_loss must be one of {LOSS_BOX_NAMES}, got {box_loss!r}")
+        if not float(focal_gamma) >= 0.0:
+            raise ValueError(f"focal_gamma must be >= 0, got {focal_gamma}")
+        if not float(box_loss_weight) >= 0.0:
+            raise ValueError(f"box_loss_weight must be >= 0, got {box_loss_weight}")
         self.hparams = SimpleNamespace(
             num_classes=num_classes, loss_ratio=loss_ratio, time_window=time_window,
             iou_threshold=iou_threshold, learning_rate=learning_rate, state_storage=state_storage,
             init_weights=init_weights, label_steps=None if label_steps is None else int(label_steps),
+            cls_loss=cls_loss, focal_gamma=float(focal_gamma), box_loss=box_loss,
+            box_loss_weight=float(box_loss_weight),
         )
         self.plotter = plotter
         self.logged = {}
@@ -61,6 +150,7 @@ class SODa(nn.Module):
         # set by trainer.FlatTrainer.attach(): called in the backward pass when it crosses the backbone / neck boundary
         # (every neck and head gradient is complete or enqueued there) to start their all-reduce early
         self._snn_neck_grads_ready = None
+        self._loss_terms = None   # (classification term, box term) of the last loss under a selected objective
 
         self.base_net = BackboneGen(self.backbone_cfgs, in_channels=2, init_weights=self.hparams.init_weights)
         self.neck_net = NeckGen(self.neck_cfgs, self.base_net.out_channels, init_weights=self.hparams.init_weights)
@@ -147,6 +237,24 @@ class SODa(nn.Module):
         preds = self.forward(X)
         return self._loss(preds, labels)
 
+    def _default_loss(self) -> bool:
+        """The reference's objective (cross entropy + L1): the steps then call exactly ``detection_loss`` /
+        ``detection_loss_steps`` and log the reference's keys."""
+        return self.hparams.cls_loss == "ce" and self.hparams.box_loss == "l1" and self.hparams.box_loss_weight == 1.0
+
+    def _loss_options(self) -> dict:
+        hp = self.hparams
+        return dict(cls_loss=hp.cls_loss, focal_gamma=hp.focal_gamma, box_loss=hp.box_loss,
+                    box_loss_weight=hp.box_loss_weight)
+
+    def _log_loss(self, stage: str, loss: torch.Tensor, batch) -> None:
+        """``<stage>_loss`` as the reference logs it; with a selected objective also its two terms (device scalars)."""
+        kw = {"prog_bar": True} if stage == "train" else {}
+        self.log(f"{stage}_loss", loss, batch_size=batch[0].shape[1], sync_dist=True, **kw)
+        if self._loss_terms is not None:
+            self.log(f"{stage}_loss_cls", self._loss_terms[0], batch_size=batch[0].shape[1], sync_dist=True)
+            self.log(f"{stage}_loss_box", self._loss_terms[1], batch_size=batch[0].shape[1], sync_dist=True)
+
     def _step_labelled_frames(self, batch: Tuple[torch.Tensor, torch.Tensor]):
         """Six-column labels ``(ts, class, x1, y1, x2, y2)``: the loss over every labelled frame the ``label_steps`` slots
         hold.  The random prefix ``t0`` is cut from the frames and subtracted from the rows' timesteps alike; the frames
@@ -169,8 +277,13 @@ class SODa(nn.Module):
         preds, _ = self._forward_impl(X, None, steps=steps)
         anchors, cls_preds, bbox_preds = preds
         bbox_offset, bbox_mask, class_labels = self.roi_blk.steps(anchors, labels, steps, t0)
-        loss = HF.detection_loss_steps(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, steps,
-                                       self.hparams.loss_ratio)
+        if self._default_loss():
+            loss = HF.detection_loss_steps(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, steps,
+                                           self.hparams.loss_ratio)
+        else:
+            loss, *self._loss_terms = HF.detection_loss_steps_ext(
+                cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, self.hparams.loss_ratio,
+                return_terms=True, **self._loss_options())
         return loss, preds, steps, t0
 
     def _eval_labelled_frames(self, batch: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
@@ -195,17 +308,17 @@ class SODa(nn.Module):
 
     def training_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
         loss = self._step(batch)
-        self.log("train_loss", loss, prog_bar=True, batch_size=batch[0].shape[1], sync_dist=True)
+        self._log_loss("train", loss, batch)
         return loss
 
     def validation_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
         if batch[1].shape[-1] == 6:
             loss = self._eval_labelled_frames(batch)
-            self.log("val_loss", loss, batch_size=batch[0].shape[1], sync_dist=True)
+            self._log_loss("val", loss, batch)
             return loss
         preds = self.forward(batch[0][self._rand_start_time():])
         loss = self._loss(preds, batch[1])
-        self.log("val_loss", loss, batch_size=batch[0].shape[1], sync_dist=True)
+        self._log_loss("val", loss, batch)
         self._map_estimate(preds, batch[1])
         return loss
 
@@ -215,11 +328,11 @@ class SODa(nn.Module):
     def test_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
         if batch[1].shape[-1] == 6:
             loss = self._eval_labelled_frames(batch)
-            self.log("test_loss", loss, batch_size=batch[0].shape[1], sync_dist=True)
+            self._log_loss("test", loss, batch)
             return loss
         preds = self.forward(batch[0][self._rand_start_time():])
         loss = self._loss(preds, batch[1])
-        self.log("test_loss", loss, batch_size=batch[0].shape[1], sync_dist=True)
+        self._log_loss("test", loss, batch)
         self._map_estimate(preds, batch[1])
         return loss
 
@@ -294,6 +407,17 @@ class SODa(nn.Module):
         # soda.py:259-281
         anchors, cls_preds, bbox_preds = preds
         bbox_offset, bbox_mask, class_labels = self.roi_blk(anchors, labels)
+        if not self._default_loss():
+            if cls_preds.is_cuda:   # the same launches from csrc/det_loss_ext.hip
+                from . import functional as HF
+                loss, *self._loss_terms = HF.detection_loss_ext(
+                    cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, self.hparams.loss_ratio,
+                    return_terms=True, **self._loss_options())
+                return loss
+            t_cls, t_box = detection_loss_host(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors,
+                                               self.hparams.loss_ratio, **self._loss_options())
+            self._loss_terms = [t_cls.detach(), t_box.detach()]
+            return t_cls + t_box
         if cls_preds.is_cuda:
             # one launch for the anchor targets (RoI above), two for the loss, one for its gradient (csrc/targets.hip)
             from . import functional as HF

@@ -26,6 +26,10 @@ def main():
     ap.add_argument("--num-steps", type=int, default=42)
     ap.add_argument("--augment", action="store_true")
     ap.add_argument("--label-steps", type=int, default=None, metavar="K")
+    ap.add_argument("--cls-loss", default="ce", choices=("ce", "focal"))
+    ap.add_argument("--focal-gamma", type=float, default=2.0)
+    ap.add_argument("--box-loss", default="l1", choices=("l1", "giou", "diou", "ciou"))
+    ap.add_argument("--box-loss-weight", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
 
@@ -33,7 +37,9 @@ def main():
     feed = S.PropheseeFeed(args.data_dir, dataset=args.dataset, split="train", batch_size=args.batch_size,
                            num_steps=args.num_steps, one_label=args.label_steps is None, seed=args.seed, augment=augment)
     torch.manual_seed(args.seed)
-    model = S.TinyYolo(num_classes=len(feed.get_labels()), label_steps=args.label_steps).cuda().train()
+    model = S.TinyYolo(num_classes=len(feed.get_labels()), label_steps=args.label_steps, cls_loss=args.cls_loss,
+                       focal_gamma=args.focal_gamma, box_loss=args.box_loss,
+                       box_loss_weight=args.box_loss_weight).cuda().train()
     trainer = FlatTrainer(model)
     batch = next(feed)
     for step in range(args.steps):
