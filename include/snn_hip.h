@@ -797,7 +797,9 @@ int snn_roi_assign(const float* anchors, const float* labels, int B, int A, int 
  *   loss = loss_ratio * mean(CE[label > 0]) + (1 - loss_ratio) * mean(CE[label == 0]) + mean |bbox*mask - offset*mask|
  * fwd writes the scalar loss and stats[5] = {sum CE pos, #pos, sum CE neg, #neg, sum L1} (fp64, kept for bwd);
  * bwd writes d loss / d logits [rows][K] and d loss / d bbox [rows][4], scaled by the device scalar *g_loss.
- * workspace: snn_det_loss_workspace_size(rows) bytes. */
+ * The kernels are those of snn_det_loss_ext_* below with SNN_LOSS_CLS_CE, SNN_LOSS_BOX_L1, box_weight 1, A = 1 and no
+ * steps, except that the two means divide by #pos / #neg as they are: an empty class gives NaN, as the reference's
+ * ce[pos].mean().  workspace: snn_det_loss_workspace_size(rows) bytes (= snn_det_loss_ext_workspace_size(rows)). */
 size_t snn_det_loss_workspace_size(int64_t rows);
 int snn_det_loss_fwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset, const float* bbox_mask,
                      const int64_t* class_labels, int64_t rows, int K, float loss_ratio, void* workspace, double* stats,
@@ -840,7 +842,8 @@ int snn_roi_assign_steps(const float* anchors, const float* labels, const int* s
  *   loss = loss_ratio * mean(CE[pos]) + (1 - loss_ratio) * mean(CE[neg]) + sum |bbox*mask - offset*mask| / (4 A V)
  * stats[6] = the five sums of snn_det_loss_fwd and V, counted on the device.  V = 0: loss 0 and zero gradients; V > 0
  * without positives (or negatives): NaN, as snn_det_loss_fwd.  bwd writes all K*B*A rows, exact zeros for empty slots.
- * workspace: snn_det_loss_steps_workspace_size(K, B, A) bytes. */
+ * The kernels of snn_det_loss_ext_* with the same fixed modes, this A and steps, and the same means as they are.
+ * workspace: snn_det_loss_steps_workspace_size(K, B, A) bytes (= snn_det_loss_ext_workspace_size(K * B * A)). */
 size_t snn_det_loss_steps_workspace_size(int K, int B, int A);
 int snn_det_loss_steps_fwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
                            const float* bbox_mask, const int64_t* class_labels, const int* steps, int K, int B, int A,
@@ -850,7 +853,8 @@ int snn_det_loss_steps_bwd(const float* cls_logits, const float* bbox_preds, con
                            int C, float loss_ratio, const double* stats, const float* g_loss, float* g_logits,
                            float* g_bbox, void* stream);
 
-/* ---- Selectable detection loss (new symbols under ABI v20; snn_det_loss_* above are unchanged).  The same rows, with
+/* ---- Selectable detection loss (new symbols under ABI v20; one kernel family serves these and snn_det_loss_* above,
+ * whose signatures and conventions are unchanged).  The same rows, with
  * anchors [A][4] corner boxes (row r uses anchor r % A; rows is a multiple of A) and steps [rows / A] int32 or NULL:
  * with steps, the rows of a frame with steps[frame] < 0 are left out of every sum and get exact zeros as gradients, and
  * V counts the other frames on the device; without, V = rows / A.

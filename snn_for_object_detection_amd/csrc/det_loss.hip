@@ -1,14 +1,19 @@
-// The selectable detection loss ("Selectable detection loss"): the structure of snn_det_loss_* of
-// targets.hip - one thread per anchor row, fp32 per-row arithmetic, fp64 block and grid sums in a fixed order - with a
-// choice of the classification term (cross entropy | focal) and of the box term (L1 | GIoU | DIoU | CIoU).
+// The detection loss: one kernel family behind the nine snn_det_loss* entry points - one thread per
+// anchor row, fp32 per-row arithmetic, fp64 block and grid sums in a fixed order - with a choice of the classification
+// term (cross entropy | focal) and of the box term (L1 | GIoU | DIoU | CIoU).
 //
-//   cls  = ratio * sum_pos f / max(n_pos, 1) + (1 - ratio) * sum_neg f / max(n_neg, 1)
+//   cls  = ratio * sum_pos f / n_pos + (1 - ratio) * sum_neg f / n_neg
 //          f = ce (cross entropy) or (1 - p_y)^gamma * ce (focal), ce = -log softmax(x)[y], pos: class > 0
-//   box  = box_weight * sum |bbox m - off m| / (4 A V)                                   (L1, the term of snn_det_loss_*)
+//   box  = box_weight * sum |bbox m - off m| / (4 A V)                                   (L1)
 //        = box_weight * sum over box rows (1 - IoU + penalty) / max(n_pos, 1)            (GIoU, DIoU, CIoU)
 //          box rows: class > 0 and all four mask entries 1; the boxes are offset_inverse(anchor[r % A], .) of the
 //          predicted and of the target offsets, the exponent argument clamped above at log(1000 / 16)
 //   loss = cls + box
+//
+// The means of cls come in two conventions.  snn_det_loss_fwd and snn_det_loss_steps_fwd (cross entropy, L1, weight 1:
+// SODa._loss, models/soda.py:259-281) divide by n_pos / n_neg as they are - an empty class gives NaN, as the reference's
+// ce[pos].mean() does; snn_det_loss_ext_fwd divides by max(n, 1) and gives 0.  The gradients do not differ: the weight of
+// an empty class multiplies no row.
 //
 // V = the frames that take part (rows / A, or the valid slots of steps[], counted on the device); rows of an empty slot
 // are left out of every sum and get exact zeros as gradients.  Nothing here synchronises with the host or allocates.
@@ -16,22 +21,22 @@
 
 namespace {
 
-constexpr int kExtThreads = 256;
-constexpr int kExtMaxBlocks = 1024;
-constexpr int kExtMaxClasses = 64;     // kMaxClasses of targets.hip
-constexpr int kExtMaxSlots = 1 << 20;  // frames (rows / A) the finalisation counts
+constexpr int kLossThreads = 256;
+constexpr int kLossMaxBlocks = 1024;
+constexpr int kMaxClasses = 64;
+constexpr int kMaxFrames = 1 << 20;    // frames (rows / A) snn_det_loss_ext_* take
 constexpr float kExpClamp = 4.135166556742356f;   // log(1000 / 16): a decoded side is at most 62.5 anchor sides
 constexpr float kIouEps = 1e-7f;
 constexpr float kFourOverPiSq = 0.4052847345693511f;
 
-__device__ __forceinline__ double ext_block_sum(double v, double* scratch) {  // all threads get the sum
+__device__ __forceinline__ double block_sum(double v, double* scratch) {  // all threads get the sum
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
     __syncthreads();
     double s = 0.0;
-    for (int k = 0; k < kExtThreads / 64; ++k) s += scratch[k];
+    for (int k = 0; k < kLossThreads / 64; ++k) s += scratch[k];
     return s;
 }
 
@@ -49,7 +54,9 @@ __device__ __forceinline__ Softmax row_softmax(const float* __restrict__ x, int 
         s.se += e;
         if (k != y) s.so += e;
     }
-    s.ce = logf(s.se) - (x[y] - s.mx);   // as k_det_loss_partial forms it
+    // -log_softmax(x)[y] as torch forms it, log(se) - (x[y] - mx): two terms >= 0.  (mx + log(se)) - x[y] rounds at the
+    // size of mx and loses the loss of a well-classified row with large logits.
+    s.ce = logf(s.se) - (x[y] - s.mx);
     return s;
 }
 
@@ -152,14 +159,14 @@ __device__ __forceinline__ float iou_loss(int mode, const float4 anc, const floa
     return (1.0f - iou) + pen;
 }
 
-struct ExtArgs {
+struct LossArgs {
     const float* logits;
     const float* bbox;
     const float* offset;
     const float* mask;
     const int64_t* cls;
-    const float* anchors;
-    const int* steps;     // [rows / A], nullptr: every frame takes part
+    const float* anchors;   // [A][4], read by the IoU box modes only
+    const int* steps;       // [rows / A], nullptr: every frame takes part
     int64_t R;
     int A, K;
     float ratio;
@@ -171,10 +178,10 @@ struct ExtArgs {
 
 // partial[block][5] = {sum f over positives, positives, sum f over negatives, negatives, box sum}
 template <bool kSteps>
-__global__ __launch_bounds__(kExtThreads) void k_det_loss_ext_partial(const ExtArgs a, double* __restrict__ partial) {
-    __shared__ double scratch[kExtThreads / 64];
+__global__ __launch_bounds__(kLossThreads) void k_det_loss_partial(const LossArgs a, double* __restrict__ partial) {
+    __shared__ double scratch[kLossThreads / 64];
     double s_pos = 0, n_pos = 0, s_neg = 0, n_neg = 0, s_box = 0;
-    for (int64_t r = (int64_t)blockIdx.x * kExtThreads + threadIdx.x; r < a.R; r += (int64_t)gridDim.x * kExtThreads) {
+    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < a.R; r += (int64_t)gridDim.x * kLossThreads) {
         if (kSteps && a.steps[r / a.A] < 0) continue;
         const int64_t y = a.cls[r];
         const Softmax s = row_softmax(a.logits + r * a.K, a.K, y);
@@ -198,29 +205,31 @@ __global__ __launch_bounds__(kExtThreads) void k_det_loss_ext_partial(const ExtA
             s_box += iou_loss<false>(a.box_mode, anc, bb, of, nullptr);
         }
     }
-    const double t0 = ext_block_sum(s_pos, scratch), t1 = ext_block_sum(n_pos, scratch);
-    const double t2 = ext_block_sum(s_neg, scratch), t3 = ext_block_sum(n_neg, scratch);
-    const double t4 = ext_block_sum(s_box, scratch);
+    const double t0 = block_sum(s_pos, scratch), t1 = block_sum(n_pos, scratch);
+    const double t2 = block_sum(s_neg, scratch), t3 = block_sum(n_neg, scratch);
+    const double t4 = block_sum(s_box, scratch);
     if (threadIdx.x == 0) {
         double* p = partial + (int64_t)blockIdx.x * 5;
         p[0] = t0; p[1] = t1; p[2] = t2; p[3] = t3; p[4] = t4;
     }
 }
 
-// stats[9] = the five totals (fixed order: reproducible), V, and the three terms of the loss: ratio * mean over the
-// positives, (1 - ratio) * mean over the negatives, the box term.  loss = (the first + the second) + the third.
-__global__ __launch_bounds__(64) void k_det_loss_ext_final(const double* __restrict__ partial, int nblocks,
-                                                           const int* __restrict__ steps, int slots, int A, float ratio,
-                                                           int box_mode, float box_weight, double* __restrict__ stats,
-                                                           float* __restrict__ loss) {
+// stats[n_stats], n_stats = 5, 6 or 9: the five totals (fixed order: reproducible), then V, then the three terms of the
+// loss: ratio * mean over the positives, (1 - ratio) * mean over the negatives, the box term.  loss = (the first + the
+// second) + the third.  strict_means: the two means divide by the counts as they are (an empty class: NaN), otherwise
+// by max(count, 1).  frames = rows / A; with steps, V counts the valid ones among them.
+__global__ __launch_bounds__(64) void k_det_loss_final(const double* __restrict__ partial, int nblocks,
+                                                       const int* __restrict__ steps, int64_t frames, int A, float ratio,
+                                                       int box_mode, float box_weight, bool strict_means, int n_stats,
+                                                       double* __restrict__ stats, float* __restrict__ loss) {
     if (blockIdx.x != 0) return;
-    int v = 0;
+    int64_t v = frames;
     if (steps) {
-        for (int i = threadIdx.x; i < slots; i += 64) v += steps[i] >= 0 ? 1 : 0;
+        int c = 0;
+        for (int i = threadIdx.x; i < frames; i += 64) c += steps[i] >= 0 ? 1 : 0;
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    } else {
-        v = slots;
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+        v = c;
     }
     // lane l adds the blocks l, l + 64, ... in that order, then the 64 lane sums meet in a butterfly: a fixed order for a
     // given block count (one thread walking up to 1024 x 5 partials costs more than the partial kernel itself)
@@ -234,32 +243,35 @@ __global__ __launch_bounds__(64) void k_det_loss_ext_final(const double* __restr
     }
     if (threadIdx.x != 0) return;
     for (int k = 0; k < 5; ++k) stats[k] = t[k];
-    stats[5] = (double)v;
     float gt = 0.f, bg = 0.f, bx = 0.f;
     if (v > 0) {
-        gt = (float)(t[0] / fmax(t[1], 1.0)) * ratio;
-        bg = (float)(t[2] / fmax(t[3], 1.0)) * (1 - ratio);
+        gt = (float)(t[0] / (strict_means ? t[1] : fmax(t[1], 1.0))) * ratio;
+        bg = (float)(t[2] / (strict_means ? t[3] : fmax(t[3], 1.0))) * (1 - ratio);
         const double den = box_mode == SNN_LOSS_BOX_L1 ? 4.0 * (double)A * (double)v : fmax(t[1], 1.0);
         bx = (float)(t[4] / den) * box_weight;
     }
-    stats[6] = gt;
-    stats[7] = bg;
-    stats[8] = bx;
+    if (n_stats > 5) stats[5] = (double)v;
+    if (n_stats > 6) {
+        stats[6] = gt;
+        stats[7] = bg;
+        stats[8] = bx;
+    }
     *loss = (gt + bg) + bx;
 }
 
+// Reads the counts stats[1], stats[3] and, with steps, V = stats[5]; without steps V = rows / A.
 template <bool kSteps>
-__global__ __launch_bounds__(kExtThreads) void k_det_loss_ext_bwd(const ExtArgs a, const double* __restrict__ stats,
-                                                                  const float* __restrict__ g_loss,
-                                                                  float* __restrict__ g_logits,
-                                                                  float* __restrict__ g_bbox) {
+__global__ __launch_bounds__(kLossThreads) void k_det_loss_bwd(const LossArgs a, const double* __restrict__ stats,
+                                                               const float* __restrict__ g_loss,
+                                                               float* __restrict__ g_logits, float* __restrict__ g_bbox) {
     const float g = *g_loss;
     const float n_pos = fmaxf((float)stats[1], 1.0f), n_neg = fmaxf((float)stats[3], 1.0f);
     const float w_pos = g * a.ratio / n_pos, w_neg = g * (1 - a.ratio) / n_neg;
-    const float w_box = a.box_mode == SNN_LOSS_BOX_L1 ? g * a.box_weight / (4.0f * (float)((int64_t)a.A * (int64_t)stats[5]))
+    const int64_t v = kSteps ? (int64_t)stats[5] : a.R / a.A;
+    const float w_box = a.box_mode == SNN_LOSS_BOX_L1 ? g * a.box_weight / (4.0f * (float)((int64_t)a.A * v))
                                                       : g * a.box_weight / n_pos;
     const int K = a.K;
-    for (int64_t r = (int64_t)blockIdx.x * kExtThreads + threadIdx.x; r < a.R; r += (int64_t)gridDim.x * kExtThreads) {
+    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < a.R; r += (int64_t)gridDim.x * kLossThreads) {
         if (kSteps && a.steps[r / a.A] < 0) {
             for (int k = 0; k < K; ++k) g_logits[r * K + k] = 0.f;
             *reinterpret_cast<float4*>(g_bbox + r * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -299,22 +311,125 @@ __global__ __launch_bounds__(kExtThreads) void k_det_loss_ext_bwd(const ExtArgs 
     }
 }
 
-int ext_blocks(int64_t R) {   // one row per thread and pass, at most kExtMaxBlocks blocks
-    int64_t b = snn_ceil_div(R, (int64_t)kExtThreads);
-    if (b > kExtMaxBlocks) b = kExtMaxBlocks;
+int ext_blocks(int64_t R) {   // one row per thread and pass, at most kLossMaxBlocks blocks
+    int64_t b = snn_ceil_div(R, (int64_t)kLossThreads);
+    if (b > kLossMaxBlocks) b = kLossMaxBlocks;
     return b < 1 ? 1 : (int)b;
+}
+size_t workspace_size(int64_t rows) { return (size_t)ext_blocks(rows) * 5 * sizeof(double); }
+
+// The launchers every entry point ends in; the arguments have been checked by the caller.  n_stats: the doubles of stats
+// the caller owns (5: the totals; 6: and V; 9: and the three terms).
+int launch_fwd(const char* name, const LossArgs& a, bool strict_means, int n_stats, void* workspace, double* stats,
+               float* loss, void* stream) {
+    const int nb = ext_blocks(a.R);
+    double* partial = static_cast<double*>(workspace);
+    if (a.steps)
+        hipLaunchKernelGGL(k_det_loss_partial<true>, dim3((unsigned)nb), dim3(kLossThreads), 0, (hipStream_t)stream, a,
+                           partial);
+    else
+        hipLaunchKernelGGL(k_det_loss_partial<false>, dim3((unsigned)nb), dim3(kLossThreads), 0, (hipStream_t)stream, a,
+                           partial);
+    hipLaunchKernelGGL(k_det_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partial, nb, a.steps,
+                       a.R / a.A, a.A, a.ratio, a.box_mode, a.box_weight, strict_means, n_stats, stats, loss);
+    SNN_CHECK_LAUNCH(name);
+    return 0;
+}
+
+int launch_bwd(const char* name, const LossArgs& a, const double* stats, const float* g_loss, float* g_logits,
+               float* g_bbox, void* stream) {
+    const int nb = ext_blocks(a.R);
+    if (a.steps)
+        hipLaunchKernelGGL(k_det_loss_bwd<true>, dim3((unsigned)nb), dim3(kLossThreads), 0, (hipStream_t)stream, a, stats,
+                           g_loss, g_logits, g_bbox);
+    else
+        hipLaunchKernelGGL(k_det_loss_bwd<false>, dim3((unsigned)nb), dim3(kLossThreads), 0, (hipStream_t)stream, a, stats,
+                           g_loss, g_logits, g_bbox);
+    SNN_CHECK_LAUNCH(name);
+    return 0;
+}
+
+// SODa._loss: cross entropy, L1, weight 1, no anchors
+LossArgs reference_objective(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                             const float* bbox_mask, const int64_t* class_labels, const int* steps, int64_t rows, int A,
+                             int K, float loss_ratio) {
+    return {cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, nullptr, steps, rows, A, K, loss_ratio,
+            SNN_LOSS_CLS_CE, 0.f, SNN_LOSS_BOX_L1, 1.0f};
 }
 
 }  // namespace
 
-extern "C" size_t snn_det_loss_ext_workspace_size(int64_t rows) { return (size_t)ext_blocks(rows) * 5 * sizeof(double); }
+// ------------------------------------------------------------------------------------------ one frame per row, stats[5]
+extern "C" size_t snn_det_loss_workspace_size(int64_t rows) { return workspace_size(rows); }
 
-// the refusals the forward and the backward share; 0 when the arguments are taken
-static int ext_check(const char* name, const ExtArgs& a) {
+extern "C" int snn_det_loss_fwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                                const float* bbox_mask, const int64_t* class_labels, int64_t rows, int K,
+                                float loss_ratio, void* workspace, double* stats, float* loss, void* stream) {
+    SNN_REQUIRE(cls_logits && bbox_preds && bbox_offset && bbox_mask && class_labels && workspace && stats && loss,
+                "snn_det_loss_fwd: null pointer");
+    SNN_REQUIRE(rows > 0 && K > 1 && K <= kMaxClasses, "snn_det_loss_fwd: bad shape");
+    SNN_REQUIRE(aligned(16, {bbox_preds, bbox_offset, bbox_mask}), "snn_det_loss_fwd: box tensors must be 16-byte aligned");
+    return launch_fwd("snn_det_loss_fwd",
+                      reference_objective(cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, nullptr, rows, 1,
+                                          K, loss_ratio), true, 5, workspace, stats, loss, stream);
+}
+
+extern "C" int snn_det_loss_bwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                                const float* bbox_mask, const int64_t* class_labels, int64_t rows, int K,
+                                float loss_ratio, const double* stats, const float* g_loss, float* g_logits,
+                                float* g_bbox, void* stream) {
+    SNN_REQUIRE(cls_logits && bbox_preds && bbox_offset && bbox_mask && class_labels && stats && g_loss && g_logits &&
+                    g_bbox, "snn_det_loss_bwd: null pointer");
+    SNN_REQUIRE(rows > 0 && K > 1 && K <= kMaxClasses, "snn_det_loss_bwd: bad shape");
+    SNN_REQUIRE(aligned(16, {bbox_preds, bbox_offset, bbox_mask, g_bbox}),
+                "snn_det_loss_bwd: box tensors must be 16-byte aligned");
+    return launch_bwd("snn_det_loss_bwd",
+                      reference_objective(cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, nullptr, rows, 1,
+                                          K, loss_ratio), stats, g_loss, g_logits, g_bbox, stream);
+}
+
+// ------------------------------------------------------------------------------------------ K x B slots, stats[6]
+extern "C" size_t snn_det_loss_steps_workspace_size(int K, int B, int A) { return workspace_size((int64_t)K * B * A); }
+
+extern "C" int snn_det_loss_steps_fwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                                      const float* bbox_mask, const int64_t* class_labels, const int* steps, int K, int B,
+                                      int A, int C, float loss_ratio, void* workspace, double* stats, float* loss,
+                                      void* stream) {
+    SNN_REQUIRE(cls_logits && bbox_preds && bbox_offset && bbox_mask && class_labels && steps && workspace && stats &&
+                    loss, "snn_det_loss_steps_fwd: null pointer");
+    SNN_REQUIRE(B > 0 && A > 0 && C > 1 && C <= kMaxClasses, "snn_det_loss_steps_fwd: bad shape");
+    SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps, "snn_det_loss_steps_fwd: K must be in 1 .. %d", kMaxLabelSteps);
+    SNN_REQUIRE(aligned(16, {bbox_preds, bbox_offset, bbox_mask}),
+                "snn_det_loss_steps_fwd: box tensors must be 16-byte aligned");
+    return launch_fwd("snn_det_loss_steps_fwd",
+                      reference_objective(cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, steps,
+                                          (int64_t)K * B * A, A, C, loss_ratio), true, 6, workspace, stats, loss, stream);
+}
+
+extern "C" int snn_det_loss_steps_bwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
+                                      const float* bbox_mask, const int64_t* class_labels, const int* steps, int K, int B,
+                                      int A, int C, float loss_ratio, const double* stats, const float* g_loss,
+                                      float* g_logits, float* g_bbox, void* stream) {
+    SNN_REQUIRE(cls_logits && bbox_preds && bbox_offset && bbox_mask && class_labels && steps && stats && g_loss &&
+                    g_logits && g_bbox, "snn_det_loss_steps_bwd: null pointer");
+    SNN_REQUIRE(B > 0 && A > 0 && C > 1 && C <= kMaxClasses, "snn_det_loss_steps_bwd: bad shape");
+    SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps, "snn_det_loss_steps_bwd: K must be in 1 .. %d", kMaxLabelSteps);
+    SNN_REQUIRE(aligned(16, {bbox_preds, bbox_offset, bbox_mask, g_bbox}),
+                "snn_det_loss_steps_bwd: box tensors must be 16-byte aligned");
+    return launch_bwd("snn_det_loss_steps_bwd",
+                      reference_objective(cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, steps,
+                                          (int64_t)K * B * A, A, C, loss_ratio), stats, g_loss, g_logits, g_bbox, stream);
+}
+
+// ------------------------------------------------------------------------------------------ selectable, stats[9]
+extern "C" size_t snn_det_loss_ext_workspace_size(int64_t rows) { return workspace_size(rows); }
+
+// the refusals the forward and the backward of snn_det_loss_ext_* share; 0 when the arguments are taken
+static int ext_check(const char* name, const LossArgs& a) {
     SNN_REQUIRE(a.logits && a.bbox && a.offset && a.mask && a.cls && a.anchors, "%s: null pointer", name);
-    SNN_REQUIRE(a.K >= 1 && a.K <= kExtMaxClasses, "%s: K must be in 1 .. %d", name, kExtMaxClasses);
-    SNN_REQUIRE(a.A > 0 && a.R > 0 && a.R % a.A == 0 && a.R / a.A <= kExtMaxSlots,
-                "%s: rows must be a positive multiple of A (at most %d frames)", name, kExtMaxSlots);
+    SNN_REQUIRE(a.K >= 1 && a.K <= kMaxClasses, "%s: K must be in 1 .. %d", name, kMaxClasses);
+    SNN_REQUIRE(a.A > 0 && a.R > 0 && a.R % a.A == 0 && a.R / a.A <= kMaxFrames,
+                "%s: rows must be a positive multiple of A (at most %d frames)", name, kMaxFrames);
     SNN_REQUIRE(a.cls_mode == SNN_LOSS_CLS_CE || a.cls_mode == SNN_LOSS_CLS_FOCAL, "%s: unknown cls_mode %d", name,
                 a.cls_mode);
     SNN_REQUIRE(a.box_mode == SNN_LOSS_BOX_L1 || a.box_mode == SNN_LOSS_BOX_GIOU || a.box_mode == SNN_LOSS_BOX_DIOU ||
@@ -330,22 +445,11 @@ extern "C" int snn_det_loss_ext_fwd(const float* cls_logits, const float* bbox_p
                                     const int* steps, int64_t rows, int A, int K, float loss_ratio, int cls_mode,
                                     float gamma, int box_mode, float box_weight, void* workspace, double* stats,
                                     float* loss, void* stream) {
-    const ExtArgs a = {cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, rows, A, K,
-                       loss_ratio, cls_mode, gamma, box_mode, box_weight};
+    const LossArgs a = {cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, rows, A, K,
+                        loss_ratio, cls_mode, gamma, box_mode, box_weight};
     if (int rc = ext_check("snn_det_loss_ext_fwd", a)) return rc;
     SNN_REQUIRE(workspace && stats && loss, "snn_det_loss_ext_fwd: null pointer");
-    const int nb = ext_blocks(rows);
-    double* partial = static_cast<double*>(workspace);
-    if (steps)
-        hipLaunchKernelGGL(k_det_loss_ext_partial<true>, dim3((unsigned)nb), dim3(kExtThreads), 0, (hipStream_t)stream, a,
-                           partial);
-    else
-        hipLaunchKernelGGL(k_det_loss_ext_partial<false>, dim3((unsigned)nb), dim3(kExtThreads), 0, (hipStream_t)stream,
-                           a, partial);
-    hipLaunchKernelGGL(k_det_loss_ext_final, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partial, nb, steps,
-                       (int)(rows / A), A, loss_ratio, box_mode, box_weight, stats, loss);
-    SNN_CHECK_LAUNCH("snn_det_loss_ext_fwd");
-    return 0;
+    return launch_fwd("snn_det_loss_ext_fwd", a, false, 9, workspace, stats, loss, stream);
 }
 
 extern "C" int snn_det_loss_ext_bwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
@@ -353,18 +457,10 @@ extern "C" int snn_det_loss_ext_bwd(const float* cls_logits, const float* bbox_p
                                     const int* steps, int64_t rows, int A, int K, float loss_ratio, int cls_mode,
                                     float gamma, int box_mode, float box_weight, const double* stats,
                                     const float* g_loss, float* g_logits, float* g_bbox, void* stream) {
-    const ExtArgs a = {cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, rows, A, K,
-                       loss_ratio, cls_mode, gamma, box_mode, box_weight};
+    const LossArgs a = {cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, rows, A, K,
+                        loss_ratio, cls_mode, gamma, box_mode, box_weight};
     if (int rc = ext_check("snn_det_loss_ext_bwd", a)) return rc;
     SNN_REQUIRE(stats && g_loss && g_logits && g_bbox, "snn_det_loss_ext_bwd: null pointer");
     SNN_REQUIRE(aligned(16, {g_bbox}), "snn_det_loss_ext_bwd: g_bbox must be 16-byte aligned");
-    const int nb = ext_blocks(rows);
-    if (steps)
-        hipLaunchKernelGGL(k_det_loss_ext_bwd<true>, dim3((unsigned)nb), dim3(kExtThreads), 0, (hipStream_t)stream, a,
-                           stats, g_loss, g_logits, g_bbox);
-    else
-        hipLaunchKernelGGL(k_det_loss_ext_bwd<false>, dim3((unsigned)nb), dim3(kExtThreads), 0, (hipStream_t)stream, a,
-                           stats, g_loss, g_logits, g_bbox);
-    SNN_CHECK_LAUNCH("snn_det_loss_ext_bwd");
-    return 0;
+    return launch_bwd("snn_det_loss_ext_bwd", a, stats, g_loss, g_logits, g_bbox, stream);
 }

@@ -46,6 +46,8 @@ static inline int snn_num_cu() {
 }
 static inline int snn_max_blocks() { return snn_num_cu() * 8; }
 
+constexpr int kMaxLabelSteps = 32;   // frame slots per sample (K) of the *_steps entry points (targets.hip, det_loss.hip)
+
 // every pointer of the list (NULL counts as aligned) on a `bytes` boundary / every value a multiple of n
 static bool aligned(size_t bytes, std::initializer_list<const void*> ptrs) {
     uintptr_t bits = 0;

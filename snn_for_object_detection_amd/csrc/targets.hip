@@ -1,21 +1,18 @@
-// Training targets and the detection loss on the device: the step after the network.
+// Training targets on the device: the step after the network, before the loss (det_loss.hip).
 //
 //   snn_roi_assign : anchor <-> ground-truth assignment + offset / mask / class targets of one batch
 //                    (utils/roi.py:18-109, utils/box.py:31-69) - one block per sample instead of ~150 tiny tensor
 //                    launches per sample and a Python loop over the ground-truth rows;
-//   snn_det_loss_fwd / _bwd : loss_ratio * mean(CE[positive]) + (1 - loss_ratio) * mean(CE[negative]) +
-//                    mean(L1(bbox * mask, offset * mask)) and its gradient (models/soda.py:259-281).
+//   snn_label_steps, snn_gather_steps_*, snn_roi_assign_steps : the same for every labelled timestep of a sequence.
 //
 // Arithmetic follows the reference expression by expression in fp32 (-ffp-contract=off), so the assignment (an
 // integer result) is the reference's: first maximum wins in the per-anchor max and in the global argmax, padding rows
-// (-1) of the label tensor take part in the greedy phase exactly as they do upstream (SURVEY a-11).  The loss sums are
-// accumulated in fp64 (torch: fp32 pairwise sums) - a 1e-7 relative difference.
+// (-1) of the label tensor take part in the greedy phase exactly as they do upstream (SURVEY a-11).
 #include "snn_common.h"
 
 namespace {
 
 constexpr int kRoiThreads = 1024;
-constexpr int kMaxLabelSteps = 32;   // frame slots per sample (K) of the *_steps entry points
 
 struct ArgMax {
     float v;
@@ -197,145 +194,6 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_assign_steps(const float* _
                       mask, cls, row0);
 }
 
-// ------------------------------------------------------------------------------------------ loss
-constexpr int kLossThreads = 256;
-constexpr int kMaxClasses = 64;
-
-__device__ __forceinline__ double block_sum(double v, double* scratch) {  // all threads get the sum
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int k = 0; k < kLossThreads / 64; ++k) s += scratch[k];
-    return s;
-}
-
-// partial[block][5] = {sum CE over positives, positives, sum CE over negatives, negatives, sum |bbox*m - off*m|}
-// kSteps: the rows are [slots][A] and those of an empty slot (steps[slot] < 0) are left out of every sum.
-template <bool kSteps>
-__global__ __launch_bounds__(kLossThreads) void k_det_loss_partial(const float* __restrict__ logits,
-                                                                   const float* __restrict__ bbox,
-                                                                   const float* __restrict__ offset,
-                                                                   const float* __restrict__ mask,
-                                                                   const int64_t* __restrict__ cls, int64_t R, int K,
-                                                                   const int* __restrict__ steps, int A,
-                                                                   double* __restrict__ partial) {
-    __shared__ double scratch[kLossThreads / 64];
-    double s_pos = 0, n_pos = 0, s_neg = 0, n_neg = 0, s_l1 = 0;
-    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < R; r += (int64_t)gridDim.x * kLossThreads) {
-        if (kSteps && steps[r / A] < 0) continue;
-        const float* x = logits + r * K;
-        float mx = x[0];
-        for (int k = 1; k < K; ++k) mx = fmaxf(mx, x[k]);
-        float se = 0.f;
-        for (int k = 0; k < K; ++k) se += expf(x[k] - mx);
-        const int64_t y = cls[r];
-        // -log_softmax(x)[y] as torch forms it, log(se) - (x[y] - mx): two terms >= 0.  (mx + log(se)) - x[y] rounds at
-        // the size of mx and loses the loss of a well-classified row with large logits.
-        const float ce = logf(se) - (x[y] - mx);
-        if (y > 0) {
-            s_pos += ce;
-            n_pos += 1;
-        } else {
-            s_neg += ce;
-            n_neg += 1;
-        }
-        const float4 bb = *reinterpret_cast<const float4*>(bbox + r * 4);
-        const float4 of = *reinterpret_cast<const float4*>(offset + r * 4);
-        const float4 mk = *reinterpret_cast<const float4*>(mask + r * 4);
-        s_l1 += (double)fabsf(bb.x * mk.x - of.x * mk.x) + (double)fabsf(bb.y * mk.y - of.y * mk.y) +
-                (double)fabsf(bb.z * mk.z - of.z * mk.z) + (double)fabsf(bb.w * mk.w - of.w * mk.w);
-    }
-    const double a = block_sum(s_pos, scratch), bq = block_sum(n_pos, scratch), c = block_sum(s_neg, scratch);
-    const double d = block_sum(n_neg, scratch), e = block_sum(s_l1, scratch);
-    if (threadIdx.x == 0) {
-        double* p = partial + (int64_t)blockIdx.x * 5;
-        p[0] = a; p[1] = bq; p[2] = c; p[3] = d; p[4] = e;
-    }
-}
-
-// loss = ratio * pos / n_pos + (1 - ratio) * neg / n_neg + l1 / (4 R) of the totals t[5]
-__device__ __forceinline__ float combine_loss(const double* t, int64_t R, float ratio) {
-    const float gt = (float)(t[0] / t[1]), bg = (float)(t[2] / t[3]), l1 = (float)(t[4] / (4.0 * (double)R));
-    return (gt * ratio + bg * (1 - ratio)) + l1;   // soda.py:277-281, same order of the three terms
-}
-
-// stats[5] = totals (block order: reproducible)
-__global__ void k_det_loss_final(const double* __restrict__ partial, int nblocks, int64_t R, float ratio,
-                                 double* __restrict__ stats, float* __restrict__ loss) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double t[5] = {0, 0, 0, 0, 0};
-    for (int b = 0; b < nblocks; ++b)
-        for (int k = 0; k < 5; ++k) t[k] += partial[(int64_t)b * 5 + k];
-    for (int k = 0; k < 5; ++k) stats[k] = t[k];
-    *loss = combine_loss(t, R, ratio);
-}
-
-// The same over the anchors of the V valid slots: stats[5] = V, counted here; R = A * V rows; no valid slot: loss 0.
-__global__ void k_det_loss_steps_final(const double* __restrict__ partial, int nblocks, const int* __restrict__ steps,
-                                       int slots, int A, float ratio, double* __restrict__ stats,
-                                       float* __restrict__ loss) {
-    if (blockIdx.x != 0) return;
-    int v = 0;
-    for (int i = threadIdx.x; i < slots; i += 64) v += steps[i] >= 0 ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (threadIdx.x != 0) return;
-    double t[5] = {0, 0, 0, 0, 0};
-    for (int b = 0; b < nblocks; ++b)
-        for (int k = 0; k < 5; ++k) t[k] += partial[(int64_t)b * 5 + k];
-    for (int k = 0; k < 5; ++k) stats[k] = t[k];
-    stats[5] = (double)v;
-    *loss = v > 0 ? combine_loss(t, (int64_t)A * v, ratio) : 0.0f;
-}
-
-// kSteps: rows [slots][A]; R = A * V with V = stats[5]; the rows of an empty slot get exact zeros.
-template <bool kSteps>
-__global__ __launch_bounds__(kLossThreads) void k_det_loss_bwd(const float* __restrict__ logits,
-                                                               const float* __restrict__ bbox,
-                                                               const float* __restrict__ offset,
-                                                               const float* __restrict__ mask,
-                                                               const int64_t* __restrict__ cls, int64_t R, int K,
-                                                               const double* __restrict__ stats, float ratio,
-                                                               const float* __restrict__ g_loss,
-                                                               const int* __restrict__ steps, int A,
-                                                               float* __restrict__ g_logits, float* __restrict__ g_bbox) {
-    const float g = *g_loss;
-    const float w_pos = g * ratio / (float)stats[1], w_neg = g * (1 - ratio) / (float)stats[3];
-    const int64_t rows_in = kSteps ? (int64_t)A * (int64_t)stats[5] : R;
-    const float w_l1 = g / (4.0f * (float)rows_in);
-    for (int64_t r = (int64_t)blockIdx.x * kLossThreads + threadIdx.x; r < R; r += (int64_t)gridDim.x * kLossThreads) {
-        if (kSteps && steps[r / A] < 0) {
-            for (int k = 0; k < K; ++k) g_logits[r * K + k] = 0.f;
-            *reinterpret_cast<float4*>(g_bbox + r * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-            continue;
-        }
-        const float* x = logits + r * K;
-        float mx = x[0];
-        for (int k = 1; k < K; ++k) mx = fmaxf(mx, x[k]);
-        float se = 0.f;
-        for (int k = 0; k < K; ++k) se += expf(x[k] - mx);
-        const int64_t y = cls[r];
-        const float w = y > 0 ? w_pos : w_neg;
-        for (int k = 0; k < K; ++k) {
-            const float p = expf(x[k] - mx) / se;
-            g_logits[r * K + k] = w * (p - (k == y ? 1.0f : 0.0f));
-        }
-        const float4 bb = *reinterpret_cast<const float4*>(bbox + r * 4);
-        const float4 of = *reinterpret_cast<const float4*>(offset + r * 4);
-        const float4 mk = *reinterpret_cast<const float4*>(mask + r * 4);
-        auto sgn = [](float v) { return v > 0.f ? 1.0f : (v < 0.f ? -1.0f : 0.0f); };
-        float4 o;
-        o.x = w_l1 * sgn(bb.x * mk.x - of.x * mk.x) * mk.x;
-        o.y = w_l1 * sgn(bb.y * mk.y - of.y * mk.y) * mk.y;
-        o.z = w_l1 * sgn(bb.z * mk.z - of.z * mk.z) * mk.z;
-        o.w = w_l1 * sgn(bb.w * mk.w - of.w * mk.w) * mk.w;
-        *reinterpret_cast<float4*>(g_bbox + r * 4) = o;
-    }
-}
-
 // ------------------------------------------------------------------------------------------ labelled-frame gather
 // Channels-last frames [T][B][M pixels][C] with pixel strides ld >= C.  An element is one channel (kVec: one channel
 // quad) of one pixel; Cq = elements per pixel.  A step outside [0, T) is an empty slot.
@@ -395,11 +253,6 @@ static int gather_blocks(int64_t total) {
     if (b > cap) b = cap;
     return b < 1 ? 1 : (int)b;
 }
-static int loss_blocks(int64_t R) {
-    int64_t b = snn_ceil_div(R, (int64_t)kLossThreads * 4);
-    if (b > 1024) b = 1024;
-    return b < 1 ? 1 : (int)b;
-}
 
 }  // namespace
 
@@ -420,42 +273,6 @@ extern "C" int snn_roi_assign(const float* anchors, const float* labels, int B, 
     hipLaunchKernelGGL(k_roi_assign, dim3((unsigned)B), dim3(kRoiThreads), 0, (hipStream_t)stream, anchors, labels, A, N,
                        iou_threshold, iou, amap, bbox_offset, bbox_mask, class_labels);
     SNN_CHECK_LAUNCH("snn_roi_assign");
-    return 0;
-}
-
-extern "C" size_t snn_det_loss_workspace_size(int64_t rows) { return (size_t)loss_blocks(rows) * 5 * sizeof(double); }
-
-extern "C" int snn_det_loss_fwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
-                                const float* bbox_mask, const int64_t* class_labels, int64_t rows, int K,
-                                float loss_ratio, void* workspace, double* stats, float* loss, void* stream) {
-    SNN_REQUIRE(cls_logits && bbox_preds && bbox_offset && bbox_mask && class_labels && workspace && stats && loss,
-                "snn_det_loss_fwd: null pointer");
-    SNN_REQUIRE(rows > 0 && K > 1 && K <= kMaxClasses, "snn_det_loss_fwd: bad shape");
-    SNN_REQUIRE(aligned16(bbox_preds) && aligned16(bbox_offset) && aligned16(bbox_mask),
-                "snn_det_loss_fwd: box tensors must be 16-byte aligned");
-    const int nb = loss_blocks(rows);
-    hipLaunchKernelGGL(k_det_loss_partial<false>, dim3((unsigned)nb), dim3(kLossThreads), 0, (hipStream_t)stream,
-                       cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, rows, K, (const int*)nullptr, 1,
-                       static_cast<double*>(workspace));
-    hipLaunchKernelGGL(k_det_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                       static_cast<const double*>(workspace), nb, rows, loss_ratio, stats, loss);
-    SNN_CHECK_LAUNCH("snn_det_loss_fwd");
-    return 0;
-}
-
-extern "C" int snn_det_loss_bwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
-                                const float* bbox_mask, const int64_t* class_labels, int64_t rows, int K,
-                                float loss_ratio, const double* stats, const float* g_loss, float* g_logits,
-                                float* g_bbox, void* stream) {
-    SNN_REQUIRE(cls_logits && bbox_preds && bbox_offset && bbox_mask && class_labels && stats && g_loss && g_logits &&
-                    g_bbox, "snn_det_loss_bwd: null pointer");
-    SNN_REQUIRE(rows > 0 && K > 1 && K <= kMaxClasses, "snn_det_loss_bwd: bad shape");
-    SNN_REQUIRE(aligned16(bbox_preds) && aligned16(bbox_offset) && aligned16(bbox_mask) && aligned16(g_bbox),
-                "snn_det_loss_bwd: box tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(k_det_loss_bwd<false>, dim3((unsigned)loss_blocks(rows)), dim3(kLossThreads), 0,
-                       (hipStream_t)stream, cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, rows, K, stats,
-                       loss_ratio, g_loss, (const int*)nullptr, 1, g_logits, g_bbox);
-    SNN_CHECK_LAUNCH("snn_det_loss_bwd");
     return 0;
 }
 
@@ -533,48 +350,5 @@ extern "C" int snn_roi_assign_steps(const float* anchors, const float* labels, c
     hipLaunchKernelGGL(k_roi_assign_steps, dim3((unsigned)slots), dim3(kRoiThreads), 0, (hipStream_t)stream, anchors,
                        labels, steps, B, A, N, t0, iou_threshold, iou, amap, lab, bbox_offset, bbox_mask, class_labels);
     SNN_CHECK_LAUNCH("snn_roi_assign_steps");
-    return 0;
-}
-
-extern "C" size_t snn_det_loss_steps_workspace_size(int K, int B, int A) {
-    return (size_t)loss_blocks((int64_t)K * B * A) * 5 * sizeof(double);
-}
-
-extern "C" int snn_det_loss_steps_fwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
-                                      const float* bbox_mask, const int64_t* class_labels, const int* steps, int K, int B,
-                                      int A, int C, float loss_ratio, void* workspace, double* stats, float* loss,
-                                      void* stream) {
-    SNN_REQUIRE(cls_logits && bbox_preds && bbox_offset && bbox_mask && class_labels && steps && workspace && stats &&
-                    loss, "snn_det_loss_steps_fwd: null pointer");
-    SNN_REQUIRE(B > 0 && A > 0 && C > 1 && C <= kMaxClasses, "snn_det_loss_steps_fwd: bad shape");
-    SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps, "snn_det_loss_steps_fwd: K must be in 1 .. %d", kMaxLabelSteps);
-    SNN_REQUIRE(aligned16(bbox_preds) && aligned16(bbox_offset) && aligned16(bbox_mask),
-                "snn_det_loss_steps_fwd: box tensors must be 16-byte aligned");
-    const int64_t rows = (int64_t)K * B * A;
-    const int nb = loss_blocks(rows);
-    hipLaunchKernelGGL(k_det_loss_partial<true>, dim3((unsigned)nb), dim3(kLossThreads), 0, (hipStream_t)stream,
-                       cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, rows, C, steps, A,
-                       static_cast<double*>(workspace));
-    hipLaunchKernelGGL(k_det_loss_steps_final, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                       static_cast<const double*>(workspace), nb, steps, K * B, A, loss_ratio, stats, loss);
-    SNN_CHECK_LAUNCH("snn_det_loss_steps_fwd");
-    return 0;
-}
-
-extern "C" int snn_det_loss_steps_bwd(const float* cls_logits, const float* bbox_preds, const float* bbox_offset,
-                                      const float* bbox_mask, const int64_t* class_labels, const int* steps, int K, int B,
-                                      int A, int C, float loss_ratio, const double* stats, const float* g_loss,
-                                      float* g_logits, float* g_bbox, void* stream) {
-    SNN_REQUIRE(cls_logits && bbox_preds && bbox_offset && bbox_mask && class_labels && steps && stats && g_loss &&
-                    g_logits && g_bbox, "snn_det_loss_steps_bwd: null pointer");
-    SNN_REQUIRE(B > 0 && A > 0 && C > 1 && C <= kMaxClasses, "snn_det_loss_steps_bwd: bad shape");
-    SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps, "snn_det_loss_steps_bwd: K must be in 1 .. %d", kMaxLabelSteps);
-    SNN_REQUIRE(aligned16(bbox_preds) && aligned16(bbox_offset) && aligned16(bbox_mask) && aligned16(g_bbox),
-                "snn_det_loss_steps_bwd: box tensors must be 16-byte aligned");
-    const int64_t rows = (int64_t)K * B * A;
-    hipLaunchKernelGGL(k_det_loss_bwd<true>, dim3((unsigned)loss_blocks(rows)), dim3(kLossThreads), 0,
-                       (hipStream_t)stream, cls_logits, bbox_preds, bbox_offset, bbox_mask, class_labels, rows, C, stats,
-                       loss_ratio, g_loss, steps, A, g_logits, g_bbox);
-    SNN_CHECK_LAUNCH("snn_det_loss_steps_bwd");
     return 0;
 }

@@ -2547,59 +2547,103 @@ def stack_time(xs: List[torch.Tensor]) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------- detection loss
+def _loss_entry(ptrs, anc, steps, dims, ratio, modes):
+    """The C entry family of ``csrc/det_loss.hip`` a call goes through, by its shape ->
+    ``(symbol stem, doubles of stats, workspace-size arguments, leading call arguments)``."""
+    rows, A, C = dims
+    if modes is not None:      # selectable objective: means over max(n, 1) rows; stats = totals, V, the three terms
+        return "snn_det_loss_ext", 9, (rows,), ptrs + [_ptr(anc), _ptr(steps), rows, A, C, ratio, *modes]
+    if steps is not None:      # the reference's objective over K x B slots: means as they are (NaN); stats = totals, V
+        K, B = steps.shape
+        return "snn_det_loss_steps", 6, (K, B, A), ptrs + [steps.data_ptr(), K, B, A, C, ratio]
+    return "snn_det_loss", 5, (rows,), ptrs + [rows, C, ratio]   # ... over all rows; stats = totals
+
+
 class _DetectionLoss(Function):
-    """``loss_ratio * mean(CE[pos]) + (1 - loss_ratio) * mean(CE[neg]) + mean(L1(bbox*mask, offset*mask))``
-    (models/soda.py:259-281) and its gradient: two kernel launches forward, one backward, no host round trip."""
+    """The detection loss and its gradient (``csrc/det_loss.hip``): two kernel launches forward, one backward, no host
+    round trip.  ``modes`` None: ``loss_ratio * mean(CE[pos]) + (1 - loss_ratio) * mean(CE[neg]) + mean(L1(bbox*mask,
+    offset*mask))`` (models/soda.py:259-281), NaN for an empty class; ``modes`` from ``check_loss_options`` (``anchors``
+    required): a selectable classification term (cross entropy | focal) and box term (L1 | GIoU | DIoU | CIoU), 0 for an
+    empty class.  ``steps`` None or ``[K,B]``: over the anchors of the valid slots only (``steps[k][b] >= 0``); their
+    number ``V`` is counted on the device, ``V = 0`` gives loss 0 and the gradients of empty slots are exact zeros.
+    Returns the loss and ``stats``; with ``modes`` its last three entries are the terms of the loss."""
 
     @staticmethod
-    def forward(ctx, cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, loss_ratio: float):
+    def forward(ctx, cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, loss_ratio: float,
+                modes: Optional[Tuple[int, float, int, float]]):
+        who = "detection_loss_steps" if modes is None else "detection_loss_steps_ext"
         _require_device(cls_preds, "loss: class predictions")
         _require_device(bbox_preds, "loss: box predictions")
-        # the targets go to the kernel as raw pointers: a host or float64 tensor would be read as a wild device address
+        # the targets and anchors go to the kernel as raw pointers: a host or float64 tensor would be a wild address
         _require_device(bbox_offset, "loss: box offsets")
         _require_device(bbox_mask, "loss: box mask")
-        for t, what in ((bbox_preds, "box predictions"), (bbox_offset, "box offsets"), (bbox_mask, "box mask"),
-                        (class_labels, "class labels")):
+        others = [(bbox_preds, "box predictions"), (bbox_offset, "box offsets"), (bbox_mask, "box mask"),
+                  (class_labels, "class labels")]
+        if modes is not None:
+            _require_device(anchors, "loss: anchors")
+            others.append((anchors, "anchors"))
+        for t, what in others:
             if t.device != cls_preds.device:
                 raise RuntimeError(f"loss: {what} are on {t.device}, the class predictions on {cls_preds.device}")
-        K = cls_preds.shape[-1]
+        A, anc = 1, None   # (without anchors and steps every row is a frame of its own)
+        if modes is not None:
+            if anchors.dim() != 2 or anchors.shape[1] != 4 or cls_preds.dim() < 2 or cls_preds.shape[-2] != anchors.shape[0]:
+                raise RuntimeError(f"detection loss: anchors [A,4] and class predictions [..., A, C+1] required, got "
+                                   f"{tuple(anchors.shape)} and {tuple(cls_preds.shape)}")
+            A, anc = int(anchors.shape[0]), anchors.detach().contiguous()
+        Ks = None
+        if steps is not None:
+            if cls_preds.dim() != 4:
+                raise RuntimeError(f"{who}: class predictions [K,B,A,C+1] required")
+            A = int(cls_preds.shape[2])
+            Ks, steps = _require_steps(steps, int(cls_preds.shape[1]), cls_preds, who)
+        C = int(cls_preds.shape[-1])
         logits, boxes = cls_preds.detach().contiguous(), bbox_preds.detach().contiguous()
         off, msk = bbox_offset.contiguous(), bbox_mask.contiguous()
         lab = class_labels.contiguous()
         rows = lab.numel()
-        if logits.numel() != rows * K or boxes.numel() != rows * 4 or off.numel() != rows * 4 or \
-                msk.numel() != rows * 4 or lab.dtype != torch.int64:
-            raise RuntimeError("detection loss: predictions and targets differ in shape")
+        with_steps = "detection loss: predictions, targets and steps differ in shape"
+        if (modes is not None and rows == 0) or logits.numel() != rows * C or boxes.numel() != rows * 4 or \
+                off.numel() != rows * 4 or msk.numel() != rows * 4 or lab.dtype != torch.int64:
+            raise RuntimeError(with_steps if Ks is not None and modes is None else
+                               "detection loss: predictions and targets differ in shape")
+        if Ks is not None and Ks != cls_preds.shape[0]:
+            raise RuntimeError(with_steps)
         dev = logits.device
-        ws = torch.empty(_hip.query("snn_det_loss_workspace_size", rows), device=dev, dtype=torch.uint8)
-        stats = torch.empty(5, device=dev, dtype=torch.float64)
+        ctx.args = ((rows, A, C), float(loss_ratio), modes)
+        entry, n_stats, size_args, head = _loss_entry([t.data_ptr() for t in (logits, boxes, off, msk, lab)], anc, steps,
+                                                      *ctx.args)
+        ws = torch.empty(_hip.query(entry + "_workspace_size", *size_args), device=dev, dtype=torch.uint8)
+        stats = torch.empty(n_stats, device=dev, dtype=torch.float64)
         loss = torch.empty((), device=dev, dtype=_F32)
-        _hip.call("snn_det_loss_fwd", logits.data_ptr(), boxes.data_ptr(), off.data_ptr(), msk.data_ptr(),
-                  lab.data_ptr(), rows, K, float(loss_ratio), ws.data_ptr(), stats.data_ptr(), loss.data_ptr(), _stream())
-        ctx.save_for_backward(logits, boxes, off, msk, lab, stats)
-        ctx.loss_ratio = float(loss_ratio)
+        _hip.call(entry + "_fwd", *head, ws.data_ptr(), stats.data_ptr(), loss.data_ptr(), _stream())
+        ctx.optional = (anc is not None, steps is not None)
+        ctx.save_for_backward(logits, boxes, off, msk, lab, stats, *(t for t in (anc, steps) if t is not None))
         ctx.shapes = (cls_preds.shape, bbox_preds.shape)
-        return loss
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
 
     @staticmethod
-    def backward(ctx, g):
-        logits, boxes, off, msk, lab, stats = ctx.saved_tensors
-        rows, K = lab.numel(), logits.shape[-1]
+    def backward(ctx, g, _g_stats):
+        logits, boxes, off, msk, lab, stats, *rest = ctx.saved_tensors
+        anc = rest.pop(0) if ctx.optional[0] else None
+        steps = rest.pop(0) if ctx.optional[1] else None
         g = g.detach().to(_F32).contiguous()
         g_logits, g_boxes = torch.empty_like(logits), torch.empty_like(boxes)
-        _hip.call("snn_det_loss_bwd", logits.data_ptr(), boxes.data_ptr(), off.data_ptr(), msk.data_ptr(),
-                  lab.data_ptr(), rows, K, ctx.loss_ratio, stats.data_ptr(), g.data_ptr(), g_logits.data_ptr(),
-                  g_boxes.data_ptr(), _stream())
-        return g_logits.view(ctx.shapes[0]), g_boxes.view(ctx.shapes[1]), None, None, None, None
+        entry, _, _, head = _loss_entry([t.data_ptr() for t in (logits, boxes, off, msk, lab)], anc, steps, *ctx.args)
+        _hip.call(entry + "_bwd", *head, stats.data_ptr(), g.data_ptr(), g_logits.data_ptr(), g_boxes.data_ptr(), _stream())
+        return (g_logits.view(ctx.shapes[0]), g_boxes.view(ctx.shapes[1])) + (None,) * 7
 
 
 def detection_loss(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox_offset: torch.Tensor,
                    bbox_mask: torch.Tensor, class_labels: torch.Tensor, loss_ratio: float) -> torch.Tensor:
-    return _DetectionLoss.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, loss_ratio)
+    """``loss_ratio * mean(CE[pos]) + (1 - loss_ratio) * mean(CE[neg]) + mean(L1(bbox*mask, offset*mask))``
+    (models/soda.py:259-281); a sample set without positives (or negatives) gives NaN, as the reference."""
+    return _DetectionLoss.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, None, None, loss_ratio, None)[0]
 
 
 # ------------------------------------------------------------------------------------------- every labelled timestep
-MAX_LABEL_STEPS = 32   # frame slots per sample the *_steps kernels take (csrc/targets.hip)
+MAX_LABEL_STEPS = 32   # frame slots per sample the *_steps kernels take (kMaxLabelSteps of csrc/snn_common.h)
 
 
 def _require_steps(steps: torch.Tensor, B: int, like: torch.Tensor, what: str) -> Tuple[int, torch.Tensor]:
@@ -2663,61 +2707,14 @@ def gather_steps(Y: torch.Tensor, steps: torch.Tensor) -> torch.Tensor:
     return _GatherSteps.apply(Y, steps)
 
 
-class _DetectionLossSteps(Function):
-    """``_DetectionLoss`` over the anchors of the valid slots only (``steps[k][b] >= 0``); their number ``V`` is counted on
-    the device.  ``V = 0`` gives loss 0 and zero gradients; the gradients of empty slots are exact zeros."""
-
-    @staticmethod
-    def forward(ctx, cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, steps, loss_ratio: float):
-        _require_device(cls_preds, "loss: class predictions")
-        _require_device(bbox_preds, "loss: box predictions")
-        _require_device(bbox_offset, "loss: box offsets")
-        _require_device(bbox_mask, "loss: box mask")
-        for t, what in ((bbox_preds, "box predictions"), (bbox_offset, "box offsets"), (bbox_mask, "box mask"),
-                        (class_labels, "class labels")):
-            if t.device != cls_preds.device:
-                raise RuntimeError(f"loss: {what} are on {t.device}, the class predictions on {cls_preds.device}")
-        if cls_preds.dim() != 4:
-            raise RuntimeError("detection_loss_steps: class predictions [K,B,A,C+1] required")
-        K, B, A, C = cls_preds.shape
-        Ks, steps = _require_steps(steps, B, cls_preds, "detection_loss_steps")
-        logits, boxes = cls_preds.detach().contiguous(), bbox_preds.detach().contiguous()
-        off, msk = bbox_offset.contiguous(), bbox_mask.contiguous()
-        lab = class_labels.contiguous()
-        rows = K * B * A
-        if Ks != K or lab.numel() != rows or boxes.numel() != rows * 4 or off.numel() != rows * 4 or \
-                msk.numel() != rows * 4 or lab.dtype != torch.int64:
-            raise RuntimeError("detection loss: predictions, targets and steps differ in shape")
-        dev = logits.device
-        ws = torch.empty(_hip.query("snn_det_loss_steps_workspace_size", K, B, A), device=dev, dtype=torch.uint8)
-        stats = torch.empty(6, device=dev, dtype=torch.float64)
-        loss = torch.empty((), device=dev, dtype=_F32)
-        _hip.call("snn_det_loss_steps_fwd", logits.data_ptr(), boxes.data_ptr(), off.data_ptr(), msk.data_ptr(),
-                  lab.data_ptr(), steps.data_ptr(), K, B, A, C, float(loss_ratio), ws.data_ptr(), stats.data_ptr(),
-                  loss.data_ptr(), _stream())
-        ctx.save_for_backward(logits, boxes, off, msk, lab, steps, stats)
-        ctx.loss_ratio = float(loss_ratio)
-        ctx.shapes = (cls_preds.shape, bbox_preds.shape)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, boxes, off, msk, lab, steps, stats = ctx.saved_tensors
-        K, B, A, C = ctx.shapes[0]
-        g = g.detach().to(_F32).contiguous()
-        g_logits, g_boxes = torch.empty_like(logits), torch.empty_like(boxes)
-        _hip.call("snn_det_loss_steps_bwd", logits.data_ptr(), boxes.data_ptr(), off.data_ptr(), msk.data_ptr(),
-                  lab.data_ptr(), steps.data_ptr(), K, B, A, C, ctx.loss_ratio, stats.data_ptr(), g.data_ptr(),
-                  g_logits.data_ptr(), g_boxes.data_ptr(), _stream())
-        return g_logits.view(ctx.shapes[0]), g_boxes.view(ctx.shapes[1]), None, None, None, None, None
-
-
 def detection_loss_steps(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox_offset: torch.Tensor,
                          bbox_mask: torch.Tensor, class_labels: torch.Tensor, steps: torch.Tensor,
                          loss_ratio: float) -> torch.Tensor:
     """``detection_loss`` of ``cls_preds[K,B,A,C+1]`` / ``bbox_preds[K,B,A,4]`` over the valid slots of ``steps[K,B]``:
     ``r mean(CE[pos]) + (1 - r) mean(CE[neg]) + sum |bbox m - off m| / (4 A V)``."""
-    return _DetectionLossSteps.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, steps, loss_ratio)
+    if steps is None:
+        raise RuntimeError("detection_loss_steps: steps[K,B] required")
+    return _DetectionLoss.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, None, steps, loss_ratio, None)[0]
 
 
 # ------------------------------------------------------------------------------------------- selectable detection loss
@@ -2734,72 +2731,11 @@ def check_loss_options(cls_loss: str, focal_gamma: float, box_loss: str, box_los
     return _hip.LOSS_CLS_MODES[cls_loss], float(focal_gamma), _hip.LOSS_BOX_MODES[box_loss], float(box_loss_weight)
 
 
-class _DetectionLossExt(Function):
-    """``_DetectionLoss`` / ``_DetectionLossSteps`` (``steps`` None or ``[K,B]``) with a selectable classification term
-    (cross entropy | focal) and box term (L1 | GIoU | DIoU | CIoU) (``csrc/det_loss_ext.hip``): two launches forward, one
-    backward, no host round trip.  Returns the loss and ``stats[9]``, whose last three entries are the terms of the loss."""
-
-    @staticmethod
-    def forward(ctx, cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, loss_ratio: float,
-                modes: Tuple[int, float, int, float]):
-        _require_device(cls_preds, "loss: class predictions")
-        _require_device(bbox_preds, "loss: box predictions")
-        # the targets and anchors go to the kernel as raw pointers: a host or float64 tensor would be a wild address
-        _require_device(bbox_offset, "loss: box offsets")
-        _require_device(bbox_mask, "loss: box mask")
-        _require_device(anchors, "loss: anchors")
-        for t, what in ((bbox_preds, "box predictions"), (bbox_offset, "box offsets"), (bbox_mask, "box mask"),
-                        (class_labels, "class labels"), (anchors, "anchors")):
-            if t.device != cls_preds.device:
-                raise RuntimeError(f"loss: {what} are on {t.device}, the class predictions on {cls_preds.device}")
-        if anchors.dim() != 2 or anchors.shape[1] != 4 or cls_preds.dim() < 2 or cls_preds.shape[-2] != anchors.shape[0]:
-            raise RuntimeError(f"detection loss: anchors [A,4] and class predictions [..., A, C+1] required, got "
-                               f"{tuple(anchors.shape)} and {tuple(cls_preds.shape)}")
-        A, C = int(anchors.shape[0]), int(cls_preds.shape[-1])
-        logits, boxes = cls_preds.detach().contiguous(), bbox_preds.detach().contiguous()
-        off, msk = bbox_offset.contiguous(), bbox_mask.contiguous()
-        lab, anc = class_labels.contiguous(), anchors.detach().contiguous()
-        rows = lab.numel()
-        if rows == 0 or logits.numel() != rows * C or boxes.numel() != rows * 4 or off.numel() != rows * 4 or \
-                msk.numel() != rows * 4 or lab.dtype != torch.int64:
-            raise RuntimeError("detection loss: predictions and targets differ in shape")
-        if steps is not None:
-            if cls_preds.dim() != 4:
-                raise RuntimeError("detection_loss_steps_ext: class predictions [K,B,A,C+1] required")
-            Ks, steps = _require_steps(steps, int(cls_preds.shape[1]), cls_preds, "detection_loss_steps_ext")
-            if Ks != cls_preds.shape[0]:
-                raise RuntimeError("detection loss: predictions, targets and steps differ in shape")
-        dev = logits.device
-        ws = torch.empty(_hip.query("snn_det_loss_ext_workspace_size", rows), device=dev, dtype=torch.uint8)
-        stats = torch.empty(9, device=dev, dtype=torch.float64)
-        loss = torch.empty((), device=dev, dtype=_F32)
-        ctx.args = (rows, A, C, float(loss_ratio), int(modes[0]), float(modes[1]), int(modes[2]), float(modes[3]))
-        _hip.call("snn_det_loss_ext_fwd", logits.data_ptr(), boxes.data_ptr(), off.data_ptr(), msk.data_ptr(),
-                  lab.data_ptr(), anc.data_ptr(), None if steps is None else steps.data_ptr(), *ctx.args, ws.data_ptr(),
-                  stats.data_ptr(), loss.data_ptr(), _stream())
-        ctx.has_steps = steps is not None
-        ctx.save_for_backward(logits, boxes, off, msk, lab, anc, stats, *(() if steps is None else (steps,)))
-        ctx.shapes = (cls_preds.shape, bbox_preds.shape)
-        ctx.mark_non_differentiable(stats)
-        return loss, stats
-
-    @staticmethod
-    def backward(ctx, g, _g_stats):
-        logits, boxes, off, msk, lab, anc, stats = ctx.saved_tensors[:7]
-        steps = ctx.saved_tensors[7] if ctx.has_steps else None
-        g = g.detach().to(_F32).contiguous()
-        g_logits, g_boxes = torch.empty_like(logits), torch.empty_like(boxes)
-        _hip.call("snn_det_loss_ext_bwd", logits.data_ptr(), boxes.data_ptr(), off.data_ptr(), msk.data_ptr(),
-                  lab.data_ptr(), anc.data_ptr(), None if steps is None else steps.data_ptr(), *ctx.args, stats.data_ptr(),
-                  g.data_ptr(), g_logits.data_ptr(), g_boxes.data_ptr(), _stream())
-        return (g_logits.view(ctx.shapes[0]), g_boxes.view(ctx.shapes[1])) + (None,) * 7
-
-
 def _loss_ext(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, loss_ratio, cls_loss,
               focal_gamma, box_loss, box_loss_weight, return_terms):
     modes = check_loss_options(cls_loss, focal_gamma, box_loss, box_loss_weight)
-    loss, stats = _DetectionLossExt.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps,
-                                          loss_ratio, modes)
+    loss, stats = _DetectionLoss.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps,
+                                       loss_ratio, modes)
     if not return_terms:
         return loss
     terms = stats[6:9].to(_F32)       # the kernel's own fp32 terms: (terms[0] + terms[1]) + terms[2] is the loss, bit for bit

@@ -19,7 +19,7 @@ Same constructor, hooks and step logic; what differs:
   per sample instead of the last frame only (DESIGN "Every labelled timestep").
 * ``cls_loss`` / ``focal_gamma`` / ``box_loss`` / ``box_loss_weight`` select the objective: focal classification and a
   GIoU / DIoU / CIoU term on the decoded boxes next to the reference's cross entropy + L1, which stays the default and
-  runs exactly as before (DESIGN "Selectable detection loss").
+  runs exactly as before (DESIGN "Detection loss").
 """
 
 import math
@@ -408,7 +408,7 @@ class SODa(nn.Module):
         anchors, cls_preds, bbox_preds = preds
         bbox_offset, bbox_mask, class_labels = self.roi_blk(anchors, labels)
         if not self._default_loss():
-            if cls_preds.is_cuda:   # the same launches from csrc/det_loss_ext.hip
+            if cls_preds.is_cuda:   # the same launches as below (csrc/det_loss.hip)
                 from . import functional as HF
                 loss, *self._loss_terms = HF.detection_loss_ext(
                     cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, self.hparams.loss_ratio,
@@ -419,7 +419,7 @@ class SODa(nn.Module):
             self._loss_terms = [t_cls.detach(), t_box.detach()]
             return t_cls + t_box
         if cls_preds.is_cuda:
-            # one launch for the anchor targets (RoI above), two for the loss, one for its gradient (csrc/targets.hip)
+            # one launch for the anchor targets (RoI above), two for the loss, one for its gradient (csrc/det_loss.hip)
             from . import functional as HF
             return HF.detection_loss(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels,
                                      self.hparams.loss_ratio)

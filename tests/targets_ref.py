@@ -1,5 +1,5 @@
-"""References for the training-target kernels of csrc/targets.hip (TEST INFRASTRUCTURE ONLY; nothing here imports the
-package).
+"""References for the training-target kernels of csrc/targets.hip and csrc/det_loss.hip (TEST INFRASTRUCTURE ONLY;
+nothing here imports the package).
 
 ``roi_assign_ref``  restates the anchor <-> ground-truth assignment of the reference (utils/roi.py:18-109 with
 utils/box.py:31-69) statement by statement in torch float32 on the host.  float32 and not float64 on purpose: the result

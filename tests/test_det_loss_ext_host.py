@@ -179,7 +179,7 @@ def test_new_symbols_are_declared_and_bound():
     assert _hip.LOSS_CLS_MODES == {"ce": 0, "focal": 1}
     assert _hip.LOSS_BOX_MODES == {"l1": 0, "giou": 1, "diou": 2, "ciou": 3}
     assert tuple(_hip.LOSS_CLS_MODES) == soda.LOSS_CLS_NAMES and tuple(_hip.LOSS_BOX_MODES) == soda.LOSS_BOX_NAMES
-    assert "det_loss_ext.hip" in _build.SOURCES
+    assert "det_loss.hip" in _build.SOURCES
     # the signatures of the existing loss entry points are the parent's
     assert len(_hip.SIGNATURES["snn_det_loss_fwd"][1]) == 12 and len(_hip.SIGNATURES["snn_det_loss_bwd"][1]) == 13
     assert len(_hip.SIGNATURES["snn_det_loss_steps_fwd"][1]) == 15 and len(_hip.SIGNATURES["snn_det_loss_steps_bwd"][1]) == 16

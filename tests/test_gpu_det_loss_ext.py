@@ -1,4 +1,4 @@
-"""The selectable detection loss kernels (csrc/det_loss_ext.hip) against the fp64 restatement of
+"""The detection loss kernels (csrc/det_loss.hip) under every selectable objective against the fp64 restatement of
 tests/det_loss_ext_ref.py: through the C ABI on the guarded, NaN-filled buffers of tests/test_gpu_targets_fp64.py, through
 ``functional.detection_loss_ext`` / ``detection_loss_steps_ext`` (the same bits) and through a tiny ``SODa``.
 
@@ -241,23 +241,93 @@ def test_ext_loss_over_slots(hip, empty):
     assert not fails, "\n  ".join(fails)
 
 
+def _flat(inp, ratio=RATIO, g_loss=1.0):
+    """The rows of ``inp`` as ``run_loss_abi`` of tests/test_gpu_targets_fp64.py takes them."""
+    K = inp.logits.shape[-1]
+    return (inp.logits.reshape(-1, K), inp.bbox.reshape(-1, 4), inp.offset.reshape(-1, 4), inp.mask.reshape(-1, 4),
+            inp.labels.reshape(-1), ratio, g_loss)
+
+
+def _assert_same_sums_and_gradients(o, old, tag):
+    """The five totals and both gradients of an ``_ext`` run and of an snn_det_loss_* / snn_det_loss_steps_* run: equal."""
+    assert torch.equal(o.stats[:5], old.stats[:5]), f"{tag}: stats {o.stats[:5].tolist()} vs {old.stats[:5].tolist()}"
+    assert torch.equal(o.g_logits.reshape(old.g_logits.shape), old.g_logits), f"{tag}: g_logits"
+    assert torch.equal(o.g_bbox.reshape(old.g_bbox.shape), old.g_bbox), f"{tag}: g_bbox"
+
+
 @pytest.mark.parametrize("cls_mode", R.CLS_MODES)
 def test_gamma_0_with_l1_is_the_existing_loss(hip, cls_mode):
-    """``gamma = 0``, L1, weight 1 against snn_det_loss_fwd / _bwd on the same inputs, with the bounds
-    tests/test_gpu_detect.py states for that kernel: loss within 1e-6 relative, gradients within 1e-5 (L2, relative)."""
+    """Cross entropy (or focal with ``gamma = 0``), L1, weight 1 against snn_det_loss_fwd / _bwd on the same inputs: the
+    same kernels in the same order, so the loss, the five totals and both gradients are equal - on 600 rows (two full
+    blocks and a ragged third) and on 270 000 (a second grid pass); the inputs have positives and negatives.  The same for
+    snn_det_loss_steps_fwd / _bwd with one empty slot among six."""
     from tests.test_gpu_targets_fp64 import run_loss_abi
-    from tests.util import rel_err
+    from tests.test_gpu_seq_targets import run_loss_steps_abi
     for Fr, A, K in SMALL_SHAPES + [LARGE_SHAPE]:
         inp = inputs(Fr, A, K, "random")
+        assert bool((inp.labels > 0).any()) and bool((inp.labels == 0).any())
         o = run_ext_abi(hip, inp, cls_mode, 0.0, "l1", 1.0)
-        flat = (inp.logits.reshape(-1, K), inp.bbox.reshape(-1, 4), inp.offset.reshape(-1, 4), inp.mask.reshape(-1, 4),
-                inp.labels.reshape(-1), RATIO, 1.0)
-        old = run_loss_abi(hip, flat)
+        old = run_loss_abi(hip, _flat(inp))
         print(f"{Fr}x{A}x{K}: ext {float(o.loss)!r} existing {float(old.loss)!r}")
-        assert abs(float(o.loss) - float(old.loss)) <= 1e-6 * abs(float(old.loss))
-        assert rel_err(o.g_logits.reshape(-1, K), old.g_logits) < 1e-5
-        assert rel_err(o.g_bbox.reshape(-1, 4), old.g_bbox) < 1e-5
-        assert float(o.stats[1]) == float(old.stats[1]) and float(o.stats[3]) == float(old.stats[3])
+        assert torch.equal(o.loss, old.loss)
+        _assert_same_sums_and_gradients(o, old, f"{Fr}x{A}x{K}")
+    Ks, B, A, K = 3, 2, 300, 3
+    inp = inputs(Ks * B, A, K, "random")
+    steps = torch.tensor([[3, -1], [5, 2], [7, 4]], dtype=torch.int32)
+    o = run_ext_abi(hip, inp, cls_mode, 0.0, "l1", 1.0, steps=steps)
+    shp = lambda t, *last: t.reshape(Ks, B, A, *last)
+    old = run_loss_steps_abi(hip, shp(inp.logits, K), shp(inp.bbox, 4), shp(inp.offset, 4), shp(inp.mask, 4),
+                             shp(inp.labels), steps, RATIO, 1.0)
+    print(f"steps: ext {float(o.loss)!r} existing {float(old.loss)!r}")
+    assert torch.equal(o.loss, old.loss) and float(old.stats[5]) == 5.0 and float(o.stats[5]) == 5.0
+    _assert_same_sums_and_gradients(o, old, "steps")
+
+
+def test_an_empty_class_is_nan_in_the_existing_loss_and_zero_in_ext(hip):
+    """The one difference between snn_det_loss_* and snn_det_loss_ext_* at cross entropy, L1, weight 1: without positives
+    the former divide 0 by 0 (NaN, as the reference's ``ce[pos].mean()``), the latter by ``max(n_pos, 1)``: the positive
+    term is 0 and the loss is (0 + negative term) + box term - the box term itself where ``loss_ratio = 1`` leaves the
+    negatives no weight.  The totals and the gradients are equal all the same.  ``detection_loss_steps``: every slot
+    empty gives 0 and zero gradients, a valid slot without positives NaN.  (``stats`` is guarded at the 5, 6 and 9
+    doubles the three entry families own: ``run_loss_abi``, ``run_loss_steps_abi``, ``run_ext_abi``.)"""
+    from snn_for_object_detection_amd import functional as HF
+    from tests.test_gpu_targets_fp64 import run_loss_abi
+    from tests.test_gpu_seq_targets import run_loss_steps_abi
+    Fr, A, K = 2, 300, 3
+    inp = inputs(Fr, A, K, "no_pos")
+    assert not bool((inp.labels > 0).any())
+    for ratio in (RATIO, 1.0):
+        old = run_loss_abi(hip, _flat(inp, ratio))
+        assert bool(torch.isnan(old.loss))
+        o = run_ext_abi(hip, inp, "ce", 0.0, "l1", 1.0, ratio=ratio)
+        terms = o.stats[6:9].float()
+        assert float(terms[0]) == 0.0 and bool(torch.isfinite(o.loss)) and float(terms[2]) > 0
+        assert torch.equal(((terms[0] + terms[1]) + terms[2]).reshape(1), o.loss.reshape(1))
+        if ratio == 1.0:
+            assert float(terms[1]) == 0.0 and float(o.loss) == float(terms[2])
+        else:
+            assert float(terms[1]) > 0 and bool(old.g_logits.any())       # (at ratio 1 the negatives' weight is 0)
+        _assert_same_sums_and_gradients(o, old, f"ratio {ratio}")
+        assert float(o.stats[1]) == 0.0 and bool(torch.isfinite(old.g_logits).all()) and bool(old.g_bbox.any())
+    d = [t.cuda() for t in inp[:5]]
+    assert bool(torch.isnan(HF.detection_loss(*d, RATIO)))
+    assert bool(torch.isfinite(HF.detection_loss_ext(*d, inp.anchors.cuda(), RATIO)))
+    # ---- two slots of one sample
+    shp = lambda t, *last: t.reshape(Fr, 1, A, *last)
+    slots = [shp(inp.logits, K), shp(inp.bbox, 4), shp(inp.offset, 4), shp(inp.mask, 4), shp(inp.labels)]
+    for steps, want_nan in (([[-1], [-1]], False), ([[0], [-1]], True)):
+        steps = torch.tensor(steps, dtype=torch.int32)
+        old = run_loss_steps_abi(hip, *slots, steps, RATIO, 1.0)
+        lg, bb = slots[0].cuda().requires_grad_(), slots[1].cuda().requires_grad_()
+        loss = HF.detection_loss_steps(lg, bb, *(t.cuda() for t in slots[2:]), steps.cuda(), RATIO)
+        loss.backward()
+        assert torch.equal(lg.grad.cpu(), old.g_logits) and torch.equal(bb.grad.cpu(), old.g_bbox)
+        if want_nan:
+            assert bool(torch.isnan(loss)) and bool(torch.isnan(old.loss)) and float(old.stats[5]) == 1.0
+            assert not bool(lg.grad[1].any()) and bool(lg.grad[0].any()) and bool(torch.isfinite(lg.grad).all())
+        else:
+            assert float(loss.detach()) == 0.0 and float(old.loss) == 0.0
+            assert not bool(lg.grad.any()) and not bool(bb.grad.any())
 
 
 def test_ext_loss_refusals(hip):

@@ -1,5 +1,5 @@
 """The kernels behind training on every labelled timestep (csrc/targets.hip: snn_label_steps, snn_gather_steps_fwd / _bwd,
-snn_roi_assign_steps, snn_det_loss_steps_fwd / _bwd) against the CPU restatement of tests/seq_targets_ref.py.
+snn_roi_assign_steps; csrc/det_loss.hip: snn_det_loss_steps_fwd / _bwd) against the CPU restatement of tests/seq_targets_ref.py.
 
 Every entry point is called through the C ABI on buffers pre-filled with NaN (0x7F bytes for integer buffers) with a
 guard region behind them, and through the Python wrappers (``functional.select_label_steps`` / ``gather_steps`` /

@@ -1,5 +1,5 @@
-"""The training-target kernels of csrc/targets.hip - snn_roi_assign and snn_det_loss_fwd / _bwd - against the references of
-tests/targets_ref.py, at the edges of their launch geometry and of their arithmetic.
+"""The training-target kernels - snn_roi_assign (csrc/targets.hip) and snn_det_loss_fwd / _bwd (csrc/det_loss.hip) -
+against the references of tests/targets_ref.py, at the edges of their launch geometry and of their arithmetic.
 
 Both entry points are called through the C ABI (``_hip.call``) on buffers pre-filled with NaN (0x7F bytes for integer
 buffers) with a guard region of the same fill behind every output and behind the workspace, and through ``roi.RoI`` /
