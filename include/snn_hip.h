@@ -699,6 +699,23 @@ int snn_adamax_step_ctl(float* param, const float* grad, float* exp_avg, float* 
                         float grad_scale, float weight_decay, float clip_value,
                         const snn_step_control* ctl, void* stream);
 
+/* Weight average (EMA) inside the step.  snn_adamax_step_ema is snn_adamax_step_ctl plus, per element and after the
+ * parameter update,  ema = ema + ema_weight * (param_new - ema)  in fp32, unfused.  ema_weight = 1 - decay is formed by
+ * the caller (in double, then rounded once): the kernel never subtracts a decay close to 1 from 1 in fp32.  param,
+ * exp_avg and exp_inf come out bit for bit as from snn_adamax_step_ctl with the same arguments (also where that call
+ * launches snn_adamax_step's kernel).  With a ctl whose `finite` is 0 the launch stores nothing, ema included.
+ * Pointer alignment as snn_adamax_step_ctl (4 bytes).  36 bytes moved per element instead of 28.
+ * snn_ema_update applies the same update from any `src` under the same ctl rule: parameters that took no Adamax step,
+ * BatchNorm buffers.  ema and src must not overlap.
+ * Both return non-zero before any launch, with a snn_last_error() that names the argument, for a NULL pointer (ctl may
+ * be NULL), n <= 0 or an ema_weight outside (0, 1] (a NaN included). */
+int snn_adamax_step_ema(float* param, const float* grad, float* exp_avg, float* exp_inf, float* ema,
+                        int64_t n, float lr, float beta1, float beta2, float eps, int step, float grad_scale,
+                        float weight_decay, float clip_value, float ema_weight,
+                        const snn_step_control* ctl, void* stream);
+int snn_ema_update(float* ema, const float* src, int64_t n, float ema_weight,
+                   const snn_step_control* ctl, void* stream);
+
 /* ---------------------------------------------------------------- event voxelisation
  * utils/datasets.py:378-435: scatter events (t_bin, p, y, x) into binary frames [T][H][W][2]
  * (channels-last image of the reference's [T,2,H,W]); x is clipped to W-1; value 1 (not a count). */

@@ -160,6 +160,8 @@ SIGNATURES = {
     "snn_grad_norm_workspace_size": (c_size_t, [_L]),
     "snn_grad_norm": (c_int, [_P, _L, _F, _F, _P, _P, _P]),
     "snn_adamax_step_ctl": (c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _F, _F, _P, _P]),
+    "snn_adamax_step_ema": (c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _F, _F, _F, _P, _P]),
+    "snn_ema_update": (c_int, [_P, _P, _L, _F, _P, _P]),
     "snn_events_to_frames": (c_int, [_P, _P, _P, _P, _L, _P, _I, _I, _I, _P]),
     "snn_events_to_frames_aug": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _L, _P]),
     "snn_events_to_frames_packed": (c_int, [_P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _L, _P]),

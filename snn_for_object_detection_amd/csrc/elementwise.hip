@@ -351,13 +351,17 @@ __global__ void k_upsample_bwd(const float* __restrict__ gy, float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------ optimizer
-// One body, two kernels in front of it.  CTL = false is the plain step; CTL = true adds, in the order of clip_grad_* followed
+// One body, four kernels in front of it.  CTL = false is the plain step; CTL = true adds, in the order of clip_grad_* followed
 // by torch.optim.Adamax: the control record's clip factor, the value clamp, the weight decay - and stores NOTHING when the
 // record says the gradient was not finite (the moments would stay non-finite for ever: u = max(b2 * inf, ...) = inf).
-template <bool CTL>
+// EMA = true moves the weight average towards the parameter it has just written, ema += ew * (p_new - ema) with
+// ew = 1 - decay formed by the caller: 8 more bytes per element in the pass that holds p_new in a register anyway.  The
+// parameter and both moments are computed by the same expressions in the same order whatever EMA is: the same bits.
+template <bool CTL, bool EMA>
 __device__ __forceinline__ void adamax_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                             float* __restrict__ u, int64_t n, float w1, float b2, float eps, float clr,
-                                            float gscale, float wd, float clip, const snn_step_control* __restrict__ ctl) {
+                                            float gscale, float wd, float clip, const snn_step_control* __restrict__ ctl,
+                                            float* __restrict__ ema, float ew) {
     float cscale = 1.0f;
     if constexpr (CTL) {
         if (ctl) {
@@ -377,17 +381,41 @@ __device__ __forceinline__ void adamax_body(float* __restrict__ p, const float* 
         float ue = fmaxf(u[e] * b2, fabsf(ge) + eps);
         m[e] = me;
         u[e] = ue;
-        p[e] = p[e] - clr * (me / ue);
+        const float pe = p[e] - clr * (me / ue);
+        p[e] = pe;
+        if constexpr (EMA) {
+            const float a = ema[e];
+            ema[e] = a + ew * (pe - a);
+        }
     }
 }
 __global__ void k_adamax(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                          float* __restrict__ u, int64_t n, float w1, float b2, float eps, float clr, float gscale) {
-    adamax_body<false>(p, g, m, u, n, w1, b2, eps, clr, gscale, 0.0f, 0.0f, nullptr);
+    adamax_body<false, false>(p, g, m, u, n, w1, b2, eps, clr, gscale, 0.0f, 0.0f, nullptr, nullptr, 0.0f);
 }
 __global__ void k_adamax_ctl(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ u, int64_t n, float w1, float b2, float eps, float clr, float gscale,
                              float wd, float clip, const snn_step_control* __restrict__ ctl) {
-    adamax_body<true>(p, g, m, u, n, w1, b2, eps, clr, gscale, wd, clip, ctl);
+    adamax_body<true, false>(p, g, m, u, n, w1, b2, eps, clr, gscale, wd, clip, ctl, nullptr, 0.0f);
+}
+// CTL mirrors snn_adamax_step_ctl's choice between the two kernels above, so the parameter and the moments come out of the
+// same instantiation of the arithmetic in either case.
+template <bool CTL>
+__global__ void k_adamax_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                             float* __restrict__ u, float* __restrict__ ema, int64_t n, float w1, float b2, float eps,
+                             float clr, float gscale, float wd, float clip, float ew,
+                             const snn_step_control* __restrict__ ctl) {
+    adamax_body<CTL, true>(p, g, m, u, n, w1, b2, eps, clr, gscale, wd, clip, ctl, ema, ew);
+}
+// The same update from an arbitrary source: parameters that received no gradient in a step (Adamax leaves them alone, the
+// average does not) and the BatchNorm buffers.  A record that says "not finite" stores nothing here either.
+__global__ void k_ema_update(float* __restrict__ ema, const float* __restrict__ src, int64_t n, float ew,
+                             const snn_step_control* __restrict__ ctl) {
+    if (ctl && !ctl->finite) return;
+    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < n; e += (int64_t)gridDim.x * kThreads) {
+        const float a = ema[e];
+        ema[e] = a + ew * (src[e] - a);
+    }
 }
 
 // ------------------------------------------------------------------------------------------ gradient norm
@@ -911,6 +939,50 @@ extern "C" int snn_adamax_step_ctl(float* param, const float* grad, float* exp_a
         hipLaunchKernelGGL(k_adamax_ctl, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, param, grad, exp_avg,
                            exp_inf, n, w1, beta2, eps, clr, grad_scale, weight_decay, clip_value, ctl);
     SNN_CHECK_LAUNCH("snn_adamax_step_ctl");
+    return 0;
+}
+
+// ema_weight = 1 - decay in (0, 1] (false for a NaN): 0 would never move the average, above 1 it would overshoot
+static bool ema_weight_ok(float w) { return w > 0.0f && w <= 1.0f; }
+
+extern "C" int snn_adamax_step_ema(float* param, const float* grad, float* exp_avg, float* exp_inf, float* ema, int64_t n,
+                                   float lr, float beta1, float beta2, float eps, int step, float grad_scale,
+                                   float weight_decay, float clip_value, float ema_weight, const snn_step_control* ctl,
+                                   void* stream) {
+    SNN_REQUIRE(param, "snn_adamax_step_ema: param is NULL");
+    SNN_REQUIRE(grad, "snn_adamax_step_ema: grad is NULL");
+    SNN_REQUIRE(exp_avg, "snn_adamax_step_ema: exp_avg is NULL");
+    SNN_REQUIRE(exp_inf, "snn_adamax_step_ema: exp_inf is NULL");
+    SNN_REQUIRE(ema, "snn_adamax_step_ema: ema is NULL");
+    SNN_REQUIRE(n > 0, "snn_adamax_step_ema: n = %lld must be positive", (long long)n);
+    SNN_REQUIRE(step >= 1, "snn_adamax_step_ema: step = %d must be at least 1", step);
+    SNN_REQUIRE(weight_decay >= 0.0f, "snn_adamax_step_ema: negative weight_decay");   // (false for a NaN too)
+    SNN_REQUIRE(ema_weight_ok(ema_weight), "snn_adamax_step_ema: ema_weight = %g is outside (0, 1]", (double)ema_weight);
+    SNN_REQUIRE(aligned(4, {ctl}), "snn_adamax_step_ema: the control record must be 4-byte aligned");
+    double bias_corr = 1.0 - pow((double)beta1, (double)step);
+    float clr = (float)((double)lr / bias_corr);
+    float w1 = (float)(1.0 - (double)beta1);
+    if (!ctl && weight_decay == 0.0f && !(clip_value > 0.0f))   // where snn_adamax_step_ctl launches the plain kernel
+        hipLaunchKernelGGL(k_adamax_ema<false>, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, param, grad,
+                           exp_avg, exp_inf, ema, n, w1, beta2, eps, clr, grad_scale, 0.0f, 0.0f, ema_weight, nullptr);
+    else
+        hipLaunchKernelGGL(k_adamax_ema<true>, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, param, grad,
+                           exp_avg, exp_inf, ema, n, w1, beta2, eps, clr, grad_scale, weight_decay, clip_value, ema_weight,
+                           ctl);
+    SNN_CHECK_LAUNCH("snn_adamax_step_ema");
+    return 0;
+}
+
+extern "C" int snn_ema_update(float* ema, const float* src, int64_t n, float ema_weight, const snn_step_control* ctl,
+                              void* stream) {
+    SNN_REQUIRE(ema, "snn_ema_update: ema is NULL");
+    SNN_REQUIRE(src, "snn_ema_update: src is NULL");
+    SNN_REQUIRE(n > 0, "snn_ema_update: n = %lld must be positive", (long long)n);
+    SNN_REQUIRE(ema_weight_ok(ema_weight), "snn_ema_update: ema_weight = %g is outside (0, 1]", (double)ema_weight);
+    SNN_REQUIRE(aligned(4, {ctl}), "snn_ema_update: the control record must be 4-byte aligned");
+    hipLaunchKernelGGL(k_ema_update, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, ema, src, n, ema_weight,
+                       ctl);
+    SNN_CHECK_LAUNCH("snn_ema_update");
     return 0;
 }
 

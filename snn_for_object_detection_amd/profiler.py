@@ -185,6 +185,10 @@ def work_of(name: str, a):
         return "k_adamax", 8.0 * a[4], 28.0 * a[4]
     if name == "snn_adamax_step_ctl":
         return "k_adamax_ctl", 12.0 * a[4], 28.0 * a[4]
+    if name == "snn_adamax_step_ema":   # the step plus a read and a write of the weight average
+        return "k_adamax_ema", 15.0 * a[5], 36.0 * a[5]
+    if name == "snn_ema_update":        # ema read and written, src read
+        return "k_ema_update", 3.0 * a[2], 12.0 * a[2]
     if name == "snn_activity_count":   # one read of the source: fp32 / bf16 elements, or one bit per neuron (kind 4)
         kind, T, M, C = a[1], a[4], a[5], a[6]
         label = "k_activity_count" + (", mask" if kind == 4 else (", bf16s" if kind in (1, 3) else ""))

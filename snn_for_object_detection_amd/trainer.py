@@ -15,8 +15,10 @@ Here, per process (= per GPU):
 ``torch.distributed`` is the transport only (backend ``nccl`` = RCCL on ROCm, ``gloo`` in CPU tests).
 """
 
+import contextlib
+import math
 import weakref
-from typing import Dict, Iterable, List, Optional, Tuple
+from typing import Callable, Dict, Iterable, List, Optional, Tuple, Union
 
 import torch
 import torch.distributed as dist
@@ -36,6 +38,24 @@ def _storage_view(flat: torch.Tensor, offset: int, like: torch.Tensor) -> torch.
     return chunk.view(like.shape)
 
 
+def warmup_cosine(base_lr: float, warmup_steps: int, total_steps: int, final_ratio: float = 0.01) -> Callable[[int], float]:
+    """Learning-rate schedule ``k -> lr`` for ``FlatTrainer(lr=...)``, k = successful optimiser steps so far: linear from
+    ``base_lr / warmup_steps`` (k = 0) up to ``base_lr`` (k = warmup_steps - 1), then half a cosine from ``base_lr``
+    (k = warmup_steps) down to ``final_ratio * base_lr`` (k >= total_steps)."""
+    if not base_lr > 0 or not 0 <= final_ratio <= 1:
+        raise ValueError(f"warmup_cosine: base_lr must be positive and final_ratio in [0, 1], not {base_lr}, {final_ratio}")
+    if warmup_steps < 0 or total_steps <= warmup_steps:
+        raise ValueError(f"warmup_cosine: need 0 <= warmup_steps < total_steps, not {warmup_steps}, {total_steps}")
+
+    def schedule(k: int) -> float:
+        if k < warmup_steps:
+            return base_lr * (k + 1) / warmup_steps
+        progress = min(1.0, (k - warmup_steps) / (total_steps - warmup_steps))
+        return base_lr * (final_ratio + (1.0 - final_ratio) * 0.5 * (1.0 + math.cos(math.pi * progress)))
+
+    return schedule
+
+
 class FlatTrainer:
     """Owns the flat parameter / gradient / optimiser-state buffers of a model.
 
@@ -43,11 +63,21 @@ class FlatTrainer:
     (all-reduce across ``process_group`` when world_size > 1, then fused Adamax).
     """
 
-    def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+    def __init__(self, model: torch.nn.Module, lr: Union[float, Callable[[int], float]] = 1e-3, betas=(0.9, 0.999),
+                 eps: float = 1e-8,
                  process_group=None, use_grad_slots: bool = True, broadcast_buffers: bool = False,
                  overlap_grad_exchange: bool = True, exchange_single_rank: bool = False,
                  find_unused_parameters: bool = True, gradient_clip_val: Optional[float] = None,
-                 gradient_clip_algorithm: str = "norm", skip_nonfinite: bool = False, weight_decay: float = 0.0):
+                 gradient_clip_algorithm: str = "norm", skip_nonfinite: bool = False, weight_decay: float = 0.0,
+                 ema_decay: Optional[float] = None, ema_warmup: int = 2000):
+        # ``lr``: a float, or a schedule ``k -> lr`` evaluated in ``step()`` at k = successful steps so far (``warmup_cosine``)
+        # ``ema_decay`` (None: no average): exponential moving average of the weights and the floating-point buffers, kept
+        # inside the fused step (``snn_adamax_step_ema``); ``ema_warmup``: time constant, in updates, of the ramp
+        # ``ema_decay_at`` that lets the young average follow the weights - see ``averaged_weights()``
+        if ema_decay is not None and not 0 <= ema_decay < 1:
+            raise ValueError(f"FlatTrainer: ema_decay must be in [0, 1) (None: no weight average), not {ema_decay}")
+        if not isinstance(ema_warmup, int) or isinstance(ema_warmup, bool) or ema_warmup < 0:
+            raise ValueError(f"FlatTrainer: ema_warmup must be a non-negative number of updates, not {ema_warmup!r}")
         # Lightning's ``gradient_clip_val`` / ``gradient_clip_algorithm`` ("norm": clip_grad_norm_, 2-norm over all
         # parameters; "value": clip_grad_value_), applied to the AVERAGED gradient inside ``step()`` - see ``step()``
         if gradient_clip_algorithm not in ("norm", "value"):
@@ -181,6 +211,20 @@ class FlatTrainer:
         self._float_buffers = [b for b in model.buffers() if b.is_floating_point()]
         self._int_buffers = [b for b in model.buffers() if not b.is_floating_point() and b.numel() == 1]
         self.broadcast_buffers = broadcast_buffers
+        # the weight average: ``flat_ema`` in the layout of ``flat_param``, ``ema_buffers`` every floating-point buffer in
+        # ``_float_buffers`` order in one flat fp32 tensor.  Without ``ema_decay`` neither exists.
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = ema_warmup
+        self.ema_updates = 0          # updates the average has taken; a skipped step gives its update back
+        self.flat_ema = self.ema_buffers = None
+        self._averaged = False        # inside ``averaged_weights()``
+        self._ema_buffer_offsets = [0]
+        for b in self._float_buffers:
+            self._ema_buffer_offsets.append(self._ema_buffer_offsets[-1] + b.numel())
+        if self.ema_decay is not None:
+            self.flat_ema = torch.empty_like(self.flat_param)
+            self.ema_buffers = torch.empty(self._ema_buffer_offsets[-1], device=dev, dtype=torch.float32)
+            self.reset_ema()
         # gradient exchange overlapped with the backward pass: see ``overlap_from``
         self._early_lo: Optional[int] = None
         self._early_first: Optional[int] = None
@@ -364,6 +408,7 @@ class FlatTrainer:
 
     # ------------------------------------------------------------------
     def zero_grad(self) -> None:
+        self._refuse_while_averaged("zero_grad")
         if self.flat_grad.is_cuda:
             wgrad_stream_sync()  # nothing may still be writing into the buffer that is about to be cleared
         if self._early_work is not None:   # a backward pass whose step() never came: let its collective finish first
@@ -456,6 +501,19 @@ class FlatTrainer:
             ranges[0] = (0, self.flat_param.numel(), ranges[0][2])   # include the padding: whole 16-byte groups
         return ranges
 
+    def _unwritten_ranges(self, written: List[bool]) -> List[Tuple[int, int]]:
+        """``(lo, hi)`` element ranges of the parameters without a gradient this step, adjacent ones coalesced."""
+        ranges: List[Tuple[int, int]] = []
+        for k, w in enumerate(written):
+            if w:
+                continue
+            lo, hi = self._offsets[k], self._offsets[k + 1]
+            if ranges and ranges[-1][1] == lo:
+                ranges[-1] = (ranges[-1][0], hi)
+            else:
+                ranges.append((lo, hi))
+        return ranges
+
     def _check_bindings(self) -> None:
         """``model.to(...)`` / ``model.float()`` / a manual ``p.data = ...`` would silently detach a parameter from
         the flat buffer (the optimiser would then update memory the model no longer reads)."""
@@ -465,12 +523,15 @@ class FlatTrainer:
                 raise RuntimeError("FlatTrainer: a parameter no longer lives in the flat parameter buffer (the model "
                                    "was moved or re-cast after the trainer was built); build a new FlatTrainer")
 
-    def sync_buffers(self, src: int = 0) -> None:
-        """Rank ``src``'s BatchNorm buffers to every rank in one broadcast (torch DDP's ``broadcast_buffers``)."""
+    def sync_buffers(self, src: int = 0, with_average: bool = False) -> None:
+        """Rank ``src``'s BatchNorm buffers to every rank in one broadcast (torch DDP's ``broadcast_buffers``);
+        ``with_average``: the averaged buffers (``ema_buffers``) travel in the same broadcast."""
         if not self.exchange or not (self._float_buffers or self._int_buffers):
             return
+        with_average = with_average and self.ema_buffers is not None
         flat = torch.cat([b.detach().reshape(-1).float() for b in self._float_buffers]
-                         + [b.detach().reshape(-1).float() for b in self._int_buffers])
+                         + [b.detach().reshape(-1).float() for b in self._int_buffers]
+                         + ([self.ema_buffers] if with_average else []))
         dist.broadcast(flat, src=src, group=self.group)
         off = 0
         with torch.no_grad():
@@ -478,6 +539,8 @@ class FlatTrainer:
                 n = b.numel()
                 b.copy_(flat[off:off + n].view(b.shape).to(b.dtype))
                 off += n
+            if with_average:
+                self.ema_buffers.copy_(flat[off:])
 
     def _reconcile_skip(self) -> None:
         """Take the last step's ``finite`` word (copied to pinned memory behind its norm kernel) and, if that step was
@@ -493,6 +556,8 @@ class FlatTrainer:
             self._skipped += 1
             for k in advanced:
                 self.param_steps[k] -= 1
+            if self.flat_ema is not None:   # the average took no update either: the next one uses this step's decay
+                self.ema_updates -= 1
 
     @property
     def last_grad_norm(self) -> torch.Tensor:
@@ -518,11 +583,17 @@ class FlatTrainer:
         Clipping sits here and not in the caller's hands because only here the sum over the ranks is complete; the
         summed buffer is the same on every rank, so every rank clips by the same factor and skips the same steps
         without another collective.  A record that says "not finite" makes every Adamax launch of the step store
-        nothing (norm clipping implies it: a clip factor from a non-finite norm means nothing)."""
+        nothing (norm clipping implies it: a clip factor from a non-finite norm means nothing).
+        With ``ema_decay`` the Adamax launches are ``snn_adamax_step_ema`` - the same parameter and moment bits, plus the
+        weight average moved towards the parameter just written - and ``snn_ema_update`` moves the average of the
+        parameters without a gradient and of the floating-point buffers; all of them obey the same record."""
+        self._refuse_while_averaged("step")
         if not self.flat_param.is_cuda:
             raise RuntimeError("FlatTrainer.step: parameters are not on a HIP device; the optimiser kernel has no "
                                "CPU fallback")
         self._reconcile_skip()
+        # a schedule sees the count of SUCCESSFUL steps: exact here, the last step's skip flag has just been taken
+        lr = self.lr(self.step_count - self._skipped) if callable(self.lr) else self.lr
         wgrad_stream_sync()  # weight-gradient kernels run on a side stream (functional._Conv2d.backward)
         self._check_bindings()
         self._collect_autograd_grads()
@@ -544,14 +615,31 @@ class FlatTrainer:
                       self.gradient_clip_val if self._norm_clip else 0.0, self._norm_ws.data_ptr(), ctl, st)
         clip_value = self.gradient_clip_val if (self.gradient_clip_val is not None and not self._norm_clip) else 0.0
         plain = ctl is None and clip_value == 0.0 and self.weight_decay == 0.0
+        ema_weight = None
+        if self.flat_ema is not None:
+            # every launch below that touches the average reads the step's control record: a skipped step leaves the
+            # average alone on the device, and ``_reconcile_skip()`` gives the update count back one step later
+            self.ema_updates += 1
+            ema_weight = 1.0 - self.ema_decay_at(self.ema_updates)   # in double; rounded to fp32 once, at the call
         for lo, hi, stp in self._ranges(written):
-            args = (self.flat_param.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + 4 * lo,
-                    self.exp_avg.data_ptr() + 4 * lo, self.exp_inf.data_ptr() + 4 * lo, hi - lo, self.lr,
-                    self.betas[0], self.betas[1], self.eps, stp, grad_scale)
-            if plain:
-                _hip.call("snn_adamax_step", *args, st)
+            moments = (self.flat_param.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + 4 * lo,
+                       self.exp_avg.data_ptr() + 4 * lo, self.exp_inf.data_ptr() + 4 * lo)
+            hyper = (hi - lo, lr, self.betas[0], self.betas[1], self.eps, stp, grad_scale)
+            if ema_weight is not None:
+                _hip.call("snn_adamax_step_ema", *moments, self.flat_ema.data_ptr() + 4 * lo, *hyper, self.weight_decay,
+                          clip_value, ema_weight, ctl, st)
+            elif plain:
+                _hip.call("snn_adamax_step", *moments, *hyper, st)
             else:
-                _hip.call("snn_adamax_step_ctl", *args, self.weight_decay, clip_value, ctl, st)
+                _hip.call("snn_adamax_step_ctl", *moments, *hyper, self.weight_decay, clip_value, ctl, st)
+        if ema_weight is not None:
+            # Adamax leaves a parameter without a gradient alone; the average still moves towards it
+            for lo, hi in self._unwritten_ranges(written):
+                _hip.call("snn_ema_update", self.flat_ema.data_ptr() + 4 * lo, self.flat_param.data_ptr() + 4 * lo, hi - lo,
+                          ema_weight, ctl, st)
+            if self._float_buffers:
+                live = self._live_buffers_flat()   # one torch.cat, as in sync_buffers
+                _hip.call("snn_ema_update", self.ema_buffers.data_ptr(), live.data_ptr(), live.numel(), ema_weight, ctl, st)
         if ctl is not None:
             # the host learns whether the step was skipped one step late: no synchronisation here
             self._finite_host.copy_(self._ctl[2:3], non_blocking=True)
@@ -565,10 +653,127 @@ class FlatTrainer:
     # ------------------------------------------------------------------ checkpoint / resume
     def checkpoint(self, model: torch.nn.Module) -> Dict:
         """``{"model": ..., "optimizer": ...}`` with the BatchNorm buffers made equal on all ranks first (rank 0's, as
-        torch DDP leaves them) - what a reference Lightning checkpoint carries."""
+        torch DDP leaves them) - what a reference Lightning checkpoint carries.  With a weight average, additionally
+        ``"ema": ema_state_dict(model)`` (its buffer average made equal on all ranks in the same broadcast)."""
+        self._refuse_while_averaged("checkpoint")
         self.synchronize()
-        self.sync_buffers()
-        return {"model": {k: v.detach().clone() for k, v in model.state_dict().items()}, "optimizer": self.state_dict()}
+        self.sync_buffers(with_average=True)
+        ckpt = {"model": {k: v.detach().clone() for k, v in model.state_dict().items()}, "optimizer": self.state_dict()}
+        if self.flat_ema is not None:
+            ckpt["ema"] = self.ema_state_dict(model)
+        return ckpt
+
+    # ------------------------------------------------------------------ weight average (EMA)
+    def _refuse_while_averaged(self, what: str) -> None:
+        if self._averaged:
+            raise RuntimeError(f"FlatTrainer.{what}: not inside averaged_weights() - the parameters hold the weight average "
+                               "there, and the live weights sit in its place; leave the block first")
+
+    def _require_average(self, what: str) -> None:
+        if self.flat_ema is None:
+            raise RuntimeError(f"FlatTrainer.{what}: this trainer keeps no weight average (built without ema_decay)")
+
+    def ema_decay_at(self, k: int) -> float:
+        """Decay of the k-th update of the average (k from 1): ``ema_decay * (1 - exp(-k / ema_warmup))``, the ramp of the
+        YOLO-family recipes - the young average follows the weights instead of remembering the initialisation for
+        1 / (1 - decay) steps - or ``ema_decay`` itself with ``ema_warmup == 0``."""
+        self._require_average("ema_decay_at")
+        if self.ema_warmup == 0:
+            return self.ema_decay
+        return self.ema_decay * (1.0 - math.exp(-k / self.ema_warmup))
+
+    def _live_buffers_flat(self) -> torch.Tensor:
+        if not self._float_buffers:
+            return torch.empty(0, device=self.flat_param.device, dtype=torch.float32)
+        return torch.cat([b.detach().reshape(-1).float() for b in self._float_buffers])
+
+    def reset_ema(self) -> None:
+        """The average becomes a fresh copy of the live weights and buffers and has taken no update."""
+        self._require_average("reset_ema")
+        self._refuse_while_averaged("reset_ema")
+        self._reconcile_skip()   # (a flag still on its way belongs to the average that is being replaced)
+        self.flat_ema.copy_(self.flat_param)
+        self.ema_buffers.copy_(self._live_buffers_flat())
+        self.ema_updates = 0
+
+    def _exchange_with_average(self) -> None:
+        """Exchange the CONTENTS of ``flat_param`` / ``flat_ema`` and of the live float buffers / ``ema_buffers`` in place
+        (every ``p.data`` view and every buffer object stays bound), then rebuild the weight images the kernels read."""
+        with torch.no_grad():
+            keep = self.flat_param.clone()
+            self.flat_param.copy_(self.flat_ema)
+            self.flat_ema.copy_(keep)
+            keep = self._live_buffers_flat()
+            for b, lo, hi in zip(self._float_buffers, self._ema_buffer_offsets[:-1], self._ema_buffer_offsets[1:]):
+                b.copy_(self.ema_buffers[lo:hi].view(b.shape))
+            self.ema_buffers.copy_(keep)
+        if self.flat_param.is_cuda:
+            self.refresh_transposed_weights()   # the weights changed behind torch's version counters
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """``with trainer.averaged_weights(): ...`` - inside, the model's parameters and floating-point buffers hold the
+        weight average (validate, export); after the block the live values are back bit for bit.  The contents are
+        exchanged in place and the transposes, pre-split pieces, fragment images and composed 1x1 products are rebuilt on
+        entry and on exit, so every kernel reads the weights the parameters show.  ``step()``, ``zero_grad()``,
+        ``checkpoint()`` and a nested ``averaged_weights()`` raise inside; ``model.eval()`` is the caller's business."""
+        self._require_average("averaged_weights")
+        self._refuse_while_averaged("averaged_weights")
+        self.synchronize()   # side streams and an exchange in flight: nothing may still read or write what moves
+        self._exchange_with_average()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._averaged = False
+            self._exchange_with_average()
+
+    def ema_state_dict(self, model: torch.nn.Module) -> Dict:
+        """``{"decay", "warmup", "updates", "model"}``; ``"model"`` has every key of ``model.state_dict()``: averaged
+        trainable parameters (logical shapes) and floating-point buffers, live integer buffers and frozen parameters -
+        ``fresh_model.load_state_dict(sd["model"])`` deploys the average."""
+        self._require_average("ema_state_dict")
+        self._refuse_while_averaged("ema_state_dict")
+        self._reconcile_skip()
+        buffer_range = {id(b): (lo, hi) for b, lo, hi in zip(self._float_buffers, self._ema_buffer_offsets[:-1],
+                                                              self._ema_buffer_offsets[1:])}
+        out = {}
+        for name, v in model.state_dict(keep_vars=True).items():
+            if id(v) in self._offset_of:
+                out[name] = _storage_view(self.flat_ema, self._offset_of[id(v)], v.data).clone()
+            elif id(v) in buffer_range:
+                lo, hi = buffer_range[id(v)]
+                out[name] = self.ema_buffers[lo:hi].view(v.shape).to(v.dtype).clone()
+            else:
+                out[name] = v.detach().clone()
+        return {"decay": self.ema_decay, "warmup": self.ema_warmup, "updates": self.ema_updates, "model": out}
+
+    def load_ema_state_dict(self, sd: Dict, model: torch.nn.Module) -> None:
+        """Inverse of ``ema_state_dict``: decay, ramp, update count and the average itself (the live weights, integer
+        buffers and frozen parameters of ``sd["model"]`` are the model's own checkpoint's business)."""
+        self._require_average("load_ema_state_dict")
+        self._refuse_while_averaged("load_ema_state_dict")
+        decay, warmup = float(sd["decay"]), sd["warmup"]
+        if not 0 <= decay < 1 or not isinstance(warmup, int) or warmup < 0:
+            raise ValueError(f"FlatTrainer.load_ema_state_dict: decay {sd['decay']!r} / warmup {warmup!r} out of range")
+        self._reconcile_skip()   # (a flag still on its way belongs to the average that is being replaced)
+        buffer_range = {id(b): (lo, hi) for b, lo, hi in zip(self._float_buffers, self._ema_buffer_offsets[:-1],
+                                                              self._ema_buffer_offsets[1:])}
+        for name, v in model.state_dict(keep_vars=True).items():
+            if id(v) not in self._offset_of and id(v) not in buffer_range:
+                continue
+            if name not in sd["model"]:
+                raise RuntimeError(f"FlatTrainer.load_ema_state_dict: the average has no entry {name!r}")
+            t = sd["model"][name]
+            if tuple(t.shape) != tuple(v.shape):
+                raise RuntimeError(f"FlatTrainer.load_ema_state_dict: {name} has shape {tuple(t.shape)}, the model's "
+                                   f"{tuple(v.shape)}")
+            if id(v) in self._offset_of:
+                _storage_view(self.flat_ema, self._offset_of[id(v)], v.data).copy_(t)
+            else:
+                lo, hi = buffer_range[id(v)]
+                self.ema_buffers[lo:hi].view(v.shape).copy_(t)
+        self.ema_decay, self.ema_warmup, self.ema_updates = decay, warmup, int(sd["updates"])
 
     def state_dict(self) -> Dict:
         """Optimiser state in ``torch.optim.Adamax.state_dict()`` form: ``state[k] = {step, exp_avg, exp_inf}`` for the
@@ -584,7 +789,9 @@ class FlatTrainer:
             state[k] = {"step": torch.tensor(float(self.param_steps[k])),
                         "exp_avg": _storage_view(self.exp_avg, self._offsets[k], p.data).clone(),
                         "exp_inf": _storage_view(self.exp_inf, self._offsets[k], p.data).clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+        # (a schedule: the value the next step would use - torch's format holds a number)
+        lr = self.lr(self.step_count - self._skipped) if callable(self.lr) else self.lr
+        group = {"lr": lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
                  "foreach": None,
                  "maximize": False, "differentiable": False, "capturable": False,
                  "params": list(range(len(self.params)))}
@@ -601,7 +808,9 @@ class FlatTrainer:
         if not weight_decay >= 0:
             raise ValueError(f"FlatTrainer: weight_decay must not be negative, not {weight_decay}")
         self._reconcile_skip()   # (a flag still on its way belongs to the state that is being replaced)
-        self.lr, self.betas, self.eps = group["lr"], tuple(group["betas"]), group["eps"]
+        if not callable(self.lr):   # a schedule stays: it is a function of the step count restored below
+            self.lr = group["lr"]
+        self.betas, self.eps = tuple(group["betas"]), group["eps"]
         self.weight_decay = weight_decay
         self.param_steps = [0] * len(self.params)
         self.exp_avg.zero_()
@@ -617,7 +826,8 @@ class FlatTrainer:
                                        f"{tuple(p.shape)}")
                 _storage_view(flat, self._offsets[k], p.data).copy_(t)
             self.param_steps[k] = int(float(st["step"]))
-        self.step_count = max(self.param_steps) if self.param_steps else 0
+        # ``step_count`` counts attempts: the successful steps of the loaded state plus what this trainer has skipped
+        self.step_count = (max(self.param_steps) if self.param_steps else 0) + self._skipped
 
     # ------------------------------------------------------------------ helpers for tests / checkpoints
     def synchronize(self) -> None:
@@ -659,8 +869,11 @@ def convert_sync_batchnorm(model: torch.nn.Module, process_group=None) -> torch.
 
 
 def broadcast_parameters(trainer: FlatTrainer, src: int = 0) -> None:
-    """Make every rank start from rank ``src``'s weights (DDP does this at construction)."""
+    """Make every rank start from rank ``src``'s weights (DDP does this at construction).  A weight average restarts from
+    them (it would otherwise start from each rank's own initialisation and stay different on every rank)."""
     if trainer.exchange:
         dist.broadcast(trainer.flat_param, src=src, group=trainer.group)
         if trainer.flat_param.is_cuda:
             trainer.refresh_transposed_weights()  # the weights changed behind torch's version counters
+    if trainer.flat_ema is not None:
+        trainer.reset_ema()
