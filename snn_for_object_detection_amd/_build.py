@@ -28,9 +28,9 @@ LIB_NAME = "libsnn_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 STAMP_PATH = LIB_PATH + ".buildstamp"
 # (the longest compiles first: the pool starts them at once and the short ones fill in around them)
-SOURCES = ("scan_bwd.hip", "conv_gather.hip", "conv_wgrad.hip", "conv_first.hip", "elementwise.hip", "bn_stats.hip",
-           "scan_fwd.hip", "bn_bwd.hip", "wgrad_halo.hip", "conv_halo.hip", "detect.hip", "targets.hip", "metrics.hip",
-           "lstm.hip", "activity.hip", "events_packed.hip", "det_loss.hip")
+SOURCES = ("scan_bwd.hip", "conv_gather.hip", "conv_wgrad.hip", "conv_first.hip", "bn_stats.hip", "scan_fwd.hip",
+           "bn_bwd.hip", "wgrad_halo.hip", "conv_halo.hip", "activity.hip", "det_loss.hip", "lstm.hip", "elementwise.hip",
+           "small_gemm.hip", "targets.hip", "metrics.hip", "abi.hip", "detect.hip", "events.hip", "optimizer.hip")
 MAX_WORKERS = 8   # hipcc processes at once: a fixed cap, never the machine's CPU count
 
 

@@ -12,11 +12,58 @@
 // The weight is not shared between the waves of a workgroup (each wave reads only the rows of its own channels), so it
 // goes from L2 straight to registers, one block ahead of the MFMAs that use it; the [x ; h] operand tile lives in LDS,
 // double-buffered, so a step costs one barrier.  No atomics, fixed reduction order: the same inputs give the same bits.
+//
+// In front of the scan: the single-step cell kernels (snn_lstm_cell_fwd / _bwd), pointwise over gates the caller's
+// convolution has already formed.
 #include <limits.h>
 #include "snn_common.h"
 
 namespace {
 
+// ------------------------------------------------------------------------------------------ ConvLSTM cell
+// gates[m][4C] = (input, forget, output, candidate) pre-activations, conv_lstm.py:66-76 (sigmoidf_: snn_common.h)
+constexpr int kThreads = 256;   // (of the cell kernels; the scan's block is 4 * Ch threads)
+
+__global__ void k_lstm_fwd(const float* __restrict__ gates, const float* __restrict__ c_prev, float* __restrict__ h,
+                           float* __restrict__ c, int64_t M, int C) {
+    const int64_t total = M * C;
+    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
+        const int64_t m = e / C;
+        const int ch = (int)(e % C);
+        const float* g = gates + m * 4 * C;
+        const float I = sigmoidf_(g[ch]), F = sigmoidf_(g[C + ch]), O = sigmoidf_(g[2 * C + ch]);
+        const float G = tanhf(g[3 * C + ch]);
+        const float cp = c_prev ? c_prev[e] : 0.0f;
+        const float cn = F * cp + I * G;
+        c[e] = cn;
+        h[e] = O * tanhf(cn);
+    }
+}
+
+__global__ void k_lstm_bwd(const float* __restrict__ gates, const float* __restrict__ c_prev,
+                           const float* __restrict__ c, const float* __restrict__ gh, const float* __restrict__ gc,
+                           float* __restrict__ g_gates, float* __restrict__ g_c_prev, int64_t M, int C) {
+    const int64_t total = M * C;
+    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
+        const int64_t m = e / C;
+        const int ch = (int)(e % C);
+        const float* g = gates + m * 4 * C;
+        const float I = sigmoidf_(g[ch]), F = sigmoidf_(g[C + ch]), O = sigmoidf_(g[2 * C + ch]);
+        const float G = tanhf(g[3 * C + ch]);
+        const float tc = tanhf(c[e]);
+        const float dh = gh ? gh[e] : 0.0f;
+        const float dc = (gc ? gc[e] : 0.0f) + dh * O * (1.0f - tc * tc);
+        const float cp = c_prev ? c_prev[e] : 0.0f;
+        float* d = g_gates + m * 4 * C;
+        d[ch] = (dc * G) * (I * (1.0f - I));
+        d[C + ch] = (dc * cp) * (F * (1.0f - F));
+        d[2 * C + ch] = (dh * tc) * (O * (1.0f - O));
+        d[3 * C + ch] = (dc * I) * (1.0f - G * G);
+        if (g_c_prev) g_c_prev[e] = dc * F;
+    }
+}
+
+// ------------------------------------------------------------------------------------------ sequence scan
 constexpr int kMinCh = 16, kMaxCh = 256, kMaxCin = 256;
 constexpr int kPad = 4;   // floats added to an LDS row: rows are = 4 (mod 16) floats apart, 16-byte row reads are conflict-free
 
@@ -299,6 +346,23 @@ template <class Kernel> int allow_lds(Kernel kernel, size_t bytes, const char* n
 }
 
 }  // namespace
+
+extern "C" int snn_lstm_cell_fwd(const float* gates, const float* c_prev, float* h, float* c, int64_t M, int C,
+                                 void* stream) {
+    SNN_REQUIRE(gates && h && c && M > 0 && C > 0, "snn_lstm_cell_fwd: bad arguments");
+    hipLaunchKernelGGL(k_lstm_fwd, dim3(snn_grid_for(M * C, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, gates,
+                       c_prev, h, c, M, C);
+    SNN_CHECK_LAUNCH("snn_lstm_cell_fwd");
+    return 0;
+}
+extern "C" int snn_lstm_cell_bwd(const float* gates, const float* c_prev, const float* c, const float* gh,
+                                 const float* gc, float* g_gates, float* g_c_prev, int64_t M, int C, void* stream) {
+    SNN_REQUIRE(gates && c && g_gates && M > 0 && C > 0, "snn_lstm_cell_bwd: bad arguments");
+    hipLaunchKernelGGL(k_lstm_bwd, dim3(snn_grid_for(M * C, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, gates,
+                       c_prev, c, gh, gc, g_gates, g_c_prev, M, C);
+    SNN_CHECK_LAUNCH("snn_lstm_cell_bwd");
+    return 0;
+}
 
 extern "C" int snn_convlstm_seq_supported(int Cin, int Ch, int64_t ldx) {
     return Ch >= kMinCh && Ch <= kMaxCh && Ch % 16 == 0 && Cin >= 1 && Cin <= kMaxCin && ldx >= Cin;

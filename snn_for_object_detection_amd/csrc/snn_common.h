@@ -45,6 +45,13 @@ static inline int snn_num_cu() {
     return 256;
 }
 static inline int snn_max_blocks() { return snn_num_cu() * 8; }
+// the 1-D grid of such a kernel: one thread per element in blocks of `threads`, at least one block, at most the cap
+static inline unsigned snn_grid_for(int64_t n, int threads) {
+    int64_t b = snn_ceil_div(n, threads);
+    if (b > snn_max_blocks()) b = snn_max_blocks();
+    if (b < 1) b = 1;
+    return (unsigned)b;
+}
 
 constexpr int kMaxLabelSteps = 32;   // frame slots per sample (K) of the *_steps entry points (targets.hip, det_loss.hip)
 
@@ -120,7 +127,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // activation tensor in HBM is fp32, or bf16 = the upper half of the fp32 pattern, rounded to nearest even when stored.
 // Kernels compute in fp32 registers either way; SnnStore<BF> moves 1 or 4 consecutive elements at ELEMENT index i.
 #ifdef __HIPCC__
-// the ConvLSTM gate non-linearity, shared by the cell kernels (elementwise.hip) and the sequence scan (lstm.hip)
+// the ConvLSTM gate non-linearity, shared by the cell kernels and the sequence scan (both in lstm.hip)
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 typedef unsigned snn_u32x2 __attribute__((ext_vector_type(2)));

@@ -246,7 +246,6 @@ __global__ __launch_bounds__(kGatherThreads) void k_gather_steps_bwd(const float
     }
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static int gather_blocks(int64_t total) {
     int64_t b = snn_ceil_div(total, (int64_t)kGatherThreads);
     const int64_t cap = (int64_t)snn_num_cu() * 8;
@@ -266,7 +265,7 @@ extern "C" int snn_roi_assign(const float* anchors, const float* labels, int B, 
     SNN_REQUIRE(anchors && labels && workspace && bbox_offset && bbox_mask && class_labels, "snn_roi_assign: null pointer");
     // flat IoU indices are int, and the strided argmax loop steps kRoiThreads past the last one before it stops
     SNN_REQUIRE(B > 0 && A > 0 && N > 0 && (int64_t)A * N < 0x7fffffffLL - kRoiThreads, "snn_roi_assign: bad shape");
-    SNN_REQUIRE(aligned16(anchors) && aligned16(bbox_offset) && aligned16(bbox_mask) && aligned16(workspace),
+    SNN_REQUIRE(aligned(16, {anchors, bbox_offset, bbox_mask, workspace}),
                 "snn_roi_assign: buffers must be 16-byte aligned");
     float* iou = static_cast<float*>(workspace);
     int* amap = reinterpret_cast<int*>(iou + (size_t)B * A * N);
@@ -287,7 +286,7 @@ extern "C" int snn_label_steps(const float* labels, int B, int N, int T, int K, 
 }
 
 static bool gather_vec(const float* a, int64_t ld_a, const float* b, int64_t ld_b, int C) {
-    return C % 4 == 0 && ld_a % 4 == 0 && ld_b % 4 == 0 && aligned16(a) && aligned16(b);
+    return C % 4 == 0 && ld_a % 4 == 0 && ld_b % 4 == 0 && aligned(16, {a, b});
 }
 
 extern "C" int snn_gather_steps_fwd(const float* src, int64_t ld_src, const int* steps, float* dst, int64_t ld_dst, int T,
@@ -341,7 +340,7 @@ extern "C" int snn_roi_assign_steps(const float* anchors, const float* labels, c
     SNN_REQUIRE(B > 0 && A > 0 && N > 0 && t0 >= 0 && (int64_t)A * N < 0x7fffffffLL - kRoiThreads,
                 "snn_roi_assign_steps: bad shape");
     SNN_REQUIRE(K >= 1 && K <= kMaxLabelSteps, "snn_roi_assign_steps: K must be in 1 .. %d", kMaxLabelSteps);
-    SNN_REQUIRE(aligned16(anchors) && aligned16(bbox_offset) && aligned16(bbox_mask) && aligned16(workspace),
+    SNN_REQUIRE(aligned(16, {anchors, bbox_offset, bbox_mask, workspace}),
                 "snn_roi_assign_steps: buffers must be 16-byte aligned");
     const size_t slots = (size_t)K * B;
     float* iou = static_cast<float*>(workspace);

@@ -193,9 +193,7 @@ class EventBatcher:
         (numpy, a memory map included, or torch): the slices are copied into a persistent pinned staging buffer, one H2D
         copy carries the events (8 bytes each) and one ``offsets | t0 | table``, one ``snn_events_to_frames_packed`` launch
         unpacks, bins and transforms.  ``table`` None: the kernel reads no table."""
-        from . import functional as _HF
         B = len(samples)
-        T, H, W = self.T, self.H, self.W
         if self.step <= 0:
             raise ValueError(f"EventBatcher: time_step_us must be positive, got {self.step}")
         words = []
@@ -213,26 +211,67 @@ class EventBatcher:
             if c:
                 slot["words_np"][at:at + c] = w
                 at += c
-        meta = slot["meta"][:meta_len]
+        if slot["done"] is None:
+            slot["done"] = torch.cuda.Event()   # recorded behind this call's copies: the slot is rewritten only after it
+
+        def copy_events():
+            ev = torch.empty((max(n, 1), 2), device=self.device, dtype=torch.int32)
+            if n:
+                ev[:n].copy_(slot["words"][:n], non_blocking=True)
+            return [ev]
+
+        return self._scatter_batch("snn_events_to_frames_packed", counts, [int(s[1]) for s in samples], table, labels,
+                                   slot["meta"][:meta_len], copy_events, done=slot["done"])
+
+    def _augmented(self, samples, labels, table: torch.Tensor):
+        """Four copies per sample into slices of the batch's event arrays, ``offsets | t0 | table`` in one small pinned
+        tensor, one ``snn_events_to_frames_aug`` launch that bins and transforms, one ``snn_labels_augment`` launch."""
+        B = len(samples)
+        if self.step <= 0:
+            raise ValueError(f"EventBatcher: time_step_us must be positive, got {self.step}")
+        counts = [int(s[0].numel()) for s in samples]
+        n = sum(counts)
+        meta = torch.empty(6 * B + 1, dtype=torch.int64, pin_memory=True)   # offsets[B + 1] | t0[B] | table[B][8] (int32)
+
+        def copy_events():
+            ev = [torch.empty(max(n, 1), device=self.device, dtype=d)
+                  for d in (torch.int64, torch.int32, torch.int32, torch.int32)]
+            at = 0
+            for sample, c in zip(samples, counts):
+                if c:
+                    for dst, src in zip(ev, sample[:4]):
+                        dst[at:at + c].copy_(src, non_blocking=True)
+                    at += c
+            return ev
+
+        return self._scatter_batch("snn_events_to_frames_aug", counts, [int(s[4]) for s in samples], table, labels, meta,
+                                   copy_events)
+
+    def _scatter_batch(self, entry: str, counts, t0s, table: Optional[torch.Tensor], labels, meta: torch.Tensor,
+                       copy_events, done=None):
+        """What ``_packed`` and ``_augmented`` share behind their staging: ``offsets | t0 | table`` into the pinned int64
+        ``meta``; on the copy stream the caller's ``copy_events()`` (its H2D copies -> the device event tensors of
+        ``entry``), the copy of ``meta`` (``done``, a HIP event, is recorded behind both) and the launch; the hand-over of
+        the streams, ``last_aug_table``, and the labels - augmented by the same table - on the main stream."""
+        from . import functional as _HF
+        B, n = len(counts), sum(counts)
+        T, H, W = self.T, self.H, self.W
         meta[0] = 0
         meta[1:B + 1] = torch.tensor(counts, dtype=torch.int64).cumsum(0)
-        meta[B + 1:2 * B + 1] = torch.tensor([int(s[1]) for s in samples], dtype=torch.int64)
+        meta[B + 1:2 * B + 1] = torch.tensor(t0s, dtype=torch.int64)
         if table is not None:
             meta[2 * B + 1:].view(torch.int32).copy_(table.reshape(-1))
         main = torch.cuda.current_stream(self.device)
         buf = torch.empty((T, B, H, W, 2), device=self.device, dtype=torch.float32)   # [T][B][H][W][C]
-        meta_dev = torch.empty(meta_len, device=self.device, dtype=torch.int64)
+        meta_dev = torch.empty(meta.numel(), device=self.device, dtype=torch.int64)
         self._copy_stream.wait_stream(main)
         with torch.cuda.stream(self._copy_stream):
-            ev = torch.empty((max(n, 1), 2), device=self.device, dtype=torch.int32)
-            if n:
-                ev[:n].copy_(slot["words"][:n], non_blocking=True)
+            ev = copy_events()
             meta_dev.copy_(meta, non_blocking=True)
-            if slot["done"] is None:
-                slot["done"] = torch.cuda.Event()
-            slot["done"].record(self._copy_stream)   # behind both copies: the slot is rewritten only after it
+            if done is not None:
+                done.record(self._copy_stream)
             aug_dev = meta_dev[2 * B + 1:].view(torch.int32) if table is not None else None
-            _hip.call("snn_events_to_frames_packed", ev.data_ptr(), meta_dev.data_ptr(), meta_dev[B + 1:].data_ptr(),
+            _hip.call(entry, *(v.data_ptr() for v in ev), meta_dev.data_ptr(), meta_dev[B + 1:].data_ptr(),
                       aug_dev.data_ptr() if aug_dev is not None else None, n, buf.data_ptr(), T, B, H, W, self.step,
                       self._copy_stream.cuda_stream)
             buf.record_stream(self._copy_stream)
@@ -248,52 +287,6 @@ class EventBatcher:
             if table is not None:
                 a = self.augment
                 lab = _HF.labels_augment(lab, aug_dev, W, H, *((a.min_visible, a.min_size_px) if a is not None else ()))
-        return X, lab
-
-    def _augmented(self, samples, labels, table: torch.Tensor):
-        """Four copies per sample into slices of the batch's event arrays, ``offsets | t0 | table`` in one small pinned
-        tensor, one ``snn_events_to_frames_aug`` launch that bins and transforms, one ``snn_labels_augment`` launch."""
-        from . import functional as _HF
-        B = len(samples)
-        T, H, W = self.T, self.H, self.W
-        if self.step <= 0:
-            raise ValueError(f"EventBatcher: time_step_us must be positive, got {self.step}")
-        counts = [int(s[0].numel()) for s in samples]
-        n = sum(counts)
-        meta = torch.empty(6 * B + 1, dtype=torch.int64, pin_memory=True)   # offsets[B + 1] | t0[B] | table[B][8] (int32)
-        meta[0] = 0
-        meta[1:B + 1] = torch.tensor(counts, dtype=torch.int64).cumsum(0)
-        meta[B + 1:2 * B + 1] = torch.tensor([int(s[4]) for s in samples], dtype=torch.int64)
-        meta[2 * B + 1:].view(torch.int32).copy_(table.reshape(-1))
-        main = torch.cuda.current_stream(self.device)
-        buf = torch.empty((T, B, H, W, 2), device=self.device, dtype=torch.float32)   # [T][B][H][W][C]
-        meta_dev = torch.empty(6 * B + 1, device=self.device, dtype=torch.int64)
-        self._copy_stream.wait_stream(main)
-        with torch.cuda.stream(self._copy_stream):
-            meta_dev.copy_(meta, non_blocking=True)
-            ev = [torch.empty(max(n, 1), device=self.device, dtype=d)
-                  for d in (torch.int64, torch.int32, torch.int32, torch.int32)]
-            at = 0
-            for sample, c in zip(samples, counts):
-                if c:
-                    for dst, src in zip(ev, sample[:4]):
-                        dst[at:at + c].copy_(src, non_blocking=True)
-                    at += c
-            aug_dev = meta_dev[2 * B + 1:].view(torch.int32)
-            _hip.call("snn_events_to_frames_aug", ev[0].data_ptr(), ev[1].data_ptr(), ev[2].data_ptr(), ev[3].data_ptr(),
-                      meta_dev.data_ptr(), meta_dev[B + 1:].data_ptr(), aug_dev.data_ptr(), n, buf.data_ptr(), T, B, H, W,
-                      self.step, self._copy_stream.cuda_stream)
-            buf.record_stream(self._copy_stream)
-            meta_dev.record_stream(self._copy_stream)
-        main.wait_stream(self._copy_stream)
-        self.last_aug_table = table.clone()
-        X = buf.permute(0, 1, 4, 2, 3)
-        if labels is None:
-            return X
-        with torch.cuda.stream(main):
-            lab = collate_labels(labels, B).to(self.device, non_blocking=True)
-            a = self.augment
-            lab = _HF.labels_augment(lab, aug_dev, W, H, *((a.min_visible, a.min_size_px) if a is not None else ()))
         return X, lab
 
     def _plain(self, samples, labels=None):

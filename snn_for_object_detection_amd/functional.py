@@ -2797,6 +2797,28 @@ def check_aug_table(table: torch.Tensor, B: int) -> torch.Tensor:
     return table.contiguous()
 
 
+def _check_batch_vectors(events, offsets: torch.Tensor, t0: torch.Tensor, aug: Optional[torch.Tensor], B: int,
+                         message: str) -> None:
+    """The ``(tensor, dtype, numel)`` triples of ``events`` and the batch's ``offsets[B + 1]``, ``t0[B]``, ``aug[B, 8]`` (or
+    None): every one a contiguous HIP tensor of its type and size, or ``ValueError(message)``."""
+    want = tuple(events) + ((offsets, torch.int64, B + 1), (t0, torch.int64, B))
+    if aug is not None:
+        want += ((aug, torch.int32, 8 * B),)
+    for v, dtype, n in want:
+        if not v.is_cuda or v.dtype != dtype or v.numel() != n or not v.is_contiguous():
+            raise ValueError(message)
+
+
+def _launch_batch_scatter(entry: str, events, n: int, offsets: torch.Tensor, t0: torch.Tensor,
+                          aug: Optional[torch.Tensor], T: int, B: int, H: int, W: int, step_us: int) -> torch.Tensor:
+    """Allocate ``[T][B][H][W][2]``, call the batch scatter ``entry`` on the ``events`` tensors and return the logical
+    ``[T, B, 2, H, W]`` view."""
+    buf = torch.empty((T, B, H, W, 2), device=events[0].device, dtype=_F32)
+    _hip.call(entry, *(v.data_ptr() for v in events), offsets.data_ptr(), t0.data_ptr(),
+              aug.data_ptr() if aug is not None else None, int(n), buf.data_ptr(), T, B, H, W, int(step_us), _stream())
+    return buf.permute(0, 1, 4, 2, 3)
+
+
 def events_to_frames_aug(t_us: torch.Tensor, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, offsets: torch.Tensor,
                          t0: torch.Tensor, aug: torch.Tensor, T: int, H: int, W: int, step_us: int) -> torch.Tensor:
     """``snn_events_to_frames_aug`` on device tensors: the events of a whole batch (``t_us`` int64, ``x, y, p`` int32,
@@ -2805,16 +2827,12 @@ def events_to_frames_aug(t_us: torch.Tensor, x: torch.Tensor, y: torch.Tensor, p
     B = int(t0.numel())
     if int(step_us) <= 0:
         raise ValueError(f"events_to_frames_aug: step_us must be positive, got {step_us}")
-    want = ((t_us, torch.int64, t_us.numel()), (x, torch.int32, t_us.numel()), (y, torch.int32, t_us.numel()),
-            (p, torch.int32, t_us.numel()), (offsets, torch.int64, B + 1), (t0, torch.int64, B), (aug, torch.int32, 8 * B))
-    for v, dtype, n in want:
-        if not v.is_cuda or v.dtype != dtype or v.numel() != n or not v.is_contiguous():
-            raise ValueError("events_to_frames_aug: contiguous HIP tensors t_us int64[n], x / y / p int32[n], offsets "
-                             "int64[B + 1], t0 int64[B], aug int32[B, 8] required")
-    buf = torch.empty((T, B, H, W, 2), device=t_us.device, dtype=_F32)
-    _hip.call("snn_events_to_frames_aug", t_us.data_ptr(), x.data_ptr(), y.data_ptr(), p.data_ptr(), offsets.data_ptr(),
-              t0.data_ptr(), aug.data_ptr(), t_us.numel(), buf.data_ptr(), T, B, H, W, int(step_us), _stream())
-    return buf.permute(0, 1, 4, 2, 3)
+    n = t_us.numel()
+    _check_batch_vectors(((t_us, torch.int64, n), (x, torch.int32, n), (y, torch.int32, n), (p, torch.int32, n)),
+                         offsets, t0, aug, B,
+                         "events_to_frames_aug: contiguous HIP tensors t_us int64[n], x / y / p int32[n], offsets "
+                         "int64[B + 1], t0 int64[B], aug int32[B, 8] required")
+    return _launch_batch_scatter("snn_events_to_frames_aug", (t_us, x, y, p), n, offsets, t0, aug, T, B, H, W, step_us)
 
 
 def events_to_frames_packed(words: torch.Tensor, offsets: torch.Tensor, t0: torch.Tensor, aug: Optional[torch.Tensor],
@@ -2832,16 +2850,11 @@ def events_to_frames_packed(words: torch.Tensor, offsets: torch.Tensor, t0: torc
     if (not words.is_cuda or words.dtype not in word_types or words.dim() != 2 or words.shape[1] != 2
             or not words.is_contiguous() or words.data_ptr() % 8):
         raise ValueError("events_to_frames_packed: words must be a contiguous 8-byte aligned HIP tensor uint32[n, 2]")
-    want = ((offsets, torch.int64, B + 1), (t0, torch.int64, B)) + (((aug, torch.int32, 8 * B),) if aug is not None else ())
-    for v, dtype, n in want:
-        if not v.is_cuda or v.dtype != dtype or v.numel() != n or not v.is_contiguous():
-            raise ValueError("events_to_frames_packed: contiguous HIP tensors offsets int64[B + 1], t0 int64[B], aug "
-                             "int32[B, 8] or None required")
-    buf = torch.empty((T, B, H, W, 2), device=words.device, dtype=_F32)
-    _hip.call("snn_events_to_frames_packed", words.data_ptr(), offsets.data_ptr(), t0.data_ptr(),
-              aug.data_ptr() if aug is not None else None, int(words.shape[0]), buf.data_ptr(), T, B, H, W, int(step_us),
-              _stream())
-    return buf.permute(0, 1, 4, 2, 3)
+    _check_batch_vectors((), offsets, t0, aug, B,
+                         "events_to_frames_packed: contiguous HIP tensors offsets int64[B + 1], t0 int64[B], aug "
+                         "int32[B, 8] or None required")
+    return _launch_batch_scatter("snn_events_to_frames_packed", (words,), words.shape[0], offsets, t0, aug, T, B, H, W,
+                                 step_us)
 
 
 def labels_augment(labels: torch.Tensor, aug: torch.Tensor, W: int, H: int, min_visible: float = 0.25,

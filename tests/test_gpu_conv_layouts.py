@@ -59,7 +59,7 @@ def _layouts(C):
     return [("dense", 0, C),                  # freshly allocated tensor: the baseline
             ("merge", 4, r4 + 8),             # Dense merge slice: 16-byte aligned, ld % 4 == 0, ld > C
             ("off1", 1, r4 + 4),              # 4-byte aligned only: vec / out_vec / pipe refuse it
-            ("off2", 2, r4 + 4),              # 8-byte aligned: what the event-frame kernels' aligned8 accepts
+            ("off2", 2, r4 + 4),              # 8-byte aligned: what the event-frame kernels' aligned(8, ...) accepts
             ("off3", 3, r4 + 4),
             ("ld_odd", 0, ld_odd)]            # aligned start, but the pixel stride breaks every 4-wide access
 

@@ -222,6 +222,34 @@ def test_grid_stride_loop_reaches_the_tail(pkg):
     assert R.frames_ref(tail_only, _table(1), T, 1, H_, W_, STEP).sum() == 5   # the tail is visible in the identity case
 
 
+def test_windows_longer_than_2_to_the_32_take_the_wide_division(pkg):
+    """``T * step`` past 2^32 microseconds: ``t - t0`` no longer fits the 32-bit division, the tuple source takes the
+    64-bit one.  The first and the last microsecond of the window are among the events of both samples."""
+    B, H_, W_, n = 2, 2, 33, 200
+    step = (1 << 32) // T + 1
+    assert T * step > 1 << 32
+    rng = np.random.default_rng(31)
+    samples = []
+    for t0 in (7000, -(1 << 33)):
+        t = rng.integers(t0, t0 + T * step, n)
+        t[0], t[-1] = t0, t0 + T * step - 1
+        x, y = rng.integers(-1, W_ + 1, n), rng.integers(0, H_, n)
+        x[[0, -1]], y[[0, -1]] = 16, 0                           # (stays inside the frame under the second row)
+        samples.append((t, x, y, rng.integers(0, 2, n), t0))
+    table = _table(B, seeds=[5, 6])
+    table[1, :5] = [1, 50000, 4, 0, 1 << 30]                     # flip + zoom + drop beside the identity row
+    want = R.frames_ref(samples, table, T, B, H_, W_, step)
+    for b in range(B):
+        assert want[0, b].sum() > 0 and want[T - 1, b].sum() > 0, b   # both ends of the window hold events
+        ends = [tuple(v[[0, -1]] for v in samples[b][:4]) + (samples[b][4],)]
+        no_drop = table[b:b + 1].copy()
+        no_drop[0, 4] = 0
+        assert R.frames_ref(ends, no_drop, T, 1, H_, W_, step).sum(axis=(1, 2, 3, 4)).tolist() == [1, 0, 1]
+        assert (R.drop_hash(np.array([0, n - 1], dtype=np.int64), int(table[b, 5])) >= np.uint64(int(table[b, 4]))).all()
+    got, _ = _frames(pkg, samples, table, T, H_, W_, step)
+    assert np.array_equal(got, want)
+
+
 # ------------------------------------------------------------------------------------------- 5. labels
 LW, LH, MIN_VISIBLE, MIN_SIZE = 64, 48, 0.25, 2.0
 MARGIN = 1e-3

@@ -117,7 +117,7 @@ def test_slices_at_odd_event_indices_and_an_odd_total(pkg, lead):
 
 
 def test_more_events_than_one_pass_of_the_grid(pkg):
-    """``grid_for`` caps the grid at 8 blocks of 256 threads per compute unit: the events behind that many are reached
+    """``snn_grid_for`` caps the grid at 8 blocks of 256 threads per compute unit: the events behind that many are reached
     by the grid-stride loop alone.  Everything in the first pass lies before the window, so every set cell comes from
     the second pass."""
     rng = np.random.default_rng(4)
