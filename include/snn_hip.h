@@ -649,7 +649,8 @@ int snn_convlstm_seq_bwd(const float* w, const float* save_gates, const float* s
                          const float* ghT, const float* gcT, float* dgates, float* dx, int64_t lddx, float* dh0,
                          float* dc0, int T, int64_t M, int Cin, int Ch, void* stream);
 
-/* Pool("A"/"M"/"S", k, stride) (layer_gen.py:146-173, common.py:18-49), no padding, floor mode. */
+/* Pool("A"/"M"/"S", k, stride) (layer_gen.py:146-173, common.py:18-49), no padding, floor mode.  Both calls refuse
+ * k > H, k > W and any Ho, Wo other than (H - k) / stride + 1, (W - k) / stride + 1 before they launch. */
 int snn_pool_fwd(int kind, const float* x, float* y, int64_t N, int H, int W, int C,
                  int Ho, int Wo, int k, int stride, void* stream);
 int snn_pool_bwd(int kind, const float* x, const float* gy, float* gx, int64_t N, int H, int W, int C,

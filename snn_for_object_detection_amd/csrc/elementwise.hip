@@ -162,19 +162,27 @@ __global__ void k_convert_bf16(const void* __restrict__ src, void* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------ activations
+// ReLU follows torch's threshold rule (x <= 0 ? 0 : x), so a NaN input stays NaN and its gradient passes through.
 __device__ __forceinline__ float act_f(int act, float x) {
     switch (act) {
-        case SNN_ACT_RELU: return x > 0.0f ? x : 0.0f;
-        case SNN_ACT_SILU: return x / (1.0f + expf(-x));
+        case SNN_ACT_RELU: return x <= 0.0f ? 0.0f : x;
+        // x / (1 + e^-x).  Below -80 the 1 no longer counts (e^-x > 2^24) and e^-x overflows at -88.7, where the quotient
+        // is still a normal number (-2.6e-37) and stays a subnormal one down to -108: x e^x there instead of x / inf = -0,
+        // in fp64 because the fp32 e^x underflows before the product does (a branch no activation of a trained net takes).
+        case SNN_ACT_SILU: return x < -80.0f ? (float)((double)x * exp((double)x)) : x / (1.0f + expf(-x));
         default: return tanhf(x);
     }
 }
 __device__ __forceinline__ float act_g(int act, float x, float y) {
     switch (act) {
-        case SNN_ACT_RELU: return x > 0.0f ? 1.0f : 0.0f;
+        case SNN_ACT_RELU: return x <= 0.0f ? 0.0f : 1.0f;
         case SNN_ACT_SILU: {
-            float s = 1.0f / (1.0f + expf(-x));
-            return s * (1.0f + x * (1.0f - s));
+            // s (1 + x (1 - s)) has a root at x = -1.2785: in fp32 the sum cancels there (50 ulps of the result one grid
+            // step away from it, unbounded nearer) and s underflows to 0 below -88.7.  fp64 keeps every fp32 input within
+            // two ulps of the exact derivative and costs what tanhf costs the tanh gradient: 183-191 us per 2^26 elements
+            // (fp32 form: 145 us; ReLU: 141 us).  No SiLU is on the TinyYolo path.
+            const double s = 1.0 / (1.0 + exp(-(double)x));
+            return (float)(s * (1.0 + (double)x * (1.0 - s)));
         }
         default: return 1.0f - y * y;
     }
@@ -434,8 +442,9 @@ extern "C" int snn_pool_fwd(int kind, const float* x, float* y, int64_t N, int H
                             int stride, void* stream) {
     SNN_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0, "snn_pool_fwd: bad arguments");
     SNN_REQUIRE(kind >= SNN_POOL_AVG && kind <= SNN_POOL_SUM, "snn_pool_fwd: bad pool kind %d", kind);
-    SNN_REQUIRE(Ho == (H - k) / stride + 1 && Wo == (W - k) / stride + 1 && Ho > 0 && Wo > 0,
-                "snn_pool_fwd: output size mismatch");
+    // (C division truncates toward zero: without this, H < k < H + stride would give Ho == 1 and a window past the image)
+    SNN_REQUIRE(k <= H && k <= W, "snn_pool_fwd: window %d larger than the %dx%d image", k, H, W);
+    SNN_REQUIRE(Ho == (H - k) / stride + 1 && Wo == (W - k) / stride + 1, "snn_pool_fwd: output size mismatch");
     hipLaunchKernelGGL(k_pool_fwd, dim3(snn_grid_for(N * Ho * Wo * C, kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, kind, x, y, N, H, W, C, Ho, Wo, k, stride);
     SNN_CHECK_LAUNCH("snn_pool_fwd");
@@ -446,6 +455,8 @@ extern "C" int snn_pool_bwd(int kind, const float* x, const float* gy, float* gx
     SNN_REQUIRE(gy && gx && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0, "snn_pool_bwd: bad arguments");
     SNN_REQUIRE(kind >= SNN_POOL_AVG && kind <= SNN_POOL_SUM, "snn_pool_bwd: bad pool kind %d", kind);
     SNN_REQUIRE(kind != SNN_POOL_MAX || x, "snn_pool_bwd: max pooling needs the forward input");
+    SNN_REQUIRE(k <= H && k <= W, "snn_pool_bwd: window %d larger than the %dx%d image", k, H, W);
+    SNN_REQUIRE(Ho == (H - k) / stride + 1 && Wo == (W - k) / stride + 1, "snn_pool_bwd: output size mismatch");
     hipLaunchKernelGGL(k_pool_bwd, dim3(snn_grid_for(N * H * W * C, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
                        kind, x, gy, gx, N, H, W, C, Ho, Wo, k, stride);
     SNN_CHECK_LAUNCH("snn_pool_bwd");
