@@ -927,6 +927,39 @@ int snn_map_accumulate(const int* order, const unsigned* match_mask, const int* 
                        int slots, const int* max_dets, int num_max_dets, const double* rec_thresholds, int num_rec,
                        int num_iou, int t50, int t75, void* workspace, float* out, void* stream);
 
+/* ---------------------------------------------------------------- mAP area ranges, per-class AP, size filter (ABI v20,
+ * symbols added).  COCOeval's area ranges on pixel sizes: a row's pixel width is (double)fl32(x2 - x1) * img_w, its
+ * height (double)fl32(y2 - y1) * img_h, its area their fp64 product; small [0, 32^2], medium [32^2, 96^2], large
+ * [96^2, 1e10], both ends inclusive.  Per range a ground-truth row outside it is ignored; a detection takes the free
+ * non-ignored row of largest IoU >= the threshold (ties to the later row) and only when none qualifies the free ignored
+ * row chosen by the same rule; a detection matched to an ignored row, or unmatched with its own area outside the range,
+ * is ignored: neither true nor false positive, though it keeps its slot among the first maxDet.  The "all" outputs of
+ * these entry points carry the bits of the three above.  Every refusal names its entry point and launches nothing.
+ * snn_map_filter_rows: one thread per row.  det_key [B][A] int32: the class id, num_classes for an id out of range,
+ * num_classes + 1 for padding; label_cls [B][G]: the labels' class column.  A row (either kind) with
+ * wp^2 + hp^2 < min_box_diag^2, wp < min_box_side or hp < min_box_side (pixels; each test active only when its limit
+ * is > 0) becomes padding (key num_classes + 1, class -1).  *bad (device int64) += rows left with an id >= num_classes.
+ * snn_map_match_areas: snn_map_match with the labels' class column read from label_cls and, with num_ranges == 3 (0: the
+ * "all" pass alone, the area pointers may be null), per slot and range area_matched / area_ignored
+ * [B][num_classes][3][slots] (bit t: at threshold t) and npig_area [3][num_classes] += the non-ignored rows.
+ * snn_map_accumulate_areas: snn_map_accumulate over masks laid out [num_classes][3][records] beside match_mask;
+ * out[3 + num_max_dets + 2 * num_ranges]: the values of snn_map_accumulate, then (map, mar) at the largest maxDet for
+ * small, medium, large; out_class (may be null) [2][num_classes]: each class's AP and AR at the largest maxDet for
+ * "all", -1 without ground truth.  workspace: snn_map_areas_workspace_size bytes. */
+int snn_map_filter_rows(const float* dets, const float* labels, int B, int A, int G, int num_classes, double img_h,
+                        double img_w, double min_box_diag, double min_box_side, int* det_key, float* label_cls,
+                        int64_t* bad, void* stream);
+int snn_map_match_areas(const float* dets, const float* labels, const float* label_cls, const int* order, const int* seg,
+                        int B, int A, int G, int num_classes, int slots, const double* iou_thresholds, int num_iou,
+                        double img_h, double img_w, int num_ranges, float* score, unsigned* match_mask,
+                        unsigned* area_matched, unsigned* area_ignored, int* npig, int* npig_area, void* stream);
+size_t snn_map_areas_workspace_size(int num_classes, int num_max_dets, int num_iou, int num_ranges);
+int snn_map_accumulate_areas(const int* order, const unsigned* match_mask, const unsigned* area_matched,
+                             const unsigned* area_ignored, const int* npig, const int* npig_area, int num_classes,
+                             int records, int slots, const int* max_dets, int num_max_dets, const double* rec_thresholds,
+                             int num_rec, int num_iou, int t50, int t75, int num_ranges, void* workspace, float* out,
+                             float* out_class, void* stream);
+
 /* ---------------------------------------------------------------- activity counts (ABI v20, symbols added)
  * Per-channel counts of the elements of a channels-last tensor src[T][M][ld] that satisfy a predicate: the spikes of a
  * LIF layer from whatever its forward scan left (spike tensor, saved potentials, bit mask) and the non-zero operands of

@@ -34,7 +34,7 @@ class NeuronParams(Structure):
                 ("surrogate", c_int), ("reset_detached", c_int)]   # (ABI 20; zero = the rule of every earlier ABI)
 
 
-_P, _I, _L, _F = c_void_p, c_int, c_int64, c_float
+_P, _I, _L, _F, _D = c_void_p, c_int, c_int64, c_float, c_double
 
 # name -> (restype, argtypes); mirrors include/snn_hip.h one to one
 SIGNATURES = {
@@ -169,6 +169,11 @@ SIGNATURES = {
     "snn_map_match":(c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "snn_map_workspace_size": (c_size_t, [_I, _I, _I]),
     "snn_map_accumulate": (c_int, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "snn_map_filter_rows": (c_int, [_P, _P, _I, _I, _I, _I, _D, _D, _D, _D, _P, _P, _P, _P]),
+    "snn_map_match_areas": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "snn_map_areas_workspace_size": (c_size_t, [_I, _I, _I, _I]),
+    "snn_map_accumulate_areas": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P,
+                                         _P]),
     "snn_activity_count": (c_int, [_P, _I, _L, _F, _I, _L, _I, _I, _P, _I, _P]),
     "snn_activity_count_plan": (c_int, [_I, _I, _L, _I, _L, _I, _P]),
 }

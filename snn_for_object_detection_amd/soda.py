@@ -31,7 +31,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import box
-from .metrics import MeanAveragePrecision
+from .metrics import AREA_RANGES, MeanAveragePrecision
 from .generator import BackboneGen, Head, ListGen, ListState, NeckGen
 from .roi import RoI
 
@@ -125,6 +125,7 @@ class SODa(nn.Module):
         focal_gamma: float = 2.0,
         box_loss: str = "l1",
         box_loss_weight: float = 1.0,
+        map_options: Optional[dict] = None,
     ):
         super().__init__()
         if label_steps is not None and not 1 <= int(label_steps) <= 32:
@@ -160,7 +161,8 @@ class SODa(nn.Module):
         self.cls_loss = nn.CrossEntropyLoss(reduction="none")
         self.box_loss = nn.L1Loss(reduction="none")
         # soda.py:89-96; a plain attribute, not a submodule: state_dict() is unchanged
-        self.map_metric = MeanAveragePrecision(self.hparams.num_classes)
+        # map_options: keyword arguments of metrics.MeanAveragePrecision (area_ranges, class_metrics, min_box_diag, ...)
+        self.map_metric = MeanAveragePrecision(self.hparams.num_classes, **(map_options or {}))
 
     # ------------------------------------------------------------------ description hooks
     def backbone_cfgs(self) -> ListGen:
@@ -303,7 +305,7 @@ class SODa(nn.Module):
             & (steps[:, :, None] >= 0)
         rows = torch.where(own.unsqueeze(-1), labels[None, :, :, 1:].expand(K, -1, -1, -1),
                            torch.full((), -1.0, device=labels.device))
-        self.map_metric.update_padded(dets, rows.reshape(K * B, labels.shape[1], 5))
+        self.map_metric.update_padded(dets, rows.reshape(K * B, labels.shape[1], 5), image_size=batch[0].shape[-2:])
         return loss
 
     def training_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
@@ -319,7 +321,7 @@ class SODa(nn.Module):
         preds = self.forward(batch[0][self._rand_start_time():])
         loss = self._loss(preds, batch[1])
         self._log_loss("val", loss, batch)
-        self._map_estimate(preds, batch[1])
+        self._map_estimate(preds, batch[1], batch[0].shape[-2:])
         return loss
 
     def on_validation_epoch_end(self) -> None:
@@ -333,22 +335,29 @@ class SODa(nn.Module):
         preds = self.forward(batch[0][self._rand_start_time():])
         loss = self._loss(preds, batch[1])
         self._log_loss("test", loss, batch)
-        self._map_estimate(preds, batch[1])
+        self._map_estimate(preds, batch[1], batch[0].shape[-2:])
         return loss
 
     def on_test_epoch_end(self) -> None:
         self._map_compute()
 
-    def _map_estimate(self, preds: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], labels: torch.Tensor) -> None:
+    def _map_estimate(self, preds: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], labels: torch.Tensor,
+                      image_size=None) -> None:
         # soda.py:294-321 without the per-image boolean masks: padded rows (class -1) are skipped by the kernels
         anchors, cls_preds, bbox_preds = (p.detach() for p in preds)
         dets = box.multibox_detection(F.softmax(cls_preds, dim=2), bbox_preds, anchors)
-        self.map_metric.update_padded(dets, labels)
+        self.map_metric.update_padded(dets, labels, image_size=image_size)
 
     def _map_compute(self) -> None:
         # soda.py:283-292
         result = self.map_metric.compute()
         self.log_dict({k: result[k] for k in ("map", "map_50", "mar_1", "mar_10", "mar_100")})
+        # beyond the reference, only what map_options selected (device scalars; no host read)
+        self.log_dict({k: v for k, v in result.items() if k.rsplit("_", 1)[-1] in AREA_RANGES})
+        if "map_per_class" in result:
+            ar = result[f"mar_{self.map_metric.max_detection_thresholds[-1]}_per_class"]
+            for c in range(self.hparams.num_classes):
+                self.log_dict({f"map_class_{c}": result["map_per_class"][c], f"mar_class_{c}": ar[c]})
         self.map_metric.reset()
 
     def predict(self, X: torch.Tensor, state: Optional[ListState]) -> Tuple[torch.Tensor, ListState]:

@@ -2,8 +2,10 @@
 
 Times, with HIP events, (1) ``update_padded`` of one batch of ``multibox_detection`` rows (B=5, A=13 545 anchors, C=2
 classes; scores / boxes drawn from a seed) and (2) ``compute()`` over ``--batches`` such updates.  Prints one JSON line.
+``--areas`` adds the small / medium / large ranges, ``--class-metrics`` the per-class AP / AR, ``--filter`` a minimum box
+diagonal and side (pixels of the ``--image-size`` frame); without them the metric runs its default launches.
 
-    python tools/map_bench.py [--batches 100] [--reps 20]
+    python tools/map_bench.py [--batches 100] [--reps 20] [--areas] [--class-metrics] [--filter]
 """
 import argparse
 import json
@@ -36,12 +38,25 @@ def main():
     ap.add_argument("--G", type=int, default=16)
     ap.add_argument("--batches", type=int, default=100)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--areas", action="store_true", help="area_ranges=True")
+    ap.add_argument("--class-metrics", action="store_true", help="class_metrics=True")
+    ap.add_argument("--filter", action="store_true", help="min_box_diag=12, min_box_side=6 (arbitrary: protocol unpinned)")
+    ap.add_argument("--image-size", type=int, nargs=2, default=[240, 304], metavar=("H", "W"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("map_bench: needs a HIP device")
     gen = torch.Generator().manual_seed(0)
     data = [batch(a.B, a.A, a.C, a.G, gen) for _ in range(a.batches)]
-    m = MeanAveragePrecision(a.C)
+    opts = {}
+    if a.areas:
+        opts.update(area_ranges=True)
+    if a.class_metrics:
+        opts.update(class_metrics=True)
+    if a.filter:
+        opts.update(min_box_diag=12.0, min_box_side=6.0)
+    if a.areas or a.filter:
+        opts.update(image_size=tuple(a.image_size))
+    m = MeanAveragePrecision(a.C, **opts)
     for d, g in data[:3]:                      # warm-up: library load, torch sort plans, threshold tables
         m.update_padded(d, g)
     m.compute()
@@ -71,7 +86,7 @@ def main():
     comp.sort()
     print(json.dumps({"update_padded_ms_median": upd[len(upd) // 2], "update_padded_ms_min": upd[0],
                       "compute_ms_median": comp[len(comp) // 2], "compute_ms_min": comp[0], "batches": a.batches,
-                      "B": a.B, "A": a.A, "C": a.C, "G": a.G, "map": float(out["map"])}))
+                      "B": a.B, "A": a.A, "C": a.C, "G": a.G, "options": sorted(opts), "map": float(out["map"])}))
 
 
 if __name__ == "__main__":
