@@ -856,6 +856,33 @@ size_t snn_roi_steps_workspace_size(int K, int B, int A, int N);
 int snn_roi_assign_steps(const float* anchors, const float* labels, const int* steps, int K, int B, int A, int N,
                          int t0, float iou_threshold, void* workspace, float* bbox_offset, float* bbox_mask,
                          int64_t* class_labels, void* stream);
+/* ---- Task-aligned anchor assignment (DESIGN section 5 "Anchor assignment"; new symbols under ABI v20): the positives
+ * are chosen from the predictions, which are read as constants.  One entry for both label forms:
+ *   steps == NULL: labels [B][N][5] rows (class, x1, y1, x2, y2), predictions [B][A][C] / [B][A][4], S = B slots, K = 1;
+ *   otherwise:     labels [B][N][6] rows (ts, class, x1, y1, x2, y2), steps [K][B] as snn_label_steps writes them,
+ *                  predictions [K][B][A][C] / [K][B][A][4], S = K * B slots, K in 1 .. 32.
+ * C = classes + 1 logits per anchor, column 0 the background.  A row takes part when 0 <= class, class + 1 < C,
+ * x2 > x1, y2 > y1 and, with steps, ts - t0 == steps[k][b]; padding rows and rows of a class the logits have no column
+ * for take no part (the class is never used as an index).  Per slot:
+ *   p_a    = offset_inverse(anchor_a, bbox_preds_a), the exponent argument o / 5 replaced by log(1000 / 16) where it
+ *            is not <= that (NaN included), as decode_box of det_loss.hip;
+ *   s[a,j] = softmax(cls_logits_a)[class_j + 1], u[a,j] = I / (U + 1e-7) of p_a and box j; what is not > 0 counts as 0;
+ *   anchor a is a candidate of row j when its centre lies strictly inside box j; t[a,j] = s^alpha * u^beta (0 when not
+ *   > 0); every row selects up to topk candidates in (t descending, anchor ascending) order, t = 0 included;
+ *   an anchor selected by several rows goes to the row of largest u[a,j] (the lower row on ties); then, in row order,
+ *   a row left without an anchor claims the still unassigned anchor of highest box_iou(anchor, box) (first maximum).
+ * Outputs as snn_roi_assign / snn_roi_assign_steps write them: bbox_offset [S][A][4] = offset_boxes(anchor, assigned
+ * box) * mask, bbox_mask [S][A][4], class_labels [S][A] int64 (class + 1, 0 = background); assigned_row [S][A] int32
+ * (may be NULL): the label-row index, -1 for background.  An empty slot (steps < 0) and a slot without a row that takes
+ * part get exact zeros (assigned_row -1).  Three launches, no host synchronisation, no allocation, no atomics.
+ * workspace: snn_tal_workspace_size(S, A, N, topk) bytes.  Refused before any launch: null pointers (steps and
+ * assigned_row may be NULL), topk outside 1 .. 64, C outside 2 .. 64, alpha or beta negative or not finite, A * N at or
+ * above 2^31 - 1024, anchors / bbox_preds / bbox_offset / bbox_mask / workspace not 16-byte aligned. */
+size_t snn_tal_workspace_size(int S, int A, int N, int topk);
+int snn_tal_assign(const float* anchors, const float* labels, const int* steps, const float* cls_logits,
+                   const float* bbox_preds, int K, int B, int A, int N, int C, int t0, int topk, float alpha, float beta,
+                   void* workspace, float* bbox_offset, float* bbox_mask, int64_t* class_labels, int* assigned_row,
+                   void* stream);
 /* The loss above over the anchors of the V valid slots (steps[k][b] >= 0) of predictions [K][B][A][C] / [K][B][A][4]:
  *   loss = loss_ratio * mean(CE[pos]) + (1 - loss_ratio) * mean(CE[neg]) + sum |bbox*mask - offset*mask| / (4 A V)
  * stats[6] = the five sums of snn_det_loss_fwd and V, counted on the device.  V = 0: loss 0 and zero gradients; V > 0

@@ -133,6 +133,8 @@ SIGNATURES = {
     "snn_gather_steps_bwd": (c_int, [_P, _L, _P, _P, _L, _I, _I, _I, _L, _I, _P]),
     "snn_roi_steps_workspace_size": (c_size_t, [_I, _I, _I, _I]),
     "snn_roi_assign_steps": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "snn_tal_workspace_size": (c_size_t, [_I, _I, _I, _I]),
+    "snn_tal_assign": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
     "snn_det_loss_steps_workspace_size": (c_size_t, [_I, _I, _I]),
     "snn_det_loss_steps_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "snn_det_loss_steps_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),

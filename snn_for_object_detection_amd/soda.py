@@ -20,6 +20,10 @@ Same constructor, hooks and step logic; what differs:
 * ``cls_loss`` / ``focal_gamma`` / ``box_loss`` / ``box_loss_weight`` select the objective: focal classification and a
   GIoU / DIoU / CIoU term on the decoded boxes next to the reference's cross entropy + L1, which stays the default and
   runs exactly as before (DESIGN "Detection loss").
+* ``assigner`` / ``tal_topk`` / ``tal_alpha`` / ``tal_beta`` select which anchors are positives: ``"iou"`` is the
+  reference's static rule (``roi.RoI``), the default, with the same calls and launches as before; ``"tal"`` is the
+  task-aligned assigner (``roi.TaskAlignedAssigner``), which reads the detached predictions of the step (DESIGN "Anchor
+  assignment").
 """
 
 import math
@@ -33,10 +37,11 @@ from torch.nn import functional as F
 from . import box
 from .metrics import AREA_RANGES, MeanAveragePrecision
 from .generator import BackboneGen, Head, ListGen, ListState, NeckGen
-from .roi import RoI
+from .roi import RoI, TaskAlignedAssigner
 
 LOSS_CLS_NAMES = ("ce", "focal")
 LOSS_BOX_NAMES = ("l1", "giou", "diou", "ciou")
+ASSIGNER_NAMES = ("iou", "tal")
 _EXP_CLAMP = math.log(1000.0 / 16.0)   # upper clamp of the exponent argument of a decoded box side
 _IOU_EPS = 1e-7
 
@@ -126,6 +131,10 @@ class SODa(nn.Module):
         box_loss: str = "l1",
         box_loss_weight: float = 1.0,
         map_options: Optional[dict] = None,
+        assigner: str = "iou",
+        tal_topk: int = 10,
+        tal_alpha: float = 1.0,
+        tal_beta: float = 6.0,
     ):
         super().__init__()
         if label_steps is not None and not 1 <= int(label_steps) <= 32:
@@ -138,12 +147,21 @@ class SODa(nn.Module):
             raise ValueError(f"focal_gamma must be >= 0, got {focal_gamma}")
         if not float(box_loss_weight) >= 0.0:
             raise ValueError(f"box_loss_weight must be >= 0, got {box_loss_weight}")
+        if assigner not in ASSIGNER_NAMES:
+            raise ValueError(f"assigner must be one of {ASSIGNER_NAMES}, got {assigner!r}")
+        if isinstance(tal_topk, bool) or int(tal_topk) != tal_topk or not 1 <= int(tal_topk) <= 64:
+            raise ValueError(f"tal_topk must be an integer in 1 .. 64, got {tal_topk}")
+        if not (float(tal_alpha) >= 0.0 and math.isfinite(float(tal_alpha))):
+            raise ValueError(f"tal_alpha must be finite and >= 0, got {tal_alpha}")
+        if not (float(tal_beta) >= 0.0 and math.isfinite(float(tal_beta))):
+            raise ValueError(f"tal_beta must be finite and >= 0, got {tal_beta}")
         self.hparams = SimpleNamespace(
             num_classes=num_classes, loss_ratio=loss_ratio, time_window=time_window,
             iou_threshold=iou_threshold, learning_rate=learning_rate, state_storage=state_storage,
             init_weights=init_weights, label_steps=None if label_steps is None else int(label_steps),
             cls_loss=cls_loss, focal_gamma=float(focal_gamma), box_loss=box_loss,
-            box_loss_weight=float(box_loss_weight),
+            box_loss_weight=float(box_loss_weight), assigner=assigner, tal_topk=int(tal_topk),
+            tal_alpha=float(tal_alpha), tal_beta=float(tal_beta),
         )
         self.plotter = plotter
         self.logged = {}
@@ -158,6 +176,9 @@ class SODa(nn.Module):
         self.head_net = Head(self.head_cfgs, self.hparams.num_classes, self.neck_net.out_shape,
                              init_weights=self.hparams.init_weights)
         self.roi_blk = RoI(self.hparams.iou_threshold)
+        # assigner="tal": the positives follow the detached predictions; None: roi_blk alone decides, as before
+        self.tal_blk = (TaskAlignedAssigner(self.hparams.tal_topk, self.hparams.tal_alpha, self.hparams.tal_beta)
+                        if assigner == "tal" else None)
         self.cls_loss = nn.CrossEntropyLoss(reduction="none")
         self.box_loss = nn.L1Loss(reduction="none")
         # soda.py:89-96; a plain attribute, not a submodule: state_dict() is unchanged
@@ -278,7 +299,11 @@ class SODa(nn.Module):
         steps = HF.select_label_steps(labels, T, K, t0)
         preds, _ = self._forward_impl(X, None, steps=steps)
         anchors, cls_preds, bbox_preds = preds
-        bbox_offset, bbox_mask, class_labels = self.roi_blk.steps(anchors, labels, steps, t0)
+        if self.tal_blk is not None:
+            bbox_offset, bbox_mask, class_labels = self.tal_blk.steps(anchors, labels, steps, t0, cls_preds.detach(),
+                                                                      bbox_preds.detach())
+        else:
+            bbox_offset, bbox_mask, class_labels = self.roi_blk.steps(anchors, labels, steps, t0)
         if self._default_loss():
             loss = HF.detection_loss_steps(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, steps,
                                            self.hparams.loss_ratio)
@@ -415,7 +440,10 @@ class SODa(nn.Module):
     def _loss(self, preds: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], labels: torch.Tensor) -> torch.Tensor:
         # soda.py:259-281
         anchors, cls_preds, bbox_preds = preds
-        bbox_offset, bbox_mask, class_labels = self.roi_blk(anchors, labels)
+        if self.tal_blk is not None:
+            bbox_offset, bbox_mask, class_labels = self.tal_blk(anchors, labels, cls_preds.detach(), bbox_preds.detach())
+        else:
+            bbox_offset, bbox_mask, class_labels = self.roi_blk(anchors, labels)
         if not self._default_loss():
             if cls_preds.is_cuda:   # the same launches as below (csrc/det_loss.hip)
                 from . import functional as HF

@@ -21,11 +21,13 @@ ap.add_argument("--clip", type=float, default=None, help="gradient_clip_val (def
 ap.add_argument("--clip-algorithm", choices=("norm", "value"), default="norm", help="gradient_clip_algorithm")
 ap.add_argument("--skip-nonfinite", action="store_true", help="leave out a step whose gradient holds an inf or a NaN")
 ap.add_argument("--weight-decay", type=float, default=0.0)
+ap.add_argument("--assigner", choices=("iou", "tal"), default="iou",
+                help="which anchors are positives: the static IoU rule or the task-aligned assigner")
 args = ap.parse_args()
 steps = args.steps
 dev = torch.device("cuda")
 torch.manual_seed(2)
-model = S.TinyYolo(num_classes=2, time_window=0).to(dev).train()
+model = S.TinyYolo(num_classes=2, time_window=0, assigner=args.assigner).to(dev).train()
 trainer = FlatTrainer(model, lr=model.hparams.learning_rate, gradient_clip_val=args.clip,
                       gradient_clip_algorithm=args.clip_algorithm, skip_nonfinite=args.skip_nonfinite,
                       weight_decay=args.weight_decay)

@@ -49,6 +49,8 @@ def main():
     ap.add_argument("--focal-gamma", type=float, default=2.0)
     ap.add_argument("--box-loss", default="l1", choices=("l1", "giou", "diou", "ciou"))
     ap.add_argument("--box-loss-weight", type=float, default=1.0)
+    ap.add_argument("--assigner", default="iou", choices=("iou", "tal"),
+                    help="which anchors are positives: the static IoU rule or the task-aligned assigner")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--ema-decay", type=float, default=None, metavar="D", help="weight average with this decay (off)")
@@ -64,7 +66,7 @@ def main():
     torch.manual_seed(args.seed)
     model = S.TinyYolo(num_classes=len(feed.get_labels()), label_steps=args.label_steps, cls_loss=args.cls_loss,
                        focal_gamma=args.focal_gamma, box_loss=args.box_loss,
-                       box_loss_weight=args.box_loss_weight).cuda().train()
+                       box_loss_weight=args.box_loss_weight, assigner=args.assigner).cuda().train()
     lr = warmup_cosine(args.lr, args.warmup_steps, args.steps) if args.warmup_steps > 0 else args.lr
     trainer = FlatTrainer(model, lr=lr, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
     batch = next(feed)
