@@ -764,6 +764,17 @@ int snn_events_to_frames_packed(const uint32_t* words, const int64_t* offsets, c
 int snn_labels_augment(const float* labels_in, float* labels_out, const int32_t* aug, int B, int N, int width, int W,
                        int H, float min_visible, float min_size_px, void* stream);
 
+/* ---------------------------------------------------------------- carried state
+ * Training on consecutive windows of a recording carries the detector state (fp32 tensors [B, ...], the sample
+ * outermost, each sample's block dense) from one step to the next.  snn_state_reset puts the samples that start a new
+ * recording back to rest in all n tensors with ONE launch: table (device, int64) has n rows {address of the tensor,
+ * elements per sample, rest value as fp32 bits in the low 32 bits}; sample b of tensor l is the `elements` floats at
+ * address + 4 * b * elements.  first[B] (device, int32): != 0 fills the sample's block of every tensor with the row's
+ * rest value, 0 leaves every byte of it alone - a block of the grid (16 chunks x B x n) then returns after reading
+ * first[b], so the usual step costs one near-empty launch and the host never reads first.  Addresses need 4-byte
+ * alignment only (16-byte stores between scalar head and tail); n, B <= 65535. */
+int snn_state_reset(const int64_t* table, int n, int B, const int32_t* first, void* stream);
+
 /* ---------------------------------------------------------------- detection decode
  * Tail of SODa.predict (models/soda.py:202-233): per anchor conf = max_k prob[k], class = argmax - 1 (background -1),
  * box = offset_inverse(anchor, offsets) (utils/box.py:72-79, 102-119).  prob [A][K], offsets / anchors / boxes [A][4]. */

@@ -30,7 +30,8 @@ STAMP_PATH = LIB_PATH + ".buildstamp"
 # (the longest compiles first: the pool starts them at once and the short ones fill in around them)
 SOURCES = ("scan_bwd.hip", "conv_gather.hip", "conv_wgrad.hip", "conv_first.hip", "bn_stats.hip", "scan_fwd.hip",
            "bn_bwd.hip", "wgrad_halo.hip", "conv_halo.hip", "activity.hip", "det_loss.hip", "lstm.hip", "elementwise.hip",
-           "small_gemm.hip", "targets.hip", "metrics.hip", "abi.hip", "detect.hip", "events.hip", "optimizer.hip")
+           "small_gemm.hip", "targets.hip", "metrics.hip", "abi.hip", "detect.hip", "events.hip", "optimizer.hip",
+           "state_carry.hip")
 MAX_WORKERS = 8   # hipcc processes at once: a fixed cap, never the machine's CPU count
 
 

@@ -168,6 +168,7 @@ SIGNATURES = {
     "snn_events_to_frames_aug": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _L, _P]),
     "snn_events_to_frames_packed": (c_int, [_P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _L, _P]),
     "snn_labels_augment": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P]),
+    "snn_state_reset": (c_int, [_P, _I, _I, _P, _P]),
     "snn_map_match":(c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "snn_map_workspace_size": (c_size_t, [_I, _I, _I]),
     "snn_map_accumulate": (c_int, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),

@@ -12,6 +12,7 @@ not on a HIP device raise.
 import collections
 import ctypes
 import os
+import struct
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -1991,9 +1992,117 @@ def affine_neuron(y: torch.Tensor, neuron: int, state: Optional[NeuronState] = N
         new_state = SynapseState(vT)
     else:
         new_state = NeuronState(vT, iT)
+        if params.v_leak != 0.0:
+            vT._snn_rest = float(params.v_leak)   # what state=None starts this potential from (reset_state_ reads it)
     if last_only and not single:
         return out, new_state
     return (out[0] if single else out), new_state
+
+
+# ------------------------------------------------------------------------------------------- carried state
+def _sample_blocks(t: torch.Tensor) -> torch.Tensor:
+    """``t[B, ...]`` with every sample's elements in one dense block (as it is, or as a dense copy)."""
+    if t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)):
+        return t
+    return _raw_dense_cl(t) if t.dim() >= 4 else t.contiguous()
+
+
+def detach_state(state_tree):
+    """The state tree with every tensor detached (same nesting and tuple types; the ``_snn_rest`` tags are kept): what is
+    carried from one training step to the next, so that no autograd graph is."""
+    if state_tree is None:
+        return None
+    if isinstance(state_tree, torch.Tensor):
+        t = state_tree.detach()
+        if hasattr(state_tree, "_snn_rest"):
+            t._snn_rest = state_tree._snn_rest
+        return t
+    if isinstance(state_tree, tuple) and hasattr(state_tree, "_fields"):   # NeuronState, SynapseState, norse's tuples
+        return type(state_tree)(*(detach_state(t) for t in state_tree))
+    if isinstance(state_tree, (list, tuple)):
+        return type(state_tree)(detach_state(t) for t in state_tree)
+    raise ValueError(f"detach_state: {type(state_tree).__name__} is no part of a state tree")
+
+
+_RESET_TABLES = []   # pinned staging tables of reset_state_, used in turn: {"pinned", "np", "done": event behind its last copy}
+_RESET_RING = 4
+
+
+def _reset_table(n: int) -> dict:
+    """The next of the pinned int64 tables (at least ``n`` entries), free to be written: the copy that last read it has
+    completed - it was enqueued ``_RESET_RING`` calls ago, so the wait on its event does not block in practice."""
+    slot = {"pinned": None, "np": None, "done": None} if len(_RESET_TABLES) < _RESET_RING else _RESET_TABLES.pop(0)
+    _RESET_TABLES.append(slot)
+    if slot["done"] is None:
+        slot["done"] = torch.cuda.Event()
+    elif not slot["done"].query():
+        slot["done"].synchronize()
+    if slot["pinned"] is None or slot["pinned"].numel() < n:
+        slot["pinned"] = torch.empty(max(n, 512), dtype=torch.int64, pin_memory=True)
+        slot["np"] = slot["pinned"].numpy()
+    return slot
+
+
+def reset_state_(state_tree, first: torch.Tensor):
+    """Put the samples ``b`` with ``first[b] != 0`` back to rest in every tensor of a detector state tree, in place, with
+    ONE launch (``snn_state_reset``) and without the host learning which samples those are.
+
+    ``state_tree`` is what ``SODa._forward_impl`` returns: nested lists of ``NeuronState(v, i)``, ``SynapseState(p)``,
+    ``(h, c)`` pairs and None.  ``first`` is an integer device tensor ``[B]``.  Every leaf is detached; a 0-dim or
+    broadcast leaf of a ``NeuronState`` (norse's initial ``v``) is expanded to its partner's shape by ``_expand_state``'s
+    rule.  Rest is what ``state=None`` starts from: zero, except the potential of a neuron whose ``v_leak`` is not zero
+    (the scans tag that tensor ``_snn_rest``).  Returns the tree (same nesting; leaves are the detached tensors - a leaf
+    that was not dense per sample is replaced by a dense copy)."""
+    if not (isinstance(first, torch.Tensor) and first.dim() == 1 and first.is_cuda
+            and first.dtype in (torch.int32, torch.int64, torch.bool, torch.uint8)):
+        raise ValueError("reset_state_: first must be an integer device tensor [B]")
+    B = int(first.numel())
+    first = first.to(torch.int32).contiguous()
+    rows = []
+
+    def leaf(t: torch.Tensor, like: Optional[torch.Tensor] = None) -> torch.Tensor:
+        rest = float(getattr(t, "_snn_rest", 0.0))
+        t = t.detach()
+        if like is not None and tuple(t.shape) != tuple(like.shape):
+            t = _expand_state(t, like.shape, like.device).clone()   # (own memory: an expanded view has none to reset)
+        if t.dtype != _F32 or t.dim() < 1 or t.shape[0] != B or t.numel() == 0:
+            raise ValueError(f"reset_state_: a state leaf must be float32 [B = {B}, ...], got {t.dtype} {tuple(t.shape)}")
+        _require_device(t, "reset_state_ leaf")
+        t = _sample_blocks(t)
+        if rest != 0.0:
+            t._snn_rest = rest
+        rows.extend((t.data_ptr(), t.numel() // B, struct.unpack("<I", struct.pack("<f", rest))[0] if rest != 0.0 else 0))
+        return t
+
+    def walk(node):
+        if node is None:
+            return None
+        if isinstance(node, torch.Tensor):
+            return leaf(node)
+        if isinstance(node, NeuronState):
+            full = node.i if node.v.dim() < node.i.dim() else node.v
+            return NeuronState(leaf(node.v, full), leaf(node.i, full))
+        if isinstance(node, SynapseState):
+            return SynapseState(leaf(node.p))
+        if isinstance(node, (list, tuple)):
+            kids = [walk(k) for k in node]
+            return kids if isinstance(node, list) else tuple(kids)
+        raise ValueError(f"reset_state_: {type(node).__name__} is no part of a state tree")
+
+    tree = walk(state_tree)
+    n = len(rows) // 3
+    if n > 65535:
+        raise ValueError(f"reset_state_: {n} state tensors are more than one launch takes (65535)")
+    if n:
+        # the addresses change with every step: the table is written into pinned memory and copied on the compute stream
+        # in front of the launch
+        slot = _reset_table(len(rows))
+        slot["np"][:len(rows)] = rows
+        table = torch.empty(len(rows), dtype=torch.int64, device=first.device)
+        table.copy_(slot["pinned"][:len(rows)], non_blocking=True)
+        slot["done"].record(torch.cuda.current_stream(first.device))
+        _hip.call("snn_state_reset", table.data_ptr(), n, B, first.data_ptr(), _stream())
+    return tree
 
 
 # ------------------------------------------------------------------------------------------- merges

@@ -258,13 +258,19 @@ class PropheseeFeed:
     ``PropheseeDataModule`` (``time_step`` in milliseconds; ``files_in_flight`` is its ``num_load_file``); ``rank`` /
     ``world`` divide the files the way the reference divides them among DataLoader workers (``per = n // world``, slice
     ``rank``).  ``one_label=False`` yields 6-column labels for ``SODa(label_steps=K)``.  ``samples()`` is the host side
-    alone (no device needed)."""
+    alone (no device needed).  ``chained=True`` (with ``one_label=False``) binds every batch slot to one recording and
+    yields its windows in time order, batches ``(X, labels, first)`` for ``SODa(carry_state=True)``
+    (``_chained_samples``)."""
 
     def __init__(self, data_dir: str, dataset: str = "gen1", split: str = "train", batch_size: int = 4,
                  num_steps: int = 42, time_step: int = 16, time_shift: int = 16, one_label: bool = True,
                  files_in_flight: int = 8, rank: int = 0, world: int = 1, seed: int = 0, device="cuda", augment=None,
-                 events_threshold: int = 4000, box_size_threshold: float = 0.01):
+                 events_threshold: int = 4000, box_size_threshold: float = 0.01, chained: bool = False):
         self.dataset = _check_dataset(dataset)
+        if chained and one_label:
+            raise ValueError("PropheseeFeed: chained=True needs one_label=False (consecutive windows carry the six-column "
+                             "labels of SODa(label_steps=K); chained single-label windows are not built)")
+        self.chained = bool(chained)
         if files_in_flight <= 0:
             raise ValueError("PropheseeFeed: files_in_flight must be more than zero")
         if batch_size <= 0 or num_steps <= 0 or time_step <= 0:
@@ -314,6 +320,9 @@ class PropheseeFeed:
 
     def samples(self, with_file: bool = False) -> Iterator:
         """Host samples ``(words_slice, t0_us, labels)`` in the feed's order (``with_file``: ``(file index, sample)``)."""
+        if self.chained:
+            yield from self._chained_samples(with_file)
+            return
         groups = self._groups()
         if self.one_label:
             # round-robin over the files in flight; an exhausted file leaves the round, the next group is opened when all have
@@ -347,8 +356,51 @@ class PropheseeFeed:
                     sample = self.sampler(boxes[k], recs[k])
                     yield (group[k], sample) if with_file else sample
 
+    def _chained_samples(self, with_file: bool = False) -> Iterator:
+        """``chained=True``: sample ``k`` belongs to batch slot ``k % batch_size``, and a slot is bound to ONE recording -
+        it yields that recording's windows in time order (``MTSampler``'s rule, window ``n + 1`` starting ``num_steps *
+        time_step`` after window ``n``, without the wrap to the start), then takes the next file of the shuffled cycle over
+        this rank's files.  A sample is ``(words_slice, t0_us, labels[n, 6], first, aug_row)``: ``first`` is 1 on the first
+        window of a recording in its slot (the very first batch included), ``aug_row`` the slot's ``EventAugment`` row
+        (``int32[8]``; None without ``augment``), drawn when the slot opens the recording and unchanged until the next -
+        the carried state keeps belonging to the same transformed scene.  (The drop stays a draw per event: the row's seed
+        is hashed with every event's index.)  A recording without events has no window and is passed over."""
+        order = list(range(len(self.files)))
+        self._rng.shuffle(order)
+        cycle = itertools.cycle(order)
+
+        def open_next():
+            for _ in range(len(self.files)):
+                i = next(cycle)
+                rec = DatRecording(self.files[i][1])
+                if len(rec):
+                    row = None if self.augment is None else self.augment.draw(1, self.width, self.height)[0]
+                    return i, load_boxes(self.files[i][0], self.dataset, self.time_step_us), rec, row
+            raise RuntimeError("PropheseeFeed: no recording of this rank holds an event")
+
+        slots = [None] * self.batch_size
+        while True:
+            for b in range(self.batch_size):
+                first = 0
+                if slots[b] is None or slots[b][2].done:
+                    slots[b], first = open_next(), 1
+                i, boxes, rec, row = slots[b]
+                sample = (*self.sampler(boxes, rec), first, row)
+                yield (i, sample) if with_file else sample
+
     def __iter__(self):
         return self
+
+    def _next_chained(self):
+        """``(X, labels[B, N, 6], first)``: ``first`` int32 ``[B]`` on the device, for ``SODa(carry_state=True)``."""
+        batch = [next(self._samples) for _ in range(self.batch_size)]
+        labels = [torch.from_numpy(np.ascontiguousarray(s[2])) for s in batch]
+        if not any(int(l.shape[0]) for l in labels):
+            labels[0] = torch.full((1, 6), -1.0)   # (a batch without any row would collate five columns wide)
+        table = None if self.augment is None else torch.stack([s[4] for s in batch])
+        X, lab = self._batcher([(s[0], s[1]) for s in batch], labels, aug_table=table)
+        first = torch.tensor([s[3] for s in batch], dtype=torch.int32).pin_memory()
+        return X, lab, first.to(X.device, non_blocking=True)
 
     def __next__(self):
         from .data import EventBatcher
@@ -356,5 +408,7 @@ class PropheseeFeed:
             self._batcher = EventBatcher(self.num_steps, self.height, self.width, self.time_step_us, device=self.device,
                                          augment=self.augment)
             self._samples = self.samples()
+        if self.chained:
+            return self._next_chained()
         batch = [next(self._samples) for _ in range(self.batch_size)]
         return self._batcher([(w, t0) for w, t0, _ in batch], [torch.from_numpy(np.ascontiguousarray(l)) for _, _, l in batch])

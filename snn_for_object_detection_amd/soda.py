@@ -24,6 +24,9 @@ Same constructor, hooks and step logic; what differs:
   reference's static rule (``roi.RoI``), the default, with the same calls and launches as before; ``"tal"`` is the
   task-aligned assigner (``roi.TaskAlignedAssigner``), which reads the detached predictions of the step (DESIGN "Anchor
   assignment").
+* ``carry_state=True`` trains on consecutive windows of a recording: the detached detector state of a step is kept (one
+  per stage) and handed to the next one, batches may carry ``first[B]`` - the samples that start a new recording, whose
+  state ``functional.reset_state_`` puts back to rest on the device (DESIGN "Carried state").
 """
 
 import math
@@ -135,6 +138,7 @@ class SODa(nn.Module):
         tal_topk: int = 10,
         tal_alpha: float = 1.0,
         tal_beta: float = 6.0,
+        carry_state: bool = False,
     ):
         super().__init__()
         if label_steps is not None and not 1 <= int(label_steps) <= 32:
@@ -155,13 +159,16 @@ class SODa(nn.Module):
             raise ValueError(f"tal_alpha must be finite and >= 0, got {tal_alpha}")
         if not (float(tal_beta) >= 0.0 and math.isfinite(float(tal_beta))):
             raise ValueError(f"tal_beta must be finite and >= 0, got {tal_beta}")
+        if carry_state and time_window:
+            raise ValueError(f"carry_state=True needs time_window=0, got time_window={time_window}: cutting a random "
+                             "prefix off a window would tear the stream the carried state belongs to")
         self.hparams = SimpleNamespace(
             num_classes=num_classes, loss_ratio=loss_ratio, time_window=time_window,
             iou_threshold=iou_threshold, learning_rate=learning_rate, state_storage=state_storage,
             init_weights=init_weights, label_steps=None if label_steps is None else int(label_steps),
             cls_loss=cls_loss, focal_gamma=float(focal_gamma), box_loss=box_loss,
             box_loss_weight=float(box_loss_weight), assigner=assigner, tal_topk=int(tal_topk),
-            tal_alpha=float(tal_alpha), tal_beta=float(tal_beta),
+            tal_alpha=float(tal_alpha), tal_beta=float(tal_beta), carry_state=bool(carry_state),
         )
         self.plotter = plotter
         self.logged = {}
@@ -170,6 +177,9 @@ class SODa(nn.Module):
         # (every neck and head gradient is complete or enqueued there) to start their all-reduce early
         self._snn_neck_grads_ready = None
         self._loss_terms = None   # (classification term, box term) of the last loss under a selected objective
+        # carry_state=True: stage ("train" / "val" / "test") -> ((B, H, W), detached state tree after the stage's last step);
+        # plain attributes - never in state_dict(), never exchanged between ranks
+        self._carried = {}
 
         self.base_net = BackboneGen(self.backbone_cfgs, in_channels=2, init_weights=self.hparams.init_weights)
         self.neck_net = NeckGen(self.neck_cfgs, self.base_net.out_channels, init_weights=self.hparams.init_weights)
@@ -278,10 +288,12 @@ class SODa(nn.Module):
             self.log(f"{stage}_loss_cls", self._loss_terms[0], batch_size=batch[0].shape[1], sync_dist=True)
             self.log(f"{stage}_loss_box", self._loss_terms[1], batch_size=batch[0].shape[1], sync_dist=True)
 
-    def _step_labelled_frames(self, batch: Tuple[torch.Tensor, torch.Tensor]):
+    def _step_labelled_frames(self, batch: Tuple[torch.Tensor, torch.Tensor], carry: Optional[list] = None):
         """Six-column labels ``(ts, class, x1, y1, x2, y2)``: the loss over every labelled frame the ``label_steps`` slots
         hold.  The random prefix ``t0`` is cut from the frames and subtracted from the rows' timesteps alike; the frames
         are chosen on the device (``steps[K,B]``), so the step stays free of host synchronisation.
+        ``carry`` (``carry_state=True``): a one-element list holding the state the window starts from; the state after the
+        window replaces it.
         -> ``(loss, preds of the K*B frames, steps, t0)``"""
         from . import functional as HF
         K = self.hparams.label_steps
@@ -297,7 +309,9 @@ class SODa(nn.Module):
             raise ValueError(f"label_steps = {K} exceeds the {T} timesteps left of the sequence")
         labels = labels.to(X.device)
         steps = HF.select_label_steps(labels, T, K, t0)
-        preds, _ = self._forward_impl(X, None, steps=steps)
+        preds, state = self._forward_impl(X, None if carry is None else carry[0], steps=steps)
+        if carry is not None:
+            carry[0] = state
         anchors, cls_preds, bbox_preds = preds
         if self.tal_blk is not None:
             bbox_offset, bbox_mask, class_labels = self.tal_blk.steps(anchors, labels, steps, t0, cls_preds.detach(),
@@ -313,10 +327,10 @@ class SODa(nn.Module):
                 return_terms=True, **self._loss_options())
         return loss, preds, steps, t0
 
-    def _eval_labelled_frames(self, batch: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+    def _eval_labelled_frames(self, batch: Tuple[torch.Tensor, torch.Tensor], carry: Optional[list] = None) -> torch.Tensor:
         """``validation_step`` / ``test_step`` on six-column labels: the loss as in training, and mAP over exactly the
         valid slots - every labelled frame is one image, with the label rows of its own timestep.  Device ``where`` only."""
-        loss, preds, steps, t0 = self._step_labelled_frames(batch)
+        loss, preds, steps, t0 = self._step_labelled_frames(batch, carry)
         anchors, cls_preds, bbox_preds = (p.detach() for p in preds)
         labels = batch[1].to(cls_preds.device).float()
         K, B, A = cls_preds.shape[:3]
@@ -333,12 +347,58 @@ class SODa(nn.Module):
         self.map_metric.update_padded(dets, rows.reshape(K * B, labels.shape[1], 5), image_size=batch[0].shape[-2:])
         return loss
 
+    def reset_carried_state(self, stage: Optional[str] = None) -> None:
+        """Drop the state kept by ``carry_state=True`` for ``stage`` (``"train"``, ``"val"``, ``"test"``; None: all): the
+        stage's next step starts every layer from rest."""
+        if stage is None:
+            self._carried.clear()
+        elif stage not in ("train", "val", "test"):
+            raise ValueError(f'reset_carried_state: stage must be "train", "val", "test" or None, got {stage!r}')
+        else:
+            self._carried.pop(stage, None)
+
+    def _carried_step(self, stage: str, batch) -> torch.Tensor:
+        """A step of ``carry_state=True`` on ``(X, labels)`` or ``(X, labels, first)``: the window starts from the state the
+        stage's last step ended in - with the samples ``first[b] != 0`` (int32 ``[B]``, device) back at rest - and the
+        detached state after the window is kept.  No gradient crosses the boundary.  A batch of another ``B`` or frame
+        size than the kept one starts from rest."""
+        from . import functional as HF
+        X, labels = batch[0], batch[1]
+        first = batch[2] if len(batch) > 2 else None
+        if X.dim() != 5:
+            raise ValueError(f"carry_state=True needs a sequence X[T,B,2,H,W], got a tensor of rank {X.dim()}")
+        key = (int(X.shape[1]), int(X.shape[-2]), int(X.shape[-1]))
+        if first is not None and tuple(first.shape) != (key[0],):
+            raise ValueError(f"carry_state=True: first must be int32 [B = {key[0]}], got shape {tuple(first.shape)}")
+        kept = self._carried.pop(stage, None)
+        state = None
+        if kept is not None and kept[0] == key:
+            state = kept[1] if first is None else HF.reset_state_(kept[1], first.to(X.device))
+        carry, pair = [state], (X, labels)
+        if labels.shape[-1] == 6:
+            if stage == "train":
+                loss = self._step_labelled_frames(pair, carry)[0]
+            else:
+                loss = self._eval_labelled_frames(pair, carry)
+        else:
+            preds, carry[0] = self._forward_impl(X, state)
+            loss = self._loss(preds, labels)
+            if stage != "train":
+                self._map_estimate(preds, labels, X.shape[-2:])
+        self._carried[stage] = (key, HF.detach_state(carry[0]))
+        self._log_loss(stage, loss, pair)
+        return loss
+
     def training_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
+        if self.hparams.carry_state:
+            return self._carried_step("train", batch)
         loss = self._step(batch)
         self._log_loss("train", loss, batch)
         return loss
 
     def validation_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
+        if self.hparams.carry_state:
+            return self._carried_step("val", batch)
         if batch[1].shape[-1] == 6:
             loss = self._eval_labelled_frames(batch)
             self._log_loss("val", loss, batch)
@@ -353,6 +413,8 @@ class SODa(nn.Module):
         self._map_compute()
 
     def test_step(self, batch: Tuple[torch.Tensor, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
+        if self.hparams.carry_state:
+            return self._carried_step("test", batch)
         if batch[1].shape[-1] == 6:
             loss = self._eval_labelled_frames(batch)
             self._log_loss("test", loss, batch)

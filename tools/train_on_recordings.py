@@ -9,7 +9,10 @@ on (flip, zoom with shift, random drop); ``--label-steps K`` trains on every lab
 ``--ema-decay D`` keeps a weight average inside the optimiser step (``--ema-warmup``: its ramp), ``--warmup-steps W`` warms
 the learning rate up over W steps and lets it fall along a cosine over the rest, and ``--val-batches N`` ends the run with
 ``validation_step`` over N batches of ``<data-dir>/<dataset>/val``: once on the live weights and, with an average, once
-under ``averaged_weights()`` - both sets of mAP keys are printed."""
+under ``averaged_weights()`` - both sets of mAP keys are printed.
+``--chained`` (with ``--label-steps K``) trains on CONSECUTIVE windows with the neuron state carried from step to step:
+``PropheseeFeed(chained=True)`` binds every batch slot to one recording, ``SODa(carry_state=True)`` keeps the detached
+state and resets the slots that open a new recording; no random prefix is cut (``time_window=0``)."""
 import argparse
 import os
 import sys
@@ -51,6 +54,8 @@ def main():
     ap.add_argument("--box-loss-weight", type=float, default=1.0)
     ap.add_argument("--assigner", default="iou", choices=("iou", "tal"),
                     help="which anchors are positives: the static IoU rule or the task-aligned assigner")
+    ap.add_argument("--chained", action="store_true",
+                    help="consecutive windows per batch slot, neuron state carried across steps (needs --label-steps)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--ema-decay", type=float, default=None, metavar="D", help="weight average with this decay (off)")
@@ -59,14 +64,18 @@ def main():
                     help="learning rate: linear warmup over W steps, then a cosine down to 1 %% at --steps (constant)")
     ap.add_argument("--val-batches", type=int, default=0, metavar="N", help="validate on N batches of the val split at the end")
     args = ap.parse_args()
+    if args.chained and args.label_steps is None:
+        ap.error("--chained needs --label-steps K (chained windows carry six-column labels)")
+    carried = dict(carry_state=True, time_window=0) if args.chained else {}
 
     augment = S.EventAugment(hflip=0.5, zoom=(0.75, 1.25), drop=(0.0, 0.1), seed=args.seed) if args.augment else None
     feed = S.PropheseeFeed(args.data_dir, dataset=args.dataset, split="train", batch_size=args.batch_size,
-                           num_steps=args.num_steps, one_label=args.label_steps is None, seed=args.seed, augment=augment)
+                           num_steps=args.num_steps, one_label=args.label_steps is None, seed=args.seed, augment=augment,
+                           chained=args.chained)
     torch.manual_seed(args.seed)
     model = S.TinyYolo(num_classes=len(feed.get_labels()), label_steps=args.label_steps, cls_loss=args.cls_loss,
                        focal_gamma=args.focal_gamma, box_loss=args.box_loss,
-                       box_loss_weight=args.box_loss_weight, assigner=args.assigner).cuda().train()
+                       box_loss_weight=args.box_loss_weight, assigner=args.assigner, **carried).cuda().train()
     lr = warmup_cosine(args.lr, args.warmup_steps, args.steps) if args.warmup_steps > 0 else args.lr
     trainer = FlatTrainer(model, lr=lr, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
     batch = next(feed)
@@ -79,7 +88,8 @@ def main():
         print(f"step {step:5d}  loss {float(loss.detach()):.6f}", flush=True)
     if args.val_batches > 0:
         val = S.PropheseeFeed(args.data_dir, dataset=args.dataset, split="val", batch_size=args.batch_size,
-                              num_steps=args.num_steps, one_label=args.label_steps is None, seed=args.seed)
+                              num_steps=args.num_steps, one_label=args.label_steps is None, seed=args.seed,
+                              chained=args.chained)
         batches = [next(val) for _ in range(args.val_batches)]
         trainer.synchronize()
         print("val live    ", validate(model, batches), flush=True)
