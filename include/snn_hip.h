@@ -649,6 +649,32 @@ int snn_convlstm_seq_bwd(const float* w, const float* save_gates, const float* s
                          const float* ghT, const float* gcT, float* dgates, float* dx, int64_t lddx, float* dh0,
                          float* dc0, int T, int64_t M, int Cin, int Ch, void* stream);
 
+/* ---------------------------------------------------------------- depthwise convolution (csrc/conv_depthwise.hip)
+ * Conv2d(C, C, K, stride, padding = K / 2, groups = C, bias = False) over channels-last frames [N][H][W][ld >= C]; the
+ * output is [N][Ho][Wo], Ho = (H + 2 pad - K) / stride + 1 (Wo alike).  fp32 storage, exact fp32 products, fp32
+ * accumulation in kh-major tap order; memory-bound stencils, no MFMA and no arithmetic mode.
+ *
+ * snn_dwconv_supported: host-only; the ONE statement of what the kernels run - K in {3, 5}, stride in {1, 2},
+ * pad = K / 2, C >= 1, N * H * W < 2^31.  Every launcher checks the same function and refuses the rest by name.
+ *
+ * wt: the TAP-MAJOR weight image [K*K][C], wt[kh*K + kw][c] = weight[c][0][kh][kw] (snn_weight_transpose with I = 1).
+ * Any float alignment; every operand may be a channel slice (pixel stride > C) at any channel offset.
+ *
+ * dgrad: dx [N][H][W][lddx] from dy [N][Ho][Wo][lddy]; every dx element is written exactly once.
+ *
+ * wgrad: dw [C][K*K] = the parameter's storage order, stored (accumulate 0) or added to (1).  workspace: what
+ * snn_dwconv_wgrad_workspace_size returns for the same arguments (fp64 slab rows, 8-byte aligned).  chunks: pixel chunks
+ * the sum is split into, 0 = the kernel's own plan (a function of the shape only).  Within a chunk at most 32 products
+ * are added in fp32 before the sum continues in fp64; no atomics - the same call gives the same bits. */
+int snn_dwconv_supported(int64_t N, int H, int W, int C, int K, int stride, int pad);
+int snn_dwconv_fwd(const float* x, int64_t ldx, const float* wt, float* y, int64_t ldy, int64_t N, int H, int W, int C,
+                   int K, int stride, int pad, void* stream);
+int snn_dwconv_dgrad(const float* dy, int64_t lddy, const float* wt, float* dx, int64_t lddx, int64_t N, int H, int W,
+                     int C, int K, int stride, int pad, void* stream);
+size_t snn_dwconv_wgrad_workspace_size(int64_t N, int H, int W, int C, int K, int stride, int pad, int chunks);
+int snn_dwconv_wgrad(const float* x, int64_t ldx, const float* dy, int64_t lddy, float* dw, int64_t N, int H, int W, int C,
+                     int K, int stride, int pad, int accumulate, void* workspace, int chunks, void* stream);
+
 /* Pool("A"/"M"/"S", k, stride) (layer_gen.py:146-173, common.py:18-49), no padding, floor mode.  Both calls refuse
  * k > H, k > W and any Ho, Wo other than (H - k) / stride + 1, (W - k) / stride + 1 before they launch. */
 int snn_pool_fwd(int kind, const float* x, float* y, int64_t N, int H, int W, int C,

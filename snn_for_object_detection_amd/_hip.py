@@ -154,6 +154,11 @@ SIGNATURES = {
     "snn_convlstm_seq_tile": (c_int, [_I, _I, _L]),
     "snn_convlstm_seq_fwd": (c_int, [_P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _P]),
     "snn_convlstm_seq_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _I, _L, _I, _I, _P]),
+    "snn_dwconv_supported": (c_int, [_L, _I, _I, _I, _I, _I, _I]),
+    "snn_dwconv_fwd": (c_int, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P]),
+    "snn_dwconv_dgrad": (c_int, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P]),
+    "snn_dwconv_wgrad_workspace_size": (c_size_t, [_L, _I, _I, _I, _I, _I, _I, _I]),
+    "snn_dwconv_wgrad": (c_int, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "snn_pool_fwd": (c_int, [_I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
     "snn_pool_bwd": (c_int, [_I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
     "snn_upsample_fwd": (c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),

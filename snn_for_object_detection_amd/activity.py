@@ -25,7 +25,8 @@ threshold, or mask bits.
 The synaptic-operation estimate is the usual one, borders ignored: every non-zero input element feeds ``Cout * KH * KW /
 stride^2`` accumulates, so ``synops = nonzero_inputs * Cout * KH * KW / stride^2``, and ``macs`` is the same with every input
 element (the dense equivalent).  At a padded border fewer taps exist, so both are slight over-estimates, by the same
-factor.
+factor.  A depthwise convolution (``Conv(groups="depthwise")``) is recorded with the fan-out ``Cout / groups = 1``:
+``synops = nonzero_inputs * KH * KW / stride^2``.
 """
 
 import contextlib

@@ -11,6 +11,7 @@ not on a HIP device raise.
 
 import collections
 import ctypes
+import functools
 import os
 import struct
 from typing import List, NamedTuple, Optional, Sequence, Tuple
@@ -1374,6 +1375,121 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int = 1, padding: int 
     if bn_stats and not single and _slot_of(weight) is not None and _wgrad_bn_ok(seq, weight, int(stride), int(padding)):
         y._snn_defer_apply = True   # (bn_stats: the BatchNorm behind is y's only consumer)
     return y
+
+
+# ------------------------------------------------------------------------------------------- depthwise conv
+def depthwise_covers(N: int, H: int, W: int, C: int, K: int, stride: int, pad: int) -> bool:
+    """What the depthwise kernels run: ``snn_dwconv_supported`` (host only; the library is the one place that says it)."""
+    return bool(_hip.query("snn_dwconv_supported", N, H, W, C, K, stride, pad))
+
+
+@functools.lru_cache(maxsize=None)
+def depthwise_sets() -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """``(kernel sizes, strides)`` the depthwise kernels take - ASKED of ``snn_dwconv_supported`` over the candidates a
+    description could name, not restated here (what ``layer_gen.Conv.get`` names in its refusals)."""
+    sizes = tuple(k for k in range(1, 16) if depthwise_covers(1, 16, 16, 1, k, 1, k // 2))
+    strides = tuple(s for s in range(1, 9) if sizes and depthwise_covers(1, 16, 16, 1, sizes[0], s, sizes[0] // 2))
+    return sizes, strides
+
+
+def _tap_major(weight: torch.Tensor, st: int) -> torch.Tensor:
+    """The kernels' weight image ``[K*K][C]`` of a depthwise ``(C,1,K,K)`` weight: FlatTrainer's ``_snn_wt`` (the batched
+    transpose of an ``I = 1`` weight IS the tap-major image, refreshed once per step), else built here by one small launch
+    - as ``_frag_image`` is for the halo kernels.  The weight's memory is read as ``[C][K*K]`` whatever torch says about its
+    layout (for ``I = 1`` OIHW and OHWI coincide)."""
+    wt = _kept_view(weight, "_snn_wt")
+    if wt is not None:
+        return wt
+    C, _, KH, KW = weight.shape
+    w = weight.detach()
+    if not (w.is_contiguous() or is_channels_last(w)):
+        w = w.contiguous()
+    wt = torch.empty((KH * KW, C), device=w.device, dtype=_F32)
+    _hip.call("snn_weight_transpose", w.data_ptr(), wt.data_ptr(), C, KH, KW, 1, st)
+    return wt
+
+
+class _DepthwiseConv2d(Function):
+    """nn.Conv2d(C, C, K, stride, padding=K//2, groups=C, bias=False) over all T*B frames (csrc/conv_depthwise.hip).  Returns
+    dx to autograd: like ``_Pool`` it takes no part in the ``GradAccumulator`` protocol."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride: int, pad: int, slot=None, dest=None, x_th=None):
+        _require_device(x, "depthwise_conv2d input")
+        _require_device(weight, "depthwise_conv2d weight")
+        T, B, C, H, W = _dims5(x)
+        Cw, I, KH, KW = weight.shape
+        if Cw != C or I != 1 or KH != KW:
+            raise RuntimeError(f"depthwise_conv2d: input has {C} channels, the weight is {tuple(weight.shape)}; expected "
+                               f"({C}, 1, K, K)")
+        if not depthwise_covers(T * B, H, W, C, KH, stride, pad):
+            raise RuntimeError(f"depthwise_conv2d: kernel_size {KH}, stride {stride}, padding {pad} on {T * B} frames of "
+                               f"{H}x{W}x{C} is not covered (snn_dwconv_supported: kernel_size in {{3, 5}}, stride in "
+                               "{1, 2}, padding = kernel_size // 2)")
+        Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+        x = _raw_to_cl(x)
+        if x_th is not None:   # saved potentials of a LIF layer that wrote no spikes: written out here (dx is d loss / d spikes)
+            x = _spikes_dense(x, x_th)
+        st = _stream()
+        wt = _tap_major(weight, st)
+        if _ACTIVITY is not None:
+            _ACTIVITY.count_conv((weight,), x, None, None, 1, KH, KW, stride)   # fan-out Cout / groups = 1
+        y = _out_tensor(dest, T, B, C, Ho, Wo, x)
+        _hip.call("snn_dwconv_fwd", x.data_ptr(), cl_stride(x), wt.data_ptr(), y.data_ptr(), cl_stride(y), T * B, H, W, C, KH,
+                  stride, pad, st)
+        ctx.save_for_backward(x)
+        ctx.weight = weight
+        ctx.wt = wt if wt is not getattr(weight, "_snn_wt", None) else None   # (a per-call image is kept; a trainer's is re-read)
+        ctx.geom = (T, B, C, H, W, KH, Ho, Wo, stride, pad)
+        ctx.slot = slot
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        T, B, C, H, W, K, Ho, Wo, stride, pad = ctx.geom
+        gy = _raw_to_cl(gy)
+        ldg, ldx = cl_stride(gy), cl_stride(x)
+        st = _stream()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            wt = ctx.wt if ctx.wt is not None else _tap_major(ctx.weight, st)
+            dx = _new_cl((T, B), C, H, W, x)
+            _hip.call("snn_dwconv_dgrad", gy.data_ptr(), ldg, wt.data_ptr(), dx.data_ptr(), cl_stride(dx), T * B, H, W, C, K,
+                      stride, pad, st)
+        if ctx.needs_input_grad[1]:
+            slot = ctx.slot
+            n_ws = _hip.query("snn_dwconv_wgrad_workspace_size", T * B, H, W, C, K, stride, pad, 0) // 4
+            # (the workspace comes from _WgradLaunch as fp32 words on the launch's stream; the kernels use it as fp64 rows)
+            with _WgradLaunch(x.device, slot is not None, 1, 1, n_ws, hold=(x, gy)) as (stream, ws, _):
+                if slot is not None:
+                    dst, accumulate = slot.buf, slot.claim()
+                else:
+                    dst, accumulate = torch.empty((C, K * K), device=x.device, dtype=_F32), 0
+                _hip.call("snn_dwconv_wgrad", x.data_ptr(), ldx, gy.data_ptr(), ldg, dst.data_ptr(), T * B, H, W, C, K,
+                          stride, pad, accumulate, ws.data_ptr(), 0, stream)
+            if slot is None:
+                dw = dst.view(C, 1, K, K)
+        return dx, dw, None, None, None, None, None
+
+
+def depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int = 1, padding: int = 0,
+                     dest: Optional[Dest] = None) -> torch.Tensor:
+    """Depthwise convolution ``conv2d(x, weight, groups=C)`` with ``weight`` ``(C,1,K,K)``, ``[B,C,H,W]`` or ``[T,B,C,H,W]``.
+    Exact fp32 products whatever the session's arithmetic modes say.  ``dest``: write the result into a channel slice of a
+    concat buffer.  The weight's ``GradSlot`` (FlatTrainer) receives the weight gradient from the side stream, as a dense
+    convolution's does.  bf16 storage: the fp32 kernels between two conversions (``conv2d``'s pattern for head layers).
+    Saved potentials (``_snn_spike_threshold``) are written out as spikes first: these kernels do not threshold on load."""
+    x_th = getattr(x, "_snn_spike_threshold", None)
+    if x.dtype == _BF16:
+        xf = to_float32(x)
+        if x_th is not None:
+            xf._snn_spike_threshold = x_th   # (bf16 -> fp32 is exact: the same comparison)
+        y = to_bfloat16(depthwise_conv2d(xf, weight, stride, padding, None))
+        return place(y, dest) if dest is not None else y
+    seq, single = as_sequence(x)
+    y = _DepthwiseConv2d.apply(seq, weight, int(stride), int(padding), _slot_of(weight), dest, x_th)
+    return y[0] if single else y
 
 
 # ------------------------------------------------------------------------------------------- norm + neuron

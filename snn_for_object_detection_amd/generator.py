@@ -51,6 +51,15 @@ def _is_plain_1x1(layer) -> bool:
             and layer.padding == (0, 0) and layer.bias is None and layer.groups == 1)
 
 
+def _takes_potentials(layer) -> bool:
+    """A plain convolution that may be handed a LIF layer's saved potentials instead of its spikes (the ``spikes_ok``
+    route): dense, with the default arithmetic.  A depthwise layer (``groups != 1``) never is - its kernels read stored
+    spikes."""
+    return (isinstance(layer, HipConv2d) and layer.groups == 1 and layer.in_channels % 32 == 0
+            and layer.out_channels % 4 == 0 and layer.kernel_size[0] <= 5
+            and layer.forward_precision is None and layer.backward_precision is None)
+
+
 class BlockGen(nn.Module):
     """Builds a block from a (nested) configuration list and runs it (generator.py:35-198).
 
@@ -128,7 +137,8 @@ class BlockGen(nn.Module):
             # unbounded activation (ReLU / SiLU / SumPool / ConvLSTM) upstream with no BatchNorm, spiking neuron or Tanh
             # since, through any chain of convolutions, pools, passes, merges, nested blocks - takes the any-range bf16x6
             # arithmetic instead (unless the description set a precision itself)
-            if isinstance(layer, HipConv2d) and layer.forward_precision is None and unbounded:
+            # (a depthwise layer, groups != 1, computes in exact fp32 and has neither contract nor switch)
+            if isinstance(layer, HipConv2d) and layer.groups == 1 and layer.forward_precision is None and unbounded:
                 layer.forward_precision = "bf16x6"
             if isinstance(layer, BlockGen):
                 unbounded = layer.out_unbounded
@@ -325,16 +335,15 @@ class BlockGen(nn.Module):
                     # in front of a C2f split): it can form the spikes from the saved potentials, none are written
                     # ... or a plain convolution (a Conv -> Norm -> LIF -> Conv stack: the deep backbones): HF.conv2d thresholds on
                     # load where its kernels cover the shape and writes the spikes itself where they do not
+                    # (never a depthwise convolution, groups != 1: its kernels read stored spikes, so the scan writes them
+                    # and no extra pass appears)
                     nxt_l = branch[plan[k + 1][1]] if (not last and plan[k + 1][0] == "layer") else None
                     to_siblings = (not last and plan[k + 1][0] == "conv_block"
                                    and branch[plan[k + 1][1] + 1]._siblings is not None and HF.USE_SIBLING_FUSION)
                     spikes_ok = (zero_copy and not last and self.training and neuron == _hip.NEURON_LIF
                                  and direct is None and shortcut is None and not isinstance(holder, StateStorage)
                                  and HF.USE_SPIKES_FROM_VDEC
-                                 and (to_siblings
-                                      or (isinstance(nxt_l, HipConv2d) and nxt_l.in_channels % 32 == 0
-                                          and nxt_l.out_channels % 4 == 0 and nxt_l.kernel_size[0] <= 5
-                                          and nxt_l.forward_precision is None and nxt_l.backward_precision is None)))
+                                 and (to_siblings or _takes_potentials(nxt_l)))
                     Y, new = HF.affine_neuron(Y, neuron, old, bn=layer, params=cell.params, dest=direct,
                                               addend=shortcut, last_only=only_last, spikes_ok=spikes_ok,
                                               tau=getattr(cell, "tau", None), spike_mask_ok=spikes_ok and to_siblings)

@@ -173,6 +173,9 @@ class FlatTrainer:
                     raise RuntimeError("FlatTrainer: a convolution weight with 2^31 or more elements (the batched transpose "
                                        "indexes a layer in 32 bits)")
                 table.append([off, o, kh * kw, i])
+                # a depthwise weight (C,1,K,K) goes through the same table with i = 1: its transpose [1][K][K][C] IS the
+                # tap-major image [K*K][C] the depthwise kernels read (functional._tap_major).  kh * kw * i is odd, so it
+                # gets no pre-split image, and i % 32 != 0, so no fragment image: no new buffer
                 p._snn_wt = self.flat_wt[off:off + p.numel()].view(i, kh, kw, o)
                 p._snn_wt_version = -1  # not valid yet
                 # rows of both matrices must start on a 4-float group of the flat buffers
