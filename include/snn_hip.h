@@ -803,7 +803,19 @@ int snn_state_reset(const int64_t* table, int n, int B, const int32_t* first, vo
 
 /* ---------------------------------------------------------------- detection decode
  * Tail of SODa.predict (models/soda.py:202-233): per anchor conf = max_k prob[k], class = argmax - 1 (background -1),
- * box = offset_inverse(anchor, offsets) (utils/box.py:72-79, 102-119).  prob [A][K], offsets / anchors / boxes [A][4]. */
+ * box = offset_inverse(anchor, offsets) (utils/box.py:72-79, 102-119).  prob [A][K], offsets / anchors / boxes [A][4].
+ * Contract of the probabilities: every entry lies in [0, 1] or is NaN.  The argmax starts from column 0 and moves on
+ * prob[k] > best only, so the first maximum wins, a NaN never replaces a finite best and a NaN in column 0 stays: a row
+ * whose column 0 is NaN (an all-NaN row among them) decodes to class -1 with confidence NaN whatever its other columns
+ * hold, and a NaN in a later column is passed over (torch.max of the host path would return that NaN and its column:
+ * the one place where the two paths differ).  A class -1 row is never an NMS candidate; snn_detect_assemble writes it
+ * as a not-kept row in anchor order with class -1, its confidence as it is (NaN < pos_threshold is false) and its
+ * decoded box.  The caller's ordering between decode and NMS (box.py: detection_order) must keep such a row inside the
+ * background band for seg to count it there; rows of one class and equal confidence are ordered by anchor, ascending,
+ * so of identical boxes with equal confidence the lowest anchor is kept.
+ * snn_detect_decode[_batched] read and write scalars: no pointer needs more than its type's 4-byte alignment (boxes
+ * included, unlike in the NMS and assemble entry points below), and K has no upper bound (K > 1, A > 0; batched:
+ * N * A < 2^31 - 256). */
 int snn_detect_decode(const float* cls_prob, const float* offsets, const float* anchors, int A, int K,
                       float* conf, int* cls, float* boxes, void* stream);
 /* Per-class greedy NMS (utils/box.py:82-99).  order[A]: anchor ids sorted by (class ascending, confidence descending);

@@ -67,10 +67,42 @@ def nms(boxes, scores, class_id, num_classes, iou_threshold) -> torch.Tensor:
     return torch.tensor(kept, device=boxes.device, dtype=torch.long)
 
 
+def detection_order(conf: torch.Tensor, cls: torch.Tensor, K: int):
+    """Candidate order and class segments that ``snn_nms_sorted[_batched]`` take, from the decoded ``conf[..., A]``
+    (float32) and ``cls[..., A]`` (int32, -1 = background) of one frame or of ``N`` frames; pure torch, any device.
+
+    ``order[..., A]`` (int32): row ids (``n * A + anchor``; the anchor itself for one frame) sorted inside each frame
+    by (class ascending, confidence descending, anchor ascending) - rows of one class and equal confidence stay in
+    anchor order (stable sort).  ``seg[..., K]`` (int32): inclusive counts over (background, class 0, ...), so the
+    members of class ``c`` are ``order[seg[c] .. seg[c + 1])`` of the frame and the background rows stand in front.
+
+    The key gives every class a band of its own, ``[2 (cls + 1) - 1, 2 (cls + 1)]``, for confidences in [0, 1].  The
+    confidence that forms it is made to lie there whatever ``conf`` holds: a NaN (a probability row whose column 0 is
+    NaN decodes to class -1 with confidence NaN) counts as 0, anything else is clamped.  A NaN key would be sorted
+    behind every class instead, and each segment that ``seg`` counts would then begin one entry early.  ``conf``
+    itself is not changed: the output rows carry it as decoded.  Outside the contract the clamp costs the order:
+    confidences above 1 (or below 0) all get the same key, so inside a class they come in anchor order, not by
+    confidence, and nothing reports it - hand this function probabilities, never logits."""
+    A = conf.shape[-1]
+    in_band = torch.nan_to_num(conf, nan=0.0).clamp(0.0, 1.0)
+    key = (cls + 1).double() * 2.0 - in_band.double()
+    order = torch.argsort(key, dim=-1, stable=True)
+    if conf.dim() > 1:
+        order = order + torch.arange(conf.shape[0], device=conf.device).unsqueeze(1) * A
+    classes = torch.arange(K, device=conf.device, dtype=torch.int32)
+    counts = (cls.unsqueeze(-1) + 1 == classes).sum(-2)                         # [..., K]: background, class 0, ...
+    seg = torch.cumsum(counts, -1).to(torch.int32).contiguous()                 # seg[c] = first member of class c
+    return order.to(torch.int32), seg
+
+
 def _multibox_detection_device(cls_probs: torch.Tensor, offset_preds: torch.Tensor, anchors: torch.Tensor,
                                nms_threshold: float, pos_threshold: float) -> torch.Tensor:
     """Same result as the loop below, on the device and without host synchronisation: decode and greedy NMS are
-    HIP kernels (``csrc/detect.hip``), ordering uses torch's device sort / prefix sums as plumbing."""
+    HIP kernels (``csrc/detect.hip``), ordering uses torch's device sort / prefix sums as plumbing
+    (``detection_order``).  Probabilities lie in [0, 1] or are NaN: a row whose background column is NaN comes out as
+    a not-kept background row (class -1, confidence NaN) in anchor order and changes no other row; a NaN in a later
+    column is passed over by the kernel's argmax (``torch.max`` on the host path returns it).  Rows of one class and
+    equal confidence are candidates in anchor order, so of identical boxes the lowest anchor is kept."""
     from . import _hip
     B, A, K = cls_probs.shape
     dev = cls_probs.device
@@ -78,7 +110,6 @@ def _multibox_detection_device(cls_probs: torch.Tensor, offset_preds: torch.Tens
     probs = cls_probs.contiguous().float()
     offs = offset_preds.contiguous().float()
     anc = anchors.contiguous().float()
-    classes = torch.arange(K, device=dev, dtype=torch.int32)
     out = []
     for b in range(B):
         conf = torch.empty(A, device=dev, dtype=torch.float32)
@@ -87,10 +118,7 @@ def _multibox_detection_device(cls_probs: torch.Tensor, offset_preds: torch.Tens
         _hip.call("snn_detect_decode", probs[b].data_ptr(), offs[b].data_ptr(), anc.data_ptr(), A, K, conf.data_ptr(),
                   cls.data_ptr(), boxes.data_ptr(), st)
         # (class ascending, confidence descending); background (class -1) sorts first and is not a candidate
-        key = (cls + 1).double() * 2.0 - conf.double()
-        order = torch.argsort(key, stable=True).to(torch.int32)
-        counts = (cls.unsqueeze(1) + 1 == classes.unsqueeze(0)).sum(0)          # [K]: background, class 0, ...
-        seg = torch.cumsum(counts, 0).to(torch.int32).contiguous()              # seg[c] = first member of class c
+        order, seg = detection_order(conf, cls, K)
         kept = torch.empty(A, device=dev, dtype=torch.int32)
         nkept = torch.zeros(K - 1, device=dev, dtype=torch.int32)
         flag = torch.zeros(A, device=dev, dtype=torch.uint8)
@@ -119,7 +147,8 @@ def multibox_detection_batched(cls_probs: torch.Tensor, offset_preds: torch.Tens
     """``_multibox_detection_device`` for ``N`` frames (``cls_probs[N,A,K]``, ``offset_preds[N,A,4]`` on the device)
     without a loop over them: decode, greedy NMS (one block per class and frame) and the output rows are one HIP launch
     each (``csrc/detect.hip``), the ordering between them is the same key and the same stable device sort, taken along
-    the anchor dimension of ``[N,A]``.  Element for element the per-frame result; no host synchronisation."""
+    the anchor dimension of ``[N,A]`` (``detection_order``).  Element for element the per-frame result, NaN rows and
+    the anchor-ascending order of equal confidences included; no host synchronisation."""
     from . import _hip
     if not cls_probs.is_cuda:
         raise RuntimeError("multibox_detection_batched runs on device tensors; multibox_detection takes host tensors")
@@ -135,12 +164,7 @@ def multibox_detection_batched(cls_probs: torch.Tensor, offset_preds: torch.Tens
     _hip.call("snn_detect_decode_batched", probs.data_ptr(), offs.data_ptr(), anc.data_ptr(), N, A, K, conf.data_ptr(),
               cls.data_ptr(), boxes.data_ptr(), st)
     # per frame (class ascending, confidence descending, anchor ascending): the per-frame key, sorted inside each row
-    key = (cls + 1).double() * 2.0 - conf.double()
-    first_row = torch.arange(N, device=dev).unsqueeze(1) * A
-    order = (torch.argsort(key, dim=1, stable=True) + first_row).to(torch.int32)
-    classes = torch.arange(K, device=dev, dtype=torch.int32)
-    counts = (cls.unsqueeze(2) + 1 == classes).sum(1)                           # [N, K]: background, class 0, ...
-    seg = torch.cumsum(counts, 1).to(torch.int32).contiguous()                  # seg[n, c] = first member of class c
+    order, seg = detection_order(conf, cls, K)
     kept = torch.empty(N, A, device=dev, dtype=torch.int32)
     nkept = torch.zeros(N, K - 1, device=dev, dtype=torch.int32)
     flag = torch.zeros(N, A, device=dev, dtype=torch.uint8)
@@ -156,7 +180,10 @@ def multibox_detection_batched(cls_probs: torch.Tensor, offset_preds: torch.Tens
 def multibox_detection(cls_probs: torch.Tensor, offset_preds: torch.Tensor, anchors: torch.Tensor,
                        nms_threshold: float = 0.1, pos_threshold: float = 0.009999999) -> torch.Tensor:
     """``[B, A, 6]`` rows ``(class, conf, x1, y1, x2, y2)``; suppressed / background rows get class -1
-    (utils/box.py:102-153)."""
+    (utils/box.py:102-153).  Probabilities lie in [0, 1] or are NaN.  On every path a row whose background column
+    is NaN is a not-kept background row (class -1, confidence NaN) in anchor order that changes no other row.  The
+    device paths order equal confidences of a class by anchor, ascending (the host sort below is not stable), and pass
+    over a NaN in a later column, which ``torch.max`` here returns with its column."""
     if cls_probs.is_cuda and cls_probs.shape[0] > 1:
         return multibox_detection_batched(cls_probs, offset_preds, anchors, nms_threshold, pos_threshold)
     if cls_probs.is_cuda:
