@@ -681,6 +681,35 @@ int snn_pool_fwd(int kind, const float* x, float* y, int64_t N, int H, int W, in
                  int Ho, int Wo, int k, int stride, void* stream);
 int snn_pool_bwd(int kind, const float* x, const float* gy, float* gx, int64_t N, int H, int W, int C,
                  int Ho, int Wo, int k, int stride, void* stream);
+
+/* ---------------------------------------------------------------- pooling with padding, SPP (csrc/pool.hip)
+ * Avg / Max / SumPool2d(k, stride, pad), floor mode, over channels-last frames [N][H][W][ld >= C], fp32; the output is
+ * [N][Ho][Wo], Ho = (H + 2 pad - k) / stride + 1 (Wo alike).  Every operand may be a channel slice (pixel stride > C) at
+ * any channel offset; 16-byte accesses where pointers and strides allow, guarded scalar ones elsewhere, same arithmetic.
+ *
+ * snn_pool2d_supported: host-only; the ONE statement of what the kernels run - 2 <= k <= 7, 1 <= stride <= k,
+ * 0 <= pad <= k / 2, H + 2 pad >= k, W + 2 pad >= k, C >= 1, N * H * W < 2^31.  The launchers refuse the rest by name.
+ *
+ * fwd: MAX pads with -inf and compares `v > acc || v != v` in window row-major order (ATen: first maximum, a NaN wins).
+ * AVG divides by k * k (count_include_pad); in-image taps are added one by one in window row-major order.  At pad = 0
+ * all three kinds give the bits of snn_pool_fwd.
+ *
+ * bwd: a gather - gx = addend (NULL: 0) + the covering windows' terms in ascending (ho, wo), added one by one; every gx
+ * element is written exactly once.  MAX routes a window's gradient to its first maximal in-image tap (NaN rule above)
+ * and is the only kind that reads x.  addend must not alias gx.  At pad = 0 without addend: the bits of snn_pool_bwd.
+ *
+ * snn_spp_fwd: y [N][H][W][ldy >= (levels + 1) * C] = x beside `levels` chained MaxPool(k, 1, k / 2) of it (slice j =
+ * j pools), in one pass over x; bit-identical to `levels` calls of snn_pool2d_fwd.  snn_spp_supported: k in {3, 5},
+ * levels in {1, 2, 3}, C >= 1, N * H * W < 2^31.  The backward is `levels` calls of snn_pool2d_bwd on slices of y. */
+int snn_pool2d_supported(int64_t N, int H, int W, int C, int k, int stride, int pad);
+int snn_pool2d_fwd(int kind, const float* x, int64_t ldx, float* y, int64_t ldy, int64_t N, int H, int W, int C, int k,
+                   int stride, int pad, void* stream);
+int snn_pool2d_bwd(int kind, const float* x, int64_t ldx, const float* gy, int64_t ldgy, const float* addend, int64_t ldadd,
+                   float* gx, int64_t ldgx, int64_t N, int H, int W, int C, int k, int stride, int pad, void* stream);
+int snn_spp_supported(int64_t N, int H, int W, int C, int k, int levels);
+int snn_spp_fwd(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t N, int H, int W, int C, int k, int levels,
+                void* stream);
+
 /* nn.Upsample(scale_factor=s, mode="nearest") (layer_gen.py:176-194) */
 int snn_upsample_fwd(const float* x, float* y, int64_t N, int H, int W, int C, int scale, void* stream);
 int snn_upsample_bwd(const float* gy, float* gx, int64_t N, int H, int W, int C, int scale, void* stream);

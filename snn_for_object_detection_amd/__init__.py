@@ -3,7 +3,8 @@
 Public names follow the reference (``models``, ``models.generator``, ``models.modules``,
 ``utils.{anchors,roi,box}``): ``SODa``, ``TinyYolo``, ``BlockGen``, ``BackboneGen``, ``NeckGen``,
 ``Head``, ``HeadGen``, ``ListGen``, ``ListState`` and the layer generators ``Conv, Norm, LIF, LI,
-Pool, Up, Pass, Return, ReLU, SiLU, Tanh, LSTM, Synapse, SLI, Residual, Dense``.
+Pool, Up, Pass, Return, ReLU, SiLU, Tanh, LSTM, Synapse, SLI, Residual, Dense``; beyond the reference ``SPP`` (spatial
+pyramid pooling) and its module ``HipSPP``.
 
 All arithmetic of the hot path runs in ``libsnn_hip.so`` (hand-written gfx950 kernels, C ABI in
 ``include/snn_hip.h``); importing the package never touches the GPU, the first forward does and

@@ -31,7 +31,7 @@ STAMP_PATH = LIB_PATH + ".buildstamp"
 SOURCES = ("scan_bwd.hip", "conv_gather.hip", "conv_wgrad.hip", "conv_first.hip", "bn_stats.hip", "scan_fwd.hip",
            "bn_bwd.hip", "wgrad_halo.hip", "conv_halo.hip", "activity.hip", "det_loss.hip", "lstm.hip", "elementwise.hip",
            "small_gemm.hip", "targets.hip", "metrics.hip", "abi.hip", "detect.hip", "events.hip", "optimizer.hip",
-           "state_carry.hip", "conv_depthwise.hip")
+           "state_carry.hip", "conv_depthwise.hip", "pool.hip")
 MAX_WORKERS = 8   # hipcc processes at once: a fixed cap, never the machine's CPU count
 
 

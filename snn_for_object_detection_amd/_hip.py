@@ -161,6 +161,11 @@ SIGNATURES = {
     "snn_dwconv_wgrad": (c_int, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "snn_pool_fwd": (c_int, [_I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
     "snn_pool_bwd": (c_int, [_I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "snn_pool2d_supported": (c_int, [_L, _I, _I, _I, _I, _I, _I]),
+    "snn_pool2d_fwd": (c_int, [_I, _P, _L, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P]),
+    "snn_pool2d_bwd": (c_int, [_I, _P, _L, _P, _L, _P, _L, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P]),
+    "snn_spp_supported": (c_int, [_L, _I, _I, _I, _I, _I]),
+    "snn_spp_fwd": (c_int, [_P, _L, _P, _L, _L, _I, _I, _I, _I, _I, _P]),
     "snn_upsample_fwd": (c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
     "snn_upsample_bwd": (c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
     "snn_adamax_step": (c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P]),

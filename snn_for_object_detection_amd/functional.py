@@ -2570,12 +2570,122 @@ class _Pool(Function):
         return gx, None, None, None
 
 
-def pool2d(x: torch.Tensor, kind: int, kernel_size: int, stride: int) -> torch.Tensor:
+def pool_covers(N: int, H: int, W: int, C: int, k: int, stride: int, pad: int) -> bool:
+    """What the padded pooling kernels run: ``snn_pool2d_supported`` (host only; the library is the one place that says it)."""
+    return bool(_hip.query("snn_pool2d_supported", N, H, W, C, k, stride, pad))
+
+
+POOL2D_COVERED = ("snn_pool2d_supported: 2 <= kernel_size <= 7, 1 <= stride <= kernel_size, 0 <= padding <= kernel_size // 2, "
+                  "the padded input at least one window in size")
+
+
+@functools.lru_cache(maxsize=None)
+def pool_sets() -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """``(kernel sizes of a padded pool, kernel sizes of SPP)`` - ASKED of the library over the candidates a description
+    could name (what ``layer_gen.Pool.get`` / ``SPP.get`` name in their refusals)."""
+    return (tuple(k for k in range(1, 16) if pool_covers(1, 16, 16, 1, k, 1, 0)),
+            tuple(k for k in range(1, 16) if spp_covers(1, 16, 16, 1, k, 1)))
+
+
+class _PoolPad(Function):
+    """Avg / Max / SumPool2d(k, stride, padding) on csrc/pool.hip: ``x`` and ``gy`` are read at their own pixel strides
+    (a channel slice of a concat buffer is not copied).  Returns dx to autograd, as ``_Pool`` does."""
+
+    @staticmethod
+    def forward(ctx, x, kind: int, k: int, stride: int, pad: int):
+        _require_device(x, "pool input")
+        T, B, C, H, W = _dims5(x)
+        if not pool_covers(T * B, H, W, C, k, stride, pad):
+            raise RuntimeError(f"pool2d: kernel_size {k}, stride {stride}, padding {pad} on {T * B} frames of {H}x{W}x{C} is "
+                               f"not covered ({POOL2D_COVERED})")
+        x = _raw_to_cl(x)
+        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        y = _new_cl((T, B), C, Ho, Wo, x)
+        _hip.call("snn_pool2d_fwd", kind, x.data_ptr(), cl_stride(x), y.data_ptr(), cl_stride(y), T * B, H, W, C, k, stride,
+                  pad, _stream())
+        ctx.geom = (kind, k, stride, pad, T, B, C, H, W)
+        if kind == _hip.POOL_MAX:
+            ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        kind, k, stride, pad, T, B, C, H, W = ctx.geom
+        x = ctx.saved_tensors[0] if kind == _hip.POOL_MAX else None
+        gy = _raw_to_cl(gy)
+        gx = _new_cl((T, B), C, H, W, gy)
+        _hip.call("snn_pool2d_bwd", kind, _ptr(x), cl_stride(x) if x is not None else 0, gy.data_ptr(), cl_stride(gy), None, 0,
+                  gx.data_ptr(), cl_stride(gx), T * B, H, W, C, k, stride, pad, _stream())
+        return gx, None, None, None, None
+
+
+def pool2d(x: torch.Tensor, kind: int, kernel_size: int, stride: int, padding: int = 0) -> torch.Tensor:
+    """``padding == 0``: ``snn_pool_fwd`` / ``snn_pool_bwd`` (dense operands).  ``padding > 0``: the padded kernels of
+    csrc/pool.hip (floor mode; max pads with -inf, average counts the padding in its divisor), which refuse what
+    ``snn_pool2d_supported`` does not cover before anything is launched."""
     def run(t, *a):
         seq, single = as_sequence(t)
-        y = _Pool.apply(seq, *a)
+        y = _PoolPad.apply(seq, *a) if a[-1] else _Pool.apply(seq, *a[:-1])
         return y[0] if single else y
-    return _through_fp32(run, x, kind, int(kernel_size), int(stride))
+    return _through_fp32(run, x, kind, int(kernel_size), int(stride), int(padding))
+
+
+# ------------------------------------------------------------------------------------------- spatial pyramid pooling
+def spp_covers(N: int, H: int, W: int, C: int, k: int, levels: int) -> bool:
+    """What the fused pyramid forward runs: ``snn_spp_supported`` (host only)."""
+    return bool(_hip.query("snn_spp_supported", N, H, W, C, k, levels))
+
+
+class _SPP(Function):
+    """``cat([x, P(x), P(P(x)), ...])`` on channels, ``P = MaxPool2d(k, 1, k // 2)``: one forward launch
+    (``snn_spp_fwd``), ``levels`` backward launches of ``snn_pool2d_bwd`` on slices of the saved OUTPUT - nothing else is
+    saved.  With ``G = [g_0 .. g_L]`` the slices of the incoming gradient: ``h_L = g_L``, ``h_j = g_j + R(y_j; h_{j+1})``
+    (``R`` routes the gradient of ``MaxPool(y_j)`` to ``y_j``), ``dx = h_0`` - what autograd gives for the chained spelling.
+    Returns dx to autograd: like ``_Pool`` it takes no part in the ``GradAccumulator`` protocol."""
+
+    @staticmethod
+    def forward(ctx, x, k: int, levels: int, dest=None):
+        _require_device(x, "spp input")
+        T, B, C, H, W = _dims5(x)
+        if not spp_covers(T * B, H, W, C, k, levels):
+            raise RuntimeError(f"spp: kernel_size {k}, levels {levels} on {T * B} frames of {H}x{W}x{C} is not covered "
+                               "(snn_spp_supported: kernel_size in {3, 5}, levels in {1, 2, 3})")
+        x = _raw_to_cl(x)
+        y = _out_tensor(dest, T, B, (levels + 1) * C, H, W, x)
+        _hip.call("snn_spp_fwd", x.data_ptr(), cl_stride(x), y.data_ptr(), cl_stride(y), T * B, H, W, C, k, levels, _stream())
+        ctx.geom = (k, levels, T, B, C, H, W)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (y,) = ctx.saved_tensors
+        k, levels, T, B, C, H, W = ctx.geom
+        gy = _raw_to_cl(gy)
+        ldy, ldg = cl_stride(y), cl_stride(gy)
+        st = _stream()
+        h, ldh = gy.data_ptr() + 4 * levels * C, ldg          # h_L = g_L, read in place
+        keep = []
+        for j in range(levels - 1, -1, -1):                    # h_j = g_j + R(y_j; h_{j+1})
+            out = _new_cl((T, B), C, H, W, gy)
+            keep.append(out)
+            _hip.call("snn_pool2d_bwd", _hip.POOL_MAX, y.data_ptr() + 4 * j * C, ldy, h, ldh, gy.data_ptr() + 4 * j * C, ldg,
+                      out.data_ptr(), C, T * B, H, W, C, k, 1, k // 2, st)
+            h, ldh = out.data_ptr(), C
+        return keep[-1], None, None, None
+
+
+def spp(x: torch.Tensor, kernel_size: int = 5, levels: int = 3, dest: Optional[Dest] = None) -> torch.Tensor:
+    """Spatial pyramid pooling (the SPPF stage of YOLOv5 / v8 without its convolutions): ``[B,C,H,W]`` or ``[T,B,C,H,W]`` ->
+    ``[..., (levels + 1) * C, H, W]`` = ``x`` beside ``levels`` chained ``MaxPool2d(kernel_size, 1, kernel_size // 2)`` of
+    it.  ``dest``: write the result into a channel slice of a concat buffer.  bf16 storage: the fp32 kernels between two
+    conversions, as every pool."""
+    if x.dtype == _BF16:
+        y = to_bfloat16(spp(to_float32(x), kernel_size, levels, None))
+        return place(y, dest) if dest is not None and y.dim() == 5 else y
+    seq, single = as_sequence(x)
+    y = _SPP.apply(seq, int(kernel_size), int(levels), dest)
+    return y[0] if single else y
 
 
 class _Upsample(Function):

@@ -26,7 +26,7 @@ from . import _hip
 from . import functional as HF
 from .anchors import AnchorGenerator
 from .layer_gen import *  # noqa: F401,F403  (the reference re-exports the layer generators here)
-from .layer_gen import (ConvLSTM, Dense, HipBatchNorm2d, HipConv2d, HipReLU, HipSiLU, HipTanh, LayerGen,
+from .layer_gen import (ConvLSTM, Dense, HipBatchNorm2d, HipConv2d, HipReLU, HipSiLU, HipSPP, HipTanh, LayerGen,
                         LICell, LIFCell, Residual, Return, SLICell, StateStorage, Storage, SumPool2d, SynapseCell)
 
 ListGen = List[Union[LayerGen, "ListGen"]]
@@ -371,6 +371,8 @@ class BlockGen(nn.Module):
                     Y = layer(Y, dest=step_dest, bn_stats=feeds_bn)
                 elif isinstance(layer, (LIFCell, LICell, SLICell, SynapseCell)):
                     Y, branch_state[idx] = layer(Y, branch_state[idx], dest=step_dest)
+                elif isinstance(layer, HipSPP):
+                    Y = layer(Y, dest=step_dest)
                 elif flags[idx]:
                     Y, branch_state[idx] = layer(Y, branch_state[idx])
                 else:
