@@ -127,8 +127,15 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // activation tensor in HBM is fp32, or bf16 = the upper half of the fp32 pattern, rounded to nearest even when stored.
 // Kernels compute in fp32 registers either way; SnnStore<BF> moves 1 or 4 consecutive elements at ELEMENT index i.
 #ifdef __HIPCC__
-// the ConvLSTM gate non-linearity, shared by the cell kernels and the sequence scan (both in lstm.hip)
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+// the ConvLSTM gate non-linearity, shared by the cell kernels and the sequence scan (both in lstm.hip).  Below -88.7
+// expf(-x) overflows and 1 / (1 + inf) is 0, where the sigmoid (e^x to fp32 precision there) is still a subnormal number
+// down to x = -103.97: that range takes expf(x).  From -88 up the expression, and with it every bit, is as before.
+// (One expf either way.)
+__device__ __forceinline__ float sigmoidf_(float x) {
+    const bool tail = x < -88.0f;
+    const float e = expf(tail ? x : -x);
+    return tail ? e : 1.0f / (1.0f + e);
+}
 
 typedef unsigned snn_u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 snn_bf16x2 __attribute__((ext_vector_type(2)));
