@@ -10,6 +10,7 @@ not on a HIP device raise.
 """
 
 import collections
+import contextlib
 import ctypes
 import functools
 import os
@@ -21,10 +22,43 @@ from torch.autograd import Function
 
 from . import _hip
 from ._hip import NeuronParams
+# The stateless families live in the modules below (each imports only the stdlib, torch, ``_hip`` and ``_layout``); this
+# module keeps every lever and all mutable state, and stays the one namespace the package, the tests and the tools use.
+from ._layout import (_BF16, _F32, ConcatPromise, Dest, _add_cl, _alias, _cl_view, _Convert, _copy_cl,  # noqa: F401
+                      _dims5, _new_cl, _out_tensor, _ptr, _raw_convert, _raw_dense_cl, _raw_to_cl, _raw_to_nchw,
+                      _require_device, _stream, _through_fp32, _ToChannelsLast, as_sequence, cl_stride, is_channels_last,
+                      to_bfloat16, to_channels_last, to_float32)
+from .pointwise import (POOL2D_COVERED, _Act, _Pool, _PoolPad, _SPP, _Upsample, activation, pool2d,  # noqa: F401
+                        pool_covers, pool_sets, spp_covers, upsample_nearest)
+from .losses import (MAX_LABEL_STEPS, _DetectionLoss, _GatherSteps, _loss_entry, _loss_ext, _require_steps,  # noqa: F401
+                     check_loss_options, detection_loss, detection_loss_ext, detection_loss_steps,
+                     detection_loss_steps_ext, gather_steps, select_label_steps)
+from .event_ops import (AUG_Q16_MAX, AUG_Q16_MIN, AUG_Q16_ONE, _check_batch_vectors, _launch_batch_scatter,  # noqa: F401
+                        check_aug_table, events_to_frames, events_to_frames_aug, events_to_frames_packed, labels_augment)
+
+# The assignable levers of this module (each is defined, with its meaning, beside the code that reads it).
+LEVERS = ("USE_WGRAD_STREAM", "USE_HEAD_STREAMS", "WGRAD_SIDE_DEPTH", "FUSE_OUTER_ADDEND", "USE_SIBLING_FUSION",
+          "USE_SPIKES_FROM_VDEC", "USE_SPIKE_MASK", "SPIKE_MASK_MIN_BYTES", "USE_HALO_CONV", "USE_DEFERRED_BN_APPLY",
+          "SCAN_SEGMENT_T", "USE_CONV_BN_STATS", "USE_PRESPLIT_WEIGHTS", "USE_PRESPLIT_DGRAD", "SCAN_FLAGS",
+          "USE_SUMS_FROM_STATE", "LIF_CHECKPOINT_BYTES", "USE_LSTM_SCAN")
+
+
+@contextlib.contextmanager
+def levers(**values):
+    """Set levers for the enclosed block and put back what was found, however the block ends.  A name that is not in
+    ``LEVERS`` raises ``AttributeError`` before anything is changed (a misspelt lever must not pass as a no-op)."""
+    unknown = sorted(set(values) - set(LEVERS))
+    if unknown:
+        raise AttributeError(f"functional has no lever {', '.join(unknown)} (LEVERS: {', '.join(LEVERS)})")
+    found = {name: globals()[name] for name in values}
+    globals().update(values)
+    try:
+        yield
+    finally:
+        globals().update(found)
 
 # norse defaults as fp32 rounds them (dt*tau_mem_inv, -dt*tau_syn_inv, v_leak, v_th, v_reset, alpha);
 # oracle/neurons.py:neuron_constants() evaluates the same torch expressions (tests pin the equality).
-_F32 = torch.float32
 DEFAULT_DT = 0.001
 
 
@@ -224,7 +258,6 @@ def get_backward_precision() -> str:
 #   last-step read-out (a few frames).  Not a parity mode: 8 significant bits per stored value; stated tolerances in
 #   tests/test_gpu_bf16_storage.py.  The mode is decided where the event frames enter (the Cin = 2 layer writes bf16) and
 #   follows the tensors from there: an operator works in the storage type of its input.
-_BF16 = torch.bfloat16
 STORAGE_MODES = {"fp32": _F32, "bf16": _BF16}
 _activation_storage = _checked(os.environ.get("SNN_ACTIVATION_STORAGE") or "fp32", STORAGE_MODES,
                                "SNN_ACTIVATION_STORAGE: storage")
@@ -258,10 +291,6 @@ def _conv_precs(prec: Optional[Tuple[int, int]], bf16_storage: bool) -> Tuple[in
 
 
 # ------------------------------------------------------------------------------------------- helpers
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
 # Weight gradients do not feed the rest of the backward pass, so they run on a second HIP stream beside the
 # data-gradient chain (fills the CUs that small feature maps leave idle).  ``wgrad_stream_sync()`` joins the
 # side stream; trainer.FlatTrainer.step() calls it before the all-reduce / optimiser read the gradients.
@@ -389,207 +418,6 @@ class _WgradLaunch:
         self.scope.__exit__(*exc)
         if self.on_side:
             _side_hold(self.stream, *self.hold)
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
-def _require_device(t: torch.Tensor, what: str, bf16_ok: bool = False) -> None:
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: tensor is on {t.device}; the MI355X path has no CPU fallback "
-                           "(move the model and its inputs to a HIP device)")
-    if t.dtype == _BF16 and not bf16_ok:
-        raise RuntimeError(f"{what}: this operator has no bf16-storage form (convolutions, Norm + LIF / LI / LI+Tanh / "
-                           "none, and the Dense / Residual merges do); run the model with activation storage \"fp32\"")
-    if t.dtype != _F32 and t.dtype != _BF16:
-        raise RuntimeError(f"{what}: expected float32, got {t.dtype}")
-
-
-def cl_stride(x: torch.Tensor) -> Optional[int]:
-    """Pixel stride ``ld`` when the logical ``[..., C, H, W]`` tensor is stored frame-contiguously as
-    ``[..., H, W, ld >= C]`` with channel stride 1 (dense channels-last, or a channel slice of a wider
-    channels-last buffer); ``None`` otherwise."""
-    if x.dim() < 3:
-        return None
-    *lead, C, H, W = x.shape
-    st = x.stride()
-    sc, sh, sw = st[-3], st[-2], st[-1]
-    if C > 1 and sc != 1:
-        return None
-    if W > 1:
-        ld = sw
-    elif H > 1:
-        ld = sh
-    else:
-        ld = C
-        for d in range(len(lead) - 1, -1, -1):
-            if lead[d] > 1:
-                ld = st[d]
-                break
-    if ld < C or (W > 1 and sw != ld) or (H > 1 and sh != W * ld):
-        return None
-    expect = H * W * ld
-    for d in range(len(lead) - 1, -1, -1):
-        if lead[d] > 1 and st[d] != expect:
-            return None
-        expect *= lead[d]
-    return ld
-
-
-def is_channels_last(x: torch.Tensor) -> bool:
-    """True when the logical ``[..., C, H, W]`` tensor is stored DENSELY as ``[..., H, W, C]``."""
-    nd = x.dim()
-    perm = list(range(nd - 3)) + [nd - 2, nd - 1, nd - 3]
-    return x.permute(perm).is_contiguous()
-
-
-def _cl_view(buf: torch.Tensor) -> torch.Tensor:
-    """dense ``[..., H, W, C]`` buffer -> logical ``[..., C, H, W]`` view."""
-    nd = buf.dim()
-    return buf.permute(list(range(nd - 3)) + [nd - 1, nd - 3, nd - 2])
-
-
-def _new_cl(lead: Sequence[int], C: int, H: int, W: int, like: torch.Tensor, dtype=None) -> torch.Tensor:
-    """Dense channels-last tensor on ``like``'s device, in ``like``'s storage type unless ``dtype`` says otherwise."""
-    return _cl_view(torch.empty((*lead, H, W, C), device=like.device, dtype=dtype or like.dtype))
-
-
-def _alias(root: torch.Tensor, storage_offset: int, T: int, B: int, C: int, H: int, W: int, ld: int) -> torch.Tensor:
-    """A fresh tensor (no autograd view relation) over ``root``'s storage: logical ``[T,B,C,H,W]``,
-    channels-last with pixel stride ``ld``.  Only the HIP kernels write through such aliases."""
-    t = torch.empty(0, device=root.device, dtype=root.dtype)
-    t.set_(root.untyped_storage(), storage_offset, (T, B, C, H, W), (B * H * W * ld, H * W * ld, 1, W * ld, ld))
-    return t
-
-
-class ConcatPromise:
-    """A lazily allocated channels-last buffer ``[T,B,H,W,total_c]`` that several producers fill slice by
-    slice (the Dense merge of generator.py:157-161 without the copy).  A promise nested in a parent
-    destination is itself a channel slice of the parent's buffer."""
-
-    def __init__(self, total_c: int, parent: "Optional[Dest]" = None):
-        self.total_c, self.parent = total_c, parent
-        self.buf: Optional[torch.Tensor] = None
-
-    def get(self, T: int, B: int, H: int, W: int, like: torch.Tensor, dtype=None) -> torch.Tensor:
-        if self.buf is None:
-            if self.parent is not None:
-                self.buf = self.parent.tensor(T, B, self.total_c, H, W, like, dtype)
-            else:
-                self.buf = _new_cl((T, B), self.total_c, H, W, like, dtype)
-        if self.buf.dtype != (dtype or like.dtype):
-            raise RuntimeError("Dense merge: branches store their outputs in different types (fp32 / bf16 storage mixed)")
-        if tuple(self.buf.shape) != (T, B, self.total_c, H, W):
-            raise RuntimeError(f"Dense merge: branch outputs differ in shape: {tuple(self.buf.shape)} vs "
-                               f"{(T, B, self.total_c, H, W)}")
-        return self.buf
-
-
-class Dest:
-    """Where an operator must put its ``[T,B,c,H,W]`` result: channels ``off .. off+c`` of a promise."""
-
-    def __init__(self, promise: ConcatPromise, off: int, c: int):
-        self.promise, self.off, self.c = promise, off, c
-
-    def tensor(self, T: int, B: int, C: int, H: int, W: int, like: torch.Tensor, dtype=None) -> torch.Tensor:
-        if C != self.c:
-            raise RuntimeError(f"destination slice holds {self.c} channels, operator produces {C}")
-        buf = self.promise.get(T, B, H, W, like, dtype)
-        return _alias(buf, buf.storage_offset() + self.off, T, B, C, H, W, cl_stride(buf))
-
-    def holds(self, x: torch.Tensor) -> bool:
-        """True when ``x`` already IS this destination (same storage, offset and pixel stride)."""
-        buf = self.promise.buf
-        if buf is None or x.dim() != 5 or x.shape[2] != self.c:
-            return False
-        return (x.untyped_storage().data_ptr() == buf.untyped_storage().data_ptr()
-                and x.storage_offset() == buf.storage_offset() + self.off and cl_stride(x) == cl_stride(buf)
-                and tuple(x.shape[:2]) == tuple(buf.shape[:2]) and tuple(x.shape[3:]) == tuple(buf.shape[3:]))
-
-
-def _out_tensor(dest: Optional[Dest], T: int, B: int, C: int, H: int, W: int, like: torch.Tensor, dtype=None) -> torch.Tensor:
-    return dest.tensor(T, B, C, H, W, like, dtype) if dest is not None else _new_cl((T, B), C, H, W, like, dtype)
-
-
-def _raw_to_cl(x: torch.Tensor) -> torch.Tensor:
-    """Non-differentiable layout change to (possibly channel-sliced) channels-last memory."""
-    if cl_stride(x) is not None:
-        return x
-    _require_device(x, "layout", bf16_ok=True)
-    if x.dtype == _BF16:   # (rare: bf16 tensors are born channels-last) torch's strided copy
-        out = _new_cl(x.shape[:-3], *x.shape[-3:], x)
-        out.copy_(x)
-        return out
-    xc = x.contiguous()
-    lead, (C, H, W) = xc.shape[:-3], xc.shape[-3:]
-    n = 1
-    for d in lead:
-        n *= d
-    out = _new_cl(lead, C, H, W, xc)
-    _hip.call("snn_nchw_to_nhwc", xc.data_ptr(), out.data_ptr(), n, C, H, W, _stream())
-    return out
-
-
-def _raw_dense_cl(x: torch.Tensor) -> torch.Tensor:
-    """Dense channels-last copy of a channel-sliced tensor (operators without a pixel-stride argument)."""
-    x = _raw_to_cl(x)
-    if is_channels_last(x):
-        return x
-    lead, (C, H, W) = x.shape[:-3], x.shape[-3:]
-    n = 1
-    for d in lead:
-        n *= d
-    out = _new_cl(lead, C, H, W, x)
-    _hip.call("snn_copy_channels_bf16" if x.dtype == _BF16 else "snn_copy_channels", x.data_ptr(), cl_stride(x),
-              out.data_ptr(), C, n * H * W, C, _stream())
-    return out
-
-
-def _raw_to_nchw(x: torch.Tensor) -> torch.Tensor:
-    if x.is_contiguous():
-        return x
-    if x.dtype == _BF16:
-        return x.contiguous()
-    x = _raw_dense_cl(x)
-    lead, (C, H, W) = x.shape[:-3], x.shape[-3:]
-    n = 1
-    for d in lead:
-        n *= d
-    out = torch.empty(x.shape, device=x.device, dtype=_F32)
-    _hip.call("snn_nhwc_to_nchw", x.data_ptr(), out.data_ptr(), n, C, H, W, _stream())
-    return out
-
-
-class _ToChannelsLast(Function):
-    @staticmethod
-    def forward(ctx, x):
-        return _raw_to_cl(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _raw_to_nchw(g)
-
-
-def to_channels_last(x: torch.Tensor) -> torch.Tensor:
-    """Differentiable entry adapter for callers holding NCHW-contiguous frames (soda.py:138-144)."""
-    if cl_stride(x) is not None:
-        return x
-    return _ToChannelsLast.apply(x)
-
-
-def as_sequence(x: torch.Tensor) -> Tuple[torch.Tensor, bool]:
-    """``[B,C,H,W]`` or ``[T,B,C,H,W]`` -> channels-last ``[T,B,C,H,W]`` and "was a single step"."""
-    if x.dim() == 4:
-        return to_channels_last(x).unsqueeze(0), True
-    if x.dim() == 5:
-        return to_channels_last(x), False
-    raise RuntimeError(f"expected [B,C,H,W] or [T,B,C,H,W], got shape {tuple(x.shape)}")
-
-
-def _dims5(x: torch.Tensor):
-    T, B, C, H, W = x.shape
-    return T, B, C, H, W
 
 
 # ------------------------------------------------------------------------------------------- gradient slots
@@ -2222,24 +2050,6 @@ def reset_state_(state_tree, first: torch.Tensor):
 
 
 # ------------------------------------------------------------------------------------------- merges
-def _copy_cl(src: torch.Tensor, dst: torch.Tensor) -> None:
-    """dst = src, both (possibly channel-sliced) channels-last ``[T,B,C,H,W]``."""
-    if src.dtype != dst.dtype:
-        raise RuntimeError("merge: operands are stored in different types (fp32 / bf16 storage mixed)")
-    T, B, C, H, W = _dims5(src)
-    _hip.call("snn_copy_channels_bf16" if src.dtype == _BF16 else "snn_copy_channels", src.data_ptr(), cl_stride(src),
-              dst.data_ptr(), cl_stride(dst), T * B * H * W, C, _stream())
-
-
-def _add_cl(a: torch.Tensor, b: torch.Tensor, dst: torch.Tensor) -> None:
-    """dst = a + b over channels-last ``[T,B,C,H,W]`` operands with their own pixel strides (dst may be a)."""
-    if not (a.dtype == b.dtype == dst.dtype):
-        raise RuntimeError("merge: operands are stored in different types (fp32 / bf16 storage mixed)")
-    T, B, C, H, W = _dims5(a)   # (bf16 storage: the sum is formed in fp32 and rounded once)
-    _hip.call("snn_add_bf16" if a.dtype == _BF16 else "snn_add", a.data_ptr(), cl_stride(a), b.data_ptr(), cl_stride(b),
-              dst.data_ptr(), cl_stride(dst), T * B * H * W, C, _stream())
-
-
 class _Concat(Function):
     """Dense merge: torch.cat(out, dim=1) per timestep (generator.py:157-158), copying form."""
 
@@ -2467,214 +2277,7 @@ def grad_ready_hook(x: torch.Tensor, fn) -> torch.Tensor:
     return _GradReady.apply(x, fn)
 
 
-# ------------------------------------------------------------------------------------------- pointwise / pooling
-class _Act(Function):
-    @staticmethod
-    def forward(ctx, x, act: int):
-        _require_device(x, "activation input")
-        x = _raw_dense_cl(x)
-        y = _cl_view(torch.empty(x.permute(0, 1, 3, 4, 2).shape, device=x.device, dtype=_F32))
-        _hip.call("snn_act_fwd", act, x.data_ptr(), y.data_ptr(), x.numel(), _stream())
-        ctx.act = act
-        ctx.save_for_backward(x, y)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, y = ctx.saved_tensors
-        gy = _raw_dense_cl(gy)
-        gx = _cl_view(torch.empty(x.permute(0, 1, 3, 4, 2).shape, device=x.device, dtype=_F32))
-        _hip.call("snn_act_bwd", ctx.act, x.data_ptr(), y.data_ptr(), gy.data_ptr(), gx.data_ptr(), x.numel(),
-                  _stream())
-        return gx, None
-
-
-def _raw_convert(x: torch.Tensor, dtype) -> torch.Tensor:
-    """fp32 <-> bf16 copy of a tensor in the same memory order (snn_convert_bf16; round to nearest even).  Dense
-    channels-last or contiguous tensors are converted in place order; anything else is made dense channels-last first."""
-    if x.dtype == dtype:
-        return x
-    _require_device(x, "storage conversion", bf16_ok=True)
-    if x.dim() >= 3 and not x.is_contiguous():
-        x = _raw_dense_cl(x)
-        out = _new_cl(x.shape[:-3], *x.shape[-3:], x, dtype)
-    else:
-        x = x.contiguous()
-        out = torch.empty(x.shape, device=x.device, dtype=dtype)
-    if x.numel():
-        _hip.call("snn_convert_bf16", x.data_ptr(), out.data_ptr(), x.numel(), 1 if dtype == _BF16 else 0, _stream())
-    return out
-
-
-class _Convert(Function):
-    """Leaves / enters the bf16-storage domain: the gradient crosses the boundary the other way."""
-
-    @staticmethod
-    def forward(ctx, x, dtype):
-        ctx.src_dtype = x.dtype
-        return _raw_convert(x, dtype)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _raw_convert(g, ctx.src_dtype), None
-
-
-def to_float32(x: torch.Tensor) -> torch.Tensor:
-    return x if x.dtype == _F32 else _Convert.apply(x, _F32)
-
-
-def to_bfloat16(x: torch.Tensor) -> torch.Tensor:
-    return x if x.dtype == _BF16 else _Convert.apply(x, _BF16)
-
-
-def _through_fp32(op, x: torch.Tensor, *args):
-    """Operators without a bf16-storage kernel (activations, pooling, up-sampling, ConvLSTM, SLI / Synapse: none of them is
-    on the TinyYolo path) still work in that mode: the tensor is widened to fp32 for the operator and its result is
-    narrowed again (two conversion passes - correct, not fast)."""
-    if x.dtype != _BF16:
-        return op(x, *args)
-    return to_bfloat16(op(to_float32(x), *args))
-
-
-def activation(x: torch.Tensor, act: int) -> torch.Tensor:
-    def run(t, a):
-        seq, single = as_sequence(t)
-        y = _Act.apply(seq, a)
-        return y[0] if single else y
-    return _through_fp32(run, x, act)
-
-
-class _Pool(Function):
-    @staticmethod
-    def forward(ctx, x, kind: int, k: int, stride: int):
-        _require_device(x, "pool input")
-        x = _raw_dense_cl(x)
-        T, B, C, H, W = _dims5(x)
-        Ho, Wo = (H - k) // stride + 1, (W - k) // stride + 1
-        if Ho <= 0 or Wo <= 0:
-            raise RuntimeError(f"pool: window {k} larger than input {H}x{W}")
-        y = _new_cl((T, B), C, Ho, Wo, x)
-        _hip.call("snn_pool_fwd", kind, x.data_ptr(), y.data_ptr(), T * B, H, W, C, Ho, Wo, k, stride, _stream())
-        ctx.geom = (kind, k, stride, T, B, C, H, W, Ho, Wo)
-        ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        kind, k, stride, T, B, C, H, W, Ho, Wo = ctx.geom
-        gy = _raw_dense_cl(gy)
-        gx = _new_cl((T, B), C, H, W, x)
-        _hip.call("snn_pool_bwd", kind, x.data_ptr(), gy.data_ptr(), gx.data_ptr(), T * B, H, W, C, Ho, Wo, k, stride,
-                  _stream())
-        return gx, None, None, None
-
-
-def pool_covers(N: int, H: int, W: int, C: int, k: int, stride: int, pad: int) -> bool:
-    """What the padded pooling kernels run: ``snn_pool2d_supported`` (host only; the library is the one place that says it)."""
-    return bool(_hip.query("snn_pool2d_supported", N, H, W, C, k, stride, pad))
-
-
-POOL2D_COVERED = ("snn_pool2d_supported: 2 <= kernel_size <= 7, 1 <= stride <= kernel_size, 0 <= padding <= kernel_size // 2, "
-                  "the padded input at least one window in size")
-
-
-@functools.lru_cache(maxsize=None)
-def pool_sets() -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
-    """``(kernel sizes of a padded pool, kernel sizes of SPP)`` - ASKED of the library over the candidates a description
-    could name (what ``layer_gen.Pool.get`` / ``SPP.get`` name in their refusals)."""
-    return (tuple(k for k in range(1, 16) if pool_covers(1, 16, 16, 1, k, 1, 0)),
-            tuple(k for k in range(1, 16) if spp_covers(1, 16, 16, 1, k, 1)))
-
-
-class _PoolPad(Function):
-    """Avg / Max / SumPool2d(k, stride, padding) on csrc/pool.hip: ``x`` and ``gy`` are read at their own pixel strides
-    (a channel slice of a concat buffer is not copied).  Returns dx to autograd, as ``_Pool`` does."""
-
-    @staticmethod
-    def forward(ctx, x, kind: int, k: int, stride: int, pad: int):
-        _require_device(x, "pool input")
-        T, B, C, H, W = _dims5(x)
-        if not pool_covers(T * B, H, W, C, k, stride, pad):
-            raise RuntimeError(f"pool2d: kernel_size {k}, stride {stride}, padding {pad} on {T * B} frames of {H}x{W}x{C} is "
-                               f"not covered ({POOL2D_COVERED})")
-        x = _raw_to_cl(x)
-        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-        y = _new_cl((T, B), C, Ho, Wo, x)
-        _hip.call("snn_pool2d_fwd", kind, x.data_ptr(), cl_stride(x), y.data_ptr(), cl_stride(y), T * B, H, W, C, k, stride,
-                  pad, _stream())
-        ctx.geom = (kind, k, stride, pad, T, B, C, H, W)
-        if kind == _hip.POOL_MAX:
-            ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        kind, k, stride, pad, T, B, C, H, W = ctx.geom
-        x = ctx.saved_tensors[0] if kind == _hip.POOL_MAX else None
-        gy = _raw_to_cl(gy)
-        gx = _new_cl((T, B), C, H, W, gy)
-        _hip.call("snn_pool2d_bwd", kind, _ptr(x), cl_stride(x) if x is not None else 0, gy.data_ptr(), cl_stride(gy), None, 0,
-                  gx.data_ptr(), cl_stride(gx), T * B, H, W, C, k, stride, pad, _stream())
-        return gx, None, None, None, None
-
-
-def pool2d(x: torch.Tensor, kind: int, kernel_size: int, stride: int, padding: int = 0) -> torch.Tensor:
-    """``padding == 0``: ``snn_pool_fwd`` / ``snn_pool_bwd`` (dense operands).  ``padding > 0``: the padded kernels of
-    csrc/pool.hip (floor mode; max pads with -inf, average counts the padding in its divisor), which refuse what
-    ``snn_pool2d_supported`` does not cover before anything is launched."""
-    def run(t, *a):
-        seq, single = as_sequence(t)
-        y = _PoolPad.apply(seq, *a) if a[-1] else _Pool.apply(seq, *a[:-1])
-        return y[0] if single else y
-    return _through_fp32(run, x, kind, int(kernel_size), int(stride), int(padding))
-
-
 # ------------------------------------------------------------------------------------------- spatial pyramid pooling
-def spp_covers(N: int, H: int, W: int, C: int, k: int, levels: int) -> bool:
-    """What the fused pyramid forward runs: ``snn_spp_supported`` (host only)."""
-    return bool(_hip.query("snn_spp_supported", N, H, W, C, k, levels))
-
-
-class _SPP(Function):
-    """``cat([x, P(x), P(P(x)), ...])`` on channels, ``P = MaxPool2d(k, 1, k // 2)``: one forward launch
-    (``snn_spp_fwd``), ``levels`` backward launches of ``snn_pool2d_bwd`` on slices of the saved OUTPUT - nothing else is
-    saved.  With ``G = [g_0 .. g_L]`` the slices of the incoming gradient: ``h_L = g_L``, ``h_j = g_j + R(y_j; h_{j+1})``
-    (``R`` routes the gradient of ``MaxPool(y_j)`` to ``y_j``), ``dx = h_0`` - what autograd gives for the chained spelling.
-    Returns dx to autograd: like ``_Pool`` it takes no part in the ``GradAccumulator`` protocol."""
-
-    @staticmethod
-    def forward(ctx, x, k: int, levels: int, dest=None):
-        _require_device(x, "spp input")
-        T, B, C, H, W = _dims5(x)
-        if not spp_covers(T * B, H, W, C, k, levels):
-            raise RuntimeError(f"spp: kernel_size {k}, levels {levels} on {T * B} frames of {H}x{W}x{C} is not covered "
-                               "(snn_spp_supported: kernel_size in {3, 5}, levels in {1, 2, 3})")
-        x = _raw_to_cl(x)
-        y = _out_tensor(dest, T, B, (levels + 1) * C, H, W, x)
-        _hip.call("snn_spp_fwd", x.data_ptr(), cl_stride(x), y.data_ptr(), cl_stride(y), T * B, H, W, C, k, levels, _stream())
-        ctx.geom = (k, levels, T, B, C, H, W)
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (y,) = ctx.saved_tensors
-        k, levels, T, B, C, H, W = ctx.geom
-        gy = _raw_to_cl(gy)
-        ldy, ldg = cl_stride(y), cl_stride(gy)
-        st = _stream()
-        h, ldh = gy.data_ptr() + 4 * levels * C, ldg          # h_L = g_L, read in place
-        keep = []
-        for j in range(levels - 1, -1, -1):                    # h_j = g_j + R(y_j; h_{j+1})
-            out = _new_cl((T, B), C, H, W, gy)
-            keep.append(out)
-            _hip.call("snn_pool2d_bwd", _hip.POOL_MAX, y.data_ptr() + 4 * j * C, ldy, h, ldh, gy.data_ptr() + 4 * j * C, ldg,
-                      out.data_ptr(), C, T * B, H, W, C, k, 1, k // 2, st)
-            h, ldh = out.data_ptr(), C
-        return keep[-1], None, None, None
-
-
 def spp(x: torch.Tensor, kernel_size: int = 5, levels: int = 3, dest: Optional[Dest] = None) -> torch.Tensor:
     """Spatial pyramid pooling (the SPPF stage of YOLOv5 / v8 without its convolutions): ``[B,C,H,W]`` or ``[T,B,C,H,W]`` ->
     ``[..., (levels + 1) * C, H, W]`` = ``x`` beside ``levels`` chained ``MaxPool2d(kernel_size, 1, kernel_size // 2)`` of
@@ -2686,34 +2289,6 @@ def spp(x: torch.Tensor, kernel_size: int = 5, levels: int = 3, dest: Optional[D
     seq, single = as_sequence(x)
     y = _SPP.apply(seq, int(kernel_size), int(levels), dest)
     return y[0] if single else y
-
-
-class _Upsample(Function):
-    @staticmethod
-    def forward(ctx, x, scale: int):
-        _require_device(x, "upsample input")
-        x = _raw_dense_cl(x)
-        T, B, C, H, W = _dims5(x)
-        y = _new_cl((T, B), C, H * scale, W * scale, x)
-        _hip.call("snn_upsample_fwd", x.data_ptr(), y.data_ptr(), T * B, H, W, C, scale, _stream())
-        ctx.geom = (scale, T, B, C, H, W)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        scale, T, B, C, H, W = ctx.geom
-        gy = _raw_dense_cl(gy)
-        gx = _new_cl((T, B), C, H, W, gy)
-        _hip.call("snn_upsample_bwd", gy.data_ptr(), gx.data_ptr(), T * B, H, W, C, scale, _stream())
-        return gx, None
-
-
-def upsample_nearest(x: torch.Tensor, scale: int) -> torch.Tensor:
-    def run(t, sc):
-        seq, single = as_sequence(t)
-        y = _Upsample.apply(seq, sc)
-        return y[0] if single else y
-    return _through_fp32(run, x, int(scale))
 
 
 # ------------------------------------------------------------------------------------------- ConvLSTM
@@ -2879,332 +2454,3 @@ def stack_time(xs: List[torch.Tensor]) -> torch.Tensor:
     if xs and xs[0].dtype == _BF16:
         return torch.stack(list(xs))   # (time-outer loops are off the layer-major path) torch's copy
     return _StackTime.apply(*xs)
-
-
-# ------------------------------------------------------------------------------------------- detection loss
-def _loss_entry(ptrs, anc, steps, dims, ratio, modes):
-    """The C entry family of ``csrc/det_loss.hip`` a call goes through, by its shape ->
-    ``(symbol stem, doubles of stats, workspace-size arguments, leading call arguments)``."""
-    rows, A, C = dims
-    if modes is not None:      # selectable objective: means over max(n, 1) rows; stats = totals, V, the three terms
-        return "snn_det_loss_ext", 9, (rows,), ptrs + [_ptr(anc), _ptr(steps), rows, A, C, ratio, *modes]
-    if steps is not None:      # the reference's objective over K x B slots: means as they are (NaN); stats = totals, V
-        K, B = steps.shape
-        return "snn_det_loss_steps", 6, (K, B, A), ptrs + [steps.data_ptr(), K, B, A, C, ratio]
-    return "snn_det_loss", 5, (rows,), ptrs + [rows, C, ratio]   # ... over all rows; stats = totals
-
-
-class _DetectionLoss(Function):
-    """The detection loss and its gradient (``csrc/det_loss.hip``): two kernel launches forward, one backward, no host
-    round trip.  ``modes`` None: ``loss_ratio * mean(CE[pos]) + (1 - loss_ratio) * mean(CE[neg]) + mean(L1(bbox*mask,
-    offset*mask))`` (models/soda.py:259-281), NaN for an empty class; ``modes`` from ``check_loss_options`` (``anchors``
-    required): a selectable classification term (cross entropy | focal) and box term (L1 | GIoU | DIoU | CIoU), 0 for an
-    empty class.  ``steps`` None or ``[K,B]``: over the anchors of the valid slots only (``steps[k][b] >= 0``); their
-    number ``V`` is counted on the device, ``V = 0`` gives loss 0 and the gradients of empty slots are exact zeros.
-    Returns the loss and ``stats``; with ``modes`` its last three entries are the terms of the loss."""
-
-    @staticmethod
-    def forward(ctx, cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, loss_ratio: float,
-                modes: Optional[Tuple[int, float, int, float]]):
-        who = "detection_loss_steps" if modes is None else "detection_loss_steps_ext"
-        _require_device(cls_preds, "loss: class predictions")
-        _require_device(bbox_preds, "loss: box predictions")
-        # the targets and anchors go to the kernel as raw pointers: a host or float64 tensor would be a wild address
-        _require_device(bbox_offset, "loss: box offsets")
-        _require_device(bbox_mask, "loss: box mask")
-        others = [(bbox_preds, "box predictions"), (bbox_offset, "box offsets"), (bbox_mask, "box mask"),
-                  (class_labels, "class labels")]
-        if modes is not None:
-            _require_device(anchors, "loss: anchors")
-            others.append((anchors, "anchors"))
-        for t, what in others:
-            if t.device != cls_preds.device:
-                raise RuntimeError(f"loss: {what} are on {t.device}, the class predictions on {cls_preds.device}")
-        A, anc = 1, None   # (without anchors and steps every row is a frame of its own)
-        if modes is not None:
-            if anchors.dim() != 2 or anchors.shape[1] != 4 or cls_preds.dim() < 2 or cls_preds.shape[-2] != anchors.shape[0]:
-                raise RuntimeError(f"detection loss: anchors [A,4] and class predictions [..., A, C+1] required, got "
-                                   f"{tuple(anchors.shape)} and {tuple(cls_preds.shape)}")
-            A, anc = int(anchors.shape[0]), anchors.detach().contiguous()
-        Ks = None
-        if steps is not None:
-            if cls_preds.dim() != 4:
-                raise RuntimeError(f"{who}: class predictions [K,B,A,C+1] required")
-            A = int(cls_preds.shape[2])
-            Ks, steps = _require_steps(steps, int(cls_preds.shape[1]), cls_preds, who)
-        C = int(cls_preds.shape[-1])
-        logits, boxes = cls_preds.detach().contiguous(), bbox_preds.detach().contiguous()
-        off, msk = bbox_offset.contiguous(), bbox_mask.contiguous()
-        lab = class_labels.contiguous()
-        rows = lab.numel()
-        with_steps = "detection loss: predictions, targets and steps differ in shape"
-        if (modes is not None and rows == 0) or logits.numel() != rows * C or boxes.numel() != rows * 4 or \
-                off.numel() != rows * 4 or msk.numel() != rows * 4 or lab.dtype != torch.int64:
-            raise RuntimeError(with_steps if Ks is not None and modes is None else
-                               "detection loss: predictions and targets differ in shape")
-        if Ks is not None and Ks != cls_preds.shape[0]:
-            raise RuntimeError(with_steps)
-        dev = logits.device
-        ctx.args = ((rows, A, C), float(loss_ratio), modes)
-        entry, n_stats, size_args, head = _loss_entry([t.data_ptr() for t in (logits, boxes, off, msk, lab)], anc, steps,
-                                                      *ctx.args)
-        ws = torch.empty(_hip.query(entry + "_workspace_size", *size_args), device=dev, dtype=torch.uint8)
-        stats = torch.empty(n_stats, device=dev, dtype=torch.float64)
-        loss = torch.empty((), device=dev, dtype=_F32)
-        _hip.call(entry + "_fwd", *head, ws.data_ptr(), stats.data_ptr(), loss.data_ptr(), _stream())
-        ctx.optional = (anc is not None, steps is not None)
-        ctx.save_for_backward(logits, boxes, off, msk, lab, stats, *(t for t in (anc, steps) if t is not None))
-        ctx.shapes = (cls_preds.shape, bbox_preds.shape)
-        ctx.mark_non_differentiable(stats)
-        return loss, stats
-
-    @staticmethod
-    def backward(ctx, g, _g_stats):
-        logits, boxes, off, msk, lab, stats, *rest = ctx.saved_tensors
-        anc = rest.pop(0) if ctx.optional[0] else None
-        steps = rest.pop(0) if ctx.optional[1] else None
-        g = g.detach().to(_F32).contiguous()
-        g_logits, g_boxes = torch.empty_like(logits), torch.empty_like(boxes)
-        entry, _, _, head = _loss_entry([t.data_ptr() for t in (logits, boxes, off, msk, lab)], anc, steps, *ctx.args)
-        _hip.call(entry + "_bwd", *head, stats.data_ptr(), g.data_ptr(), g_logits.data_ptr(), g_boxes.data_ptr(), _stream())
-        return (g_logits.view(ctx.shapes[0]), g_boxes.view(ctx.shapes[1])) + (None,) * 7
-
-
-def detection_loss(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox_offset: torch.Tensor,
-                   bbox_mask: torch.Tensor, class_labels: torch.Tensor, loss_ratio: float) -> torch.Tensor:
-    """``loss_ratio * mean(CE[pos]) + (1 - loss_ratio) * mean(CE[neg]) + mean(L1(bbox*mask, offset*mask))``
-    (models/soda.py:259-281); a sample set without positives (or negatives) gives NaN, as the reference."""
-    return _DetectionLoss.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, None, None, loss_ratio, None)[0]
-
-
-# ------------------------------------------------------------------------------------------- every labelled timestep
-MAX_LABEL_STEPS = 32   # frame slots per sample the *_steps kernels take (kMaxLabelSteps of csrc/snn_common.h)
-
-
-def _require_steps(steps: torch.Tensor, B: int, like: torch.Tensor, what: str) -> Tuple[int, torch.Tensor]:
-    """``steps[K,B]`` as the kernels read it: int32, on ``like``'s device, contiguous.  Returns ``(K, steps)``."""
-    if steps.dim() != 2 or steps.shape[1] != B or steps.dtype != torch.int32 or steps.device != like.device:
-        raise RuntimeError(f"{what}: steps must be an int32 [K, {B}] tensor on {like.device}, got {steps.dtype} "
-                           f"{tuple(steps.shape)} on {steps.device}")
-    return int(steps.shape[0]), steps.contiguous()
-
-
-def select_label_steps(labels: torch.Tensor, T: int, K: int, t0: int = 0) -> torch.Tensor:
-    """The labelled frames of a batch, chosen on the device: ``labels[B,N,6]`` rows ``(ts, class, x1, y1, x2, y2)`` (``ts``
-    counts the steps of the uncut sequence, padding rows are -1) -> ``steps[K,B]`` int32.  For every sample the latest
-    ``K`` distinct steps ``ts - t0`` of its real rows that lie inside the cut sequence ``[0, T)``, in ascending order from
-    slot 0; unused slots hold -1.  One launch, no host synchronisation."""
-    if not labels.is_cuda or labels.dim() != 3 or labels.shape[2] != 6:
-        raise RuntimeError(f"select_label_steps: labels[B,N,6] on a HIP device required, got {tuple(labels.shape)} on "
-                           f"{labels.device}")
-    lab = labels.detach().float().contiguous()
-    B, N, _ = lab.shape
-    if N == 0:
-        return torch.full((int(K), B), -1, device=lab.device, dtype=torch.int32)
-    steps = torch.empty((int(K), B), device=lab.device, dtype=torch.int32)
-    _hip.call("snn_label_steps", lab.data_ptr(), B, N, int(T), int(K), int(t0), steps.data_ptr(), _stream())
-    return steps
-
-
-class _GatherSteps(Function):
-    """``Y[T,B,C,H,W] -> out[K,B,C,H,W]`` with ``out[k][b] = Y[steps[k][b]][b]`` (zeros for an empty slot); the backward
-    writes every frame of the gradient in one pass (zeros where no slot selected the frame)."""
-
-    @staticmethod
-    def forward(ctx, Y, steps):
-        _require_device(Y, "gather_steps")
-        Y = _raw_to_cl(Y)
-        T, B, C, H, W = Y.shape
-        K, steps = _require_steps(steps, B, Y, "gather_steps")
-        out = _new_cl((K, B), C, H, W, Y)
-        _hip.call("snn_gather_steps_fwd", Y.data_ptr(), cl_stride(Y), steps.data_ptr(), out.data_ptr(), C, T, B, K, H * W,
-                  C, _stream())
-        ctx.save_for_backward(steps)
-        ctx.dims = (T, B, C, H, W)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        (steps,) = ctx.saved_tensors
-        T, B, C, H, W = ctx.dims
-        g = _raw_to_cl(g)
-        gY = _new_cl((T, B), C, H, W, g)
-        _hip.call("snn_gather_steps_bwd", g.data_ptr(), cl_stride(g), steps.data_ptr(), gY.data_ptr(), C, T, B,
-                  int(steps.shape[0]), H * W, C, _stream())
-        return gY, None
-
-
-def gather_steps(Y: torch.Tensor, steps: torch.Tensor) -> torch.Tensor:
-    """The frames ``steps[K,B]`` names (``select_label_steps``) out of a sequence ``Y[T,B,C,H,W]`` - dense or an aliased
-    channel slice of a wider channels-last buffer - as a dense channels-last ``[K,B,C,H,W]``."""
-    if Y.dim() != 5:
-        raise RuntimeError(f"gather_steps takes a sequence Y[T,B,C,H,W], got a tensor of rank {Y.dim()}")
-    return _GatherSteps.apply(Y, steps)
-
-
-def detection_loss_steps(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox_offset: torch.Tensor,
-                         bbox_mask: torch.Tensor, class_labels: torch.Tensor, steps: torch.Tensor,
-                         loss_ratio: float) -> torch.Tensor:
-    """``detection_loss`` of ``cls_preds[K,B,A,C+1]`` / ``bbox_preds[K,B,A,4]`` over the valid slots of ``steps[K,B]``:
-    ``r mean(CE[pos]) + (1 - r) mean(CE[neg]) + sum |bbox m - off m| / (4 A V)``."""
-    if steps is None:
-        raise RuntimeError("detection_loss_steps: steps[K,B] required")
-    return _DetectionLoss.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, None, steps, loss_ratio, None)[0]
-
-
-# ------------------------------------------------------------------------------------------- selectable detection loss
-def check_loss_options(cls_loss: str, focal_gamma: float, box_loss: str, box_loss_weight: float) -> Tuple[int, float, int, float]:
-    """The loss options by name -> ``(cls_mode, gamma, box_mode, box_weight)`` as the kernels take them, or ``ValueError``."""
-    if cls_loss not in _hip.LOSS_CLS_MODES:
-        raise ValueError(f"cls_loss must be one of {sorted(_hip.LOSS_CLS_MODES)}, got {cls_loss!r}")
-    if box_loss not in _hip.LOSS_BOX_MODES:
-        raise ValueError(f"box_loss must be one of {sorted(_hip.LOSS_BOX_MODES)}, got {box_loss!r}")
-    if not float(focal_gamma) >= 0.0:
-        raise ValueError(f"focal_gamma must be >= 0, got {focal_gamma}")
-    if not float(box_loss_weight) >= 0.0:
-        raise ValueError(f"box_loss_weight must be >= 0, got {box_loss_weight}")
-    return _hip.LOSS_CLS_MODES[cls_loss], float(focal_gamma), _hip.LOSS_BOX_MODES[box_loss], float(box_loss_weight)
-
-
-def _loss_ext(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, loss_ratio, cls_loss,
-              focal_gamma, box_loss, box_loss_weight, return_terms):
-    modes = check_loss_options(cls_loss, focal_gamma, box_loss, box_loss_weight)
-    loss, stats = _DetectionLoss.apply(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps,
-                                       loss_ratio, modes)
-    if not return_terms:
-        return loss
-    terms = stats[6:9].to(_F32)       # the kernel's own fp32 terms: (terms[0] + terms[1]) + terms[2] is the loss, bit for bit
-    return loss, terms[0] + terms[1], terms[2]
-
-
-def detection_loss_ext(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox_offset: torch.Tensor,
-                       bbox_mask: torch.Tensor, class_labels: torch.Tensor, anchors: torch.Tensor, loss_ratio: float,
-                       cls_loss: str = "ce", focal_gamma: float = 2.0, box_loss: str = "l1",
-                       box_loss_weight: float = 1.0, return_terms: bool = False):
-    """``detection_loss`` with a selectable objective: ``cls_loss`` ``"ce"`` or ``"focal"`` (``(1 - p_y)^gamma ce``, same
-    ``loss_ratio`` weighting, means over ``max(n, 1)`` rows), ``box_loss`` ``"l1"`` (the term of ``detection_loss``) or
-    ``"giou" | "diou" | "ciou"`` of the boxes decoded from ``anchors[A,4]`` with the predicted and the target offsets,
-    summed over the positive rows and divided by ``max(n_pos, 1)``; the box term is scaled by ``box_loss_weight``.
-    ``return_terms``: ``(loss, classification term, box term)`` - device scalars, ``loss`` is their fp32 sum."""
-    return _loss_ext(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, None, loss_ratio, cls_loss,
-                     focal_gamma, box_loss, box_loss_weight, return_terms)
-
-
-def detection_loss_steps_ext(cls_preds: torch.Tensor, bbox_preds: torch.Tensor, bbox_offset: torch.Tensor,
-                             bbox_mask: torch.Tensor, class_labels: torch.Tensor, anchors: torch.Tensor,
-                             steps: torch.Tensor, loss_ratio: float, cls_loss: str = "ce", focal_gamma: float = 2.0,
-                             box_loss: str = "l1", box_loss_weight: float = 1.0, return_terms: bool = False):
-    """``detection_loss_ext`` of ``cls_preds[K,B,A,C+1]`` / ``bbox_preds[K,B,A,4]`` over the valid slots of ``steps[K,B]``
-    (their number ``V`` is counted on the device; the L1 term divides by ``4 A V``); no valid slot: loss 0, zero gradients."""
-    if steps is None:
-        raise RuntimeError("detection_loss_steps_ext: steps[K,B] required")
-    return _loss_ext(cls_preds, bbox_preds, bbox_offset, bbox_mask, class_labels, anchors, steps, loss_ratio, cls_loss,
-                     focal_gamma, box_loss, box_loss_weight, return_terms)
-
-
-# ------------------------------------------------------------------------------------------- events
-def events_to_frames(t_bin: torch.Tensor, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, T: int, H: int,
-                     W: int) -> torch.Tensor:
-    """Scatter events into binary frames ``[T, 2, H, W]`` (utils/datasets.py:378-435), on device."""
-    for t in (t_bin, x, y, p):
-        if not t.is_cuda or t.dtype != torch.int32:
-            raise RuntimeError("events_to_frames: int32 HIP tensors required")
-    buf = torch.empty((T, H, W, 2), device=t_bin.device, dtype=_F32)
-    _hip.call("snn_events_to_frames", t_bin.data_ptr(), x.data_ptr(), y.data_ptr(), p.data_ptr(), t_bin.numel(),
-              buf.data_ptr(), T, H, W, _stream())
-    return buf.permute(0, 3, 1, 2)
-
-
-AUG_Q16_ONE, AUG_Q16_MIN, AUG_Q16_MAX = 1 << 16, 1 << 14, 1 << 18   # zoom factors 1, 0.25 and 4 of an augmentation table
-
-
-def check_aug_table(table: torch.Tensor, B: int) -> torch.Tensor:
-    """A host augmentation table for ``B`` samples (``int32[B, 8]`` rows ``flip, a_q16, ox, oy, drop_bits, seed_bits, 0,
-    0``, include/snn_hip.h) or ``ValueError``: the kernels take any contents without harm, the zoom range is kept here."""
-    if not isinstance(table, torch.Tensor) or table.is_cuda or table.dtype != torch.int32:
-        raise ValueError("aug_table: a host int32 tensor is required")
-    if tuple(table.shape) != (B, 8):
-        raise ValueError(f"aug_table: shape {tuple(table.shape)} is not [{B}, 8]")
-    if B and not bool(((table[:, 0] == 0) | (table[:, 0] == 1)).all()):
-        raise ValueError("aug_table: flip must be 0 or 1")
-    if B and (int(table[:, 1].min()) < AUG_Q16_MIN or int(table[:, 1].max()) > AUG_Q16_MAX):
-        raise ValueError(f"aug_table: a_q16 outside [{AUG_Q16_MIN}, {AUG_Q16_MAX}] (zoom 0.25 to 4)")
-    return table.contiguous()
-
-
-def _check_batch_vectors(events, offsets: torch.Tensor, t0: torch.Tensor, aug: Optional[torch.Tensor], B: int,
-                         message: str) -> None:
-    """The ``(tensor, dtype, numel)`` triples of ``events`` and the batch's ``offsets[B + 1]``, ``t0[B]``, ``aug[B, 8]`` (or
-    None): every one a contiguous HIP tensor of its type and size, or ``ValueError(message)``."""
-    want = tuple(events) + ((offsets, torch.int64, B + 1), (t0, torch.int64, B))
-    if aug is not None:
-        want += ((aug, torch.int32, 8 * B),)
-    for v, dtype, n in want:
-        if not v.is_cuda or v.dtype != dtype or v.numel() != n or not v.is_contiguous():
-            raise ValueError(message)
-
-
-def _launch_batch_scatter(entry: str, events, n: int, offsets: torch.Tensor, t0: torch.Tensor,
-                          aug: Optional[torch.Tensor], T: int, B: int, H: int, W: int, step_us: int) -> torch.Tensor:
-    """Allocate ``[T][B][H][W][2]``, call the batch scatter ``entry`` on the ``events`` tensors and return the logical
-    ``[T, B, 2, H, W]`` view."""
-    buf = torch.empty((T, B, H, W, 2), device=events[0].device, dtype=_F32)
-    _hip.call(entry, *(v.data_ptr() for v in events), offsets.data_ptr(), t0.data_ptr(),
-              aug.data_ptr() if aug is not None else None, int(n), buf.data_ptr(), T, B, H, W, int(step_us), _stream())
-    return buf.permute(0, 1, 4, 2, 3)
-
-
-def events_to_frames_aug(t_us: torch.Tensor, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, offsets: torch.Tensor,
-                         t0: torch.Tensor, aug: torch.Tensor, T: int, H: int, W: int, step_us: int) -> torch.Tensor:
-    """``snn_events_to_frames_aug`` on device tensors: the events of a whole batch (``t_us`` int64, ``x, y, p`` int32,
-    sample ``b`` at ``offsets[b]:offsets[b+1]``, window starts ``t0[B]``) binned, transformed by the rows of ``aug``
-    (a device copy of a table ``check_aug_table`` passed) and scattered -> ``[T, B, 2, H, W]``, channels-last memory."""
-    B = int(t0.numel())
-    if int(step_us) <= 0:
-        raise ValueError(f"events_to_frames_aug: step_us must be positive, got {step_us}")
-    n = t_us.numel()
-    _check_batch_vectors(((t_us, torch.int64, n), (x, torch.int32, n), (y, torch.int32, n), (p, torch.int32, n)),
-                         offsets, t0, aug, B,
-                         "events_to_frames_aug: contiguous HIP tensors t_us int64[n], x / y / p int32[n], offsets "
-                         "int64[B + 1], t0 int64[B], aug int32[B, 8] required")
-    return _launch_batch_scatter("snn_events_to_frames_aug", (t_us, x, y, p), n, offsets, t0, aug, T, B, H, W, step_us)
-
-
-def events_to_frames_packed(words: torch.Tensor, offsets: torch.Tensor, t0: torch.Tensor, aug: Optional[torch.Tensor],
-                            T: int, B: int, H: int, W: int, step_us: int) -> torch.Tensor:
-    """``snn_events_to_frames_packed`` on device tensors: the DAT records of a whole batch (``words`` uint32 or int32
-    ``[n, 2]`` rows ``ts_us, data``, any storage offset that is a whole record; sample ``b`` at
-    ``offsets[b]:offsets[b+1]``, window starts ``t0[B]``) unpacked, binned, transformed by the rows of ``aug`` (``None``: the
-    identity, no table is read) and scattered -> ``[T, B, 2, H, W]``, channels-last memory."""
-    T, B, H, W = int(T), int(B), int(H), int(W)
-    if int(step_us) <= 0:
-        raise ValueError(f"events_to_frames_packed: step_us must be positive, got {step_us}")
-    if min(T, B, H, W) <= 0:
-        raise ValueError(f"events_to_frames_packed: T, B, H, W must be positive, got {(T, B, H, W)}")
-    word_types = tuple(d for d in (getattr(torch, "uint32", None), torch.int32) if d is not None)
-    if (not words.is_cuda or words.dtype not in word_types or words.dim() != 2 or words.shape[1] != 2
-            or not words.is_contiguous() or words.data_ptr() % 8):
-        raise ValueError("events_to_frames_packed: words must be a contiguous 8-byte aligned HIP tensor uint32[n, 2]")
-    _check_batch_vectors((), offsets, t0, aug, B,
-                         "events_to_frames_packed: contiguous HIP tensors offsets int64[B + 1], t0 int64[B], aug "
-                         "int32[B, 8] or None required")
-    return _launch_batch_scatter("snn_events_to_frames_packed", (words,), words.shape[0], offsets, t0, aug, T, B, H, W,
-                                 step_us)
-
-
-def labels_augment(labels: torch.Tensor, aug: torch.Tensor, W: int, H: int, min_visible: float = 0.25,
-                   min_size_px: float = 2.0) -> torch.Tensor:
-    """``snn_labels_augment``: the boxes of device ``labels[B, N, 5 | 6]`` under the rows of the device table ``aug`` -
-    clipped to the frame, dropped (-1 rows) when too little stays visible or the box gets too small, the kept rows of a
-    sample in front in their order.  Same shape out."""
-    if not labels.is_cuda or labels.dtype != _F32 or labels.dim() != 3 or labels.shape[2] not in (5, 6):
-        raise ValueError("labels_augment: fp32 HIP labels [B, N, 5 | 6] required")
-    B, N, width = (int(v) for v in labels.shape)
-    if not aug.is_cuda or aug.dtype != torch.int32 or aug.numel() != 8 * B or not aug.is_contiguous():
-        raise ValueError("labels_augment: aug int32[B, 8] on the device required")
-    labels = labels.contiguous()
-    out = torch.empty_like(labels)
-    if B and N:
-        _hip.call("snn_labels_augment", labels.data_ptr(), out.data_ptr(), aug.data_ptr(), B, N, width, int(W), int(H),
-                  float(min_visible), float(min_size_px), _stream())
-    return out

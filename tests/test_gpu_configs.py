@@ -439,15 +439,11 @@ def test_config4_deep12_real_per_gpu_share_b2_t128(S):
         blk.train(train)
         tr = FlatTrainer(blk)
         tr.zero_grad()
-        old = HF.SCAN_SEGMENT_T
-        HF.SCAN_SEGMENT_T = segment
-        try:
+        with HF.levers(SCAN_SEGMENT_T=segment):
             out, _ = blk(X[:, sl], last_only=True)
             (out * probe[sl]).sum().backward()
             tr.synchronize()
-        finally:
-            HF.SCAN_SEGMENT_T = old
-        g = tr.flat_grad.clone()
+        g =tr.flat_grad.clone()
         del blk, tr, out
         gc.collect()
         torch.cuda.empty_cache()

@@ -203,8 +203,7 @@ def test_halo_kernel_serves_the_model_layers_and_matches_the_implicit_gemm(H_):
     x = (torch.rand(T, B, 32, H, W, device="cuda") < 0.3).float()
     res = {}
     for on in (True, False):
-        HF.USE_HALO_CONV = on
-        try:
+        with HF.levers(USE_HALO_CONV=on):
             for m in blk.modules():
                 if isinstance(m, torch.nn.BatchNorm2d):
                     m.reset_running_stats()
@@ -213,8 +212,6 @@ def test_halo_kernel_serves_the_model_layers_and_matches_the_implicit_gemm(H_):
             blk.zero_grad(set_to_none=True)
             out.square().mean().backward()
             res[on] = (out.detach().clone(), xin.grad.clone(), [p.grad.clone() for p in blk.parameters()])
-        finally:
-            HF.USE_HALO_CONV = True
     assert rel_err(res[True][0], res[False][0]) < 1e-5
     assert rel_err(res[True][1], res[False][1]) < 1e-4
     for a, b in zip(res[True][2], res[False][2]):
@@ -300,10 +297,8 @@ def test_bottleneck_layers_do_not_defer_their_batchnorm_apply_and_toggling_it_is
         return real_call(name, *a)
 
     res = {}
-    was = HF.USE_DEFERRED_BN_APPLY
     for fused in (True, False):
-        HF.USE_DEFERRED_BN_APPLY = fused
-        try:
+        with HF.levers(USE_DEFERRED_BN_APPLY=fused):
             torch.manual_seed(12)
             blk = BlockGen(64, [Conv(64, 3), Norm(), LIF(), Conv(128, 3), Norm(), LIF(), Conv(128, 3), Norm(), LIF()])
             blk = blk.cuda().train()
@@ -320,8 +315,6 @@ def test_bottleneck_layers_do_not_defer_their_batchnorm_apply_and_toggling_it_is
             tr.synchronize()
             res[fused] = (xin.grad.clone(), tr.flat_grad.clone(), list(calls))
             assert not HF._PENDING_APPLY
-        finally:
-            HF.USE_DEFERRED_BN_APPLY = was
     assert res[True][2].count("snn_bn_bwd_apply") == 3 and res[False][2].count("snn_bn_bwd_apply") == 3
     assert "snn_conv2d_wgrad_bn" not in res[True][2] and "snn_conv2d_wgrad_bn" not in res[False][2]
     assert torch.equal(res[True][0], res[False][0]) and torch.equal(res[True][1], res[False][1])

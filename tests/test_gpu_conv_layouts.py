@@ -664,21 +664,19 @@ def test_spike_branch_writing_into_a_misaligned_concat_slice_trains(H_, net):
     probe = torch.randn(T, B, Ct, Ho, Wo, generator=torch.Generator().manual_seed(2))
 
     def run(on):
-        was = HF.USE_SPIKES_FROM_VDEC
-        HF.USE_SPIKES_FROM_VDEC = on
         calls = []
         _spy(_hip, calls)
         try:
-            blk.zero_grad(set_to_none=True)
-            y, _ = blk(X.cuda())
-            (y * probe.cuda()).sum().backward()
-            torch.cuda.synchronize()
-            HF.wgrad_stream_sync()
-            torch.cuda.synchronize()
-            return y.detach().cpu(), {n: p.grad.detach().cpu().clone() for n, p in blk.named_parameters()}, calls
+            with HF.levers(USE_SPIKES_FROM_VDEC=on):
+                blk.zero_grad(set_to_none=True)
+                y, _ = blk(X.cuda())
+                (y * probe.cuda()).sum().backward()
+                torch.cuda.synchronize()
+                HF.wgrad_stream_sync()
+                torch.cuda.synchronize()
+                return y.detach().cpu(), {n: p.grad.detach().cpu().clone() for n, p in blk.named_parameters()}, calls
         finally:
             _hip.PROFILER = None
-            HF.USE_SPIKES_FROM_VDEC = was
 
     y1, g1, calls1 = run(True)
     fwd = [a for nm, a in calls1 if nm == "snn_conv2d_spikes_fwd"]

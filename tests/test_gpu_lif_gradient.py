@@ -56,11 +56,8 @@ def run_device(HF, cs, inp, prm, variant="default", ckpt_bytes=None):
     """F.run_device for the rows of this file, with the layer's own parameters; also returns the saved potentials."""
     from snn_for_object_detection_amd import _hip
     from snn_for_object_detection_amd.layer_gen import HipBatchNorm2d
-    saved = (HF.USE_SUMS_FROM_STATE, HF.LIF_CHECKPOINT_BYTES, HF.SCAN_FLAGS)
-    HF.USE_SUMS_FROM_STATE = variant != "no_yfree"
-    HF.LIF_CHECKPOINT_BYTES = ckpt_bytes
-    HF.SCAN_FLAGS = _hip.SCAN_WIDE_ADDRESSING if variant == "wide" else 0
-    try:
+    with HF.levers(USE_SUMS_FROM_STATE=variant != "no_yfree", LIF_CHECKPOINT_BYTES=ckpt_bytes,
+                   SCAN_FLAGS=_hip.SCAN_WIDE_ADDRESSING if variant == "wide" else 0):
         bn = None
         if cs.bn is not None:
             bn = HipBatchNorm2d(cs.C).cuda()
@@ -102,8 +99,6 @@ def run_device(HF, cs, inp, prm, variant="default", ckpt_bytes=None):
                           {k: v.to(D) for k, v in raw_grads.items()}, True)
         bits = {"out": raw, "vT": st.v.detach().clone(), "iT": st.i.detach().clone(), "vdec": vdec}
         return res, bits, raw_grads
-    finally:
-        HF.USE_SUMS_FROM_STATE, HF.LIF_CHECKPOINT_BYTES, HF.SCAN_FLAGS = saved
 
 
 # ------------------------------------------------------------------------------------------------------ checks

@@ -75,9 +75,7 @@ def _run(d, dims, scan: bool):
     buf[..., 3 * bool(pad):3 * bool(pad) + Cin] = d["x"].cuda().permute(0, 1, 3, 4, 2)
     x = buf[..., 3 * bool(pad):3 * bool(pad) + Cin].permute(0, 1, 4, 2, 3).requires_grad_()
     state = None if d["state"] is None else tuple(s.cuda().requires_grad_() for s in d["state"])
-    old = HF.USE_LSTM_SCAN
-    HF.USE_LSTM_SCAN = scan
-    try:
+    with HF.levers(USE_LSTM_SCAN=scan):
         assert cell.takes_scan(x, state) == scan
         hs, (hT, cT) = cell(x, state)
         loss = 0.0
@@ -85,8 +83,6 @@ def _run(d, dims, scan: bool):
             if g is not None:
                 loss = loss + (out * g.cuda()).sum()
         loss.backward()
-    finally:
-        HF.USE_LSTM_SCAN = old
     torch.cuda.synchronize()
     assert torch.equal(hT, hs[-1])
     res = {"hs": hs.detach(), "c_T": cT.detach(), "dx": x.grad, "dw": cell.conv.weight.grad,
@@ -197,14 +193,10 @@ def test_flat_trainer_writes_the_weight_gradient_through_its_slot(S):
         blk = BlockGen(Cin, [Conv(16, 1), Norm(), LSTM(), LSTM(32)]).cuda()
         tr = FlatTrainer(blk)
         tr.zero_grad()
-        old = HF.USE_LSTM_SCAN
-        HF.USE_LSTM_SCAN = scan
-        try:
+        with HF.levers(USE_LSTM_SCAN=scan):
             out, _ = blk(x)
             (out * g).sum().backward()
             tr.synchronize()
-        finally:
-            HF.USE_LSTM_SCAN = old
         for cell in (m for m in blk.modules() if isinstance(m, ConvLSTM)):
             p = cell.conv.weight
             assert p.grad is None and p._snn_grad_slot.written

@@ -237,11 +237,8 @@ def run_device(HF, cs, inp, variant, sync_group=None, batch=None):
     """``sync_group``: the layer is a SyncBatchNorm one over that process group; ``batch``: this rank's samples."""
     from snn_for_object_detection_amd import _hip
     from snn_for_object_detection_amd.layer_gen import HipBatchNorm2d
-    saved = (HF.USE_SUMS_FROM_STATE, HF.LIF_CHECKPOINT_BYTES, HF.SCAN_FLAGS)
-    HF.USE_SUMS_FROM_STATE = variant != "no_yfree"
-    HF.LIF_CHECKPOINT_BYTES = 0 if variant == "ckpt" else None
-    HF.SCAN_FLAGS = _hip.SCAN_WIDE_ADDRESSING if variant == "wide" else 0
-    try:
+    with HF.levers(USE_SUMS_FROM_STATE=variant != "no_yfree", LIF_CHECKPOINT_BYTES=0 if variant == "ckpt" else None,
+                   SCAN_FLAGS=_hip.SCAN_WIDE_ADDRESSING if variant == "wide" else 0):
         if batch is not None:
             cs, inp = batch_share(cs, inp, batch)
         T, B, C, H, W = cs.T, cs.B, cs.C, cs.H, cs.W
@@ -324,8 +321,6 @@ def run_device(HF, cs, inp, variant, sync_group=None, batch=None):
                         None if bn is None else bn.running_mean.detach().to(D),
                         None if bn is None else bn.running_var.detach().to(D), grads, guard_ok)
         return res
-    finally:
-        HF.USE_SUMS_FROM_STATE, HF.LIF_CHECKPOINT_BYTES, HF.SCAN_FLAGS = saved
 
 
 # ------------------------------------------------------------------------------------------------------ reference

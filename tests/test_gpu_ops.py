@@ -201,8 +201,7 @@ def test_flat_trainer_presplit_weights_leave_the_step_bit_identical(HF):
         blk = BlockGen(32, [Conv(64, 3), Norm(), LIF(), Conv(128, 3, 2), Norm(), LIF(), Conv(64, 1)]).cuda().train()
         tr = FlatTrainer(blk, lr=1e-2)
         x = (torch.rand(4, 2, 32, 24, 30, device="cuda") < 0.3).float()
-        HF.USE_PRESPLIT_WEIGHTS = use
-        try:
+        with HF.levers(USE_PRESPLIT_WEIGHTS=use):
             losses = []
             for _ in range(3):
                 tr.zero_grad()
@@ -212,8 +211,6 @@ def test_flat_trainer_presplit_weights_leave_the_step_bit_identical(HF):
                 tr.step()
                 losses.append(loss.item())
             tr.synchronize()
-        finally:
-            HF.USE_PRESPLIT_WEIGHTS = True
         outs.append((losses, tr.flat_grad.clone(), tr.flat_param.clone()))
     assert outs[0][0] == outs[1][0]
     assert torch.equal(outs[0][1], outs[1][1]) and torch.equal(outs[0][2], outs[1][2])
@@ -232,12 +229,9 @@ def test_conv_feeds_batchnorm_statistics_through_the_modules(HF):
         blk = BlockGen(C, [Conv(32, 3), Norm(), LIF(), Conv(64, 3, 2), Norm(), LIF()]).cuda()
         blk.train()
         x = (torch.rand(T, B, C, H, W, device="cuda") < 0.3).float().requires_grad_()
-        HF.USE_CONV_BN_STATS = use
-        try:
+        with HF.levers(USE_CONV_BN_STATS=use):
             y, _ = blk(x)
             (y * torch.linspace(0.5, 1.5, y.numel(), device="cuda").view_as(y)).sum().backward()
-        finally:
-            HF.USE_CONV_BN_STATS = True
         results.append((y.detach(), x.grad, [p.grad for p in blk.parameters()],
                         [b.clone() for b in blk.buffers()]))
     (ya, ga, pa, ba), (yb, gb, pb, bb) = results
@@ -263,14 +257,11 @@ def test_long_backward_scan_in_segments_equals_one_launch(HF, neuron):
     gv = torch.randn(B, C, H, W).cuda()
     results = []
     for seg in (None, 32):
-        HF.SCAN_SEGMENT_T = seg
-        try:
+        with HF.levers(SCAN_SEGMENT_T=seg):
             bn = torch.nn.BatchNorm2d(C).cuda().train()
             y = y0.cuda().requires_grad_()
             out, state = HF.affine_neuron(y, kind, None, bn=bn)
             results.append(torch.autograd.grad((out, state.v), (y, bn.weight, bn.bias), (g, gv)))
-        finally:
-            HF.SCAN_SEGMENT_T = 32
     (gy_a, gw_a, gb_a), (gy_b, gw_b, gb_b) = results
     assert torch.isfinite(gy_a).all() and rel_err(gy_b, gy_a) < 1e-6      # coefficients use t-ordered sums per segment
     assert rel_err(gw_b, gw_a) < 1e-5 and rel_err(gb_b, gb_a) < 1e-5
@@ -428,14 +419,11 @@ def test_checkpointed_lif_is_bit_identical(HF, C, H, W, T, B, with_bn):
     g_v, g_i = torch.randn(B, C, H, W).cuda(), torch.randn(B, C, H, W).cuda()
     results = []
     for threshold in (None, 0):
-        HF.LIF_CHECKPOINT_BYTES = threshold
-        try:
+        with HF.levers(LIF_CHECKPOINT_BYTES=threshold):
             bn = torch.nn.BatchNorm2d(C).cuda().train() if with_bn else None
             out, st = HF.affine_neuron(y, _hip.NEURON_LIF, HF.NeuronState(v0, i0), bn=bn, addend=x)
             inputs = (y, x, v0, i0) + ((bn.weight, bn.bias) if with_bn else ())
             grads = torch.autograd.grad((out, st.v, st.i), inputs, (g, g_v, g_i))
-        finally:
-            HF.LIF_CHECKPOINT_BYTES = None
         results.append((out, st.v, st.i) + tuple(grads))
     assert float((results[0][0] - x).detach().abs().sum()) > 0  # spikes present
     # C = 6 takes the LDS-atomics reduction (group count not a power of two): its BatchNorm sums are not ordered
@@ -461,17 +449,12 @@ def test_backward_scan_addressing_variants_agree(HF, C, H, W, T, B):
     x = torch.randn(T, B, C, H, W).cuda().requires_grad_()
     g = torch.randn(T, B, C, H, W).cuda()
     results = []
-    was = HF.USE_SUMS_FROM_STATE
-    HF.USE_SUMS_FROM_STATE = False   # both forms of the scan that READS y (the other one has a buffer-addressed form only)
     for no_buf in (False, True):
-        HF.SCAN_FLAGS = _hip.SCAN_WIDE_ADDRESSING if no_buf else 0
-        try:
+        # both forms of the scan that READS y (the other one has a buffer-addressed form only)
+        with HF.levers(USE_SUMS_FROM_STATE=False, SCAN_FLAGS=_hip.SCAN_WIDE_ADDRESSING if no_buf else 0):
             bn = torch.nn.BatchNorm2d(C).cuda().train()
             out, st = HF.affine_neuron(y, _hip.NEURON_LIF, None, bn=bn, addend=x)
             results.append(torch.autograd.grad(out, (y, x, bn.weight, bn.bias), g))
-        finally:
-            HF.SCAN_FLAGS = 0
-    HF.USE_SUMS_FROM_STATE = was
     ordered = (C // 4) & (C // 4 - 1) == 0
     for a, b in zip(*results):
         assert torch.isfinite(a).all()
@@ -505,8 +488,6 @@ def test_reverse_scan_statistic_from_the_saved_state(HF, C, H, W, T, B, shortcut
     bias = 0.4 * torch.randn(C)
     results, flags = [], []
     for on in (True, False):
-        was = HF.USE_SUMS_FROM_STATE
-        HF.USE_SUMS_FROM_STATE = on
         calls = []
 
         class Spy:
@@ -517,15 +498,15 @@ def test_reverse_scan_statistic_from_the_saved_state(HF, C, H, W, T, B, shortcut
                 pass
         _hip.PROFILER = Spy()
         try:
-            bn = torch.nn.BatchNorm2d(C).cuda().train()
-            bn.weight.data.copy_(gamma)
-            bn.bias.data.copy_(bias)
-            out, st = HF.affine_neuron(y, _hip.NEURON_LIF, None, bn=bn, addend=x)
-            inputs = (y, bn.weight, bn.bias) + ((x,) if shortcut else ())
-            results.append(torch.autograd.grad(out, inputs, g))
+            with HF.levers(USE_SUMS_FROM_STATE=on):
+                bn = torch.nn.BatchNorm2d(C).cuda().train()
+                bn.weight.data.copy_(gamma)
+                bn.bias.data.copy_(bias)
+                out, st = HF.affine_neuron(y, _hip.NEURON_LIF, None, bn=bn, addend=x)
+                inputs = (y, bn.weight, bn.bias) + ((x,) if shortcut else ())
+                results.append(torch.autograd.grad(out, inputs, g))
         finally:
             _hip.PROFILER = None
-            HF.USE_SUMS_FROM_STATE = was
         flags.append([a[19] for nm, a in calls if nm == "snn_affine_neuron_bwd"])
         names = [nm for nm, _ in calls]
         assert ("snn_bn_bwd_finalize_from_state" in names) == on and ("snn_bn_bwd_finalize" in names) == (not on)
@@ -647,17 +628,13 @@ def test_last_step_only_lif_long_sequence_in_segments(HF):
     x = torch.randn(T, B, C, H, W, device="cuda") * 2
     g_last = torch.randn(B, C, H, W, device="cuda")
     res = []
-    was = HF.USE_SUMS_FROM_STATE
-    HF.USE_SUMS_FROM_STATE = False   # the full scan that reads y, as the last-step-only one does: same bits
-    try:
+    with HF.levers(USE_SUMS_FROM_STATE=False):   # the full scan that reads y, as the last-step-only one does: same bits
         for last_only in (True, False):
             bn = HipBatchNorm2d(C).cuda().train()
             xin = x.clone().requires_grad_()
             out, st = HF.affine_neuron(xin, _hip.NEURON_LIF, None, bn=bn, last_only=last_only)
             (out if last_only else out[-1]).backward(g_last)
             res.append(((out if last_only else out[-1]).detach(), xin.grad, bn.weight.grad, st.v.detach(), st.i.detach()))
-    finally:
-        HF.USE_SUMS_FROM_STATE = was
     for a, b in zip(*res):
         assert torch.equal(a, b)
     assert res[0][0].sum() > 0 and res[0][1].abs().sum() > 0
@@ -675,8 +652,7 @@ def test_last_step_only_never_takes_the_checkpointed_scan(HF):
     g_last = torch.randn(B, C, H, W, device="cuda")
     res = []
     for lever in (0, None):
-        HF.LIF_CHECKPOINT_BYTES = lever          # 0 = every LIF layer, None = never
-        try:
+        with HF.levers(LIF_CHECKPOINT_BYTES=lever):          # 0 = every LIF layer, None = never
             bn = HipBatchNorm2d(C).cuda().train()
             xin = x.clone().requires_grad_()
             guard = torch.full((4 * T * B * C * H * W,), 7.0, device="cuda")   # neighbours of the small output buffer
@@ -685,8 +661,6 @@ def test_last_step_only_never_takes_the_checkpointed_scan(HF):
             out.backward(g_last)
             assert bool((guard == 7.0).all())
             res.append((out.detach(), xin.grad, bn.weight.grad, st.v.detach(), st.i.detach()))
-        finally:
-            HF.LIF_CHECKPOINT_BYTES = None
     for a, b in zip(*res):
         assert torch.equal(a, b)
 

@@ -36,22 +36,15 @@ def _c2f(S, c, n):
 
 
 def _build(S, cfg, fused, seed=3):
-    HF = S.functional
-    was = HF.USE_SIBLING_FUSION
-    HF.USE_SIBLING_FUSION = fused
-    try:
+    with S.functional.levers(USE_SIBLING_FUSION=fused):
         torch.manual_seed(seed)
         blk = S.BlockGen(2, cfg)
-    finally:
-        HF.USE_SIBLING_FUSION = was
     return blk.cuda().train()
 
 
 def _run(S, blk, x, fused, probe):
     HF = S.functional
-    was = HF.USE_SIBLING_FUSION
-    HF.USE_SIBLING_FUSION = fused
-    try:
+    with HF.levers(USE_SIBLING_FUSION=fused):
         for p in blk.parameters():
             p.grad = None
         x = x.clone().requires_grad_()
@@ -60,8 +53,6 @@ def _run(S, blk, x, fused, probe):
         torch.cuda.synchronize()
         HF.wgrad_stream_sync()
         torch.cuda.synchronize()
-    finally:
-        HF.USE_SIBLING_FUSION = was
     return out.detach(), x.grad.detach(), {n: p.grad.detach().clone() for n, p in blk.named_parameters()}
 
 
@@ -244,8 +235,6 @@ def test_stage_entry_lif_writes_no_spike_tensor_and_nothing_changes(S):
     probe = torch.randn(T, B, c, H // 2, W // 2, generator=torch.Generator().manual_seed(4)).cuda()
 
     def run(on):
-        was = HF.USE_SPIKES_FROM_VDEC
-        HF.USE_SPIKES_FROM_VDEC = on
         calls = []
 
         class Spy:
@@ -256,10 +245,10 @@ def test_stage_entry_lif_writes_no_spike_tensor_and_nothing_changes(S):
                 pass
         _hip.PROFILER = Spy()
         try:
-            return _run(S, blk, x, True, probe), calls
+            with HF.levers(USE_SPIKES_FROM_VDEC=on):
+                return _run(S, blk, x, True, probe), calls
         finally:
             _hip.PROFILER = None
-            HF.USE_SPIKES_FROM_VDEC = was
     (y1, gx1, g1), calls1 = run(True)
     (y0, gx0, g0), calls0 = run(False)
     assert torch.equal(y1, y0) and torch.equal(gx1, gx0)
@@ -399,8 +388,6 @@ def test_plain_convolution_stack_writes_no_spike_tensor_between_its_layers(S):
     probe = torch.randn(T, B, 2 * c, H // 4, W // 4, generator=torch.Generator().manual_seed(4)).cuda()
 
     def run(on):
-        was = HF.USE_SPIKES_FROM_VDEC
-        HF.USE_SPIKES_FROM_VDEC = on
         calls = []
 
         class Spy:
@@ -411,14 +398,14 @@ def test_plain_convolution_stack_writes_no_spike_tensor_between_its_layers(S):
                 pass
         _hip.PROFILER = Spy()
         try:
-            blk.zero_grad(set_to_none=True)
-            y, _ = blk(x)
-            (y * probe).sum().backward()
-            torch.cuda.synchronize()
-            return y.detach().clone(), {k: p.grad.detach().clone() for k, p in blk.named_parameters()}, calls
+            with HF.levers(USE_SPIKES_FROM_VDEC=on):
+                blk.zero_grad(set_to_none=True)
+                y, _ = blk(x)
+                (y * probe).sum().backward()
+                torch.cuda.synchronize()
+                return y.detach().clone(), {k: p.grad.detach().clone() for k, p in blk.named_parameters()}, calls
         finally:
             _hip.PROFILER = None
-            HF.USE_SPIKES_FROM_VDEC = was
     y1, g1, calls1 = run(True)
     y0, g0, calls0 = run(False)
     assert float(y0.abs().sum()) > 0 and torch.equal(y1, y0)

@@ -329,22 +329,20 @@ def test_tiny_model_is_bit_equal_with_and_without_the_mask(S):
     probe = torch.randn(3, 1, c, 8, 12, generator=_gen(4)).cuda()
 
     def run(on):
-        was = HF.USE_SPIKE_MASK, HF.SPIKE_MASK_MIN_BYTES
-        HF.USE_SPIKE_MASK, HF.SPIKE_MASK_MIN_BYTES = on, 0
         spy = _Spy()
         _hip.PROFILER = spy
         try:
-            for p in blk.parameters():
-                p.grad = None
-            out, _ = blk(x)
-            loss = (out * probe).sum()
-            loss.backward()
-            torch.cuda.synchronize()
-            HF.wgrad_stream_sync()
-            torch.cuda.synchronize()
+            with HF.levers(USE_SPIKE_MASK=on, SPIKE_MASK_MIN_BYTES=0):
+                for p in blk.parameters():
+                    p.grad = None
+                out, _ = blk(x)
+                loss = (out * probe).sum()
+                loss.backward()
+                torch.cuda.synchronize()
+                HF.wgrad_stream_sync()
+                torch.cuda.synchronize()
         finally:
             _hip.PROFILER = None
-            HF.USE_SPIKE_MASK, HF.SPIKE_MASK_MIN_BYTES = was
         return loss.detach().clone(), {n: p.grad.detach().clone() for n, p in blk.named_parameters()}, spy.names
 
     loss1, g1, names1 = run(True)

@@ -151,11 +151,8 @@ def plain_takes_state_sums(HF, cs, inp, variant, **kw):
     seg = HF.SCAN_SEGMENT_T
     if seg and cs.T > seg and cs.T % seg == 1:
         assert not took, "a plain scan whose second segment is one step long reads y"
-        HF.SCAN_SEGMENT_T = None
-        try:
+        with HF.levers(SCAN_SEGMENT_T=None):
             _, names = run_recorded(HF, cs, inp, variant, **kw)
-        finally:
-            HF.SCAN_SEGMENT_T = seg
         assert names.count("snn_affine_neuron_bwd") == 1
         took = "snn_bn_bwd_finalize_from_state" in names
     return took

@@ -267,11 +267,8 @@ def test_cached_weight_images_follow_the_parameter_not_the_trainer(S):
     m.eval()
     with torch.no_grad():
         _, cls_a, box_a = m(X)
-        HF.USE_PRESPLIT_WEIGHTS = False          # the same forward converting the weights in every block
-        try:
+        with HF.levers(USE_PRESPLIT_WEIGHTS=False):          # the same forward converting the weights in every block
             _, cls_b, box_b = m(X)
-        finally:
-            HF.USE_PRESPLIT_WEIGHTS = True
     assert torch.isfinite(cls_a).all() and torch.equal(cls_a, cls_b) and torch.equal(box_a, box_b)
     del junk
     # a new trainer starts from a clean slate: no image of the old one survives on the parameters
@@ -357,8 +354,7 @@ def test_event_frame_layer_forms_dy_inside_its_weight_gradient(S):
 
     res = {}
     for fused in (True, False):
-        HF.USE_DEFERRED_BN_APPLY = fused
-        try:
+        with HF.levers(USE_DEFERRED_BN_APPLY=fused):
             torch.manual_seed(4)
             blk = BlockGen(2, [Conv(64, 3, 2), Norm(), LIF(), Conv(16, 1), Norm(), LIF()]).cuda().train()
             tr = FlatTrainer(blk, lr=1e-3)
@@ -373,8 +369,6 @@ def test_event_frame_layer_forms_dy_inside_its_weight_gradient(S):
             tr.synchronize()
             res[fused] = (tr.flat_grad.clone(), list(calls))
             assert not HF._PENDING_APPLY                       # every record was consumed
-        finally:
-            HF.USE_DEFERRED_BN_APPLY = True
     assert res[True][1].count("snn_conv2d_wgrad_bn") == 1 and res[False][1].count("snn_conv2d_wgrad_bn") == 0
     assert res[True][1].count("snn_bn_bwd_apply") == res[False][1].count("snn_bn_bwd_apply") - 1
     assert res[True][0].abs().max() > 0 and torch.equal(res[True][0], res[False][0])
