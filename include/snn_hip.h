@@ -809,6 +809,45 @@ int snn_events_to_frames_packed(const uint32_t* words, const int64_t* offsets, c
                                 int64_t n_events, float* frames, int T, int B, int H, int W, int64_t step_us,
                                 void* stream);
 
+/* Event representations: the same two feeds with another rule 7.  Rules 1-6 of snn_events_to_frames_aug pick the event
+ * and its cell exactly as above; frames stays [T][B][H][W][2] fp32, polarity the channel.  A cell holds a uint32
+ * accumulator from zero (the zero fill: zero bits are +0.0f), updated with integer atomics - add and max are order
+ * independent, so the result is bit-identical from run to run and under any permutation of a sample's events - and one
+ * in-place finalize pass turns accumulators into values, every operation a single fp32 round-to-nearest (fl):
+ *   SNN_EVREP_BINARY  the idempotent 1.0f store of the entries above, bit for bit; clip = 0 and scale = 1 only, no
+ *                     finalize pass.
+ *   SNN_EVREP_COUNT   n += 1 per event;  v = fl(fl(min(n, clip)) scale);  0 <= clip <= 2^24, clip = 0: no clip.
+ *   SNN_EVREP_TIME    m = max over the events of r + 1, r = d - t_bin step_us the offset inside the bin (d = t_us -
+ *                     t0[b], 0 <= r < step_us): the latest event of the bin;  v = fl(fl(fl(m) / fl(step_us)) scale), in
+ *                     (0, 1] scale;  clip must be 0, step_us <= 2^32 - 1.
+ *   SNN_EVREP_VOXEL   bilinear in time around the bin centres, in Q16.  Rule 1 keeps its window test (0 <= d < T
+ *                     step_us) and its bin is replaced:  u = 2d - step_us,  k = floor(u / (2 step_us)) in -1 .. T-1,
+ *                     rem = u - 2 k step_us,  q = floor(rem 2^16 / (2 step_us)) in 64-bit integers;  the event adds
+ *                     65536 - q to bin k if k >= 0 and q to bin k + 1 if k + 1 <= T - 1 and q > 0 (weight that falls
+ *                     outside the window is lost);  v = fl(fl(fl(min(acc, clip 65536)) 2^-16) scale);  0 <= clip <=
+ *                     65535 (0: no clip), step_us < 2^40.  A cell that collects more than 2^16 - 1 events' weight in
+ *                     one bin wraps modulo 2^32: outside the contract, and still nothing is written outside frames.
+ * Empty cells stay +0.0f.  scale must be finite and > 0.  The finalize pass asks frames 4-byte alignment only (16-byte
+ * accesses between a scalar head and tail).  n_events = 0 zero-fills and launches nothing.
+ * snn_events_rep_supported (host only) answers 1 / 0 for (rep, step_us, clip) by the ranges above (step_us > 0).
+ * snn_events_to_frames_aug_rep is snn_events_to_frames_aug, snn_events_to_frames_packed_rep
+ * snn_events_to_frames_packed - arguments, checks and refusals under their own names - except that aug may be NULL for
+ * both (the identity, no table read).  On top they refuse, naming the argument: an unknown rep, a clip out of range for
+ * the rep, a scale that is not finite or <= 0 (or not 1 for binary), a step_us too large for time / voxel, and for the
+ * non-binary representations n_events >= 2^32. */
+#define SNN_EVREP_BINARY 0
+#define SNN_EVREP_COUNT 1
+#define SNN_EVREP_TIME 2
+#define SNN_EVREP_VOXEL 3
+int snn_events_rep_supported(int rep, int64_t step_us, int clip);
+int snn_events_to_frames_aug_rep(const int64_t* t_us, const int32_t* x, const int32_t* y, const int32_t* p,
+                                 const int64_t* offsets, const int64_t* t0, const int32_t* aug, int64_t n_events,
+                                 float* frames, int T, int B, int H, int W, int64_t step_us, int rep, int clip,
+                                 float scale, void* stream);
+int snn_events_to_frames_packed_rep(const uint32_t* words, const int64_t* offsets, const int64_t* t0, const int32_t* aug,
+                                    int64_t n_events, float* frames, int T, int B, int H, int W, int64_t step_us,
+                                    int rep, int clip, float scale, void* stream);
+
 /* The boxes of the same transform.  labels_in / labels_out: fp32 [B][N][width], width 5 (class, x1, y1, x2, y2) or 6
  * (ts in front, copied untouched), boxes normalised to [0, 1]; a row whose class is below 0 is padding and stays
  * padding.  A valid row, s = a_q16 2^-16:  flip (x1, x2) = (1 - x2, 1 - x1);  x' = x s + ox / W, y' = y s + oy / H;

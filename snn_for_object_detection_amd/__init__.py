@@ -13,7 +13,7 @@ raises if the library is missing - there is no CPU / eager fallback.
 
 from . import activity, box, functional  # noqa: F401
 from .anchors import AnchorGenerator  # noqa: F401
-from .data import EventAugment, EventBatcher  # noqa: F401
+from .data import EventAugment, EventBatcher, EventRepresentation  # noqa: F401
 from .generator import BackboneGen, BlockGen, Head, HeadGen, ListGen, ListState, ModelGen, NeckGen  # noqa: F401
 from .layer_gen import *  # noqa: F401,F403
 from .metrics import MeanAveragePrecision  # noqa: F401

@@ -23,6 +23,7 @@ SCAN_SPIKE_MASK = 32   # forward only (shares its value with the backward-only f
 SURR_SUPER, SURR_TRIANGLE, SURR_SIGMOID, SURR_ATAN = 0, 1, 2, 3   # SNN_SURR_* of include/snn_hip.h
 # SNN_ACT_* of include/snn_hip.h (snn_activity_count; not the ACT_* activations above)
 ACTIVITY_NONZERO_F32, ACTIVITY_NONZERO_BF16, ACTIVITY_ABOVE_F32, ACTIVITY_ABOVE_BF16, ACTIVITY_MASK = 0, 1, 2, 3, 4
+EVENT_REPS = {"binary": 0, "count": 1, "time": 2, "voxel": 3}   # SNN_EVREP_* of include/snn_hip.h
 LOSS_CLS_MODES = {"ce": 0, "focal": 1}                        # SNN_LOSS_CLS_* of include/snn_hip.h
 LOSS_BOX_MODES = {"l1": 0, "giou": 1, "diou": 2, "ciou": 3}   # SNN_LOSS_BOX_*
 
@@ -177,6 +178,9 @@ SIGNATURES = {
     "snn_events_to_frames": (c_int, [_P, _P, _P, _P, _L, _P, _I, _I, _I, _P]),
     "snn_events_to_frames_aug": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _L, _P]),
     "snn_events_to_frames_packed": (c_int, [_P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _L, _P]),
+    "snn_events_rep_supported": (c_int, [_I, _L, _I]),
+    "snn_events_to_frames_aug_rep": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _L, _I, _I, _F, _P]),
+    "snn_events_to_frames_packed_rep": (c_int, [_P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _L, _I, _I, _F, _P]),
     "snn_labels_augment": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P]),
     "snn_state_reset": (c_int, [_P, _I, _I, _P, _P]),
     "snn_map_match":(c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),

@@ -2,7 +2,9 @@
 // buffer) and the label side of the augmentation.  k_events takes one sample's pre-binned events; k_events_batch bins the
 // raw timestamps of a whole batch and applies a per-sample flip / zoom / shift / random drop, reading the events either as
 // four arrays or as the 8-byte records of a Prophesee DAT recording.  HBM-bound on the read, uncoalesced 4-byte stores by
-// nature; include/snn_hip.h states the rules.
+// nature; include/snn_hip.h states the rules.  The count / time-surface / voxel-grid representations replace the store
+// by integer atomics on the same buffer viewed as uint32 (order independent, so bit-reproducible) and k_events_finalize
+// turns the accumulators into fp32 values in place.
 #include "snn_common.h"
 
 namespace {
@@ -55,8 +57,10 @@ __device__ __forceinline__ uint32_t fmix32(uint32_t u) {   // murmur3's finalise
 
 // The scatter with the binning of the raw timestamps and a per-sample flip / zoom / shift / random drop inside it
 // (include/snn_hip.h states the rules).  A thread finds the sample of its event by binary search over the batch's
-// offsets.  AUG = false: no table is read (the identity), the field checks alone decide what is stored.
-template <class Source, bool AUG>
+// offsets.  AUG = false: no table is read (the identity), the field checks alone decide what is stored.  REP says what
+// is written (rule 7): the 1.0f store, or an integer atomic on the cell's bits - a count, the latest offset inside the
+// bin + 1, or Q16 weights to the two bins whose centres enclose the event.  The atomics return nothing.
+template <class Source, bool AUG, int REP = SNN_EVREP_BINARY>
 __global__ __launch_bounds__(kThreads) void k_events_batch(
         const Source src, const int64_t* __restrict__ offsets, const int64_t* __restrict__ t0s,
         const int32_t* __restrict__ aug, int64_t n, float* __restrict__ frames, int T, int B, int H, int W,
@@ -111,7 +115,72 @@ __global__ __launch_bounds__(kThreads) void k_events_batch(
             xo = (int)xw, yo = (int)yw;
         }
         // 0 <= t < T, 0 <= b < B, 0 <= yo < H, 0 <= xo < W, p in {0, 1}: inside the buffer for any event contents
-        frames[((((int64_t)t * B + b) * H + yo) * W + xo) * 2 + p] = 1.0f;  // idempotent store: races are benign
+        const int64_t cell = ((((int64_t)t * B + b) * H + yo) * W + xo) * 2 + p;
+        if constexpr (REP == SNN_EVREP_BINARY) {
+            frames[cell] = 1.0f;  // idempotent store: races are benign
+        } else {
+            unsigned int* acc = reinterpret_cast<unsigned int*>(frames);
+            if constexpr (REP == SNN_EVREP_COUNT) {
+                atomicAdd(acc + cell, 1u);
+            } else {
+                const uint64_t r = (uint64_t)d - (uint64_t)t * (uint64_t)step_us;   // 0 <= r < step_us
+                if constexpr (REP == SNN_EVREP_TIME) {
+                    atomicMax(acc + cell, (unsigned int)(r + 1));   // step_us <= 2^32 - 1 (checked by the launcher)
+                } else {
+                    // u = 2d - step_us = 2 t step_us + (2r - step_us):  k = t, rem = 2r - step_us in the second half of
+                    // the bin, k = t - 1, rem = 2r + step_us in the first.  step_us < 2^40, so rem 2^16 < 2^57.
+                    const uint64_t step = (uint64_t)step_us;
+                    const bool late = 2 * r >= step;
+                    const uint64_t rem = late ? 2 * r - step : 2 * r + step;
+                    const unsigned int q = step < (1ull << 15) ? ((unsigned int)rem << 16) / (2u * (unsigned int)step)
+                                                               : (unsigned int)((rem << 16) / (2 * step));   // < 2^16
+                    const int k = late ? t : t - 1;   // -1 .. T - 1
+                    const int64_t bin = (int64_t)B * H * W * 2;
+                    const int64_t at = cell + (int64_t)(k - t) * bin;   // the same cell of bin k
+                    if (k >= 0) atomicAdd(acc + at, 65536u - q);
+                    if (k + 1 <= T - 1 && q > 0) atomicAdd(acc + at + bin, q);
+                }
+            }
+        }
+    }
+}
+
+// Accumulators -> values, in place: every operation one fp32 round-to-nearest (include/snn_hip.h states the three
+// forms).  frames is 4-byte aligned only: the elements in front of the first 16-byte boundary and behind the last whole
+// uint4 go one by one (block 0), the rest as 16-byte accesses.  `lim` is the clip on the accumulator (0xFFFFFFFF: none).
+template <int REP>
+__device__ __forceinline__ unsigned int rep_value(unsigned int a, unsigned int lim, float step_f, float scale) {
+    float v;
+    if constexpr (REP == SNN_EVREP_COUNT)
+        v = (float)(a < lim ? a : lim);
+    else if constexpr (REP == SNN_EVREP_TIME)
+        v = __fdiv_rn((float)a, step_f);
+    else
+        v = __fmul_rn((float)(a < lim ? a : lim), 1.0f / 65536.0f);
+    return __float_as_uint(__fmul_rn(v, scale));   // a = 0 stays +0.0f: scale is finite and positive
+}
+
+template <int REP>
+__global__ __launch_bounds__(kThreads) void k_events_finalize(unsigned int* __restrict__ acc, int64_t n, unsigned int lim,
+                                                              float step_f, float scale) {
+    int64_t head = (int64_t)((4 - ((reinterpret_cast<uintptr_t>(acc) >> 2) & 3)) & 3);
+    if (head > n) head = n;
+    const int64_t nvec = (n - head) / 4;
+    const int64_t tail = n - head - nvec * 4;   // 0 .. 3
+    if (blockIdx.x == 0) {
+        const int t = threadIdx.x;
+        if (t < head) acc[t] = rep_value<REP>(acc[t], lim, step_f, scale);
+        else if (t >= 4 && t - 4 < tail) {
+            unsigned int* q = acc + head + nvec * 4 + (t - 4);
+            *q = rep_value<REP>(*q, lim, step_f, scale);
+        }
+    }
+    uint4* vec = reinterpret_cast<uint4*>(acc + head);
+    for (int64_t v = (int64_t)blockIdx.x * kThreads + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * kThreads) {
+        uint4 a = vec[v];
+        a.x = rep_value<REP>(a.x, lim, step_f, scale), a.y = rep_value<REP>(a.y, lim, step_f, scale);
+        a.z = rep_value<REP>(a.z, lim, step_f, scale), a.w = rep_value<REP>(a.w, lim, step_f, scale);
+        vec[v] = a;
     }
 }
 
@@ -191,6 +260,76 @@ int events_batch_prologue(const char* name, bool tables, bool events, const char
     return 0;
 }
 
+// What the kernels take of a representation: the clip range of each, and the step the time offset (uint32) and the
+// voxel weight (rem 2^16 in 64 bits) are computed for.  The one statement of it: snn_events_rep_supported answers from it.
+bool events_rep_ok(int rep, int64_t step_us, int clip) {
+    if (step_us <= 0) return false;
+    switch (rep) {
+        case SNN_EVREP_BINARY: return clip == 0;
+        case SNN_EVREP_COUNT: return clip >= 0 && clip <= (1 << 24);
+        case SNN_EVREP_TIME: return clip == 0 && step_us <= 0xFFFFFFFFll;
+        case SNN_EVREP_VOXEL: return clip >= 0 && clip <= 65535 && step_us < (1ll << 40);
+    }
+    return false;
+}
+
+// The refusals the *_rep entry points add to the prologue's, by name, before anything is touched.
+int events_rep_check(const char* name, int rep, int clip, float scale, int64_t step_us, int64_t n_events) {
+    SNN_REQUIRE(rep >= SNN_EVREP_BINARY && rep <= SNN_EVREP_VOXEL, "%s: unknown representation %d (0 binary, 1 count, "
+                "2 time, 3 voxel)", name, rep);
+    SNN_REQUIRE(std::isfinite(scale) && scale > 0.0f, "%s: scale must be finite and positive, got %g", name,
+                (double)scale);
+    SNN_REQUIRE(rep != SNN_EVREP_BINARY || scale == 1.0f, "%s: the binary representation takes scale 1 only, got %g",
+                name, (double)scale);
+    if (step_us > 0) {   // (a step_us <= 0 is the prologue's refusal)
+        SNN_REQUIRE(events_rep_ok(rep, step_us, 0), "%s: step_us %lld is too large for this representation (time: at "
+                    "most 2^32 - 1, voxel: below 2^40)", name, (long long)step_us);
+        SNN_REQUIRE(events_rep_ok(rep, step_us, clip), "%s: clip %d is out of range for this representation (binary and "
+                    "time: 0, count: 0 .. 2^24, voxel: 0 .. 65535)", name, clip);
+    }
+    SNN_REQUIRE(rep == SNN_EVREP_BINARY || n_events < (1ll << 32), "%s: n_events of 2^32 or more (the accumulators are "
+                "32 bits wide)", name);
+    return 0;
+}
+
+// The scatter of representation `rep` from `src` and, for the integer accumulators, the finalize pass behind it.
+template <class Source>
+void events_rep_launch(const Source src, const int64_t* offsets, const int64_t* t0, const int32_t* aug, int64_t n_events,
+                       float* frames, int T, int B, int H, int W, int64_t step_us, int rep, int clip, float scale,
+                       hipStream_t stream) {
+    const dim3 grid(snn_grid_for(n_events, kThreads)), block(kThreads);
+    const uint64_t window_us = (uint64_t)(step_us * T);
+#define SNN_EVENTS_REP_CASE(REP)                                                                                        \
+    case REP:                                                                                                           \
+        if (aug)                                                                                                        \
+            hipLaunchKernelGGL((k_events_batch<Source, true, REP>), grid, block, 0, stream, src, offsets, t0, aug,      \
+                               n_events, frames, T, B, H, W, step_us, window_us);                                       \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_events_batch<Source, false, REP>), grid, block, 0, stream, src, offsets, t0, aug,     \
+                               n_events, frames, T, B, H, W, step_us, window_us);                                       \
+        break;
+    switch (rep) {
+        SNN_EVENTS_REP_CASE(SNN_EVREP_BINARY)
+        SNN_EVENTS_REP_CASE(SNN_EVREP_COUNT)
+        SNN_EVENTS_REP_CASE(SNN_EVREP_TIME)
+        SNN_EVENTS_REP_CASE(SNN_EVREP_VOXEL)
+    }
+#undef SNN_EVENTS_REP_CASE
+    if (rep == SNN_EVREP_BINARY) return;
+    const int64_t n = (int64_t)T * B * H * W * 2;   // < 2^31 (the prologue)
+    unsigned int* acc = reinterpret_cast<unsigned int*>(frames);
+    const dim3 fgrid(snn_grid_for(snn_ceil_div(n, 4), kThreads));
+    const float step_f = (float)step_us;   // fl(step_us)
+    if (rep == SNN_EVREP_COUNT)
+        hipLaunchKernelGGL(k_events_finalize<SNN_EVREP_COUNT>, fgrid, block, 0, stream, acc, n,
+                           clip ? (unsigned int)clip : 0xFFFFFFFFu, step_f, scale);
+    else if (rep == SNN_EVREP_TIME)
+        hipLaunchKernelGGL(k_events_finalize<SNN_EVREP_TIME>, fgrid, block, 0, stream, acc, n, 0xFFFFFFFFu, step_f, scale);
+    else
+        hipLaunchKernelGGL(k_events_finalize<SNN_EVREP_VOXEL>, fgrid, block, 0, stream, acc, n,
+                           clip ? (unsigned int)clip << 16 : 0xFFFFFFFFu, step_f, scale);
+}
+
 }  // namespace
 
 // -------------------------------------------------------------------------------------------- C ABI
@@ -247,6 +386,50 @@ extern "C" int snn_events_to_frames_packed(const uint32_t* words, const int64_t*
         hipLaunchKernelGGL((k_events_batch<PackedEvents, false>), grid, dim3(kThreads), 0, (hipStream_t)stream, src,
                            offsets, t0, aug, n_events, frames, T, B, H, W, step_us, window_us);
     SNN_CHECK_LAUNCH("snn_events_to_frames_packed");
+    return 0;
+}
+
+extern "C" int snn_events_rep_supported(int rep, int64_t step_us, int clip) {
+    return events_rep_ok(rep, step_us, clip) ? 1 : 0;
+}
+
+extern "C" int snn_events_to_frames_aug_rep(const int64_t* t_us, const int32_t* x, const int32_t* y, const int32_t* p,
+                                            const int64_t* offsets, const int64_t* t0, const int32_t* aug,
+                                            int64_t n_events, float* frames, int T, int B, int H, int W,
+                                            int64_t step_us, int rep, int clip, float scale, void* stream) {
+    const char* name = "snn_events_to_frames_aug_rep";
+    if (int rc = events_rep_check(name, rep, clip, scale, step_us, n_events)) return rc;
+    if (int rc = events_batch_prologue(name,
+                                       frames && offsets && t0,          // tables (aug may be NULL: the identity)
+                                       t_us && x && y && p, "arrays",    // events: "null event arrays"
+                                       nullptr,                          // misaligned: this entry point asks nothing
+                                       n_events, frames, T, B, H, W, step_us, (hipStream_t)stream))
+        return rc;
+    if (n_events == 0) return 0;
+    events_rep_launch(TupleEvents{t_us, x, y, p}, offsets, t0, aug, n_events, frames, T, B, H, W, step_us, rep, clip,
+                      scale, (hipStream_t)stream);
+    SNN_CHECK_LAUNCH(name);
+    return 0;
+}
+
+extern "C" int snn_events_to_frames_packed_rep(const uint32_t* words, const int64_t* offsets, const int64_t* t0,
+                                               const int32_t* aug, int64_t n_events, float* frames, int T, int B,
+                                               int H, int W, int64_t step_us, int rep, int clip, float scale,
+                                               void* stream) {
+    const char* name = "snn_events_to_frames_packed_rep";
+    if (int rc = events_rep_check(name, rep, clip, scale, step_us, n_events)) return rc;
+    const bool is_aligned = aligned(8, {words, offsets, t0}) && aligned(4, {aug, frames});
+    if (int rc = events_batch_prologue(
+            name,
+            frames && offsets && t0,   // tables: "null pointer" without one (aug may be NULL: the identity)
+            words, "words",            // events: "null event words"
+            is_aligned ? nullptr : "words, offsets and t0 must be 8-byte aligned, aug and frames 4-byte aligned",
+            n_events, frames, T, B, H, W, step_us, (hipStream_t)stream))
+        return rc;
+    if (n_events == 0) return 0;
+    events_rep_launch(PackedEvents{reinterpret_cast<const uint2*>(words)}, offsets, t0, aug, n_events, frames, T, B, H,
+                      W, step_us, rep, clip, scale, (hipStream_t)stream);
+    SNN_CHECK_LAUNCH(name);
     return 0;
 }
 

@@ -18,6 +18,10 @@ random event drop - inside the scatter: a batcher that has one hands the raw int
 A sample may also be ``(words, t0_us)`` - the 8-byte records of a Prophesee DAT recording as they lie in the file
 (``recordings.DatRecording``): the slices go through one of two persistent pinned staging buffers, one copy carries
 8 bytes per event, and ``snn_events_to_frames_packed`` unpacks the words inside the scatter.
+
+``EventRepresentation`` (not in the reference) chooses what a cell holds: the binary flag (the default), an event count,
+a per-bin time surface or a temporally interpolated voxel grid - integer atomics inside the same scatter and one
+finalize pass (``snn_events_to_frames_aug_rep`` / ``snn_events_to_frames_packed_rep``).
 """
 from typing import List, Optional, Sequence, Tuple
 
@@ -25,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _hip
+from .event_ops import EventRepresentation  # noqa: F401  (defined beside the scatters that take it)
 
 
 def collate_labels(labels: Sequence[torch.Tensor], B: int) -> torch.Tensor:
@@ -121,8 +126,11 @@ class EventAugment:
 
 class EventBatcher:
     def __init__(self, num_steps: int, height: int, width: int, time_step_us: int, device="cuda",
-                 augment: Optional[EventAugment] = None):
+                 augment: Optional[EventAugment] = None, representation="binary"):
         self.T, self.H, self.W, self.step = int(num_steps), int(height), int(width), int(time_step_us)
+        self.representation = EventRepresentation.of(representation, "EventBatcher")
+        if not self.representation.is_binary:
+            self.representation.check(self.step, "EventBatcher")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("EventBatcher: a HIP device is required (no CPU fallback)")
@@ -164,7 +172,9 @@ class EventBatcher:
                              "call")
         packed = forms == {2}
         if aug_table is None and self.augment is None:
-            return self._packed(samples, labels, None) if packed else self._plain(samples, labels)
+            if packed or not self.representation.is_binary:   # (no table: the kernel reads none)
+                return self._packed(samples, labels, None) if packed else self._augmented(samples, labels, None)
+            return self._plain(samples, labels)
         from . import functional as _HF
         B = len(samples)
         if aug_table is not None:
@@ -223,15 +233,17 @@ class EventBatcher:
         return self._scatter_batch("snn_events_to_frames_packed", counts, [int(s[1]) for s in samples], table, labels,
                                    slot["meta"][:meta_len], copy_events, done=slot["done"])
 
-    def _augmented(self, samples, labels, table: torch.Tensor):
+    def _augmented(self, samples, labels, table: Optional[torch.Tensor]):
         """Four copies per sample into slices of the batch's event arrays, ``offsets | t0 | table`` in one small pinned
-        tensor, one ``snn_events_to_frames_aug`` launch that bins and transforms, one ``snn_labels_augment`` launch."""
+        tensor, one ``snn_events_to_frames_aug`` launch that bins and transforms, one ``snn_labels_augment`` launch.
+        ``table`` None (a representation other than binary on un-augmented samples): the kernel reads no table."""
         B = len(samples)
         if self.step <= 0:
             raise ValueError(f"EventBatcher: time_step_us must be positive, got {self.step}")
         counts = [int(s[0].numel()) for s in samples]
         n = sum(counts)
-        meta = torch.empty(6 * B + 1, dtype=torch.int64, pin_memory=True)   # offsets[B + 1] | t0[B] | table[B][8] (int32)
+        # offsets[B + 1] | t0[B] | table[B][8] (int32)
+        meta = torch.empty((6 if table is not None else 2) * B + 1, dtype=torch.int64, pin_memory=True)
 
         def copy_events():
             ev = [torch.empty(max(n, 1), device=self.device, dtype=d)
@@ -252,10 +264,15 @@ class EventBatcher:
         """What ``_packed`` and ``_augmented`` share behind their staging: ``offsets | t0 | table`` into the pinned int64
         ``meta``; on the copy stream the caller's ``copy_events()`` (its H2D copies -> the device event tensors of
         ``entry``), the copy of ``meta`` (``done``, a HIP event, is recorded behind both) and the launch; the hand-over of
-        the streams, ``last_aug_table``, and the labels - augmented by the same table - on the main stream."""
+        the streams, ``last_aug_table``, and the labels - augmented by the same table - on the main stream.  A
+        representation other than binary takes ``entry``'s ``_rep`` form with its three arguments."""
         from . import functional as _HF
         B, n = len(counts), sum(counts)
         T, H, W = self.T, self.H, self.W
+        rep = self.representation
+        if not rep.is_binary:
+            entry += "_rep"
+        rep_args = () if rep.is_binary else (rep.rep, rep.clip, rep.scale)
         meta[0] = 0
         meta[1:B + 1] = torch.tensor(counts, dtype=torch.int64).cumsum(0)
         meta[B + 1:2 * B + 1] = torch.tensor(t0s, dtype=torch.int64)
@@ -273,7 +290,7 @@ class EventBatcher:
             aug_dev = meta_dev[2 * B + 1:].view(torch.int32) if table is not None else None
             _hip.call(entry, *(v.data_ptr() for v in ev), meta_dev.data_ptr(), meta_dev[B + 1:].data_ptr(),
                       aug_dev.data_ptr() if aug_dev is not None else None, n, buf.data_ptr(), T, B, H, W, self.step,
-                      self._copy_stream.cuda_stream)
+                      *rep_args, self._copy_stream.cuda_stream)
             buf.record_stream(self._copy_stream)
             meta_dev.record_stream(self._copy_stream)
         main.wait_stream(self._copy_stream)

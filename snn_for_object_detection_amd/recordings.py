@@ -260,12 +260,14 @@ class PropheseeFeed:
     ``rank``).  ``one_label=False`` yields 6-column labels for ``SODa(label_steps=K)``.  ``samples()`` is the host side
     alone (no device needed).  ``chained=True`` (with ``one_label=False``) binds every batch slot to one recording and
     yields its windows in time order, batches ``(X, labels, first)`` for ``SODa(carry_state=True)``
-    (``_chained_samples``)."""
+    (``_chained_samples``).  ``representation`` (a name or a ``data.EventRepresentation``) is handed to the batcher: what
+    a cell of ``X`` holds; samples, labels and their order do not depend on it."""
 
     def __init__(self, data_dir: str, dataset: str = "gen1", split: str = "train", batch_size: int = 4,
                  num_steps: int = 42, time_step: int = 16, time_shift: int = 16, one_label: bool = True,
                  files_in_flight: int = 8, rank: int = 0, world: int = 1, seed: int = 0, device="cuda", augment=None,
-                 events_threshold: int = 4000, box_size_threshold: float = 0.01, chained: bool = False):
+                 events_threshold: int = 4000, box_size_threshold: float = 0.01, chained: bool = False,
+                 representation="binary"):
         self.dataset = _check_dataset(dataset)
         if chained and one_label:
             raise ValueError("PropheseeFeed: chained=True needs one_label=False (consecutive windows carry the six-column "
@@ -280,6 +282,10 @@ class PropheseeFeed:
         self.height, self.width = GEOMETRY[dataset]
         self.batch_size, self.num_steps, self.one_label = int(batch_size), int(num_steps), bool(one_label)
         self.time_step_us = int(time_step) * 1000
+        from .data import EventRepresentation
+        self.representation = EventRepresentation.of(representation, "PropheseeFeed")
+        if not self.representation.is_binary:
+            self.representation.check(self.time_step_us, "PropheseeFeed")
         self.files_in_flight, self.device, self.augment = int(files_in_flight), device, augment
         directory = os.path.join(data_dir, dataset, split)
         gt_files = sorted(glob.glob(os.path.join(directory, "*_bbox.npy")))
@@ -406,7 +412,7 @@ class PropheseeFeed:
         from .data import EventBatcher
         if self._batcher is None:
             self._batcher = EventBatcher(self.num_steps, self.height, self.width, self.time_step_us, device=self.device,
-                                         augment=self.augment)
+                                         augment=self.augment, representation=self.representation)
             self._samples = self.samples()
         if self.chained:
             return self._next_chained()

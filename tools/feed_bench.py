@@ -12,7 +12,10 @@ training step with that augmentation beside the plain one.
 ``--packed`` adds the packed feed (8-byte DAT records unpacked inside the scatter kernel, one staging copy and one H2D
 copy per batch): plain beside (b) and augmented beside (d), alternating, the training step fed by it, the bytes per batch
 of the three forms, and the host time per batch of ``PropheseeFeed`` reading seeded recordings from a temporary
-directory."""
+directory.
+
+``--representation NAME`` (count, time or voxel) times the feed of that representation beside the binary one in the same
+run, alternating: packed records with ``--packed``, tuple samples otherwise, augmented with ``--augment``."""
 import argparse
 import os
 import sys
@@ -29,6 +32,8 @@ ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDe
 ap.add_argument("--augment", action="store_true", help="also time the augmented feed and the training step fed by it")
 ap.add_argument("--packed", action="store_true", help="also time the packed feed (DAT records unpacked in the kernel), "
                 "the training step fed by it and PropheseeFeed's host time per batch")
+ap.add_argument("--representation", default=None, choices=("count", "time", "voxel"),
+                help="also time the feed with this event representation beside the binary feed")
 args = ap.parse_args()
 
 T, B, H, W, step_us = 32, 5, 240, 304, 1000
@@ -125,6 +130,20 @@ if args.packed:
     for k, (name, _) in enumerate(feeds):
         ms = sorted(r[k] for r in rounds)
         print(f"{name:<86}: {ms[2]:6.2f} ms per batch (median of 5 x 20; {ms[0]:.2f} .. {ms[-1]:.2f})")
+
+if args.representation:
+    # the same samples through two batchers that differ in the representation alone, alternating over five rounds
+    kw = dict(augment=S.EventAugment(hflip=0.5, zoom=(0.75, 1.25), drop=(0.0, 0.1), seed=0)) if args.augment else {}
+    pair = [S.EventBatcher(T, H, W, step_us, representation=r, **kw) for r in ("binary", args.representation)]
+    fed = samples_packed if args.packed else (samples_aug if args.augment else samples)
+    form = ("packed records" if args.packed else "tuple events") + (", flip / zoom / shift / drop" if args.augment else "")
+    X_rep = pair[1](fed)
+    torch.cuda.synchronize()
+    print(f"representation {args.representation}: max {float(X_rep.max()):.4f}, {int((X_rep != 0).sum())} cells set")
+    rounds = [[timeit(lambda b=b: b(fed), n=20) for b in pair] for _ in range(5)]
+    for k, name in enumerate(("binary", args.representation)):
+        ms = sorted(r[k] for r in rounds)
+        print(f"(r) {form}, {name:<6}: {ms[2]:6.2f} ms per batch (median of 5 x 20; {ms[0]:.2f} .. {ms[-1]:.2f})")
 
 torch.manual_seed(2)
 model = S.TinyYolo(num_classes=2, time_window=0).cuda().train()

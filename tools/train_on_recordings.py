@@ -12,7 +12,9 @@ the learning rate up over W steps and lets it fall along a cosine over the rest,
 under ``averaged_weights()`` - both sets of mAP keys are printed.
 ``--chained`` (with ``--label-steps K``) trains on CONSECUTIVE windows with the neuron state carried from step to step:
 ``PropheseeFeed(chained=True)`` binds every batch slot to one recording, ``SODa(carry_state=True)`` keeps the detached
-state and resets the slots that open a new recording; no random prefix is cut (``time_window=0``)."""
+state and resets the slots that open a new recording; no random prefix is cut (``time_window=0``).
+``--representation {binary,count,time,voxel}`` (with ``--rep-clip N``, ``--rep-scale S``) chooses what a cell of the event
+frames holds (``EventRepresentation``), for the training and the validation feed alike."""
 import argparse
 import os
 import sys
@@ -63,7 +65,12 @@ def main():
     ap.add_argument("--warmup-steps", type=int, default=0, metavar="W",
                     help="learning rate: linear warmup over W steps, then a cosine down to 1 %% at --steps (constant)")
     ap.add_argument("--val-batches", type=int, default=0, metavar="N", help="validate on N batches of the val split at the end")
+    ap.add_argument("--representation", default="binary", choices=S.EventRepresentation.KINDS,
+                    help="what a cell of the event frames holds: a flag, an event count, a time surface, a voxel grid")
+    ap.add_argument("--rep-clip", type=int, default=None, metavar="N", help="clip of count / voxel cells (none)")
+    ap.add_argument("--rep-scale", type=float, default=1.0, metavar="S", help="factor on the cell values")
     args = ap.parse_args()
+    representation = S.EventRepresentation(args.representation, clip=args.rep_clip, scale=args.rep_scale)
     if args.chained and args.label_steps is None:
         ap.error("--chained needs --label-steps K (chained windows carry six-column labels)")
     carried = dict(carry_state=True, time_window=0) if args.chained else {}
@@ -71,7 +78,7 @@ def main():
     augment = S.EventAugment(hflip=0.5, zoom=(0.75, 1.25), drop=(0.0, 0.1), seed=args.seed) if args.augment else None
     feed = S.PropheseeFeed(args.data_dir, dataset=args.dataset, split="train", batch_size=args.batch_size,
                            num_steps=args.num_steps, one_label=args.label_steps is None, seed=args.seed, augment=augment,
-                           chained=args.chained)
+                           chained=args.chained, representation=representation)
     torch.manual_seed(args.seed)
     model = S.TinyYolo(num_classes=len(feed.get_labels()), label_steps=args.label_steps, cls_loss=args.cls_loss,
                        focal_gamma=args.focal_gamma, box_loss=args.box_loss,
@@ -89,7 +96,7 @@ def main():
     if args.val_batches > 0:
         val = S.PropheseeFeed(args.data_dir, dataset=args.dataset, split="val", batch_size=args.batch_size,
                               num_steps=args.num_steps, one_label=args.label_steps is None, seed=args.seed,
-                              chained=args.chained)
+                              chained=args.chained, representation=representation)
         batches = [next(val) for _ in range(args.val_batches)]
         trainer.synchronize()
         print("val live    ", validate(model, batches), flush=True)
