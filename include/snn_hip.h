@@ -388,6 +388,39 @@ int snn_conv1x1_mask_fwd(const uint32_t* mask, int64_t ld_mask, const float* w, 
 int snn_conv1x1_mask_wgrad(const uint32_t* mask, int64_t ld_mask, const float* dy, int64_t lddy, float* dw, int64_t N, int H,
                            int W, int Cin, int Cout, int accumulate, float* workspace, int splitk, void* stream);
 
+/* ---- BOTH gradients of a 1x1 / stride 1 / pad 0 convolution from one pass over dy.  The weight-gradient kernel
+ * has every stage of dy in LDS; where one block owns all output channels (Cout <= 128) it also forms the data gradient of
+ * the stage, dx = dy wt^T + addend + addend2, from the same LDS images.  SNN_PREC_BF16X3 on fp32 tensors only.  Results
+ * are bit-identical to the separate calls given the same splitk: dx to snn_conv2d_dgrad(dy, wt, NULL, ...), dw to
+ * snn_conv2d_wgrad (snn_conv1x1_mask_wgrad for the mask form).
+ *   snn_conv1x1_bwd       : x fp32 [N*H*W][ldx]; the arguments of snn_conv2d_dgrad and snn_conv2d_wgrad merged.  wt is the
+ *                           transposed weight [Cin][Cout]; workspace = splitk * Cout * Cin floats, splitk from
+ *                           snn_conv2d_wgrad_splitk.  dw == NULL: the slabs stay in the workspace and
+ *                           snn_conv2d_wgrad_reduce sums them later - on another stream if the caller orders the two.
+ *   snn_conv1x1_mask_bwd  : the same over the spike bit mask of the scan in front (snn_conv1x1_mask_wgrad's operand).
+ *   snn_conv1x1_bwd_supported : host-only; 1 when the launch the arguments describe is taken AND its layer class measured
+ *                           faster fused.  It returns 0 for everything the launch refuses: Cout > 128 (or a weight-gradient
+ *                           tile that does not own all output channels), Cin or Cout no multiple of 4 (mask: Cin % 32),
+ *                           pixel strides below the channel counts or no multiples of 4, x / dy / wt / dx / addends not
+ *                           16-byte aligned (mask: 4), a pixel split of dy or x (the whole mask) beyond 2 GiB, any
+ *                           precision but SNN_PREC_BF16X3 (bf16 storage, exact fp32, bf16 x 1).  is_mask: x is the bit mask
+ *                           and ldx its words per pixel.  dw may be NULL (unchecked).  splitk 0: snn_conv2d_wgrad_splitk's.
+ *   snn_conv2d_wgrad_reduce : dw[n] (+)= the splitk slabs of `workspace` in slab order - the reduction every weight
+ *                           gradient ends with. */
+int snn_conv1x1_bwd_supported(int64_t N, int H, int W, int Cin, int Cout, const void* x, int64_t ldx, int is_mask,
+                              const float* dy, int64_t lddy, const float* wt, const float* dx, int64_t lddx,
+                              const float* addend, int64_t ld_addend, const float* addend2, int64_t ld_addend2,
+                              const float* dw, int splitk, int precision);
+int snn_conv1x1_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* wt, float* dx, int64_t lddx,
+                    const float* addend, int64_t ld_addend, const float* addend2, int64_t ld_addend2, float* dw, int64_t N,
+                    int H, int W, int Cin, int Cout, int accumulate, float* workspace, int splitk, int precision,
+                    void* stream);
+int snn_conv1x1_mask_bwd(const uint32_t* mask, int64_t ld_mask, const float* dy, int64_t lddy, const float* wt, float* dx,
+                         int64_t lddx, const float* addend, int64_t ld_addend, const float* addend2, int64_t ld_addend2,
+                         float* dw, int64_t N, int H, int W, int Cin, int Cout, int accumulate, float* workspace, int splitk,
+                         int precision, void* stream);
+int snn_conv2d_wgrad_reduce(float* workspace, float* dw, int64_t n, int splitk, int accumulate, void* stream);
+
 /* ---------------------------------------------------------------- batch-norm statistics
  * Train-mode nn.BatchNorm2d (layer_gen.py:211-214) applied per TIMESTEP: for every (t,c)
  * the biased mean/var over the M = B*h*w pixels of timestep t (generator.py:190-195 calls the

@@ -82,6 +82,10 @@ SIGNATURES = {
     "snn_conv1x1_mask_supported": (c_int, [_L, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P, _L, _P, _I, _I]),
     "snn_conv1x1_mask_fwd": (c_int, [_P, _L, _P, _P, _L, _L, _I, _I, _I, _I, _P]),
     "snn_conv1x1_mask_wgrad": (c_int, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "snn_conv1x1_bwd_supported": (c_int, [_L, _I, _I, _I, _I, _P, _L, _I, _P, _L, _P, _P, _L, _P, _L, _P, _L, _P, _I, _I]),
+    "snn_conv1x1_bwd": (c_int, [_P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "snn_conv1x1_mask_bwd": (c_int, [_P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "snn_conv2d_wgrad_reduce": (c_int, [_P, _P, _L, _I, _I, _P]),
     "snn_conv2d_spikes_supported": (c_int, [_L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _I, _I]),
     "snn_conv2d_spikes_fwd": (c_int, [_P, _L, _F, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "snn_conv2d_spikes_wgrad": (c_int, [_P, _L, _F, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),

@@ -237,12 +237,35 @@ __global__ __launch_bounds__(kThreads, SNN_CONV_MIN_WAVES) void k_conv_wgrad(con
 // thread (at most one load instruction per wave and stage, against 4 * XQ 16-byte ones), staged as words (Xw[group][pixel]);
 // lane (r, h) reads the 8 words of its 8 pixels (two broadcast ds_read_b128) and takes bit r of each as a bf16 1.0 / 0.  The
 // MFMAs, their operands' bits and their order are those of XSP.
-template <int TM, int TN, int WM, int WN, int WBK, bool ONE, bool SB = false, bool XSP = false, bool XM = false>   // ONE: bf16 x 1 (hi pieces only, one product)
-__global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __restrict__ x,
+// DX (bf16 x 3, 1x1 / stride 1, the block owns every output channel: tiles_m == 1; snn_conv1x1_bwd / snn_conv1x1_mask_bwd): the
+// kernel also writes the DATA gradient of its stage pixels and its column tile, dx[pixel][kc0 ..] = sum_co dy[pixel][co] *
+// wt[ci][co] (+ up to two addends), so dy is read from HBM once for both gradients.  dx contracts over co, the ROW index of
+// the dy images the weight gradient reads by rows: the same images are read with the transposing LDS read
+// (ds_read_b64_tr_b16, 4 co x 16 pixels per 16-lane group) - no second image, no register transposition.  Each wave owns
+// one 32-ci x 32-pixel tile of the stage; its wt rows (all co chunks, bf16 hi / lo) are loaded and split ONCE per block
+// and stay in registers.  wt is the A operand (rows = ci), dy the B operand (columns = pixels): the accumulator of a lane
+// then holds 4 x 4 CONSECUTIVE ci of one pixel - 16-byte addend loads and dx stores straight from the registers, no
+// staging through LDS - and the sums are those of k_conv_gather<DGRAD> (dy as A, wt as B): per 16-wide co chunk in
+// ascending order dy_lo * w_hi, dy_hi * w_lo, dy_hi * w_hi, the k slots of a chunk in the same order.  The slabs are
+// untouched: same splits, stages and k slots as the kernel without DX.
+struct WgradDx {
+    const float* wt;       // [Cin][Cout]
+    float* dx;
+    const float* add1;     // nullptr: none
+    const float* add2;
+    int64_t lddx, ld_add1, ld_add2;
+};
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+template <int TM, int TN, int WM, int WN, int WBK, bool ONE, bool SB = false, bool XSP = false, bool XM = false, bool DX = false>   // ONE: bf16 x 1 (hi pieces only, one product)
+// (DX on the 128 x 128 tile with fp32 x - 64 accumulator, 64 wt-fragment and 64 operand-pipeline registers - spills at two
+// waves per SIMD: that one instance is compiled for one)
+__global__ __launch_bounds__(kThreads, (DX && TM * TN == 4 && !XM) ? 1 : 2) void k_conv_wgrad_pipe(const float* __restrict__ x,
                                                                  const float* __restrict__ dy,
-                                                                 float* __restrict__ ws, WgradGeom g) {
+                                                                 float* __restrict__ ws, WgradGeom g, WgradDx d) {
     static_assert(WM * WN == 4, "4 waves");
     constexpr int BMc = 32 * TM * WM, BNk = 32 * TN * WN;
+    static_assert(!DX || (!ONE && !SB && XSP == XM), "fused data gradient: bf16 x 3 on fp32 x or on the spike bit mask");
+    static_assert(!DX || (BNk / 32) * (WBK / 32) == 4, "fused data gradient: one 32 x 32 dx tile per wave and stage");
     constexpr int DG = BMc / 4, XG = BNk / 4;
     // WBK pixels per LDS stage: 32 for the large tiles; 64 for the small ones, whose 6-MFMA stages were shorter than
     // the memory latency they have to cover (PMC: 58 % of the wave cycles parked in s_waitcnt / barriers)
@@ -479,6 +502,40 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
+    // ---- DX: the wave's dx tile (ci group dx_cg of the column tile, pixel group dx_pg of the stage), its wt rows as bf16
+    // hi / lo A fragments (lane (r, h): ci = kc0 + 32 dx_cg + r, co = 16 c + 8 h .. + 7), and the lane's address in the dy
+    // images for the transposing read: lane 4 q + p of 16-lane group G supplies row (co) 16 c + 8 (G >> 1) + 4 s + q,
+    // columns (pixels) 32 dx_pg + 16 (G & 1) + 4 p .. + 3 and receives its own pixel's 4 co - the B fragment of lane (r, h).
+    constexpr int NCH = BMc / 16;   // 16-wide co chunks (rows past Cout hold zeros)
+    [[maybe_unused]] bf16x8 wh[DX ? NCH : 1], wl[DX ? NCH : 1];
+    [[maybe_unused]] const int dx_cg = wave % (BNk / 32), dx_pg = wave / (BNk / 32);
+    [[maybe_unused]] int dx_tr = 0;
+    if constexpr (DX) {
+        const int ci = kc0 + dx_cg * 32 + r;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int co = 16 * c + 8 * h;
+            f32x4 v[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            if (ci < g.Cin) {
+                if (co < g.Cout) v[0] = *reinterpret_cast<const f32x4*>(d.wt + (int64_t)ci * g.Cout + co);
+                if (co + 4 < g.Cout) v[1] = *reinterpret_cast<const f32x4*>(d.wt + (int64_t)ci * g.Cout + co + 4);
+            }
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) {   // the split of k_conv_gather's loader (and of snn_weight_presplit)
+                f32x2 rest = {v[e >> 2][e & 3], v[e >> 2][(e & 3) + 1]};
+                bf16x2 pp = __builtin_convertvector(rest, bf16x2);
+                const unsigned bits = __builtin_bit_cast(unsigned, pp);
+                wh[c][e] = pp[0]; wh[c][e + 1] = pp[1];
+                rest[0] -= __builtin_bit_cast(float, bits << 16);
+                rest[1] -= __builtin_bit_cast(float, bits & 0xffff0000u);
+                pp = __builtin_convertvector(rest, bf16x2);
+                wl[c][e] = pp[0]; wl[c][e + 1] = pp[1];
+            }
+        }
+        const int grp = lane_id >> 4, i16 = lane_id & 15;
+        dx_tr = (8 * (grp >> 1) + (i16 >> 2)) * LDW + dx_pg * 32 + 16 * (grp & 1) + 4 * (i16 & 3);
+    }
+
     auto mfma_group = [&](int ks) {
         bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
 #pragma unroll
@@ -543,6 +600,19 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
     int slot = 0;  // Pinfo slot of tile k+2
 #pragma unroll 1
     for (unsigned p0 = p_lo; p0 < p_hi; p0 += WBK) {
+        // DX: the addend rows of this stage's dx tile are requested before the stage's MFMAs
+        [[maybe_unused]] f32x4 ad1[4], ad2[4];
+        [[maybe_unused]] const unsigned dx_p = p0 + (unsigned)(dx_pg * 32 + r);
+        [[maybe_unused]] const int dx_ci = kc0 + dx_cg * 32 + 4 * h;   // + 8 jj: the 4 consecutive ci of registers 4 jj .. 4 jj + 3
+        if constexpr (DX) {
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                const bool ok = dx_p < p_hi && dx_ci + 8 * jj < g.Cin;
+                ad1[jj] = ad2[jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (d.add1 && ok) ad1[jj] = SnnStore<false>::ld4_last(d.add1, (int64_t)dx_p * d.ld_add1 + dx_ci + 8 * jj);
+                if (d.add2 && ok) ad2[jj] = SnnStore<false>::ld4_last(d.add2, (int64_t)dx_p * d.ld_add2 + dx_ci + 8 * jj);
+            }
+        }
         mfma_group(0);
 #pragma unroll
         for (int q = 0; q < DQ; ++q) convert_quad(rd[q], pd[q]);
@@ -571,6 +641,33 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv_wgrad_pipe(const float* __
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ks = 2; ks < WBK / 16; ++ks) mfma_group(ks);
+        if constexpr (DX) {
+            f32x16 dacc;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) dacc[e] = 0.f;
+            typedef __attribute__((address_space(3))) s16x4* LdsQuad;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {   // (uniform control flow: the transposing read needs every lane of the wave)
+                const int o = dx_tr + 16 * c * LDW;
+                const s16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LdsQuad)&Dh[o]);
+                const s16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LdsQuad)&Dh[o + 4 * LDW]);
+                const s16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LdsQuad)&Dl[o]);
+                const s16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LdsQuad)&Dl[o + 4 * LDW]);
+                const bf16x8 dh = __builtin_bit_cast(bf16x8, __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7));
+                const bf16x8 dl = __builtin_bit_cast(bf16x8, __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7));
+                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[c], dl, dacc, 0, 0, 0);   // dy_lo * w_hi: small terms first
+                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[c], dh, dacc, 0, 0, 0);   // dy_hi * w_lo
+                dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[c], dh, dacc, 0, 0, 0);   // dy_hi * w_hi
+            }
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                if (!(dx_p < p_hi && dx_ci + 8 * jj < g.Cin)) continue;
+                f32x4 v = {dacc[4 * jj], dacc[4 * jj + 1], dacc[4 * jj + 2], dacc[4 * jj + 3]};
+                if (d.add1) v += ad1[jj];
+                if (d.add2) v += ad2[jj];
+                SnnStore<false>::st4(d.dx, (int64_t)dx_p * d.lddx + dx_ci + 8 * jj, v);
+            }
+        }
         load_tiles(p0 + 2 * WBK, slot);
         __syncthreads();
         write_tiles();
@@ -1037,7 +1134,7 @@ static int wgrad_common(const float* x, int64_t ldx, const float* dy, int64_t ld
                                    workspace, g);
             } else if constexpr ((!SB() || ONE()) && (!XSP() || (!ONE() && !SB())) && (!XM() || XSP())) {   // bf16 storage: one product; spikes: three
                 hipLaunchKernelGGL((k_conv_wgrad_pipe<t.tm, t.tn, t.wm, t.wn, WBK(), ONE(), SB(), XSP(), XM()>), grid, dim3(kThreads), 0,
-                                   st, x, dy, workspace, g);
+                                   st, x, dy, workspace, g, WgradDx{});
             }
             return true;
         },
@@ -1163,4 +1260,129 @@ extern "C" int snn_conv1x1_mask_wgrad(const uint32_t* mask, int64_t ld_mask, con
                 "snn_conv1x1_mask_wgrad: call not covered (ask snn_conv1x1_mask_supported)");
     return wgrad_common(reinterpret_cast<const float*>(mask), ld_mask, dy, lddy, dw, N, H, W, Cin, H, W, Cout, 1, 1, 1, 0,
                         accumulate, workspace, splitk, SNN_PREC_BF16X3, stream, true, 0.0f, true);
+}
+
+// ---- both gradients of a 1x1 / stride 1 convolution from ONE pass over dy (see k_conv_wgrad_pipe DX, include/snn_hip.h)
+namespace {
+struct Bwd1x1Call {
+    const void* x;   // fp32 activations, or (xm) the spike bit mask
+    int64_t ldx;
+    bool xm;
+    const float* dy;
+    int64_t lddy;
+    const float* wt;
+    const float* dx;
+    int64_t lddx;
+    const float *add1, *add2;
+    int64_t ld_add1, ld_add2;
+    const float* dw;   // may be null (query: unchecked; launch: the slabs stay in the workspace)
+};
+// nullptr: snn_conv1x1_bwd / snn_conv1x1_mask_bwd take the call (plan in *out); else why not.  The ONE place both the query
+// and the launches ask.  splitk 0: the count of snn_conv2d_wgrad_splitk.
+static const char* bwd1x1_refusal(int64_t N, int H, int W, int Cin, int Cout, const Bwd1x1Call& c, int splitk, int precision,
+                                  WgradPlan* out) {
+    if (!(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0)) return "bad shape";
+    if (!(c.x && c.dy && c.wt && c.dx)) return "null pointer";
+    if (precision != SNN_PREC_BF16X3) return "bf16 x 3 arithmetic on fp32 tensors only";
+    if (Cout > 128) return "more than 128 output channels (a block must own all of them)";
+    if (Cout % 4 || Cin % 4) return "channel counts must be multiples of 4";
+    if (splitk < 0 || splitk > 32768) return "bad splitk";
+    if (c.xm ? !(Cin % 32 == 0 && c.ldx >= Cin / 32) : !(c.ldx >= Cin && c.ldx % 4 == 0))
+        return "x: pixel stride smaller than the channel count or no multiple of 4 (mask: Cin % 32, ld >= Cin / 32)";
+    if (!(c.lddy >= Cout && c.lddy % 4 == 0 && c.lddx >= Cin && c.lddx % 4 == 0))
+        return "dy / dx: pixel stride smaller than the channel count or no multiple of 4";
+    if (!(aligned(c.xm ? 4 : 16, {c.x}) && aligned(16, {c.dy, c.wt, c.dx}))) return "x, dy, wt and dx must be 16-byte aligned (mask: 4)";
+    if (c.add1 && !(c.ld_add1 >= Cin && c.ld_add1 % 4 == 0 && aligned(16, {c.add1}))) return "addend: stride or alignment";
+    if (c.add2 && !(c.ld_add2 >= Cin && c.ld_add2 % 4 == 0 && aligned(16, {c.add2}))) return "addend2: stride or alignment";
+    if (c.dw && !aligned(4, {c.dw})) return "dw must be 4-byte aligned";
+    // (the 2 GiB spans of k_conv_wgrad_pipe - dy and x of one pixel split, the whole mask - are wgrad_plan's to check, with
+    // this call's slab count; dx and the addends are addressed with 64 bits)
+    if (!(N * H * (int64_t)W < 0x7fffffffLL - 64)) return "more than 2^31 pixels";
+    const unsigned align = kAlignIn16 | kAlignDy16 | kAlignDy8 | ((c.dw && aligned(16, {c.dw})) ? kAlignDw16 : 0u);
+    const WgradPlan p = wgrad_plan(N, H, W, Cin, H, W, Cout, 1, 1, 1, 0, c.ldx, c.lddy, align, precision, c.xm, 0, splitk, false, c.xm);
+    if (!(p.ok && p.kernel == kWgradPipe && !p.one)) return "the weight gradient does not take the pipelined bf16 x 3 kernel";
+    if (p.tiles_m != 1) return "the weight-gradient tile does not own all output channels";
+    if (!(p.t.id == 0 || p.t.id == 4)) return "no fused instance for this weight-gradient tile";
+    if (out) *out = p;
+    return nullptr;
+}
+
+// Layer classes whose fused launch measured slower than the two launches it replaces are not offered by the query (the
+// launch still takes them: the kernels are tested on every tile they have an instance for).
+static bool bwd1x1_pays(const WgradPlan& p, bool xm) {
+    // the 128 x 128 tile on fp32 x (the C2f exit 320 -> 128 at 60 x 76): its instance runs one wave per SIMD against a
+    // split count planned for three blocks per CU - 888 us fused against 405 + 305 us in two launches
+    return !(p.t.id == 0 && !xm);
+}
+
+static int bwd1x1_common(const char* name, const Bwd1x1Call& c, float* dx, float* dw, int64_t N, int H, int W, int Cin, int Cout,
+                         int accumulate, float* workspace, int splitk, int precision, void* stream) {
+    SNN_REQUIRE(workspace, "%s: null workspace", name);
+    SNN_REQUIRE(splitk >= 1, "%s: bad splitk %d", name, splitk);
+    WgradPlan p;
+    const char* why = bwd1x1_refusal(N, H, W, Cin, Cout, c, splitk, precision, &p);
+    SNN_REQUIRE(!why, "%s: call not covered: %s (ask snn_conv1x1_bwd_supported)", name, why);
+    WgradGeom g;
+    g.Mtot = N * H * (int64_t)W;
+    g.H = H; g.W = W; g.Cin = Cin; g.Ho = H; g.Wo = W; g.Cout = Cout;
+    g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0;
+    g.ldx = c.ldx; g.lddy = c.lddy;
+    g.Ktot = Cin;
+    g.x_th = 0.0f;
+    g.pix_per_split = p.pix_per_split;
+    g.nimg = (int)N;
+    g.tiles_m = p.tiles_m;
+    g.tiles_n = p.tiles_n;
+    g.splitk = splitk;
+    const WgradDx d = {c.wt, dx, c.add1, c.add2, c.lddx, c.ld_add1, c.ld_add2};
+    const dim3 grid((unsigned)((int64_t)g.tiles_m * g.tiles_n * splitk));
+    hipStream_t st = (hipStream_t)stream;
+    const float* xf = static_cast<const float*>(c.x);
+    dispatch(
+        [&](auto ID, auto XM) {
+            constexpr WgradShape t = kWgradShapes[ID()];
+            constexpr int wbk = ID() >= 4 ? 64 : 32;
+            hipLaunchKernelGGL((k_conv_wgrad_pipe<t.tm, t.tn, t.wm, t.wn, wbk, false, false, XM(), XM(), true>), grid, dim3(kThreads), 0, st,
+                               xf, c.dy, workspace, g, d);
+            return true;
+        },
+        OneOf<0, 4>{p.t.id}, Flag{c.xm});
+    SNN_CHECK_LAUNCH(name);
+    if (!dw) return 0;   // the slabs stay in the workspace: snn_conv2d_wgrad_reduce sums them (on any stream)
+    return wgrad_reduce_slabs(workspace, dw, (int64_t)Cout * Cin, splitk, accumulate, st);
+}
+}  // namespace
+
+extern "C" int snn_conv1x1_bwd_supported(int64_t N, int H, int W, int Cin, int Cout, const void* x, int64_t ldx, int is_mask,
+                                         const float* dy, int64_t lddy, const float* wt, const float* dx, int64_t lddx,
+                                         const float* addend, int64_t ld_addend, const float* addend2, int64_t ld_addend2,
+                                         const float* dw, int splitk, int precision) {
+    const Bwd1x1Call c = {x, ldx, is_mask != 0, dy, lddy, wt, dx, lddx, addend, addend2, ld_addend, ld_addend2, dw};
+    WgradPlan p;
+    if (bwd1x1_refusal(N, H, W, Cin, Cout, c, splitk, precision, &p)) return 0;
+    // the launch would run; whether it PAYS is a matter of the layer class ("1x1 backward in one pass")
+    return bwd1x1_pays(p, c.xm) ? 1 : 0;
+}
+
+extern "C" int snn_conv1x1_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* wt, float* dx, int64_t lddx,
+                               const float* addend, int64_t ld_addend, const float* addend2, int64_t ld_addend2, float* dw,
+                               int64_t N, int H, int W, int Cin, int Cout, int accumulate, float* workspace, int splitk,
+                               int precision, void* stream) {
+    const Bwd1x1Call c = {x, ldx, false, dy, lddy, wt, dx, lddx, addend, addend2, ld_addend, ld_addend2, dw};
+    return bwd1x1_common("snn_conv1x1_bwd", c, dx, dw, N, H, W, Cin, Cout, accumulate, workspace, splitk, precision, stream);
+}
+
+extern "C" int snn_conv1x1_mask_bwd(const uint32_t* mask, int64_t ld_mask, const float* dy, int64_t lddy, const float* wt, float* dx,
+                                    int64_t lddx, const float* addend, int64_t ld_addend, const float* addend2,
+                                    int64_t ld_addend2, float* dw, int64_t N, int H, int W, int Cin, int Cout, int accumulate,
+                                    float* workspace, int splitk, int precision, void* stream) {
+    const Bwd1x1Call c = {mask, ld_mask, true, dy, lddy, wt, dx, lddx, addend, addend2, ld_addend, ld_addend2, dw};
+    return bwd1x1_common("snn_conv1x1_mask_bwd", c, dx, dw, N, H, W, Cin, Cout, accumulate, workspace, splitk, precision, stream);
+}
+
+// dw (+)= the workspace slabs of any weight-gradient launch, in slab order: the reducer every snn_conv2d_wgrad call ends
+// with, for a caller that ran the slab kernel with dw = NULL (snn_conv1x1_bwd on the main stream, the reduction elsewhere)
+extern "C" int snn_conv2d_wgrad_reduce(float* workspace, float* dw, int64_t n, int splitk, int accumulate, void* stream) {
+    SNN_REQUIRE(workspace && dw && n > 0 && splitk >= 1 && splitk <= 32768, "snn_conv2d_wgrad_reduce: bad arguments");
+    return wgrad_reduce_slabs(workspace, dw, n, splitk, accumulate, (hipStream_t)stream);
 }

@@ -40,7 +40,8 @@ from .event_ops import (AUG_Q16_MAX, AUG_Q16_MIN, AUG_Q16_ONE, _check_batch_vect
 LEVERS = ("USE_WGRAD_STREAM", "USE_HEAD_STREAMS", "WGRAD_SIDE_DEPTH", "FUSE_OUTER_ADDEND", "USE_SIBLING_FUSION",
           "USE_SPIKES_FROM_VDEC", "USE_SPIKE_MASK", "SPIKE_MASK_MIN_BYTES", "USE_HALO_CONV", "USE_DEFERRED_BN_APPLY",
           "SCAN_SEGMENT_T", "USE_CONV_BN_STATS", "USE_PRESPLIT_WEIGHTS", "USE_PRESPLIT_DGRAD", "SCAN_FLAGS",
-          "USE_SUMS_FROM_STATE", "LIF_CHECKPOINT_BYTES", "USE_LSTM_SCAN")
+          "USE_SUMS_FROM_STATE", "LIF_CHECKPOINT_BYTES", "USE_LSTM_SCAN", "USE_FUSED_BWD1X1",
+          "FUSED_BWD1X1_MIN_BYTES")
 
 
 @contextlib.contextmanager
@@ -583,9 +584,12 @@ def _slot_of(param) -> Optional[GradSlot]:
 
 
 # ------------------------------------------------------------------------------------------- conv
-def _dgrad_accumulate(acc, gy, ldg, wt, x, geom, st, prec, wt_split=None, wt_image=None):
+def _dgrad_accumulate(acc, gy, ldg, wt, x, geom, st, prec, wt_split=None, wt_image=None, fuse=None):
     """Data gradient of a convolution with the gradient accumulation of its input folded into the epilogue
-    (up to two addends; see ``GradAccumulator``).  ``wt`` is the transposed weight ``[Cin][KH][KW][Cout]``."""
+    (up to two addends; see ``GradAccumulator``).  ``wt`` is the transposed weight ``[Cin][KH][KW][Cout]``.
+    ``fuse(dx, addend, ld_add, addend2, ld_add2) -> bool``: a launch that writes this ``dx`` together with something else
+    (``_FusedBwd1x1``); asked once the addends and ``dx`` are settled, True: it ran, no data-gradient kernel is launched here.
+    The bookkeeping around the launch is the same either way."""
     T, B, Cin, H, W, Cout, KH, KW, Ho, Wo, stride, pad = geom
     dx, dx_shape = None, (T, B, Cin, H, W)
     addend, ld_add, addend2, ld_add2 = None, 0, None, 0
@@ -624,7 +628,9 @@ def _dgrad_accumulate(acc, gy, ldg, wt, x, geom, st, prec, wt_split=None, wt_ima
         chained = True
     if dx is None:
         dx = _new_cl((T, B), Cin, H, W, x)
-    if (prec in _HALO_BWD_PRECS and _halo_operand_ok(gy.data_ptr(), ldg, prec == _hip.PREC_BF16S) and USE_HALO_CONV
+    if fuse is not None and fuse(dx, addend, ld_add, addend2, ld_add2):
+        pass
+    elif (prec in _HALO_BWD_PRECS and _halo_operand_ok(gy.data_ptr(), ldg, prec == _hip.PREC_BF16S) and USE_HALO_CONV
             and (KH, KW, stride, pad) == (3, 3, 2, 1)
             and _hip.query("snn_conv3x3_s2_dgrad_supported", T * B, H, W, Cin, Ho, Wo, Cout)):
         # stride 2: all four phase classes of dx from ONE staged pass over dy (k_conv_s2dgrad3)
@@ -654,6 +660,48 @@ def _dgrad_accumulate(acc, gy, ldg, wt, x, geom, st, prec, wt_split=None, wt_ima
         o_acc.fused[o_key] = dx   # what the inner fanout will hand back for this alias
         o_acc.set_result(dx)
     return dx
+
+
+# A stride-1 1x1 convolution that owes both gradients runs ONE kernel over dy where snn_conv1x1_bwd_supported covers the
+# call: the weight-gradient kernel also writes dx (k_conv_wgrad_pipe DX; SNN_NO_FUSED_BWD1X1: A/B and bisecting aid - the
+# two launches, same bits)
+USE_FUSED_BWD1X1 = not os.environ.get("SNN_NO_FUSED_BWD1X1")
+# The fusion removes one HBM read of dy.  A dy smaller than one XCD's L2 (4 MiB) is read the second time from cache, its
+# launches are latency-bound and the fused kernel (fewer resident waves) has nothing to win: such a layer keeps its two
+# launches, as a layer below SPIKE_MASK_MIN_BYTES keeps its potentials.
+FUSED_BWD1X1_MIN_BYTES = 4 << 20
+
+
+class _FusedBwd1x1:
+    """The ``fuse`` hook of ``_dgrad_accumulate`` for a 1x1 / stride 1 convolution whose weight gradient is wanted too.
+    ``xop`` is the weight gradient's x operand - the fp32 activations, or (``is_mask``) the spike bit mask - with its pixel
+    stride.  Called, it asks the query with the settled ``dx`` and addends and, on a yes, launches the fused kernel on the
+    CURRENT stream (dx is on the critical path) into a split-K workspace allocated there: ``ws`` then holds the slabs and
+    the caller reduces them (``snn_conv2d_wgrad_reduce``) on the weight-gradient stream, keeping ``ws`` in that launch's
+    ``hold`` so that it is neither freed nor reused before the reduction has run."""
+
+    __slots__ = ("gy", "ldg", "wt", "xop", "ldxop", "is_mask", "geom", "prec", "splitk", "ws")
+
+    def __init__(self, gy, ldg, wt, xop, ldxop, is_mask, geom, prec, splitk):
+        self.gy, self.ldg, self.wt, self.xop, self.ldxop, self.is_mask = gy, ldg, wt, xop, ldxop, is_mask
+        self.geom, self.prec, self.splitk, self.ws = geom, prec, splitk, None
+
+    @staticmethod
+    def eligible(geom, prec, gy, x) -> bool:
+        T, B, _, H, W, Cout = geom[:6]
+        return (USE_FUSED_BWD1X1 and tuple(geom[6:8]) == (1, 1) and tuple(geom[10:12]) == (1, 0)
+                and T * B * H * W * Cout * 4 >= FUSED_BWD1X1_MIN_BYTES and prec == _hip.PREC_BF16X3 and gy.dtype == _F32 and x.dtype == _F32)
+
+    def __call__(self, dx, addend, ld_add, addend2, ld_add2) -> bool:
+        T, B, Cin, H, W, Cout = self.geom[:6]
+        tail = (self.gy.data_ptr(), self.ldg, self.wt.data_ptr(), dx.data_ptr(), cl_stride(dx), addend, ld_add, addend2, ld_add2)
+        if not _hip.query("snn_conv1x1_bwd_supported", T * B, H, W, Cin, Cout, self.xop.data_ptr(), self.ldxop,
+                          int(self.is_mask), *tail, None, self.splitk, self.prec):
+            return False
+        self.ws = torch.empty((self.splitk, Cout * Cin), device=dx.device, dtype=_F32)
+        _hip.call("snn_conv1x1_mask_bwd" if self.is_mask else "snn_conv1x1_bwd", self.xop.data_ptr(), self.ldxop, *tail, None,
+                  T * B, H, W, Cin, Cout, 0, self.ws.data_ptr(), self.splitk, self.prec, _stream())
+        return True
 
 
 # Halo-resident 3x3 kernel (csrc/conv_halo.hip) for the 64 / 128-channel stride-1 layers, forward and data gradient
@@ -868,6 +916,7 @@ class _Conv2d(Function):
                               Wo, Cout, KH, KW, stride, pad, ctx.slot.claim(), ws.data_ptr(), splitk, stream)
                 return None, None, None, None, None, None, None, None, None, None
             _apply_pending(pend)   # this convolution takes a materialised dy after all
+        fuse = None
         if ctx.needs_input_grad[0]:
             wt = _kept_view(ctx.weight, "_snn_wt")   # transposed once per optimiser step for all layers (FlatTrainer)
             wt16 = wt_img = None
@@ -878,18 +927,25 @@ class _Conv2d(Function):
             else:
                 wt = torch.empty((Cin, KH, KW, Cout), device=x.device, dtype=_F32)
                 _hip.call("snn_weight_transpose", w_ohwi.data_ptr(), wt.data_ptr(), Cout, KH, KW, Cin, st)
-            dx = _dgrad_accumulate(ctx.acc, gy, ldg, wt, x, ctx.geom, st, ctx.prec, wt_split=wt16, wt_image=wt_img)
+            if ctx.needs_input_grad[1] and ctx.x_th is None and _FusedBwd1x1.eligible(ctx.geom, ctx.prec, gy, x):
+                # plain 1x1: dx and the weight-gradient slabs from one pass over gy (when the query covers the call)
+                fuse = _FusedBwd1x1(gy, ldg, wt, x, ldx, False, ctx.geom, ctx.prec, _hip.query(
+                    "snn_conv2d_wgrad_splitk", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ctx.prec))
+            dx = _dgrad_accumulate(ctx.acc, gy, ldg, wt, x, ctx.geom, st, ctx.prec, wt_split=wt16, wt_image=wt_img, fuse=fuse)
         if ctx.needs_input_grad[1]:
             splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ctx.prec)
             xw, ldxw, x_th = _spikes_wgrad_operand(x, ldx, ctx.x_th, gy, ldg)
             slot = ctx.slot
-            with _WgradLaunch(x.device, slot is not None, splitk, Cout, KH * KW * Cin,
-                              hold=(x, xw, gy)) as (stream, ws, _):
+            fws = fuse.ws if fuse is not None else None   # the slabs are there already: only their reduction is left
+            with _WgradLaunch(x.device, slot is not None, 0 if fws is not None else splitk, Cout, KH * KW * Cin,
+                              hold=(x, xw, gy, fws)) as (stream, ws, _):
                 if slot is not None:
                     dst, accumulate = slot.buf, slot.claim()
                 else:
                     dst, accumulate = torch.empty((Cout, KH, KW, Cin), device=x.device, dtype=_F32), 0
-                if x_th is not None:   # x holds potentials: thresholded on load
+                if fws is not None:
+                    _hip.call("snn_conv2d_wgrad_reduce", fws.data_ptr(), dst.data_ptr(), Cout * Cin, splitk, accumulate, stream)
+                elif x_th is not None:   # x holds potentials: thresholded on load
                     _hip.call("snn_conv2d_spikes_wgrad", xw.data_ptr(), ldxw, x_th, gy.data_ptr(), ldg, dst.data_ptr(),
                               T * B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, accumulate, ws.data_ptr(), splitk,
                               stream)
@@ -1098,18 +1154,32 @@ class _SiblingConv1x1(Function):
         ldg, ldx = cl_stride(gy), cl_stride(x)
         dx = dw1 = None
         dw2s = [None] * len(widths)
+        want_dw = any(ctx.needs_input_grad[9:]) or (composed and ctx.needs_input_grad[1])
+        fuse = None
         if ctx.needs_input_grad[0]:
-            dx = _dgrad_accumulate(ctx.acc, gy, ldg, ctx.wct, x, ctx.geom, _stream(), ctx.prec)
-        if any(ctx.needs_input_grad[9:]) or (composed and ctx.needs_input_grad[1]):
+            if want_dw and _FusedBwd1x1.eligible(ctx.geom, ctx.prec, gy, x) and (ctx.x_th is None or ctx.x_mask is not None):
+                # dx and the slabs of G from one pass over gy (when the query covers the call); x as the weight gradient
+                # below would read it: the spike bit mask of the LIF layer in front, or stored activations
+                splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, H, W, Ct, 1, 1, 1, 0, ctx.prec)
+                if ctx.x_mask is None:
+                    fuse = _FusedBwd1x1(gy, ldg, ctx.wct, x, ldx, False, ctx.geom, ctx.prec, splitk)
+                else:
+                    fuse = _FusedBwd1x1(gy, ldg, ctx.wct, ctx.x_mask, ctx.x_mask.shape[-1], True, ctx.geom, ctx.prec, splitk)
+            dx = _dgrad_accumulate(ctx.acc, gy, ldg, ctx.wct, x, ctx.geom, _stream(), ctx.prec, fuse=fuse)
+        if want_dw:
             slot1, slots2 = ctx.slot1, ctx.slots2
             slotted = all(s_ is not None for s_ in slots2) and (slot1 is not None or not composed)
             splitk = _hip.query("snn_conv2d_wgrad_splitk", T * B, H, W, Cin, H, W, Ct, 1, 1, 1, 0, ctx.prec)
             xw, ldxw, x_th = _spikes_wgrad_operand(x, ldx, ctx.x_th, gy, ldg)
             x_mask = ctx.x_mask
-            with _WgradLaunch(x.device, slotted, splitk, Ct, Cin, hold=(x, xw, gy, x_mask), with_g=True) as (stream, ws, G):
-                if x_mask is not None and _hip.query("snn_conv1x1_mask_supported", T * B, H, W, Cin, Ct, x_mask.data_ptr(),
-                                                     x_mask.shape[-1], None, None, 0, gy.data_ptr(), ldg, G.data_ptr(),
-                                                     ctx.fwd_prec, ctx.prec):
+            fws = fuse.ws if fuse is not None else None   # the slabs are there already: only their reduction is left
+            with _WgradLaunch(x.device, slotted, 0 if fws is not None else splitk, Ct, Cin, hold=(x, xw, gy, x_mask, fws),
+                              with_g=True) as (stream, ws, G):
+                if fws is not None:
+                    _hip.call("snn_conv2d_wgrad_reduce", fws.data_ptr(), G.data_ptr(), Ct * Cin, splitk, 0, stream)
+                elif x_mask is not None and _hip.query("snn_conv1x1_mask_supported", T * B, H, W, Cin, Ct, x_mask.data_ptr(),
+                                                       x_mask.shape[-1], None, None, 0, gy.data_ptr(), ldg, G.data_ptr(),
+                                                       ctx.fwd_prec, ctx.prec):
                     # the spikes of the LIF layer in front as its bit mask; otherwise its potentials, which are always there
                     _hip.call("snn_conv1x1_mask_wgrad", x_mask.data_ptr(), x_mask.shape[-1], gy.data_ptr(), ldg, G.data_ptr(),
                               T * B, H, W, Cin, Ct, 0, ws.data_ptr(), splitk, stream)

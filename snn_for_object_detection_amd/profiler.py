@@ -90,6 +90,15 @@ def work_of(name: str, a):
             return WGRAD_LABELS[0] + ", mask, spikes", flops, byts
         tile = "32, 4, 1" if cout <= 32 else ("64, 2, 2" if cout <= 64 else "128, 2, 2")
         return f"k_conv_gather<{tile}, false, true>, mask, spikes", flops, byts
+    if name in ("snn_conv1x1_bwd", "snn_conv1x1_mask_bwd"):   # both gradients of a 1x1 from one pass over dy
+        # (x | mask, ldx, dy, lddy, wt, dx, lddx, addend, ld, addend2, ld, dw, N, H, W, Cin, Cout, ...)
+        mask = name == "snn_conv1x1_mask_bwd"
+        n, h, w, cin, cout = a[12:17]
+        px = float(n) * h * w
+        flops = 4.0 * px * cout * cin   # the data gradient and the weight gradient
+        addends = (a[7] is not None) + (a[9] is not None)
+        byts = 4.0 * px * cout + (px * cin / 8.0 if mask else 4.0 * px * cin) + 4.0 * px * cin * (1 + addends) + 8.0 * cout * cin
+        return WGRAD_LABELS[0] + ", dgrad+wgrad" + (", mask, spikes" if mask else ""), flops, byts
     if name in ("snn_conv2d_spikes_fwd", "snn_conv2d_spikes_wgrad"):   # any kernel size over spikes formed from saved potentials
         # (vdec, ld, v_th, w | dy, y | lddy, ldy | dw, N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, ...)
         fwd = name.endswith("_fwd")

@@ -25,6 +25,8 @@ def shape_of(name, a):
         a = tuple(a[:3]) + tuple(a[4:])   # without the pre-split weight pointer: the positions snn_conv2d_wgrad has
     if name == "snn_conv2d_wgrad_bn":   # (x, gx, y, the four coefficient rows, ... first: geometry starts at position 10)
         return f"N{a[10]} {a[11]}x{a[12]} {a[13]}->{a[16]} k{a[17]} s{a[19]} +bn-apply"
+    if name == "snn_conv2d_wgrad_reduce":   # (workspace, dw, n, splitk, ...): the slabs a fused 1x1 backward left
+        return f"n{a[2]} slabs{a[3]}"
     if name.startswith("snn_conv2d"):
         return f"N{a[5]} {a[6]}x{a[7]} {a[8]}->{a[11]} k{a[12]} s{a[14]}"
     if name == "snn_conv3x3_halo":
@@ -35,8 +37,10 @@ def shape_of(name, a):
         return f"N{a[6]} {a[7]}x{a[8]} {a[9]}->{a[10]}"
     if name in ("snn_conv1x1_mask_fwd", "snn_conv1x1_mask_wgrad"):       # (mask, ld_mask, w | dy, y | lddy, ldy | dw, N, H, W, Cin, Cout)
         return f"N{a[5]} {a[6]}x{a[7]} {a[8]}->{a[9]}"
+    if name in ("snn_conv1x1_bwd", "snn_conv1x1_mask_bwd"):   # (x | mask, ldx, dy, lddy, wt, dx, lddx, addend, ld, addend2, ld, dw, N, H, W, Cin, Cout)
+        return f"N{a[12]} {a[13]}x{a[14]} {a[15]}->{a[16]} dgrad+wgrad{' +add' if a[7] is not None else ''}{' +add2' if a[9] is not None else ''}"
     if name in ("snn_affine_neuron_fwd", "snn_affine_neuron_fwd_mask"):
-        if a[7] is None:   # no output tensor (SNN_SCAN_SPIKES_FROM_VDEC); + the spike bit mask
+        if a[7] is None:  # no output tensor (SNN_SCAN_SPIKES_FROM_VDEC); + the spike bit mask
             return f"n{a[0]} T{a[14]} M{a[15]} C{a[16]} no-out{' +mask' if name.endswith('_mask') else ''}"
         return f"n{a[0]} T{a[14]} M{a[15]} C{a[16]}{' +shortcut' if a[9] is not None else ''}"
     if name == "snn_affine_neuron_bwd":
